@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mcells/s of the 3-D FDTD time-stepping hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NS|C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--workload NS|C2|C3|C4|C5] [--full] [--dump-outputs DIR]
 
 One bench "step" = `--ts-per-step` (default 500, so the driver's `--steps 20` times BASELINE's 10 000 timesteps) full FDTD timesteps (E half-step + H half-step incl.
 CPML, source, port probes and NF2FF running-DFT surfaces) of the named BASELINE workload; default
@@ -11,11 +11,16 @@ per GPU) the SAME global grid is z-slab decomposed over the ranks (strong scalin
 states the target); the halo planes travel inside libfdtd_hip.so — P2P mailboxes written by the update
 kernels over xGMI by default, RCCL send/recv on a second stream with `--halo rccl`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (begin-to-end durations of the
-dominant kernel, from start / stop events carried by every main launch = the interval a rocprofv3 kernel trace reports,
-vs 36 algorithmic bytes per cell per half-step), at N = 1 `roofline_hbm_resident` (the same measurement on C3,
-400x400x80, whose fields do not fit the 256 MiB Infinity Cache) and `cpu_baseline` (the oracle, test infrastructure,
-timed on the host cores as a reported non-target).
+Prints ONE JSON line on rank 0.  A plain run sets up, pre-fills and warms up, times the
+K steps and prints the headline (`value`, `ms_per_step`).  With `--full` the line also carries `roofline` (begin-to-end
+durations of the dominant kernel, from start / stop events carried by every main launch = the interval a rocprofv3 kernel
+trace reports, vs 36 algorithmic bytes per cell per half-step; a profiled pass of its own after the timed steps), at N = 1
+`roofline_hbm_resident` (the same measurement on C3, 400x400x80, whose fields do not fit the 256 MiB Infinity Cache), the
+side points of the reference's default scenes and `cpu_baseline` (the oracle, test infrastructure, timed on the host cores
+as a reported non-target).
+
+`--dump-outputs DIR` writes what the timed path computed by the end of its last step as DIR/<name>.npy (see dump_outputs):
+the inputs are fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -56,6 +61,12 @@ def main():
     ap.add_argument("--no-hbm-point", action="store_true", help="skip the C3 (HBM-resident) roofline block")
     ap.add_argument("--no-small-grid-point", action="store_true", help="skip the side points: the reference's default GUI scene (resident schedule) and its multi-patch default (MUR, two launches)")
     ap.add_argument("--cpu-steps", type=int, default=0, help="oracle timesteps for the cpu_baseline leg (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline, the roofline pass, the C3 HBM-resident point and the "
+                         "side points of the reference's default scenes (the --no-* options above thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the fields (a fixed, seeded sample of cells), the port series and the NF2FF surface "
+                         "data as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args()
 
     import numpy as np
@@ -93,7 +104,7 @@ def main():
     # The CPU leg FIRST (rank 0, N = 1 only; ~10 s on the host cores), so that everything after it is GPU work and an outside
     # observer sampling the GPU sees the timed region at the end of the run instead of a 10 s CPU phase.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(capi, simm, w, vox, args)
     # Untimed pre-fill on top of the W warm-up steps: the step time depends on the field VALUES (all-zero fields stream 6-15 %
     # faster, profiles/r02/step_time_vs_field_values.txt), so nothing is timed before the pulse has reached every corner of
@@ -171,16 +182,20 @@ def main():
     ncells = w.grid.ncells
     timesteps = args.steps * tps
     value = ncells * timesteps / elapsed / 1e6
+    if args.dump_outputs:                       # before anything else steps the grid: the state the last timed step left
+        dump_outputs(args.dump_outputs, sim, eng, w.grid, world, rank, comm)
 
     # roofline of the dominant kernel (E half-step == H half-step in algorithmic bytes): a second pass of the same
     # length in which every main launch carries start / stop events (hipExtLaunchKernelGGL) = the dispatch's begin
     # and end timestamps, the interval a rocprofv3 kernel trace reports; nothing is subtracted.
-    if sim.external_transport is not None:      # host transport: no in-library step loop to profile
-        run_steps(min(timesteps, 2000))         # the same second pass, so that every transport ends on the same timestep
-        prof = capi.FdtdProfile(ms_total=elapsed * 1e3, ms_update_e=float("nan"), ms_update_h=float("nan"), steps=timesteps)
-    else:
-        prof = eng.run_profiled(min(timesteps, 2000))
-    roofline = roofline_block(args.workload, eng, prof, world, sim.external_transport is not None, elapsed / timesteps * 1e3)
+    prof = roofline = None
+    if args.full:
+        if sim.external_transport is not None:      # host transport: no in-library step loop to profile
+            run_steps(min(timesteps, 2000))         # the same second pass, so that every transport ends on the same timestep
+            prof = capi.FdtdProfile(ms_total=elapsed * 1e3, ms_update_e=float("nan"), ms_update_h=float("nan"), steps=timesteps)
+        else:
+            prof = eng.run_profiled(min(timesteps, 2000))
+        roofline = roofline_block(args.workload, eng, prof, world, sim.external_transport is not None, elapsed / timesteps * 1e3)
     finite = bool(np.isfinite(eng.get_field(0, 2)).all())
     # L2 norm of the first port's voltage series over every timestep stepped so far (rank-summed): identical for every
     # N and every halo transport, since the decomposed run is bit-identical to the single-slab run
@@ -202,7 +217,7 @@ def main():
                 "slab_k0": int(eng.k0), "slab_planes": int(eng.nk), "slab_z_cpml_planes": int(zl[eng.k0:eng.k0 + eng.nk].sum()),
                 "slab_max_abs_V": vmax, "device": local_rank,
                 "launches_per_timestep": sched["launches_per_timestep"], "lag_planes": sched["lag_planes"],
-                "us_main_kernels": None if not (prof.ms_update_e == prof.ms_update_e) else round((prof.ms_update_e + prof.ms_update_h) * 1e3, 3),
+                "us_main_kernels": None if prof is None or not (prof.ms_update_e == prof.ms_update_e) else round((prof.ms_update_e + prof.ms_update_h) * 1e3, 3),
                 "ms_halo_host_exchange": round(getattr(comm, "ms_exchange", 0.0) / max(args.steps + args.warmup, 1), 4),
                 "rccl_nranks": eng.comm_nranks()}
         if comm.transport_used == "p2p":     # what the runtime says about the way to each neighbour's GPU: xGMI or PCIe, hops
@@ -226,18 +241,18 @@ def main():
             coupling["transport_note"] = "fell back to host-copied halos (fdtd_half_step + torch.distributed send/recv): a debugging transport, milliseconds per timestep"
     operator_form, steps_total = sim.operator_form, int(eng.step)
     hbm_point = None
-    if rank == 0 and world == 1 and not args.no_hbm_point and args.workload != "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_hbm_point and args.workload != "C3":
         del eng
         sim.engine = None                     # frees the NS context before the C3 one is built
         hbm_point = hbm_resident_point(capi, wl, sc, simm, hip, args)
     small_point = None
-    if rank == 0 and world == 1 and not args.no_small_grid_point:
+    if args.full and rank == 0 and world == 1 and not args.no_small_grid_point:
         try:
             small_point = small_grid_point(capi, simm, hip)
         except Exception as exc:      # the side point never takes the headline number down with it
             small_point = {"error": f"{type(exc).__name__}: {exc}"}
     mur_point = None
-    if rank == 0 and world == 1 and not args.no_small_grid_point:
+    if args.full and rank == 0 and world == 1 and not args.no_small_grid_point:
         try:
             mur_point = mur_scene_point(hip)
         except Exception as exc:
@@ -256,8 +271,9 @@ def main():
                        "cells": ncells, "timesteps_per_step": tps, "prefill_timesteps": prefill, "operator": operator_form,
                        "parallelism": f"z-slab x{world}, halo transport {comm.transport_used}" if world > 1 else "single GPU",
                        "fields_finite": finite, "port_u_l2": port_u_l2, "timesteps_total": steps_total},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if hbm_point is not None:
             out["roofline_hbm_resident"] = hbm_point
         if small_point is not None:
@@ -273,6 +289,61 @@ def main():
         if world == 1:
             dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20240917
+DUMP_FIELD_CELLS = 1 << 20      # cells sampled per field component (float32: 4 MiB each, 24 MiB for the six)
+DUMP_SERIES_MAX = 1 << 17       # samples kept per port series (float64: 1 MiB each)
+DUMP_NF2FF_MAX = 1 << 20        # complex NF2FF surface values kept (real and imaginary part: 16 MiB)
+
+
+def _dump_sample(n, cap, salt):
+    """Sorted indices of a fixed, seeded sample of `cap` out of `n` (all of them when n <= cap): the same for every run."""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, sim, eng, grid, world, rank, comm):
+    """What a caller of the timed path receives after its last step, as out_dir/<name>.npy:
+      V_x V_y V_z I_x I_y I_z  float32  the six field components (E as voltages, H as currents) at a fixed, seeded sample of
+                                        cells of the whole grid (all cells when the grid is small), in the order of `cell_index`
+      cell_index               float64  flat index k*ny*nx + j*nx + i of every sampled cell
+      port<P>_u, port<P>_i     float64  voltage / current series of lumped port P (a fixed sample when longer than 2^17)
+      nf2ff_re, nf2ff_im       float64  the NF2FF surface data (all recording boxes, flattened in order; a fixed sample when larger)
+    At N > 1 every rank contributes its slab and rank 0 writes."""
+    import numpy as np
+    import torch.distributed as dist
+    allreduce = comm.allreduce if world > 1 else None
+    nz, ny, nx = grid.shape[2], grid.shape[1], grid.shape[0]
+    idx = _dump_sample(nz * ny * nx, DUMP_FIELD_CELLS, 0)
+    lo = int(eng.k0) * ny * nx
+    mine = idx[(idx >= lo) & (idx < lo + int(eng.nk) * ny * nx)] - lo
+    arrays = {"cell_index": idx.astype(np.float64)}
+    for kind, kname in ((0, "V"), (1, "I")):
+        for c, cname in enumerate("xyz"):
+            vals = eng.get_field(kind, c).reshape(-1)[mine]
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, vals)
+                vals = np.concatenate(parts)            # slabs in rank order = ascending k
+            assert vals.size == idx.size
+            arrays[f"{kname}_{cname}"] = vals.astype(np.float32)
+    for p, (u, i) in enumerate(sim.port_series(allreduce)):
+        for tag, a in (("u", u), ("i", i)):
+            a = np.asarray(a, np.float64)
+            arrays[f"port{p}_{tag}"] = a[_dump_sample(a.size, DUMP_SERIES_MAX, 1 + 2 * p + (tag == "i"))]
+    if sim.nf2ff_freqs is not None and len(sim.nf2ff_freqs):
+        flat = np.concatenate([np.asarray(b, np.complex128).reshape(-1) for b in sim.nf2ff_boxes(allreduce)])
+        flat = flat[_dump_sample(flat.size, DUMP_NF2FF_MAX, 1000)]
+        arrays["nf2ff_re"], arrays["nf2ff_im"] = flat.real.copy(), flat.imag.copy()
+    if rank != 0:
+        return
+    assert sum(a.nbytes for a in arrays.values()) < 64_000_000
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def working_set_bytes(eng):

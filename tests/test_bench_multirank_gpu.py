@@ -14,7 +14,7 @@ import pytest
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-ARGS = ["--steps", "2", "--warmup", "1", "--ts-per-step", "100", "--workload", "C2", "--no-cpu-baseline", "--no-hbm-point",
+ARGS = ["--steps", "2", "--warmup", "1", "--ts-per-step", "100", "--workload", "C2", "--full", "--no-cpu-baseline", "--no-hbm-point",
         "--prefill-seconds", "0"]
 
 
