@@ -25,6 +25,10 @@ ABI_SYMBOLS = [
     "fdtd_halo_get", "fdtd_halo_put", "fdtd_get_field", "fdtd_set_field", "fdtd_farfield",
 ]
 
+# include/fdtd_hip_sheet.h: conducting sheets, exported by libfdtd_hip.so only (not part of ABI_SYMBOLS / FDTD_ABI_VERSION)
+SHEET_SYMBOLS = ["fdtd_sheet_set", "fdtd_sheet_get"]
+SHEET_MAX_K = 8
+
 
 class FdtdDesc(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
@@ -102,7 +106,22 @@ def bind(lib: C.CDLL) -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    sheet_sig = {
+        "fdtd_sheet_set": (C.c_int, [p, C.c_int, p, p, p, p, C.c_int, C.c_int, p, p]),
+        "fdtd_sheet_get": (C.c_int, [p, p, p]),
+    }
+    assert sorted(sheet_sig) == sorted(SHEET_SYMBOLS)
+    for name, (res, args) in sheet_sig.items():     # optional: bound when the library has them
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_sheets(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the conducting-sheet entry points (include/fdtd_hip_sheet.h)."""
+    return all(hasattr(lib, n) for n in SHEET_SYMBOLS)
 
 
 def hip_library_path(lib_dir: Optional[str] = None) -> str:
@@ -426,6 +445,32 @@ class Engine:
             raise ValueError("unique id must be 128 bytes")
         buf = C.create_string_buffer(uid, 128)
         self._ck(self.lib.fdtd_comm_init(self._ctx, buf), "comm_init")
+
+    # -- conducting sheets (include/fdtd_hip_sheet.h) ------------------------------------------------
+    def _sheet_lib(self):
+        if not has_sheets(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no conducting sheets (fdtd_sheet_set / fdtd_sheet_get)")
+
+    def set_sheets(self, idx, comp, vi, cls, alpha, b):
+        """Sheet edges: global flat node index, component, full vi coefficient, class; alpha / b: [ncls][K] (b = scale * b_k)."""
+        self._sheet_lib()
+        idx, comp, vi, cls = _arr(idx, np.int64), _arr(comp, np.int8), _arr(vi, np.float32), _arr(cls, np.int32)
+        alpha, b = _arr(alpha, np.float32), _arr(b, np.float32)
+        if not (idx.size == comp.size == vi.size == cls.size) or alpha.ndim != 2 or alpha.shape != b.shape:
+            raise ValueError("sheet arrays differ in length / class tables must be [ncls][K]")
+        ncls, K = alpha.shape
+        self._ck(self.lib.fdtd_sheet_set(self._ctx, int(idx.size), _ptr(idx), _ptr(comp), _ptr(vi), _ptr(cls), int(ncls), int(K),
+                                         _ptr(alpha), _ptr(b)), "sheet_set")
+        self.sheet_n, self.sheet_K = int(idx.size), int(K)
+
+    def sheet_state(self):
+        """(v_prev float32 [n], branch currents float32 [K][n]) of the sheet edges."""
+        self._sheet_lib()
+        n, K = getattr(self, "sheet_n", 0), getattr(self, "sheet_K", 0)
+        v = np.zeros(n, np.float32)
+        ib = np.zeros((K, n), np.float32)
+        self._ck(self.lib.fdtd_sheet_get(self._ctx, _ptr(v), _ptr(ib)), "sheet_get")
+        return v, ib
 
     # -- fields -------------------------------------------------------------------------------
     def get_field(self, kind: int, comp: int) -> np.ndarray:

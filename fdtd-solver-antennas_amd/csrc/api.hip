@@ -273,6 +273,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   for (int b = 0; b < c->nbox; ++b) { hipFree(c->box[b].acc); hipFree(c->box[b].rec); }
   hipFree(c->d_probe); hipFree(c->d_box); hipFree(c->tw_v); hipFree(c->tw_i);
   hipFree(c->d_energy); hipFree(c->src_rng); hipFree(c->src_ids);
+  sheet_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
   hipFree(c->mbox);
@@ -949,6 +950,7 @@ static bool wf_mur_possible(const fdtd_ctx* c) {
   return c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, sources_fusable(c)) && 9 * c->p.nbs <= FDTD_BLOCK && wf_lag_for(c) >= c->d.nk;
 }
 static bool wavefront_possible(const fdtd_ctx* c) {
+  if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
   return (c->d.world == 1 || c->p.p2p) && (!c->any_mur || wf_mur_possible(c)) && c->d.nk >= 2 && 2 * (1 + c->p.P4 / FDTD_BLOCK) + 3 <= 64 &&
          (c->p.src_dense_ok || c->src_max_per_strip_plane <= FDTD_BLOCK);   // (sources are always fused into k_step)
@@ -984,7 +986,7 @@ static bool wavefront_active(const fdtd_ctx* c) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0) return false;
   if (!sources_fusable(c) || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -1127,6 +1129,11 @@ static int wf_check(fdtd_ctx* c) {
 
 static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
+  if (c->sheet_n > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: the two-launch schedule only (their correction runs between the E phase and the H update)");
+    if (c->d.world > 1 || c->p.p2p) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: single slab only (world = 1)");
+  }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";
     if (!res_possible(c, &why)) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: %s", why);
@@ -1152,6 +1159,7 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     c->mur_direct = direct;
     int r = phase_E(c, multi, fused, pe, n);
     if (r) return r;
+    launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
     if (multi && (r = exchange(c, FDTD_HALO_E_DOWN))) return r;
     if ((r = phase_H(c, multi, fused, pe, n))) return r;
     if (multi && (r = exchange(c, FDTD_HALO_H_UP))) return r;
@@ -1318,6 +1326,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_mur(c, 2, s);
     launch_post(c, FDTD_KIND_V, c->step, true, s);
     launch_dft(c, FDTD_KIND_V, c->step, s);
+    launch_sheet(c, s);
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);

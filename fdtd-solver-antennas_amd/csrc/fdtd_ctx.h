@@ -254,6 +254,11 @@ struct fdtd_ctx {
   bool tables_dirty = true;
   int launch_failed = 0;         // a main-kernel launch the runtime refused (launch_main): the step loop returns this code, message in err
   hipEvent_t kev0 = nullptr, kev1 = nullptr;   // profiled run: start / stop events the next main launch carries
+  // conducting sheets (sheet.hip, include/fdtd_hip_sheet.h): per edge offset, component, vi, class, v_prev and K branch currents
+  // [K][n]; per class alpha and scale * b [ncls][K]
+  int sheet_n = 0, sheet_K = 0, sheet_ncls = 0;
+  int* sheet_off = nullptr; int8_t* sheet_comp = nullptr; float* sheet_vi = nullptr; int* sheet_cls = nullptr;
+  float* sheet_vprev = nullptr; float* sheet_ib = nullptr; float* sheet_alpha = nullptr; float* sheet_b = nullptr;
   std::string err;
 };
 
@@ -290,6 +295,9 @@ bool res_possible(fdtd_ctx* c, const char** why);
 int res_prepare(fdtd_ctx* c, int max_chunk);
 int launch_resident(fdtd_ctx* c, long long step, int nsteps, hipStream_t s);
 void res_free(fdtd_ctx* c);
+// sheet.hip: conducting sheets — the sparse correction after the E phase (no-op without sheets)
+void launch_sheet(fdtd_ctx* c, hipStream_t s);
+void sheet_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

@@ -167,6 +167,12 @@ class ContinuousStructure:
         self.properties.append(p)
         return p
 
+    def AddConductingSheet(self, name, conductivity, thickness):
+        """Metal of finite conductivity [S/m] and thickness [m]: its surface becomes a surface impedance (sheet.py)."""
+        p = CSProperty(self._log, "ConductingSheet", name, conductivity=float(conductivity), thickness=float(thickness))
+        self.properties.append(p)
+        return p
+
 
 # ---------------------------------------------------------------------------------------------------
 # openEMS side
@@ -384,7 +390,8 @@ class openEMS:
                 for b in p.boxes:
                     m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
             else:
-                m = sc.add_metal(p.name)
+                m = (sc.add_conducting_sheet(p.name, p.params["conductivity"], p.params["thickness"]) if p.kind == "ConductingSheet"
+                     else sc.add_metal(p.name))
                 for b in p.boxes:
                     m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
         for port in self._ports:

@@ -5,6 +5,9 @@ Yee grid (what [EXT] openEMS does when ``FDTD.Run`` sets up its operator):
 
   * material boxes -> per-cell eps_r / kappa (highest priority box containing the cell centre);
   * metal boxes (PEC, any thickness incl. zero) -> every edge with both end nodes inside is PEC;
+  * conducting-sheet boxes (``add_conducting_sheet``: finite conductivity and thickness, sheet.py) -> the edges on the metal's
+    surface become sheet edges (surface impedance, stepped by the engine); interior edges stay PEC.  Where metals overlap, the
+    highest box priority wins, as for materials;
   * lumped port  -> per-edge conductance, soft-source edges, voltage line and current loop.
 
 Coordinates are in drawing units (``unit`` metres per unit, 1e-3 in every reference scene).
@@ -17,6 +20,7 @@ import numpy as np
 
 from .grid import RectGrid
 from .ecoperator import LumpedEdge
+from . import sheet as _sheet
 
 
 @dataclass
@@ -50,6 +54,13 @@ class Metal:
 
 
 @dataclass
+class ConductingSheet(Metal):
+    """AddConductingSheet(name, conductivity, thickness): a metal of finite conductivity [S/m] and thickness [m]."""
+    conductivity: float = 5.8e7
+    thickness: float = 35e-6
+
+
+@dataclass
 class LumpedPort:
     """AddLumpedPort(port_nr, R, start, stop, p_dir, excite, priority) as plain data."""
     number: int
@@ -76,6 +87,13 @@ class Scene:
 
     def add_metal(self, name) -> Metal:
         m = Metal(name)
+        self.metals.append(m)
+        return m
+
+    def add_conducting_sheet(self, name, conductivity, thickness) -> ConductingSheet:
+        if not (float(conductivity) > 0 and float(thickness) > 0):
+            raise ValueError("a conducting sheet needs conductivity > 0 and thickness > 0")
+        m = ConductingSheet(name, conductivity=float(conductivity), thickness=float(thickness))
         self.metals.append(m)
         return m
 
@@ -108,6 +126,7 @@ class VoxelScene:
     kappa: np.ndarray
     pec: np.ndarray           # bool [3][nz][ny][nx]
     ports: List[PortOnGrid]
+    sheets: Optional[_sheet.SheetEdges] = None   # conducting-sheet edges (None: the scene has no conducting sheet)
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -173,6 +192,8 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
             win = mask & (prio[sl] <= bx.priority)
             e = eps[sl]; k = kap[sl]; p = prio[sl]
             e[win] = mat.eps_r; k[win] = mat.kappa; p[win] = bx.priority
+    if any(isinstance(m, ConductingSheet) for m in scene.metals):
+        return _voxelize_with_sheets(scene, grid, eps, kap)
     pec = np.zeros((3, nz, ny, nx), dtype=bool)
     for met in scene.metals:
         for bx in met.boxes:
@@ -192,6 +213,90 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
                 pec[c][tuple(sl)] |= edge
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
     return VoxelScene(eps, kap, pec, ports)
+
+
+def _box_edges(node: np.ndarray, c: int):
+    """Edges of direction c with both end nodes in the node block (shape along c one less, padded back with False)."""
+    npa = 2 - c
+    if node.shape[npa] < 2:
+        return None
+    a = [slice(None)] * 3; b = [slice(None)] * 3
+    a[npa] = slice(0, -1); b[npa] = slice(1, None)
+    return node[tuple(a)] & node[tuple(b)]
+
+
+def _voxelize_with_sheets(scene: Scene, grid: RectGrid, eps, kap) -> VoxelScene:
+    """voxelize() for a scene with conducting sheets: the metal that owns an edge is the one of the highest-priority box (later
+    boxes win ties); edges owned by a sheet metal that lie on its surface become sheet edges, all other metal edges PEC."""
+    nx, ny, nz = grid.shape
+    u = scene.unit
+    tol = _tol(grid)
+    centers = [grid.centers(a) for a in range(3)]
+    eprio = np.full((3, nz, ny, nx), np.iinfo(np.int64).min, np.int64)
+    eown = np.full((3, nz, ny, nx), -1, np.int32)
+    node_masks = {}
+    for mi, met in enumerate(scene.metals):
+        for bx in met.boxes:
+            r = _inside_mask(bx, u, tol, grid.lines)
+            if r is None:
+                continue
+            node, off = r
+            if isinstance(met, ConductingSheet):
+                full = np.zeros((nz, ny, nx), bool)
+                full[off[2]:off[2] + node.shape[0], off[1]:off[1] + node.shape[1], off[0]:off[0] + node.shape[2]] = node
+                node_masks.setdefault(mi, []).append(full)
+            for c in range(3):
+                edge = _box_edges(node, c)
+                if edge is None:
+                    continue
+                sl = (slice(off[2], off[2] + edge.shape[0]), slice(off[1], off[1] + edge.shape[1]),
+                      slice(off[0], off[0] + edge.shape[2]))
+                win = edge & (eprio[c][sl] <= bx.priority)
+                eprio[c][sl][win] = bx.priority
+                eown[c][sl][win] = mi
+    pec = eown >= 0
+    ports = [_port_on_grid(p, grid, u) for p in scene.ports]
+    sh = _sheet.SheetEdges()
+    parts = []
+    # The surface of a metal is taken from all sheet metals of the same conductivity and thickness together: where two of them meet
+    # edge to edge (a patch and its feed line), the junction is inside one conductor, not a rim of each (half a dual width twice).
+    groups = {}
+    for mi in node_masks:
+        groups.setdefault((scene.metals[mi].conductivity, scene.metals[mi].thickness), []).append(mi)
+    for members in groups.values():
+        filled = np.zeros((nz, ny, nx), bool)
+        for mi in members:
+            for bx in scene.metals[mi].boxes:
+                r = _inside_mask(bx, u, -tol, centers)
+                if r is None:
+                    continue
+                mask, off = r
+                sl = tuple(slice(off[a], off[a] + mask.shape[2 - a]) for a in (2, 1, 0))
+                filled[sl] |= mask
+        S = _sheet.surface_faces([m for mi in members for m in node_masks[mi]], filled)
+        for mi in members:
+            met = scene.metals[mi]
+            q = len(sh.metals)
+            sh.metals.append(_sheet.SheetMetal(met.name, met.conductivity, met.thickness))
+            for c in range(3):
+                on, scale = _sheet.edge_geometry(grid, c, eown[c] == mi, S, filled)
+                flat = np.flatnonzero(on)
+                pec[c][on] = False
+                parts.append((flat.astype(np.int64), np.full(flat.size, c, np.int8), scale[on].astype(np.float64),
+                              np.full(flat.size, q, np.int32)))
+    if parts:
+        sh.idx, sh.comp, sh.scale, sh.metal = (np.concatenate([p[t] for p in parts]) for t in range(4))
+    # edges the correction must not touch: port edges (sources, lumped resistors) and voltage-probe lines
+    key = sh.idx * 3 + sh.comp
+    for p in ports:
+        for what, idx, comp in (("voltage-probe line", p.v_idx, p.v_comp), ("port edge", p.src_idx, p.src_comp)):
+            hit = np.isin(key, np.asarray(idx, np.int64) * 3 + np.asarray(comp, np.int64))
+            if hit.any():
+                e = int(np.argmax(hit))
+                k, r = divmod(int(sh.idx[e]), nx * ny)
+                raise ValueError(f"conducting sheet '{sh.metals[sh.metal[e]].name}': the edge at node {(r % nx, r // nx, k)} "
+                                 f"({'xyz'[sh.comp[e]]}) is a {what} of lumped port {p.port.number}")
+    return VoxelScene(eps, kap, pec, ports, sh)
 
 
 def _port_on_grid(port: LumpedPort, grid: RectGrid, u: float) -> PortOnGrid:

@@ -15,7 +15,8 @@ import numpy as np
 from .constants import C0, EPS0, MU0
 from .grid import RectGrid
 from .scene import VoxelScene
-from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_tables, lumped_overrides
+from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_tables, lumped_overrides, LumpedEdge
+from . import sheet as _sheet
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox
@@ -126,6 +127,9 @@ class RunStats:
     schedule_fallback: Optional[str] = None   # set when the run was repeated under the two-launch schedule (see Simulation.run)
     transports_failed: tuple = ()             # decomposed run: halo transports that set up but failed in the first timesteps (see Simulation.run)
     transport_failure_reasons: tuple = ()     # ... and what the library said each time
+    sheet_edges: int = 0                      # conducting-sheet edges stepped by the engine (sheet.py)
+    sheet_fit_error: Optional[float] = None   # largest band error of the sheets' admittance fits (relative)
+    schedule: Optional[dict] = None           # the schedule the engine ran (Engine.schedule_info)
 
 
 class Simulation:
@@ -133,7 +137,8 @@ class Simulation:
                  cpml_cells: Optional[int] = None, nr_ts: int = 30000, end_criteria: float = 1e-4,
                  dt: Optional[float] = None, nf2ff_freqs: Optional[Sequence[float]] = None,
                  nf2ff_inset: Optional[int] = None, dft_oversample: float = 4.0, use_classes: bool = True,
-                 device_operator: bool = True, nf2ff_mode: str = "dft", rec_budget_bytes: Optional[int] = None):
+                 device_operator: bool = True, nf2ff_mode: str = "dft", rec_budget_bytes: Optional[int] = None,
+                 sheet_band: Optional[Sequence[float]] = None, sheet_K: int = _sheet.MAX_K):
         self.grid, self.vox = grid, vox
         self.f0, self.fc = float(f0), float(fc)
         self.bc = BoundarySpec.parse(boundary, cpml_cells)
@@ -206,6 +211,23 @@ class Simulation:
             budget = int(os.environ.get("FDTD_REC_BUDGET_BYTES", 32 << 30)) if rec_budget_bytes is None else int(rec_budget_bytes)
             self.nf2ff_mode = nf2ff_mode if nf2ff_mode != "auto" else ("record" if self.rec_bytes <= budget else "dft")
             self.nf2ff_fmax = fmax
+        # conducting sheets: admittance fit per metal over the excitation band (or sheet_band), the implicit part of the update
+        # folded into the sheet edges' conductance (lumped-edge overrides), the rest stepped by the engine (fdtd_sheet_set)
+        self.sheets = vox.sheets if (vox.sheets is not None and len(vox.sheets)) else None
+        self.sheet_fits, self.sheet_lumped, self.sheet_K = [], [], int(sheet_K)
+        self.sheet_fit_error = None
+        if self.sheets is not None:
+            band = _sheet.fit_band(self.f0, self.fc) if sheet_band is None else tuple(map(float, sheet_band))
+            self.sheet_fits = [_sheet.fit(m.conductivity, m.thickness, band[0], band[1], K=self.sheet_K) for m in self.sheets.metals]
+            self.sheet_fit_error = max(f.band_error for f in self.sheet_fits)
+            reqs = [] if self.nf2ff_box is None else [(r.kind, r.comp, r.lo, r.hi) for r in self.nf2ff_box.requests]
+            _sheet.check_placement(grid, self.sheets, mur_faces=tuple(self.mur_enable), dft_boxes=reqs)
+            nx, ny, _ = grid.shape
+            gimp = [f.implicit_G(self.dt) for f in self.sheet_fits]
+            k, r = np.divmod(self.sheets.idx, nx * ny)
+            j, i = np.divmod(r, nx)
+            self.sheet_lumped = [LumpedEdge(int(c), int(a), int(b), int(q), float(sc * gimp[m]))
+                                 for c, a, b, q, sc, m in zip(self.sheets.comp, i, j, k, self.sheets.scale, self.sheets.metal)]
         self.engine: Optional[Engine] = None
         self.lib = None
         self.external_transport = None     # distributed.SlabComm when halos travel through the host
@@ -217,7 +239,7 @@ class Simulation:
         """The operator in its host (numpy) formulation — built on first use; the default product path never asks."""
         if self._op is None:
             v = self.vox
-            self._op = build_operator(self.grid, v.eps_r, v.kappa, v.pec, self.dt, v.lumped)
+            self._op = build_operator(self.grid, v.eps_r, v.kappa, v.pec, self.dt, v.lumped + self.sheet_lumped)
         return self._op
 
     # ---------------------------------------------------------------------------------------------
@@ -239,13 +261,15 @@ class Simulation:
         self.partition = partition
         if nk < 2:
             raise ValueError(f"slab of rank {rank} has {nk} planes; need >= 2")
+        if self.sheets is not None and world > 1:
+            raise _capi.FdtdError("conducting sheets need a single slab (world = 1): a decomposed lossy-metal run is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
             v = self.vox
             emet, hmet = pack_metric_tables(*metric_lists(g, self.dt), g, k0, nk)
             e.build_operator(g.d, v.eps_r, v.kappa, v.pec, EPS0,
-                             lumped_overrides(g, v.eps_r, v.kappa, v.pec, self.dt, v.lumped), emet, hmet,
+                             lumped_overrides(g, v.eps_r, v.kappa, v.pec, self.dt, v.lumped + self.sheet_lumped), emet, hmet,
                              prefer_classes=self.use_classes)
             self.operator_form = "raw" if e.operator_form()[0] == "raw" else "classes"
         else:
@@ -257,6 +281,8 @@ class Simulation:
             else:
                 e.set_operator_raw(*self.op.raw(k0, nk))
                 self.operator_form = "raw"
+        if self.sheets is not None:
+            e.set_sheets(*self.sheet_tables())
         if self.cpml is not None:
             e.set_cpml(*self.cpml.for_slab(k0, nk))
         if self.mur_enable.any():
@@ -287,6 +313,29 @@ class Simulation:
         self.rank, self.world, self.device = rank, world, device
         self._build_flags = int(flags)
         return e
+
+    def sheet_vi(self) -> np.ndarray:
+        """float32 vi of the sheet edges, as the engine expands it: m (the edge's lumped-edge override, float32) times the separable
+        metric ex[i] * (ey[j] * ez[k]) in float32 — the association of ECOperator.raw, which the raw and class forms share.  Evaluated
+        for the sheet edges alone (no download of the expanded operator)."""
+        sh, g, v = self.sheets, self.grid, self.vox
+        m = lumped_overrides(g, v.eps_r, v.kappa, v.pec, self.dt, self.sheet_lumped)[3]
+        nx, ny, _ = g.shape
+        k, r = np.divmod(sh.idx, nx * ny)
+        j, i = np.divmod(r, nx)
+        emet, _ = metric_lists(g, self.dt)
+        vi = np.empty(len(sh), np.float32)
+        for c in range(3):
+            q = np.nonzero(sh.comp == c)[0]
+            ex, ey, ez = emet[c]
+            vi[q] = m[q] * (ex[i[q]] * (ey[j[q]] * ez[k[q]]))
+        return vi
+
+    def sheet_tables(self):
+        """(idx, comp, vi, cls, alpha, b) of fdtd_sheet_set."""
+        sh = self.sheets
+        cls, alpha, b = _sheet.class_tables(sh, self.sheet_fits, self.dt, self.sheet_K)
+        return sh.idx, sh.comp, self.sheet_vi(), cls, alpha, b
 
     # ---------------------------------------------------------------------------------------------
     def run(self, *, max_steps: Optional[int] = None, check_every: int = 200, verbose: int = 0,
@@ -377,6 +426,9 @@ class Simulation:
                 break
         stats.steps = done
         stats.seconds = time.perf_counter() - t0
+        stats.sheet_edges = 0 if self.sheets is None else len(self.sheets)
+        stats.sheet_fit_error = self.sheet_fit_error
+        stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
         return stats
 

@@ -115,6 +115,11 @@ class FDTDResult:
     port_i: Optional[np.ndarray] = None
     dt: Optional[float] = None
     stats: Optional[dict] = None
+    # filled when the run has a port and an NF2FF result (at f_pattern; efficiency_and_gain): Prad / P_acc, peak gain Dmax * eta, realised gain
+    # gain * (1 - |S11|^2) — with several excited ports (multi-patch designer) P_acc and P_inc are summed over them
+    radiation_efficiency: Optional[float] = None
+    gain_dBi: Optional[float] = None
+    realized_gain_dBi: Optional[float] = None
 
 
 # upstream names, so `from ... import OpenEMSResult` style callers keep working
@@ -133,6 +138,14 @@ def _load(dll_dir: Optional[str], backend: Optional[dict] = None):
     if backend is not None:
         backend.pop("lib", None)
     return _capi.load_hip_library(dll_dir or None)
+
+
+def _add_metal(csx, name, params, metal_loss: bool):
+    """PEC (AddMetal) or, with metal_loss, the params' metal as a conducting sheet (its conductivity and thickness)."""
+    if metal_loss:
+        return csx.AddConductingSheet(name, conductivity=float(params.metal.conductivity_s_per_m),
+                                      thickness=float(params.metal.thickness_m))
+    return csx.AddMetal(name)
 
 
 def _patch_dims_mm(p) -> tuple:
@@ -206,7 +219,7 @@ probe_hip_fixed = probe_hip_microstrip = probe_hip
 # prepare: single patch, lumped port at x = -6 mm  (fixed.py:113-254)
 # ---------------------------------------------------------------------------------------------------
 def prepare_hip_patch_fixed(params, *, dll_dir: Optional[str] = None, work_dir: str = "fdtd_hip_out_fixed",
-                            cleanup: bool = True, verbose: int = 0, **backend) -> FDTDPrepared:
+                            cleanup: bool = True, verbose: int = 0, metal_loss: bool = False, **backend) -> FDTDPrepared:
     try:
         lib = _load(dll_dir, backend)
         f0 = params.frequency_hz
@@ -221,13 +234,13 @@ def prepare_hip_patch_fixed(params, *, dll_dir: Optional[str] = None, work_dir: 
         mesh.AddLine("x", [-box[0] / 2, box[0] / 2])
         mesh.AddLine("y", [-box[1] / 2, box[1] / 2])
         mesh.AddLine("z", [-box[2] / 3, box[2] * 2 / 3])
-        patch = csx.AddMetal("patch")
+        patch = _add_metal(csx, "patch", params, metal_loss)
         patch.AddBox(priority=10, start=[-pw / 2, -pl / 2, h], stop=[pw / 2, pl / 2, h])
         fdtd.AddEdges2Grid(dirs="xy", properties=patch, metal_edge_res=res / 2)
         sub = csx.AddMaterial("substrate", epsilon=params.eps_r, kappa=kappa)
         sub.AddBox(priority=0, start=[-30.0, -30.0, 0], stop=[30.0, 30.0, h])
         mesh.AddLine("z", np.linspace(0, h, 5))
-        gnd = csx.AddMetal("gnd")
+        gnd = _add_metal(csx, "gnd", params, metal_loss)
         gnd.AddBox([-30.0, -30.0, 0], [30.0, 30.0, 0], priority=10)
         fdtd.AddEdges2Grid(dirs="xy", properties=gnd)
         port = fdtd.AddLumpedPort(1, 50, [-6, 0, 0], [-6, 0, h], "z", 1.0, priority=5, edges2grid="xy")
@@ -245,7 +258,7 @@ def prepare_hip_patch_fixed(params, *, dll_dir: Optional[str] = None, work_dir: 
 # ---------------------------------------------------------------------------------------------------
 # prepare: microstrip-fed patch (microstrip.py:134-366) and its 3-D sampling sibling (microstrip_3d.py:19-196)
 # ---------------------------------------------------------------------------------------------------
-def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, ppw, extra_feed_lines, lib, backend):
+def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, ppw, extra_feed_lines, lib, backend, metal_loss=False):
     f0 = params.frequency_hz
     fc = 0.5 * f0
     pw, pl = _patch_dims_mm(params)
@@ -265,10 +278,10 @@ def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, pp
     sub = csx.AddMaterial("substrate", epsilon=params.eps_r, kappa=kappa)
     sub.AddBox(priority=0, start=[-sw / 2, -sl / 2, 0], stop=[sw / 2, sl / 2, h])
     mesh.AddLine("z", np.linspace(0, h, 5))
-    gnd = csx.AddMetal("ground")
+    gnd = _add_metal(csx, "ground", params, metal_loss)
     gnd.AddBox(priority=10, start=[-sw / 2, -sl / 2, 0], stop=[sw / 2, sl / 2, 0])
     fdtd.AddEdges2Grid(dirs="xy", properties=gnd)
-    patch = csx.AddMetal("patch")
+    patch = _add_metal(csx, "patch", params, metal_loss)
     patch.AddBox(priority=10, start=[-pw / 2, -pl / 2, h], stop=[pw / 2, pl / 2, h])
     fdtd.AddEdges2Grid(dirs="xy", properties=patch, metal_edge_res=res / 2)
     # feed strip from the substrate edge to the patch edge, and the feed point at the patch edge centre
@@ -276,7 +289,7 @@ def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, pp
              FeedDirection.POS_X: ([pw / 2, -fw / 2, h], [sw / 2, fw / 2, h], (pw / 2, 0.0)),
              FeedDirection.NEG_Y: ([-fw / 2, -sl / 2, h], [fw / 2, -pl / 2, h], (0.0, -pl / 2)),
              FeedDirection.POS_Y: ([-fw / 2, pl / 2, h], [fw / 2, sl / 2, h], (0.0, pl / 2))}[fd]
-    feed = csx.AddMetal("feed_line")
+    feed = _add_metal(csx, "feed_line", params, metal_loss)
     feed.AddBox(priority=10, start=strip[0], stop=strip[1])
     fdtd.AddEdges2Grid(dirs="xy", properties=feed, metal_edge_res=res / 2)
     px, py = strip[2]
@@ -296,11 +309,11 @@ def prepare_hip_microstrip_patch(params, *, dll_dir: Optional[str] = None,
                                  feed_direction: FeedDirection = FeedDirection.NEG_X,
                                  feed_line_length_mm: float = 20.0, boundary: str = "MUR",
                                  theta_step_deg: float = 2.0, work_dir: str = "fdtd_hip_out_microstrip",
-                                 cleanup: bool = True, verbose: int = 0, **backend) -> FDTDPrepared:
+                                 cleanup: bool = True, verbose: int = 0, metal_loss: bool = False, **backend) -> FDTDPrepared:
     try:
         lib = _load(dll_dir, backend)
         fdtd, nf, port, h, fd = _microstrip_scene(params, feed_direction, feed_line_length_mm, boundary, 50.0, 20,
-                                                  True, lib, backend)
+                                                  True, lib, backend, metal_loss)
         theta = np.arange(0.0, 181.0, max(0.5, float(theta_step_deg)))
         return FDTDPrepared(True, f"Microstrip patch prepared (feed: {fd}, fdtd-hip backend)", FDTD=fdtd, nf=nf,
                             sim_path=_unique_sim_path(work_dir), theta=theta, phi=np.array([0.0, 90.0]),
@@ -314,12 +327,12 @@ def prepare_hip_microstrip_patch_3d(params, *, dll_dir: Optional[str] = None,
                                     feed_line_length_mm: float = 20.0, boundary: str = "MUR",
                                     theta_step_deg: float = 2.0, phi_step_deg: float = 5.0, mesh_quality: int = 3,
                                     work_dir: str = "fdtd_hip_out_microstrip", cleanup: bool = True, verbose: int = 0,
-                                    **backend) -> FDTDPrepared:
+                                    metal_loss: bool = False, **backend) -> FDTDPrepared:
     try:
         lib = _load(dll_dir, backend)
         ppw = _PPW_5[_quality(mesh_quality, 5)]
         fdtd, nf, port, h, fd = _microstrip_scene(params, feed_direction, feed_line_length_mm, boundary, 80.0, ppw,
-                                                  False, lib, backend)
+                                                  False, lib, backend, metal_loss)
         theta = np.arange(0.0, 181.0, max(0.5, float(theta_step_deg)))
         phi = np.arange(0.0, 361.0, max(1.0, float(phi_step_deg)))
         return FDTDPrepared(True, "Microstrip 3D prepared", FDTD=fdtd, nf=nf, sim_path=_unique_sim_path(work_dir),
@@ -358,7 +371,7 @@ def prepare_hip_microstrip_multi_3d(patches: Sequence, *, dll_dir: Optional[str]
                                     feed_line_length_mm: float = 20.0, port_mode: str = "lumped",
                                     end_criteria_db: float = -25.0, work_dir: str = "fdtd_hip_out_multi",
                                     cleanup: bool = True, verbose: int = 0, log_cb: Optional[Callable] = None,
-                                    **backend) -> FDTDPrepared:
+                                    metal_loss: bool = False, **backend) -> FDTDPrepared:
     try:
         if not patches:
             return FDTDPrepared(False, "No patch instances provided.")
@@ -429,7 +442,7 @@ def prepare_hip_microstrip_multi_3d(patches: Sequence, *, dll_dir: Optional[str]
             fw = calculate_microstrip_width(p.frequency_hz, p.eps_r, p.h_m) * 1e3
             kappa = 2 * np.pi * p.frequency_hz * EPS0 * p.eps_r * p.loss_tangent
             sub = csx.AddMaterial(f"substrate_{idx}", epsilon=p.eps_r, kappa=kappa)
-            m_gnd, m_patch, m_feed = (csx.AddMetal(f"{n}_{idx}") for n in ("ground", "patch", "feed"))
+            m_gnd, m_patch, m_feed = (_add_metal(csx, f"{n}_{idx}", p, metal_loss) for n in ("ground", "patch", "feed"))
             t = max(0.02, float(p.metal.thickness_m) * 1e3)
             _placed(sub.AddBox(priority=0, start=[-sw / 2, -sl / 2, -h / 2], stop=[sw / 2, sl / 2, h / 2]), *rot, T)
             normal = np.array([0.0, 0.0, 1.0]) @ R
@@ -490,7 +503,10 @@ def prepare_hip_microstrip_multi_3d(patches: Sequence, *, dll_dir: Optional[str]
 # prepare: legacy full-3D variant (openems.py:140-268)
 # ---------------------------------------------------------------------------------------------------
 def prepare_hip_patch(params, *, dll_dir: Optional[str] = None, work_dir: str = "fdtd_hip_out", cleanup: bool = True,
-                      verbose: int = 0, **backend) -> FDTDPrepared:
+                      verbose: int = 0, metal_loss: bool = False, **backend) -> FDTDPrepared:
+    if metal_loss:   # (the NF2FF box records voltages on the ground plane where it crosses the box: conducting-sheet edges may not lie there)
+        return FDTDPrepared(False, "prepare failed: metal_loss=True is not available for this variant: its ground plane crosses the NF2FF "
+                                   "box, where conducting-sheet edges may not lie (use the fixed or microstrip variants)")
     try:
         lib = _load(dll_dir, backend)
         f0 = params.frequency_hz
@@ -506,9 +522,9 @@ def prepare_hip_patch(params, *, dll_dir: Optional[str] = None, work_dir: str = 
         sub = csx.AddMaterial("substrate", epsilon=params.eps_r, kappa=kappa)
         sub.AddBox([-100.0, -100.0, 0.0], [100.0, 100.0, h])
         mesh.AddLine("z", np.linspace(0.0, h, 5).tolist())
-        gnd = csx.AddMetal("gnd")
+        gnd = _add_metal(csx, "gnd", params, metal_loss)
         gnd.AddBox([-100.0, -100.0, 0.0], [100.0, 100.0, 0.0], priority=10)
-        patch = csx.AddMetal("patch")
+        patch = _add_metal(csx, "patch", params, metal_loss)
         patch.AddBox([-W / 2.0, -L / 2.0, h], [W / 2.0, L / 2.0, h], priority=10)
         fdtd.AddEdges2Grid(dirs="xy", properties=patch, metal_edge_res=res / 2.0)
         fdtd.AddEdges2Grid(dirs="xy", properties=gnd)
@@ -613,6 +629,23 @@ def s11_from_port(port, sim_path, f_center: float, npts: int = 201):
     return f, s11, s11_dB, f_res
 
 
+def efficiency_and_gain(ports, sim_path, f: float, prad: float, dmax: float):
+    """(radiation efficiency, peak gain [dBi], peak realised gain [dBi]) at f, or None where the powers do not allow it.  Every EXCITED
+    port feeds the antenna (the multi-patch designer drives all of them): eta = Prad / sum P_acc, gain = Dmax eta, realised gain =
+    Dmax Prad / sum P_inc (one port: gain (1 - |S11|^2)).  A port that is not excited only loads the antenna: what it absorbs is loss."""
+    acc = inc = 0.0
+    for p in ports:
+        if p is None or getattr(p, "excite", 1.0) == 0:
+            continue
+        p.CalcPort(sim_path, [f])
+        acc += float(np.atleast_1d(p.P_acc)[0])
+        inc += float(np.atleast_1d(p.P_inc)[0])
+    if not (acc > 0 and inc > 0 and prad > 0 and dmax > 0):
+        return None
+    eta = prad / acc
+    return eta, float(10 * np.log10(dmax * eta)), float(10 * np.log10(dmax * prad / inc))
+
+
 def _merged_lines(fdtd) -> dict:
     try:
         return {"xyz"[a]: list(m) for a, m in enumerate(fdtd.GetCSX().GetGrid().merged_lines) if m}
@@ -666,6 +699,13 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
             out.port_u = prepared.port.u_data.ui_val[0]
             out.port_i = prepared.port.i_data.ui_val[0]
             out.dt = fdtd.sim.dt
+            try:
+                g = efficiency_and_gain(prepared.ports or [prepared.port], sim_path, out.f_pattern,
+                                        float(np.atleast_1d(res.Prad)[0]), Dmax)
+                if g is not None:
+                    out.radiation_efficiency, out.gain_dBi, out.realized_gain_dBi = g
+            finally:       # the first port's spectra of the S11 band stay what s11_from_port left for the caller
+                s11_from_port(prepared.port, sim_path, frequency_hz)
         st = fdtd.stats
         out.stats = {"steps": st.steps, "seconds": st.seconds, "mcells_per_s": st.mcells_per_s,
                      "energy_db": float(st.energy_db), "cells": fdtd.sim.grid.ncells,
@@ -674,7 +714,9 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
                      "nf2ff_warning": getattr(fdtd.sim, "nf2ff_warning", None),
                      "excitation_warning": getattr(fdtd.sim, "excitation_warning", None),
                      # hint-line pairs the mesher merged (mesher.merge_close_lines): where this mesh differs from the one openEMS would build
-                     "mesh_lines_merged": _merged_lines(fdtd)}
+                     "mesh_lines_merged": _merged_lines(fdtd),
+                     "sheet_edges": getattr(st, "sheet_edges", 0), "sheet_fit_error": getattr(st, "sheet_fit_error", None),
+                     "schedule": getattr(st, "schedule", None)}
         if verbose:
             print(f"[fdtd-hip] done: {st.steps} steps, {st.mcells_per_s:.0f} MC/s, Dmax {10 * np.log10(Dmax):.2f} dBi", flush=True)
         return out
