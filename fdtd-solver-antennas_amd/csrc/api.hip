@@ -223,7 +223,6 @@ int fdtd_create(const fdtd_desc* d, fdtd_ctx** out) {
   if (const char* v = getenv("FDTD_NT")) p.nt = atoi(v) ? 1 : 0;                       // experiments
   if (const char* v = getenv("FDTD_OCC_WF")) c->occ_wf = std::max(0, std::min(16, atoi(v)));
   if (const char* e = getenv("FDTD_MUR_APPLY_PASS")) c->mur_no_apply = atoi(e) == 0;   // =1: keep the apply pass as a launch of its own (A/B, tests)
-  if (getenv("FDTD_MUR_UNFUSED")) c->mur_fuse_post = false;   // experiments: the Mur post pass as a launch of its own
   if (const char* v = getenv("FDTD_WAVEFRONT")) c->wf_mode = atoi(v) ? 1 : 0;
   if (const char* v = getenv("FDTD_WF_LAG")) c->wf_lag = std::max(0, std::min(4096, atoi(v)));
   if (const char* v = getenv("FDTD_RCCL_INLINE")) c->rccl_inline_mode = atoi(v) ? 1 : 0;  // RCCL halos in stream order on the compute stream (1) / overlapped on the communication stream (0)
@@ -765,21 +764,9 @@ static int exchange_linked(fdtd_ctx* c, int which) {
   return FDTD_OK;
 }
 
-// RCCL exchange INLINE on the compute stream: [E sweep][grouped send/recv][H sweep][grouped send/recv], nothing else.  The overlapped schedule
-// (communication stream, four stream-to-stream event hops per timestep, sweeps split into interior + halo-dependent plane) costs a thin slab
-// 80-85 us per timestep whatever the payload — each hop is 10-20 us of latency, there is nothing of that length to overlap with (an 8-plane
-// north-star slab: 14 us of kernels) — and 8 GPUs deliver less than one (profiles/r01/halo_transport_thin_slab_timing.txt).  In stream order no
-// event is needed at all: the exchange starts when the sweep before it has finished and the next sweep starts when the exchange has.  Taken when
-// a sweep is short (fewer than 4096 blocks of 1024 cells: < ~50 us; larger slabs have sweeps worth overlapping), $FDTD_RCCL_INLINE=0/1 decides.
-static bool rccl_inline(const fdtd_ctx* c) {
-  if (!c->comm) return false;
-  if (c->rccl_inline_mode >= 0) return c->rccl_inline_mode != 0;
-  return (size_t)c->d.nk * c->p.nstrips * c->p.nbs < 4096;
-}
-
-static int exchange(fdtd_ctx* c, int which) {
+static int exchange(fdtd_ctx* c, int which, bool inl) {   // inl: the plan's rccl_inline
   HIPCK(c, hipSetDevice(c->d.device));
-  if (rccl_inline(c)) return exchange_rccl(c, which, c->stream);
+  if (inl) return exchange_rccl(c, which, c->stream);
   // nothing of this exchange may start before this slab's own half-step is complete (it both produces the
   // plane that leaves and is the last reader of the ghost plane that is about to be overwritten)
   HIPCK(c, hipStreamWaitEvent(c->comm_stream, which == FDTD_HALO_E_DOWN ? c->ev_E : c->ev_H, 0));
@@ -789,6 +776,8 @@ static int exchange(fdtd_ctx* c, int which) {
   else { HIPCK(c, hipEventRecord(c->ev_haloH, c->comm_stream)); c->haloH_pending = true; }
   return FDTD_OK;
 }
+
+// ---- the step schedule: what a context runs, and if not, why not (plan_schedule and the predicates only it calls) ----------------------
 
 // Soft sources may stay inside update_E (and the probes in the extra blocks of the main kernels) also in a scene with
 // Mur faces, as long as no source edge sits on a Mur face or on the plane next to it: the Mur "post" pass reads the
@@ -811,14 +800,19 @@ static bool sources_fusable(const fdtd_ctx* c) {
   return true;
 }
 
+// The Mur post pass inside update_E (E+post, apply, H+pre: three launches per timestep instead of four — on the reference's default
+// 56x55x50 scene every launch is a ~4 us latency floor): a single slab with fused sources, at least 6 x 5 x 5 nodes (nx = 5: both inner
+// x nodes, 1 and 3, sit in ONE thread's four cells, and MurVals holds one x pair).
+static bool mur_post_fusable(const fdtd_ctx* c, bool multi, bool fused) {
+  return fused && c->any_mur && !multi && c->d_mur != nullptr && c->d.nx >= 6 && c->d.ny >= 5 && c->d.nz >= 5;
+}
+
 // Mur faces without an apply pass (two launches per timestep instead of three).  Between update_E and update_H the boundary
 // voltages in memory are then the E update's own, and inside update_H they are being overwritten: whoever reads V there —
 // V-probes (sampled by update_H's extra block), NF2FF / DFT boxes (sampled between the two launches) — must not hold a
-// node of a Mur face.  (The reference's probes and boxes sit inside the grid.)  Same conditions as the post pass inside
-// update_E otherwise (phase_E).
+// node of a Mur face.  (The reference's probes and boxes sit inside the grid.)  Needs the post pass inside update_E.
 static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
-  if (!c->mur_no_apply || !c->any_mur || multi || !fused || !c->d_mur || !c->mur_fuse_post) return false;
-  if (c->d.nx < 6 || c->d.ny < 5 || c->d.nz < 5) return false;
+  if (!c->mur_no_apply || !mur_post_fusable(c, multi, fused)) return false;
   const int dim[3] = {c->d.nx, c->d.ny, c->d.nk};
   auto on_face = [&](const int lo[3], const int hi[3]) {
     for (int f = 0; f < 6; ++f) {
@@ -845,119 +839,22 @@ static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
   return true;
 }
 
-// a main-kernel launch the runtime refused (kernels.hip: launch_main keeps the first one): reported once, as an error code
-static int launch_status(fdtd_ctx* c) {
-  const int r = c->launch_failed;
-  c->launch_failed = 0;
-  return r;
-}
-
-struct ProfEvents {
-  std::vector<hipEvent_t> e0, e1, h0, h1;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  int launches = -1;   // main launches of the profiled run when they are not one per timestep (several timesteps per launch)
-};
-
-// One leapfrog step = two main launches.  Without Mur faces the soft sources are injected inside update_E
-// and the probes are sampled by one extra block of the main kernels (update_H(n): V-probes of step n;
-// update_E(n+1): I-probes of step n; the last step's I-probes are flushed at the end of the call).
-//
-// Multi-slab schedule (RCCL ranks or linked contexts): the E halo is only needed by the TOP plane of the H
-// sweep and the H halo only by the BOTTOM plane of the next E sweep, so every sweep launches all other planes
-// first (overlapping the exchange in flight on the communication stream), then waits for the halo event and
-// launches the one dependent plane.
-// Split a sweep into "all planes but one" + "the halo-dependent plane" so that the exchange in flight overlaps
-// the first part.  Measured with 8 linked NS slabs on one MI355X the split schedule is the faster one even for
-// 7-plane slabs (220 vs 251 us per step for all eight), so it is the default; FDTD_FLAG_OVERLAP_OFF disables it.
-static bool rccl_inline(const fdtd_ctx* c);
-static bool overlap_split(const fdtd_ctx* c) { return !(c->d.flags & FDTD_FLAG_OVERLAP_OFF) && !rccl_inline(c); }
-
-static int phase_E(fdtd_ctx* c, bool multi, bool fused, ProfEvents* pe, int n) {
-  HIPCK(c, hipSetDevice(c->d.device));
-  const int nk = c->d.nk;
-  const long long step = c->step;
-  hipStream_t s = c->stream;
-  if (c->mur_pre_step != step) launch_mur(c, 0, s);   // else the previous update_H launch has done it (extra blocks)
-  if (pe) { c->kev0 = pe->e0[n]; c->kev1 = pe->e1[n]; }   // the first main launch below carries them (kernel begin / end timestamps)
-  const bool lower = multi && c->d.rank > 0;           // plane 0 reads the H ghost and is the plane that leaves
-  const bool split = lower && overlap_split(c);
-  auto wait_halo = [&]() -> int {
-    if (c->haloH_pending) { HIPCK(c, hipStreamWaitEvent(s, c->ev_haloH, 0)); c->haloH_pending = false; }
-    // linked transport: the lower neighbour pulls my plane 0 itself; do not overwrite it before that copy ran
-    if (lower && !c->comm && c->link_lo && c->link_lo->haloE_issued) HIPCK(c, hipStreamWaitEvent(s, c->link_lo->ev_haloE, 0));
-    return FDTD_OK;
-  };
-  if (!split) { int r = wait_halo(); if (r) return r; }
-  // single slab with Mur faces and fused sources: the post pass rides in the update_E launch (E+post, apply, H+pre: three
-  // launches per timestep instead of four — on the reference's default 56x55x50 scene every launch is a ~4 us latency floor)
-  c->mur_post_in_E = fused && c->any_mur && !multi && c->d_mur != nullptr && c->mur_fuse_post &&
-                     c->d.nx >= 6 && c->d.ny >= 5 && c->d.nz >= 5;   // (nx = 5: both inner x nodes, 1 and 3, sit in ONE thread's four cells, and MurVals holds one x pair)
-  launch_update_E(c, split ? 1 : 0, nk, step, fused, true, s);
-  c->kev0 = c->kev1 = nullptr;
-  if (split) {
-    int r = wait_halo();
-    if (r) return r;
-    launch_update_E(c, 0, 1, step, fused, false, s);
-  }
-  if (!c->mur_post_in_E) launch_mur(c, 1, s);   // post + apply (no-ops without Mur faces)
-  // no apply launch when update_H takes the candidates itself (step_loop decides: mur_direct_possible)
-  if (!(c->mur_direct && c->mur_post_in_E)) { launch_mur(c, 2, s); c->mur_direct = false; }
-  c->mur_post_in_E = false;
-  if (!fused) launch_post(c, FDTD_KIND_V, step, true, s);
-  launch_dft(c, FDTD_KIND_V, step, s);
-  if (multi && !rccl_inline(c)) HIPCK(c, hipEventRecord(c->ev_E, s));
-  return FDTD_OK;
-}
-
-static int phase_H(fdtd_ctx* c, bool multi, bool fused, ProfEvents* pe, int n) {
-  HIPCK(c, hipSetDevice(c->d.device));
-  const int nk = c->d.nk;
-  const long long step = c->step;
-  hipStream_t s = c->stream;
-  if (pe) { c->kev0 = pe->h0[n]; c->kev1 = pe->h1[n]; }
-  const bool upper = multi && c->d.rank < c->d.world - 1;   // top plane reads the E ghost and is the plane that leaves
-  const bool split = upper && overlap_split(c);
-  auto wait_halo = [&]() -> int {
-    if (c->haloE_pending) { HIPCK(c, hipStreamWaitEvent(s, c->ev_haloE, 0)); c->haloE_pending = false; }
-    if (upper && !c->comm && c->link_hi && c->link_hi->haloH_issued) HIPCK(c, hipStreamWaitEvent(s, c->link_hi->ev_haloH, 0));
-    return FDTD_OK;
-  };
-  if (!split) { int r = wait_halo(); if (r) return r; }
-  // Mur scenes: the pre pass of step + 1 rides in this launch (it reads V only, which is final and not written here)
-  launch_update_H(c, 0, split ? nk - 1 : nk, step, fused, s, fused && c->any_mur);
-  if (fused && c->any_mur && (c->p.mur_nb > 0 || c->p.mur_direct)) c->mur_pre_step = step + 1;   // (mur_direct: the main blocks ran the pre pass)
-  c->kev0 = c->kev1 = nullptr;
-  if (split) {
-    int r = wait_halo();
-    if (r) return r;
-    launch_update_H(c, nk - 1, nk, step, false, s);
-  }
-  if (!fused) launch_post(c, FDTD_KIND_I, step, false, s);
-  launch_dft(c, FDTD_KIND_I, step, s);
-  if (multi && !rccl_inline(c)) HIPCK(c, hipEventRecord(c->ev_H, s));
-  return FDTD_OK;
-}
-
-static int step_loop_p2p(fdtd_ctx* c, int nsteps, struct ProfEvents* pe);
-static int p2p_check(fdtd_ctx* c);
-
 // One launch per timestep (k_step, kernels.hip): single slab, no Mur faces.  AUTO picks it where it measured faster: grids
 // whose fields do not fit the 256 MiB Infinity Cache (there the H sweep finds what the E sweep just touched in that cache
 // instead of in HBM); FDTD_FLAG_KERNEL_WAVEFRONT / $FDTD_WAVEFRONT=1 force it, FDTD_FLAG_KERNEL_DIRECT / =0 forbid it.
 // Mur faces inside the one launch (k_step<..., MUR>): what the two-launch schedule without an apply pass needs (mur_direct_possible), a single slab
 // whose fields fit the Infinity Cache (all E blocks, then all H blocks), and strips of at most 28 blocks (wf_wait_mur polls 9 * nbs flags, one thread each).
-static bool wf_mur_possible(const fdtd_ctx* c) {
-  return c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, sources_fusable(c)) && 9 * c->p.nbs <= FDTD_BLOCK && wf_lag_for(c) >= c->d.nk;
-}
-static bool wavefront_possible(const fdtd_ctx* c) {
+static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
   if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
+  const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
+                                      wf_lag_for(c) >= c->d.nk);
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
-  return (c->d.world == 1 || c->p.p2p) && (!c->any_mur || wf_mur_possible(c)) && c->d.nk >= 2 && 2 * (1 + c->p.P4 / FDTD_BLOCK) + 3 <= 64 &&
+  return (c->d.world == 1 || c->p.p2p) && mur_ok && c->d.nk >= 2 && 2 * (1 + c->p.P4 / FDTD_BLOCK) + 3 <= 64 &&
          (c->p.src_dense_ok || c->src_max_per_strip_plane <= FDTD_BLOCK);   // (sources are always fused into k_step)
 }
-static bool wavefront_active(const fdtd_ctx* c) {
+static bool wavefront_active(const fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (!wavefront_possible(c) || sel == FDTD_FLAG_KERNEL_DIRECT) return false;
+  if (!wavefront_possible(c, fused) || sel == FDTD_FLAG_KERNEL_DIRECT) return false;
   if (sel == FDTD_FLAG_KERNEL_WAVEFRONT) return true;
   if (c->wf_mode >= 0) return c->wf_mode != 0;
   // single slab: always (beyond the Infinity Cache with H a few planes behind E, below it with all E blocks first: wf_lag_for).
@@ -984,10 +881,10 @@ static bool wavefront_active(const fdtd_ctx* c) {
 // The grid resident in registers for the length of a launch (k_resident, resident.hip): small single slabs — the reference GUI's default
 // scenes, MUR and PML_8 alike.  FDTD_FLAG_KERNEL_RESIDENT / $FDTD_RESIDENT=1 take it wherever it is possible, DIRECT / WAVEFRONT /
 // $FDTD_RESIDENT=0 never, AUTO as below.
-static bool resident_active(fdtd_ctx* c) {
+static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
   if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0) return false;
-  if (!sources_fusable(c) || !res_possible(c, nullptr)) return false;
+  if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
   // CU — 175 ... 400 tiles step in 4.4 ... 7.3 us against 9.7 ... 19.9 us of the flag-coupled launches (x 2.2 - 3.3); at 640 tiles the hop
@@ -996,44 +893,17 @@ static bool resident_active(fdtd_ctx* c) {
   if (res_prepare(c, c->res_chunk) != FDTD_OK) return false;
   return c->res.nblocks <= 2 * chip_cus(c->d.device);
 }
-static int res_check(fdtd_ctx* c) {
-  if (!c->res.err) return FDTD_OK;
-  int e = 0;
-  HIPCK(c, hipMemcpy(&e, c->res.err, sizeof(int), hipMemcpyDeviceToHost));
-  if (e) {
-    hipMemset(c->res.err, 0, sizeof(int));
-    return fdtd_fail(c, FDTD_E_DEVICE, "resident schedule: a workgroup waited more than 2 s for a neighbour tile's halo (not all workgroups resident at once?); the fields of this run are invalid — re-initialise them and select FDTD_FLAG_KERNEL_DIRECT (simulation.Simulation.run does both by itself)");
-  }
-  return FDTD_OK;
-}
-static int step_loop_res(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
-  HIPCK(c, hipSetDevice(c->d.device));
-  hipStream_t s = c->stream;
-  int r = res_prepare(c, c->res_chunk);
-  if (r) return r;
-  // NF2FF faces: the time-domain record is written by the kernel itself (res_record); running-DFT sums (k_dft) read the arrays, so there
-  // a launch ends at every sampled timestep
-  const bool sampling = c->nfreq && !c->recorder && c->nbox && c->every > 0;
-  int launches = 0;
-  for (int n = 0; n < nsteps;) {
-    int chunk = std::min(c->res_chunk, nsteps - n);
-    if (sampling) {   // ... so that the sampled timestep (a multiple of `every`) is the launch's last
-      const long long next = (c->step + c->every - 1) / c->every * c->every;
-      chunk = (int)std::min<long long>(chunk, next - c->step + 1);
-    }
-    if (pe) { c->kev0 = pe->e0[launches]; c->kev1 = pe->e1[launches]; }
-    r = launch_resident(c, c->step, chunk, s);
-    c->kev0 = c->kev1 = nullptr;
-    if (r) return r;
-    c->step += chunk;
-    if (sampling) launch_dft(c, -1, c->step - 1, s);
-    n += chunk;
-    ++launches;
-  }
-  c->mur_pre_step = -1;   // (the Mur state arrays are not kept by the resident kernel: the next two-launch timestep runs its own pre pass)
-  if (pe) pe->launches = launches;
-  HIPCK(c, hipGetLastError());
-  return launch_status(c);
+
+// RCCL exchange INLINE on the compute stream: [E sweep][grouped send/recv][H sweep][grouped send/recv], nothing else.  The overlapped schedule
+// (communication stream, four stream-to-stream event hops per timestep, sweeps split into interior + halo-dependent plane) costs a thin slab
+// 80-85 us per timestep whatever the payload — each hop is 10-20 us of latency, there is nothing of that length to overlap with (an 8-plane
+// north-star slab: 14 us of kernels) — and 8 GPUs deliver less than one (profiles/r01/halo_transport_thin_slab_timing.txt).  In stream order no
+// event is needed at all: the exchange starts when the sweep before it has finished and the next sweep starts when the exchange has.  Taken when
+// a sweep is short (fewer than 4096 blocks of 1024 cells: < ~50 us; larger slabs have sweeps worth overlapping), $FDTD_RCCL_INLINE=0/1 decides.
+static bool rccl_inline(const fdtd_ctx* c) {
+  if (!c->comm) return false;
+  if (c->rccl_inline_mode >= 0) return c->rccl_inline_mode != 0;
+  return (size_t)c->d.nk * c->p.nstrips * c->p.nbs < 4096;
 }
 
 // ---- slabs on the mailbox transport that share ONE GPU: when can they not starve each other? ------------------------------------------
@@ -1063,13 +933,213 @@ static unsigned chip_slots(const fdtd_ctx* c) {   // resident workgroups of the 
   for (int cap : {c->occ_e, c->occ_h, c->occ_wf}) if (cap > 0) per_cu = std::min(per_cu, cap);
   return (unsigned)chip_cus(c->d.device) * (unsigned)std::max(per_cu, 1);
 }
-static int p2p_shared_device_refuse(fdtd_ctx* c, unsigned pinned, unsigned slabs) {
+// the bound: `slabs` slabs on one device that together pin `pinned` workgroups (StepPlan::pinned, summed), against the chip's `slots`
+static int p2p_shared_device_ok(fdtd_ctx* c, unsigned pinned, unsigned slabs, unsigned slots) {
+  if (pinned < slots) return FDTD_OK;
   return fdtd_fail(c, FDTD_E_UNSUPPORTED, "p2p transport between slabs that share one GPU: %u slabs could pin %u workgroups waiting for each other's halos and the chip holds %u — not starvation-free; use fewer / thicker strips, FDTD_FLAG_KERNEL_DIRECT, or fdtd_link (event-ordered copies)",
-                   slabs, pinned, chip_slots(c));
+                   slabs, pinned, slots);
 }
 
-static void p2p_prime_if_needed(fdtd_ctx* c);
-static int step_loop_wf(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
+struct StepPlan {
+  enum Kind { NOT_STEPPABLE, RESIDENT, ONE_LAUNCH, TWO_LAUNCH } kind = NOT_STEPPABLE;
+  bool fused = false;          // soft sources inside update_E, probes in the extra blocks of the main launches (sources_fusable)
+  MurStep mur = MUR_NONE;      // two launches: where the Mur post / apply passes run
+  bool rccl_inline = false;    // two launches on RCCL: the exchange in stream order on the compute stream (no split sweeps, no events)
+  int lag = 0, multi_max = 0;  // one launch: wf_lag_for, wf_multi_max; RESIDENT: timesteps per launch at most in multi_max
+  unsigned pinned = 0, slots = 0;   // p2p: workgroups this slab's launches may pin (p2p_pinned_blocks), the chip's slots (chip_slots)
+};
+
+// What this context runs, or the code and message of why it cannot run.  Every decision and refusal of the step loops is here, in
+// the order callers have always seen them (the message prefixes matter: simulation.Simulation.run sorts failures by them).  `linked`:
+// the caller is fdtd_run_linked, or asks on its behalf (fdtd_schedule_info) — linked neighbours are a halo transport, and the bound
+// of slabs that share a device is the caller's, which knows every slab.
+static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
+  StepPlan& pl = *out;
+  pl = StepPlan{};
+  const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
+  const bool multi = c->d.world > 1;
+  const bool fused = sources_fusable(c);
+  if (c->sheet_n > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: the two-launch schedule only (their correction runs between the E phase and the H update)");
+    if (multi || c->p.p2p) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: single slab only (world = 1)");
+  }
+  if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
+    const char* why = "";
+    if (!res_possible(c, &why)) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: %s", why);
+    if (!fused) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: a source edge lies on or next to a Mur face");
+  }
+  if (sel > FDTD_FLAG_KERNEL_DIRECT && sel != FDTD_FLAG_KERNEL_WAVEFRONT && sel != FDTD_FLAG_KERNEL_RESIDENT)
+    return fdtd_fail(c, FDTD_E_UNSUPPORTED, "kernel selection %u: the one-pass variants were removed (measured slower than the two-pass kernels on every workload)", sel);
+  if (sel == FDTD_FLAG_KERNEL_WAVEFRONT && !wavefront_possible(c, fused))
+    return fdtd_fail(c, FDTD_E_UNSUPPORTED, "wavefront schedule: single slab or slabs on the p2p mailbox transport, at least 2 planes, rows of at most %d cells; with Mur faces a single slab within the Infinity Cache, no source edge, voltage probe or NF2FF box on or next to a face", 30 * FDTD_BLOCK * 4);
+  pl.fused = fused;
+  if (c->p.p2p) {   // P2P mailbox transport: the halos travel inside the update kernels (sources always fused)
+    if (c->any_mur || c->d.nk < 2) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "p2p transport: needs >= 2 planes per slab and no Mur faces");
+    if (!fused) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "p2p transport: more than %d source edges in one strip-plane with several sources on one edge", FDTD_BLOCK);
+    const bool one = wavefront_active(c, fused);
+    pl.pinned = p2p_pinned_blocks(c, one);
+    pl.slots = chip_slots(c);
+    // a neighbour's slab on THIS device (ranks sharing a GPU): all `world` slabs may be here, under this slab's schedule
+    if (!linked && !(c->d.flags & FDTD_FLAG_LOOPBACK) && (c->link_info[0][7] == 1 || c->link_info[1][7] == 1)) {
+      const int r = p2p_shared_device_ok(c, (unsigned)c->d.world * pl.pinned, (unsigned)c->d.world, pl.slots);
+      if (r) return r;
+    }
+    if (one) { pl.lag = wf_lag_for(c); pl.multi_max = wf_multi_max(c); }
+    pl.kind = one ? StepPlan::ONE_LAUNCH : StepPlan::TWO_LAUNCH;
+    return FDTD_OK;
+  }
+  if (resident_active(c, fused)) { pl.kind = StepPlan::RESIDENT; pl.multi_max = c->res_chunk; return FDTD_OK; }
+  if (multi && !c->comm && !(linked && (c->link_lo || c->link_hi)))
+    return fdtd_fail(c, FDTD_E_STATE, "world > 1: call fdtd_p2p_attach (mailbox transport), fdtd_comm_init (RCCL), fdtd_link + fdtd_run_linked, or drive fdtd_half_step + fdtd_halo_*");
+  if (wavefront_active(c, fused)) {
+    pl.kind = StepPlan::ONE_LAUNCH; pl.lag = wf_lag_for(c); pl.multi_max = wf_multi_max(c);
+    return FDTD_OK;
+  }
+  pl.kind = StepPlan::TWO_LAUNCH;
+  pl.rccl_inline = rccl_inline(c);
+  if (c->any_mur) pl.mur = mur_direct_possible(c, multi, fused) ? MUR_DIRECT : mur_post_fusable(c, multi, fused) ? MUR_POST_IN_E : MUR_PASSES;
+  return FDTD_OK;
+}
+
+// a main-kernel launch the runtime refused (kernels.hip: launch_main keeps the first one): reported once, as an error code
+static int launch_status(fdtd_ctx* c) {
+  const int r = c->launch_failed;
+  c->launch_failed = 0;
+  return r;
+}
+
+struct ProfEvents {
+  std::vector<hipEvent_t> e0, e1, h0, h1;
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  int launches = -1;   // main launches of the profiled run when they are not one per timestep (several timesteps per launch)
+};
+
+// One leapfrog step = two main launches.  Without Mur faces the soft sources are injected inside update_E
+// and the probes are sampled by one extra block of the main kernels (update_H(n): V-probes of step n;
+// update_E(n+1): I-probes of step n; the last step's I-probes are flushed at the end of the call).
+//
+// Multi-slab schedule (RCCL ranks or linked contexts): the E halo is only needed by the TOP plane of the H
+// sweep and the H halo only by the BOTTOM plane of the next E sweep, so every sweep launches all other planes
+// first (overlapping the exchange in flight on the communication stream), then waits for the halo event and
+// launches the one dependent plane.
+// Split a sweep into "all planes but one" + "the halo-dependent plane" so that the exchange in flight overlaps
+// the first part.  Measured with 8 linked NS slabs on one MI355X the split schedule is the faster one even for
+// 7-plane slabs (220 vs 251 us per step for all eight), so it is the default; FDTD_FLAG_OVERLAP_OFF disables it.
+static bool overlap_split(const fdtd_ctx* c, const StepPlan& pl) { return !(c->d.flags & FDTD_FLAG_OVERLAP_OFF) && !pl.rccl_inline; }
+
+static int phase_E(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
+  HIPCK(c, hipSetDevice(c->d.device));
+  const int nk = c->d.nk;
+  const long long step = c->step;
+  const bool multi = c->d.world > 1;
+  hipStream_t s = c->stream;
+  if (c->mur_pre_step != step) launch_mur(c, 0, s);   // else the previous update_H launch has done it (extra blocks)
+  if (pe) { c->kev0 = pe->e0[n]; c->kev1 = pe->e1[n]; }   // the first main launch below carries them (kernel begin / end timestamps)
+  const bool lower = multi && c->d.rank > 0;           // plane 0 reads the H ghost and is the plane that leaves
+  const bool split = lower && overlap_split(c, pl);
+  auto wait_halo = [&]() -> int {
+    if (c->haloH_pending) { HIPCK(c, hipStreamWaitEvent(s, c->ev_haloH, 0)); c->haloH_pending = false; }
+    // linked transport: the lower neighbour pulls my plane 0 itself; do not overwrite it before that copy ran
+    if (lower && !c->comm && c->link_lo && c->link_lo->haloE_issued) HIPCK(c, hipStreamWaitEvent(s, c->link_lo->ev_haloE, 0));
+    return FDTD_OK;
+  };
+  if (!split) { int r = wait_halo(); if (r) return r; }
+  const bool post_in_E = pl.mur == MUR_DIRECT || pl.mur == MUR_POST_IN_E;
+  launch_update_E(c, split ? 1 : 0, nk, step, pl.fused, true, s, post_in_E);
+  c->kev0 = c->kev1 = nullptr;
+  if (split) {
+    int r = wait_halo();
+    if (r) return r;
+    launch_update_E(c, 0, 1, step, pl.fused, false, s, post_in_E);
+  }
+  if (!post_in_E) launch_mur(c, 1, s);          // post pass (a no-op without Mur faces)
+  if (pl.mur != MUR_DIRECT) launch_mur(c, 2, s);   // apply pass, unless update_H takes the candidates itself
+  if (!pl.fused) launch_post(c, FDTD_KIND_V, step, true, s);
+  launch_dft(c, FDTD_KIND_V, step, s);
+  if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_E, s));
+  return FDTD_OK;
+}
+
+static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
+  HIPCK(c, hipSetDevice(c->d.device));
+  const int nk = c->d.nk;
+  const long long step = c->step;
+  const bool multi = c->d.world > 1;
+  hipStream_t s = c->stream;
+  if (pe) { c->kev0 = pe->h0[n]; c->kev1 = pe->h1[n]; }
+  const bool upper = multi && c->d.rank < c->d.world - 1;   // top plane reads the E ghost and is the plane that leaves
+  const bool split = upper && overlap_split(c, pl);
+  auto wait_halo = [&]() -> int {
+    if (c->haloE_pending) { HIPCK(c, hipStreamWaitEvent(s, c->ev_haloE, 0)); c->haloE_pending = false; }
+    if (upper && !c->comm && c->link_hi && c->link_hi->haloH_issued) HIPCK(c, hipStreamWaitEvent(s, c->link_hi->ev_haloH, 0));
+    return FDTD_OK;
+  };
+  if (!split) { int r = wait_halo(); if (r) return r; }
+  // Mur scenes: the pre pass of step + 1 rides in this launch (it reads V only, which is final and not written here)
+  launch_update_H(c, 0, split ? nk - 1 : nk, step, pl.fused, s, pl.fused ? pl.mur : MUR_NONE);
+  if (pl.fused && c->any_mur && (c->p.mur_nb > 0 || c->p.mur_direct)) c->mur_pre_step = step + 1;   // (mur_direct: the main blocks ran the pre pass)
+  c->kev0 = c->kev1 = nullptr;
+  if (split) {
+    int r = wait_halo();
+    if (r) return r;
+    launch_update_H(c, nk - 1, nk, step, false, s);
+  }
+  if (!pl.fused) launch_post(c, FDTD_KIND_I, step, false, s);
+  launch_dft(c, FDTD_KIND_I, step, s);
+  if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_H, s));
+  return FDTD_OK;
+}
+
+static int res_check(fdtd_ctx* c) {
+  if (!c->res.err) return FDTD_OK;
+  int e = 0;
+  HIPCK(c, hipMemcpy(&e, c->res.err, sizeof(int), hipMemcpyDeviceToHost));
+  if (e) {
+    hipMemset(c->res.err, 0, sizeof(int));
+    return fdtd_fail(c, FDTD_E_DEVICE, "resident schedule: a workgroup waited more than 2 s for a neighbour tile's halo (not all workgroups resident at once?); the fields of this run are invalid — re-initialise them and select FDTD_FLAG_KERNEL_DIRECT (simulation.Simulation.run does both by itself)");
+  }
+  return FDTD_OK;
+}
+static int step_loop_res(fdtd_ctx* c, const StepPlan& pl, int nsteps, ProfEvents* pe) {
+  HIPCK(c, hipSetDevice(c->d.device));
+  hipStream_t s = c->stream;
+  int r = res_prepare(c, pl.multi_max);
+  if (r) return r;
+  // NF2FF faces: the time-domain record is written by the kernel itself (res_record); running-DFT sums (k_dft) read the arrays, so there
+  // a launch ends at every sampled timestep
+  const bool sampling = c->nfreq && !c->recorder && c->nbox && c->every > 0;
+  int launches = 0;
+  for (int n = 0; n < nsteps;) {
+    int chunk = std::min(pl.multi_max, nsteps - n);
+    if (sampling) {   // ... so that the sampled timestep (a multiple of `every`) is the launch's last
+      const long long next = (c->step + c->every - 1) / c->every * c->every;
+      chunk = (int)std::min<long long>(chunk, next - c->step + 1);
+    }
+    if (pe) { c->kev0 = pe->e0[launches]; c->kev1 = pe->e1[launches]; }
+    r = launch_resident(c, c->step, chunk, s);
+    c->kev0 = c->kev1 = nullptr;
+    if (r) return r;
+    c->step += chunk;
+    if (sampling) launch_dft(c, -1, c->step - 1, s);
+    n += chunk;
+    ++launches;
+  }
+  c->mur_pre_step = -1;   // (the Mur state arrays are not kept by the resident kernel: the next two-launch timestep runs its own pre pass)
+  if (pe) pe->launches = launches;
+  HIPCK(c, hipGetLastError());
+  return launch_status(c);
+}
+
+// p2p transport, before the first timestep: the halo of "step -1" = the INITIAL Ix, Iy of this slab's top plane goes up
+static void p2p_prime_if_needed(fdtd_ctx* c) {
+  if (!c->p.p2p || c->step != 0 || c->p2p_primed) return;
+  hipSetDevice(c->d.device);
+  launch_p2p_prime(c, c->stream);
+  c->p2p_primed = true;
+}
+
+static int step_loop_wf(fdtd_ctx* c, const StepPlan& pl, int nsteps, ProfEvents* pe) {
   HIPCK(c, hipSetDevice(c->d.device));
   hipStream_t s = c->stream;
   // the last launch of a call of at least 16 timesteps is a calibration launch of the XCD shares (kernels.hip: xcd_adapt) —
@@ -1078,11 +1148,11 @@ static int step_loop_wf(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
   if (!pe && nsteps >= 16) c->xcd_adapt_calls++;
   // Cache-resident single slabs: SEVERAL timesteps per launch (k_step<.., MULTI>) — up to the next timestep whose NF2FF faces
   // are sampled (a launch of its own reads them), the calibration launch on its own.
-  const int multi = wf_multi_max(c);
+  const int multi = pl.multi_max;
   const bool sampling = (c->nfreq || c->recorder) && c->nbox && c->every > 0;
   int launches = 0;
-  c->wf_mur = c->any_mur;   // (wavefront_possible has checked that this slab can carry them)
-  if (c->wf_mur && nsteps > 0 && c->mur_pre_step != c->step) launch_mur(c, 0, s);   // the pre pass of the first timestep (later ones: the H blocks)
+  // Mur faces ride in k_step<..., MUR> (the planner has checked that this slab can carry them)
+  if (c->any_mur && nsteps > 0 && c->mur_pre_step != c->step) launch_mur(c, 0, s);   // the pre pass of the first timestep (later ones: the H blocks)
   for (int n = 0; n < nsteps;) {
     p2p_prime_if_needed(c);
     int chunk = 1;
@@ -1096,7 +1166,7 @@ static int step_loop_wf(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     }
     if (pe) { c->kev0 = pe->e0[launches]; c->kev1 = pe->e1[launches]; }
     if (calibrate && n + chunk == nsteps && chunk == 1) { int ra = xcd_stamp_arm(c, s); if (ra) return ra; }
-    int r = launch_step_wf(c, c->step, s, chunk);
+    int r = launch_step_wf(c, c->step, s, chunk, pl.lag);
     c->kev0 = c->kev1 = nullptr;
     if (r) return r;
     c->step += chunk;
@@ -1105,7 +1175,7 @@ static int step_loop_wf(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     ++launches;
   }
   if (pe) pe->launches = launches;
-  if (c->wf_mur && nsteps > 0) c->mur_pre_step = c->step;
+  if (c->any_mur && nsteps > 0) c->mur_pre_step = c->step;
   HIPCK(c, hipGetLastError());
   return launch_status(c);
 }
@@ -1127,59 +1197,8 @@ static int wf_check(fdtd_ctx* c) {
   return FDTD_OK;
 }
 
-static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
-  const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (c->sheet_n > 0) {
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: the two-launch schedule only (their correction runs between the E phase and the H update)");
-    if (c->d.world > 1 || c->p.p2p) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: single slab only (world = 1)");
-  }
-  if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
-    const char* why = "";
-    if (!res_possible(c, &why)) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: %s", why);
-    if (!sources_fusable(c)) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: a source edge lies on or next to a Mur face");
-  }
-  if (sel > FDTD_FLAG_KERNEL_DIRECT && sel != FDTD_FLAG_KERNEL_WAVEFRONT && sel != FDTD_FLAG_KERNEL_RESIDENT)
-    return fdtd_fail(c, FDTD_E_UNSUPPORTED, "kernel selection %u: the one-pass variants were removed (measured slower than the two-pass kernels on every workload)", sel);
-  if (sel == FDTD_FLAG_KERNEL_WAVEFRONT && !wavefront_possible(c))
-    return fdtd_fail(c, FDTD_E_UNSUPPORTED, "wavefront schedule: single slab or slabs on the p2p mailbox transport, at least 2 planes, rows of at most %d cells; with Mur faces a single slab within the Infinity Cache, no source edge, voltage probe or NF2FF box on or next to a face", 30 * FDTD_BLOCK * 4);
-  if (c->p.p2p) return step_loop_p2p(c, nsteps, pe);
-  const bool multi = c->d.world > 1;
-  if (resident_active(c)) return step_loop_res(c, nsteps, pe);
-  if (multi && !c->comm) return fdtd_fail(c, FDTD_E_STATE, "world > 1: call fdtd_p2p_attach (mailbox transport), fdtd_comm_init (RCCL), fdtd_link + fdtd_run_linked, or drive fdtd_half_step + fdtd_halo_*");
-  if (wavefront_active(c)) return step_loop_wf(c, nsteps, pe);
-  const bool fused = sources_fusable(c);
-  if (multi && c->step == 0 && !c->p2p_primed) {   // the H halo of "step -1": the initial fields (runs from non-zero fields decompose too)
-    int r = exchange(c, FDTD_HALO_H_UP);
-    if (r) return r;
-    c->p2p_primed = true;
-  }
-  const bool direct = mur_direct_possible(c, multi, fused);
-  for (int n = 0; n < nsteps; ++n) {
-    c->mur_direct = direct;
-    int r = phase_E(c, multi, fused, pe, n);
-    if (r) return r;
-    launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
-    if (multi && (r = exchange(c, FDTD_HALO_E_DOWN))) return r;
-    if ((r = phase_H(c, multi, fused, pe, n))) return r;
-    if (multi && (r = exchange(c, FDTD_HALO_H_UP))) return r;
-    c->step++;
-  }
-  c->mur_direct = false;
-  if (fused && nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);   // flush the last step's I-probes
-  HIPCK(c, hipGetLastError());
-  return launch_status(c);
-}
-
-// P2P mailbox transport: the halos travel inside the update kernels, so a step is two launches on ONE stream —
-// no communication stream, no events, no RCCL call; neighbouring ranks couple only through the mailbox flags.
-// p2p transport, before the first timestep: the halo of "step -1" = the INITIAL Ix, Iy of this slab's top plane goes up
-static void p2p_prime_if_needed(fdtd_ctx* c) {
-  if (!c->p.p2p || c->step != 0 || c->p2p_primed) return;
-  hipSetDevice(c->d.device);
-  launch_p2p_prime(c, c->stream);
-  c->p2p_primed = true;
-}
+// P2P mailbox transport, two launches per timestep: the halos travel inside the update kernels, so a step is two launches on ONE
+// stream — no communication stream, no events, no RCCL call; neighbouring ranks couple only through the mailbox flags.
 static int p2p_enqueue_E(fdtd_ctx* c, ProfEvents* pe, int n) {
   HIPCK(c, hipSetDevice(c->d.device));
   p2p_prime_if_needed(c);
@@ -1197,18 +1216,7 @@ static int p2p_enqueue_H(fdtd_ctx* c, ProfEvents* pe, int n) {
   launch_dft(c, FDTD_KIND_I, c->step, c->stream);
   return FDTD_OK;
 }
-static bool wavefront_active(const fdtd_ctx* c);
-static int step_loop_wf(fdtd_ctx* c, int nsteps, ProfEvents* pe);
 static int step_loop_p2p(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
-  if (c->any_mur || c->d.nk < 2) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "p2p transport: needs >= 2 planes per slab and no Mur faces");
-  if (!c->p.src_dense_ok && c->src_max_per_strip_plane > FDTD_BLOCK) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "p2p transport: more than %d source edges in one strip-plane with several sources on one edge", FDTD_BLOCK);
-  const bool one_launch = wavefront_active(c);
-  // a neighbour's slab on THIS device (ranks sharing a GPU): all `world` slabs may be here, under this slab's schedule — the bound above
-  if (!(c->d.flags & FDTD_FLAG_LOOPBACK) && (c->link_info[0][7] == 1 || c->link_info[1][7] == 1)) {
-    const unsigned pinned = (unsigned)c->d.world * p2p_pinned_blocks(c, one_launch);
-    if (pinned >= chip_slots(c)) return p2p_shared_device_refuse(c, pinned, (unsigned)c->d.world);
-  }
-  if (one_launch) return step_loop_wf(c, nsteps, pe);   // one launch per timestep, halos inside it as well
   for (int n = 0; n < nsteps; ++n) {
     int r;
     if ((r = p2p_enqueue_E(c, pe, n)) || (r = p2p_enqueue_H(c, pe, n))) return r;
@@ -1218,6 +1226,33 @@ static int step_loop_p2p(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
   HIPCK(c, hipGetLastError());
   return launch_status(c);
 }
+
+static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
+  StepPlan pl;
+  int r = plan_schedule(c, false, &pl);
+  if (r) return r;
+  if (pl.kind == StepPlan::RESIDENT) return step_loop_res(c, pl, nsteps, pe);
+  if (pl.kind == StepPlan::ONE_LAUNCH) return step_loop_wf(c, pl, nsteps, pe);
+  if (c->p.p2p) return step_loop_p2p(c, nsteps, pe);
+  const bool multi = c->d.world > 1;
+  if (multi && c->step == 0 && !c->p2p_primed) {   // the H halo of "step -1": the initial fields (runs from non-zero fields decompose too)
+    if ((r = exchange(c, FDTD_HALO_H_UP, pl.rccl_inline))) return r;
+    c->p2p_primed = true;
+  }
+  for (int n = 0; n < nsteps; ++n) {
+    if ((r = phase_E(c, pl, pe, n))) return r;
+    launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
+    if (multi && (r = exchange(c, FDTD_HALO_E_DOWN, pl.rccl_inline))) return r;
+    if ((r = phase_H(c, pl, pe, n))) return r;
+    if (multi && (r = exchange(c, FDTD_HALO_H_UP, pl.rccl_inline))) return r;
+    c->step++;
+  }
+  if (pl.fused && nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);   // flush the last step's I-probes
+  HIPCK(c, hipGetLastError());
+  return launch_status(c);
+}
+
+static int p2p_check(fdtd_ctx* c);
 
 int fdtd_run(fdtd_ctx* c, int nsteps) {
   int r = check_ready(c);
@@ -1673,19 +1708,21 @@ int fdtd_schedule_info(fdtd_ctx* c, int32_t info[8]) {
   if (!c || !info) return fdtd_fail(c, FDTD_E_ARG, "null argument");
   for (int q = 0; q < 8; ++q) info[q] = 0;
   const bool multi = c->d.world > 1;
-  const bool steppable = c->have_op && (!multi || c->p.p2p || c->comm || c->link_lo || c->link_hi);
-  const bool res = steppable && resident_active(c);
-  const bool wf = steppable && !res && wavefront_active(c);
-  info[0] = !steppable ? 0 : res ? 1 : wf ? 1 : !c->any_mur ? 2 : mur_direct_possible(c, multi, sources_fusable(c)) ? 2 : (sources_fusable(c) && !multi && c->mur_fuse_post) ? 3 : 5;
-  info[1] = res ? -1 : wf ? wf_lag_for(c) : 0;
+  StepPlan pl;   // (a context that cannot step reports 0 launches; the refusal is not this call's error)
+  const std::string err = c->err;
+  if (c->have_op) plan_schedule(c, true, &pl);
+  c->err = err;
+  const bool res = pl.kind == StepPlan::RESIDENT, wf = pl.kind == StepPlan::ONE_LAUNCH;
+  info[0] = res || wf ? 1 : pl.kind != StepPlan::TWO_LAUNCH ? 0 : pl.mur == MUR_POST_IN_E ? 3 : pl.mur == MUR_PASSES ? 5 : 2;
+  info[1] = res ? -1 : wf ? pl.lag : 0;
   info[2] = c->p.tys;
   info[3] = c->d.nk * c->p.nstrips * c->p.nbs;
   info[4] = !multi ? 0 : c->p.p2p ? 1 : c->comm ? 2 : (c->link_lo || c->link_hi) ? 3 : 4;
   info[5] = (c->xcd_balance && c->have_cpml) ? 1 : 0;
   info[6] = c->xcd_adapt_done;
-  info[7] = res ? c->res_chunk : wf ? wf_multi_max(c) : 0;
+  info[7] = res || wf ? pl.multi_max : 0;
   if (res) {   // tiles instead of strip blocks
-    if (res_prepare(c, c->res_chunk) == FDTD_OK) { info[2] = c->res.nstrips; info[3] = c->res.nblocks; }
+    if (res_prepare(c, pl.multi_max) == FDTD_OK) { info[2] = c->res.nstrips; info[3] = c->res.nblocks; }
   }
   return FDTD_OK;
 }
@@ -1726,9 +1763,17 @@ int fdtd_run_linked(fdtd_ctx** ctxs, int n, int nsteps) {
     if (c->d.world != n || c->d.rank != r || c->comm) return fdtd_fail(c, FDTD_E_ARG, "fdtd_run_linked: contexts must be ranks 0..n-1 of a world of n without an RCCL communicator");
     if (!c->p.p2p && ((r > 0 && c->link_lo != ctxs[r - 1]) || (r < n - 1 && c->link_hi != ctxs[r + 1]))) return fdtd_fail(c, FDTD_E_STATE, "fdtd_run_linked: call fdtd_link (or fdtd_p2p_attach) on every adjacent pair first");
   }
-  const bool multi = n > 1 || (ctxs[0]->d.flags & FDTD_FLAG_LOOPBACK);
+  if (n == 1 && ctxs[0]->d.world == 1) return fdtd_run(ctxs[0], nsteps);   // a single slab: nothing to link
+  std::vector<StepPlan> plan((size_t)n);
   if (ctxs[0]->p.p2p) {   // mailbox transport between contexts of this process: interleave the ranks' launches
     for (int r = 0; r < n; ++r) if (!ctxs[r]->p.p2p || ctxs[r]->any_mur) return fdtd_fail(ctxs[r], FDTD_E_STATE, "fdtd_run_linked: every context must use the p2p transport (no Mur)");
+    for (int r = 0; r < n; ++r) if (int rc = plan_schedule(ctxs[r], true, &plan[r])) return rc;
+    // slabs of this process that share a device: the starvation-freedom bound (p2p_shared_device_ok), with every slab's own schedule
+    for (int r = 0; r < n; ++r) {
+      unsigned pinned = 0, slabs = 0;
+      for (int q = 0; q < n; ++q) if (ctxs[q]->d.device == ctxs[r]->d.device) { pinned += plan[q].pinned; ++slabs; }
+      if (slabs > 1) if (int rc = p2p_shared_device_ok(ctxs[r], pinned, slabs, plan[r].slots)) return rc;
+    }
     for (int r = 0; r < n; ++r) p2p_prime_if_needed(ctxs[r]);   // every rank's initial halo is on its way before any rank's first launch
     // Slabs of different size may step under different schedules (AUTO: one launch per timestep only above a block count).
     // Submission order of a timestep, TOP rank first: the one launch of a one-launch slab / the E launch of a two-launch
@@ -1737,22 +1782,15 @@ int fdtd_run_linked(fdtd_ctx** ctxs, int n, int nsteps) {
     // submitted EARLIER: H of a slab's top plane (inside its one launch, or its H launch) needs the E blocks of plane 0 of
     // the rank above for the SAME step — submitted before it in the first pass; E of plane 0 needs the H halo of the rank
     // below of the PREVIOUS step.  (Bottom rank first timed out in exactly that way.)
-    std::vector<char> wf((size_t)n);
-    for (int r = 0; r < n; ++r) wf[r] = wavefront_active(ctxs[r]) ? 1 : 0;
-    // slabs of this process that share a device: the starvation-freedom bound (p2p_pinned_blocks), with every slab's own schedule
-    for (int r = 0; r < n; ++r) {
-      unsigned pinned = 0, slabs = 0;
-      for (int q = 0; q < n; ++q) if (ctxs[q]->d.device == ctxs[r]->d.device) { pinned += p2p_pinned_blocks(ctxs[q], wf[q] != 0); ++slabs; }
-      if (slabs > 1 && pinned >= chip_slots(ctxs[r])) return p2p_shared_device_refuse(ctxs[r], pinned, slabs);
-    }
+    auto one = [&](int r) { return plan[r].kind == StepPlan::ONE_LAUNCH; };
     for (int s = 0; s < nsteps; ++s) {
       int rc;
-      for (int r = n - 1; r >= 0; --r) { if ((rc = wf[r] ? step_loop_wf(ctxs[r], 1, nullptr) : p2p_enqueue_E(ctxs[r], nullptr, 0))) return rc; }
-      for (int r = 0; r < n; ++r) if (!wf[r]) { if ((rc = p2p_enqueue_H(ctxs[r], nullptr, 0))) return rc; ctxs[r]->step++; }
+      for (int r = n - 1; r >= 0; --r) { if ((rc = one(r) ? step_loop_wf(ctxs[r], plan[r], 1, nullptr) : p2p_enqueue_E(ctxs[r], nullptr, 0))) return rc; }
+      for (int r = 0; r < n; ++r) if (!one(r)) { if ((rc = p2p_enqueue_H(ctxs[r], nullptr, 0))) return rc; ctxs[r]->step++; }
     }
     for (int r = 0; r < n; ++r) {
       fdtd_ctx* c = ctxs[r];
-      if (wf[r]) continue;
+      if (one(r)) continue;
       HIPCK(c, hipSetDevice(c->d.device));
       if (nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);
     }
@@ -1767,26 +1805,27 @@ int fdtd_run_linked(fdtd_ctx** ctxs, int n, int nsteps) {
     }
     return FDTD_OK;
   }
-  if (multi)   // the H halo of "step -1": the initial fields
-    for (int r = 0; r < n; ++r) {
-      fdtd_ctx* c = ctxs[r];
-      if (c->step != 0 || c->p2p_primed) continue;
-      int rc = exchange(c, FDTD_HALO_H_UP);
-      if (rc) return rc;
-      c->haloH_issued = true; c->p2p_primed = true;
-    }
+  // event-ordered peer copies: two launches per timestep on every slab
+  for (int r = 0; r < n; ++r) if (int rc = plan_schedule(ctxs[r], true, &plan[r])) return rc;
+  for (int r = 0; r < n; ++r) {   // the H halo of "step -1": the initial fields
+    fdtd_ctx* c = ctxs[r];
+    if (c->step != 0 || c->p2p_primed) continue;
+    int rc = exchange(c, FDTD_HALO_H_UP, plan[r].rccl_inline);
+    if (rc) return rc;
+    c->haloH_issued = true; c->p2p_primed = true;
+  }
   for (int s = 0; s < nsteps; ++s) {
     int rc;
-    for (int r = 0; r < n; ++r) if ((rc = phase_E(ctxs[r], multi, sources_fusable(ctxs[r]), nullptr, 0))) return rc;
-    if (multi) for (int r = 0; r < n; ++r) { if ((rc = exchange(ctxs[r], FDTD_HALO_E_DOWN))) return rc; ctxs[r]->haloE_issued = true; }
-    for (int r = 0; r < n; ++r) if ((rc = phase_H(ctxs[r], multi, sources_fusable(ctxs[r]), nullptr, 0))) return rc;
-    if (multi) for (int r = 0; r < n; ++r) { if ((rc = exchange(ctxs[r], FDTD_HALO_H_UP))) return rc; ctxs[r]->haloH_issued = true; }
+    for (int r = 0; r < n; ++r) if ((rc = phase_E(ctxs[r], plan[r], nullptr, 0))) return rc;
+    for (int r = 0; r < n; ++r) { if ((rc = exchange(ctxs[r], FDTD_HALO_E_DOWN, plan[r].rccl_inline))) return rc; ctxs[r]->haloE_issued = true; }
+    for (int r = 0; r < n; ++r) if ((rc = phase_H(ctxs[r], plan[r], nullptr, 0))) return rc;
+    for (int r = 0; r < n; ++r) { if ((rc = exchange(ctxs[r], FDTD_HALO_H_UP, plan[r].rccl_inline))) return rc; ctxs[r]->haloH_issued = true; }
     for (int r = 0; r < n; ++r) ctxs[r]->step++;
   }
   for (int r = 0; r < n; ++r) {
     fdtd_ctx* c = ctxs[r];
     HIPCK(c, hipSetDevice(c->d.device));
-    if (sources_fusable(c) && nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);
+    if (plan[r].fused && nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);
     HIPCK(c, hipGetLastError());
   }
   for (int r = 0; r < n; ++r) {

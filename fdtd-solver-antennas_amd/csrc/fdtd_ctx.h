@@ -217,11 +217,7 @@ struct fdtd_ctx {
   bool any_mur = false;
   MurH h_murh{};
   MurDev h_mur{}; MurDev* d_mur = nullptr;   // face table (built by fdtd_set_mur), host and device copy
-  bool mur_fuse_post = true;                 // allow it ($FDTD_MUR_UNFUSED clears)
-  bool mur_post_in_E = false;                // this launch of update_E runs the Mur post pass as well (set by phase_E)
   bool mur_no_apply = true;                  // allow the schedule without an apply pass ($FDTD_MUR_APPLY_PASS=1 clears): api.hip mur_direct_possible
-  bool mur_direct = false;                   // this timestep: update_H reads the candidates itself and stores them (no k_mur apply launch)
-  bool wf_mur = false;                       // this one-launch run carries Mur faces (k_step<..., MUR>; api.hip step_loop_wf)
   int64_t mur_pre_step = -1;                 // step whose Mur pre pass has already run (inside the previous update_H launch)
   // excitation
   float* sig = nullptr; int nsig = 0;
@@ -270,14 +266,21 @@ int fdtd_fail(fdtd_ctx* c, int code, const char* fmt, ...);
       return fdtd_fail(c, FDTD_E_DEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// Where the Mur passes of a two-launch timestep run (api.hip plan_schedule decides): NONE without Mur faces; DIRECT: the post pass
+// inside update_E, no apply pass, update_H reads the candidates itself; POST_IN_E: the post pass inside update_E, the apply pass a
+// launch of its own; PASSES: post and apply as launches of their own.  Except under NONE, update_H with fused sources carries the
+// pre pass of the next timestep.
+enum MurStep { MUR_NONE, MUR_DIRECT, MUR_POST_IN_E, MUR_PASSES };
+
 // kernels.hip
 // `fused`: sources injected inside update_E; `probe_block`: one extra block samples the probes
 // (update_E: I-probes of step-1, update_H: V-probes of step) so a step is exactly two launches.
 int upload_metric_tables(fdtd_ctx* c, const float* emet, const float* hmet);
-void launch_update_E(fdtd_ctx* c, int k_begin, int k_end, long long step, bool fused, bool probe_block, hipStream_t s);
-void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, bool mur_pre = false);
-// one launch = E and H half-step of all planes (single slab, no Mur, fusable sources); probes are sampled by launch_probes
-int launch_step_wf(fdtd_ctx* c, long long step, hipStream_t s, int nsteps = 1);   // nsteps > 1: that many timesteps in ONE launch
+void launch_update_E(fdtd_ctx* c, int k_begin, int k_end, long long step, bool fused, bool probe_block, hipStream_t s, bool mur_post = false);
+void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, MurStep mur = MUR_NONE);
+// one launch = E and H half-step of all planes (single slab or p2p slab, fusable sources; Mur faces where the planner admits them);
+// nsteps > 1: that many timesteps in ONE launch; lag: wf_lag_for
+int launch_step_wf(fdtd_ctx* c, long long step, hipStream_t s, int nsteps, int lag);
 int wf_multi_max(const fdtd_ctx* c);   // timesteps one launch may hold (1: this context steps one timestep per launch)
 int wf_lag_for(const fdtd_ctx* c);
 void launch_p2p_prime(fdtd_ctx* c, hipStream_t s);   // p2p transport, before step 0: initial Ix, Iy of the top plane -> upper rank's mailbox

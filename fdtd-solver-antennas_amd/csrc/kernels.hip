@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <mutex>
 #include <vector>
 
 #include "kernel_common.hpp"
@@ -1235,8 +1236,10 @@ int xcd_adapt(fdtd_ctx* c) {
 // What the launchers need to know about the chip, asked of the runtime once per device (round 3 hard-coded 256 CUs and 160 KiB: wrong on a
 // partitioned gfx950 — CPX / DPX logical devices of 32 / 128 CUs — and one __shared__ edit away from an over-sized launch).
 struct ChipInfo { int cus = 256; unsigned lds_cu = 163840u, lds_block = 65536u; bool ok = false; };
-static const ChipInfo& chip_info(int device) {
+static const ChipInfo& chip_info(int device) {   // (any ABI entry point may ask, from any host thread: ctypes releases the GIL)
+  static std::mutex mu;
   static ChipInfo info[64];
+  std::lock_guard<std::mutex> lk(mu);
   ChipInfo& ci = info[device & 63];
   if (!ci.ok) {
     hipDeviceProp_t prop;
@@ -1253,7 +1256,9 @@ static const ChipInfo& chip_info(int device) {
 int chip_cus(int device) { return chip_info(device).cus; }
 // static LDS of a kernel as compiled (hipFuncGetAttributes), cached per kernel; ~0u: the runtime would not say
 static unsigned static_lds_of(const void* fn) {
+  static std::mutex mu;
   static std::map<const void*, unsigned> cache;
+  std::lock_guard<std::mutex> lk(mu);
   auto it = cache.find(fn);
   if (it != cache.end()) return it->second;
   hipFuncAttributes at;
@@ -1299,7 +1304,7 @@ static void launch_main(fdtd_ctx* c, K kern, dim3 grid, unsigned dyn, int cap, h
 }
 
 template <int COEF, bool PML>
-static void launch_E2(fdtd_ctx* c, int k_begin, int nkr, long long step, bool fused, int extra, hipStream_t s) {
+static void launch_E2(fdtd_ctx* c, int k_begin, int nkr, long long step, bool fused, bool mur_post, int extra, hipStream_t s) {
   const unsigned lut_bytes = (unsigned)(c->raw_op ? 0 : (c->p.lut_n + 1) / 2) * 16u;   // dynamic LDS: the coefficient table, whole 16-byte LDS-DMA pieces
   const unsigned pad = lut_bytes;
   const int cap = c->occ_e;
@@ -1314,7 +1319,7 @@ static void launch_E2(fdtd_ctx* c, int k_begin, int nkr, long long step, bool fu
   set_xcd_shares(c, k_begin, nkr);
   const dim3 grid(c->p.xgrid + (unsigned)extra);
   const FastDiv fd_ps = make_fastdiv((unsigned)nkr * (unsigned)c->p.nbs);
-  if (fused && c->mur_post_in_E) {
+  if (fused && mur_post) {
     launch_main(c, k_update_E_mur<COEF, PML>, grid, pad, cap, s, c->p, k_begin, fd_ps, step, extra, c->h_mur);
     return;
   }
@@ -1322,19 +1327,19 @@ static void launch_E2(fdtd_ctx* c, int k_begin, int nkr, long long step, bool fu
   else launch_main(c, k_update_E<COEF, PML, false, false>, grid, pad, cap, s, c->p, k_begin, fd_ps, step, 0, 0u);
 }
 
-void launch_update_E(fdtd_ctx* c, int k_begin, int k_end, long long step, bool fused, bool probe_block, hipStream_t s) {
+void launch_update_E(fdtd_ctx* c, int k_begin, int k_end, long long step, bool fused, bool probe_block, hipStream_t s, bool mur_post) {
   const int nkr = k_end - k_begin;
   if (nkr <= 0) return;
   const int extra = (fused && probe_block) ? c->nprobe : 0;   // one block per probe (those of the other kind leave at once)
   const int coef = c->raw_op ? 0 : (c->packed_op ? 2 : 1);
   if (c->have_cpml) {
-    if (coef == 0) launch_E2<0, true>(c, k_begin, nkr, step, fused, extra, s);
-    else if (coef == 1) launch_E2<1, true>(c, k_begin, nkr, step, fused, extra, s);
-    else launch_E2<2, true>(c, k_begin, nkr, step, fused, extra, s);
+    if (coef == 0) launch_E2<0, true>(c, k_begin, nkr, step, fused, mur_post, extra, s);
+    else if (coef == 1) launch_E2<1, true>(c, k_begin, nkr, step, fused, mur_post, extra, s);
+    else launch_E2<2, true>(c, k_begin, nkr, step, fused, mur_post, extra, s);
   } else {
-    if (coef == 0) launch_E2<0, false>(c, k_begin, nkr, step, fused, extra, s);
-    else if (coef == 1) launch_E2<1, false>(c, k_begin, nkr, step, fused, extra, s);
-    else launch_E2<2, false>(c, k_begin, nkr, step, fused, extra, s);
+    if (coef == 0) launch_E2<0, false>(c, k_begin, nkr, step, fused, mur_post, extra, s);
+    else if (coef == 1) launch_E2<1, false>(c, k_begin, nkr, step, fused, mur_post, extra, s);
+    else launch_E2<2, false>(c, k_begin, nkr, step, fused, mur_post, extra, s);
   }
 }
 
@@ -1357,14 +1362,15 @@ static void launch_H2(fdtd_ctx* c, int k_begin, int nkr, long long step, int ext
   else launch_main(c, k_update_H<RAW, PML, false>, grid, pad, cap, s, c->p, k_begin, fd_ps, step, extra, 0u, c->h_murh);
 }
 
-void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, bool mur_pre) {
+void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, MurStep mur) {
   const int nkr = k_end - k_begin;
   if (nkr <= 0) return;
   // extra blocks behind the main ones: [Mur pre pass of the next step (12 rows of mur_nbx blocks)] [probe block]; the Mur
-  // blocks only ride along when the probe block does (the kernel tells them apart by their distance from the end)
-  c->p.mur_nb = (mur_pre && probe_block && c->any_mur && c->d_mur) ? 12 * c->p.mur_nbx : 0;
-  c->p.mur_direct = (c->mur_direct && c->p.mur_nb > 0) ? 1 : 0;   // (phase_E skipped the apply launch on the same condition)
-  if (c->p.mur_direct) c->p.mur_nb = 0;                           // no apply pass: the main blocks store boundary voltages and st themselves
+  // blocks only ride along when the probe block does (the kernel tells them apart by their distance from the end).  MUR_DIRECT:
+  // no apply pass ran — the main blocks take the candidates, store boundary voltages and st themselves, no extra Mur blocks
+  const bool pre = mur != MUR_NONE && probe_block && c->any_mur && c->d_mur;
+  c->p.mur_direct = (pre && mur == MUR_DIRECT) ? 1 : 0;
+  c->p.mur_nb = (pre && mur != MUR_DIRECT) ? 12 * c->p.mur_nbx : 0;
   const int extra = (probe_block ? c->nprobe : 0) + c->p.mur_nb;
   if (c->raw_op) {
     if (c->have_cpml) launch_H2<true, true>(c, k_begin, nkr, step, extra, s);
@@ -1423,7 +1429,7 @@ static void launch_step3(fdtd_ctx* c, long long step, int lag, hipStream_t s, in
         if (cap < FDTD_WF_MINBLOCKS) cap_m = cap;
       }
       if constexpr (!P2P) {
-        if (c->wf_mur)
+        if (c->any_mur)   // k_step<..., MUR>: the planner (api.hip plan_schedule) admits Mur faces only where it can carry them
           launch_main(c, k_step<COEF, PML, false, true, true>, dim3(per * (unsigned)nsteps), pad, cap_m, s, c->p, step, -1, c->wf_epoch - (unsigned)(nsteps - 1), nbp,
                       make_fastdiv((unsigned)c->p.nk * (unsigned)c->p.nbs), 0, 2u * nE, make_fastdiv(per), c->h_mur, c->h_murh);
         else
@@ -1433,7 +1439,7 @@ static void launch_step3(fdtd_ctx* c, long long step, int lag, hipStream_t s, in
       return;
     }
     if constexpr (!P2P) {
-      if (c->wf_mur) {
+      if (c->any_mur) {
         launch_main(c, k_step<COEF, PML, false, false, true>, dim3(2u * nE + (unsigned)c->nprobe), pad, c->occ_wf, s, c->p, step, -1, c->wf_epoch, nbp,
                     make_fastdiv((unsigned)c->p.nk * (unsigned)c->p.nbs), down, 2u * nE, make_fastdiv(1u), c->h_mur, c->h_murh);
         c->p.xstamp = nullptr;
@@ -1506,7 +1512,7 @@ int wf_multi_max(const fdtd_ctx* c) {
   return (int)std::max(1ull, std::min<unsigned long long>((unsigned long long)c->wf_multi, fit));
 }
 
-int launch_step_wf(fdtd_ctx* c, long long step, hipStream_t s, int nsteps) {
+int launch_step_wf(fdtd_ctx* c, long long step, hipStream_t s, int nsteps, int lag) {
   const size_t nflags = (size_t)c->p.nk * c->p.nstrips * c->p.nbs;
   if (!c->wf_flags || c->wf_nflags != nflags) {   // first use (or a new tiling): flags start at 0, the epoch counts the launches
     if (c->wf_flags) hipFree(c->wf_flags);
@@ -1529,9 +1535,7 @@ int launch_step_wf(fdtd_ctx* c, long long step, hipStream_t s, int nsteps) {
   c->p.wf_wait_bias = 0u;
   if (c->wf_fault_step >= step && c->wf_fault_step < step + nsteps) { c->p.wf_wait_bias = 1u; c->p.wf_limit = 2000ull; }   // test hook: a flag value nobody publishes, 20 us
   if (2 * (1 + c->p.P4 / FDTD_BLOCK) + 3 > 64) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "wavefront schedule: rows of more than %d cells", 30 * FDTD_BLOCK * 4);
-  if (nsteps > 1 && nsteps > wf_multi_max(c)) return fdtd_fail(c, FDTD_E_ARG, "%d timesteps in one launch: at most %d here", nsteps, wf_multi_max(c));
-  c->wf_epoch += (unsigned)nsteps;      // the flag value of the launch's LAST timestep
-  const int lag = wf_lag_for(c);
+  c->wf_epoch += (unsigned)nsteps;      // the flag value of the launch's LAST timestep (nsteps: at most wf_multi_max, the planner's)
   const int coef = c->raw_op ? 0 : (c->packed_op ? 2 : 1);
   if (c->have_cpml) {
     if (coef == 0) launch_step2<0, true>(c, step, lag, s, nsteps);

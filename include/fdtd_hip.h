@@ -70,7 +70,10 @@ enum { FDTD_HALO_H_UP = 0, FDTD_HALO_E_DOWN = 1 };   /* Ix,Iy top plane -> rank+
 
 /* Kernel selection (fdtd_desc.flags). */
 enum {
-  FDTD_FLAG_KERNEL_AUTO   = 0,   /* the schedule measured faster (fdtd_schedule_info tells which one a context took).  One launch per
+  FDTD_FLAG_KERNEL_AUTO   = 0,   /* the schedule measured faster (fdtd_schedule_info tells which one a context took).  First the grid
+                                    resident in registers (RESIDENT below) where it is possible: for a slab with Mur faces whenever its
+                                    tiles fit the chip, for a PEC / CPML slab while it has at most 2 tiles per CU ($FDTD_RESIDENT=0:
+                                    never, also under an explicit RESIDENT).  Else one launch per
                                     timestep (WAVEFRONT below) where it is possible — at least 2 planes, rows of at most
                                     30 720 cells — AND: on a single slab, when the fields exceed the 256 MiB Infinity Cache, or the slab
                                     has CPML layers, or a sweep has >= 1700 blocks of 1024 cells (Mur faces: single slabs within the cache); on a slab of a decomposed grid (p2p
@@ -98,9 +101,11 @@ enum {
                                     (1-2 planes x a few rows x all of x), keeps its fields and coefficients in registers over up to 256
                                     timesteps (cut at the timesteps whose NF2FF faces are sampled) and exchanges tile halos as data-tagged
                                     granules through a device-scope buffer — one ~1 us hop per half-step instead of a kernel boundary.
-                                    Single slab, PEC / Mur faces (no CPML layers), rows of at most 1024 cells (256 with Mur z faces), no
+                                    Single slab of at least 6 x 5 x 5 nodes, PEC / Mur faces / CPML layers (the psi of a tile in registers as
+                                    well), rows of at most 1024 cells (256 with Mur z faces), no source edge on or next to a Mur face, no
                                     more tiles than the chip holds resident workgroups (else FDTD_E_UNSUPPORTED).  AUTO takes it for
-                                    every such slab with Mur faces: the reference GUI's default scenes.  Results identical bit for bit. */
+                                    every such slab with Mur faces (the reference GUI's default scenes), and for PEC / CPML slabs of at
+                                    most 2 tiles per CU.  Results identical bit for bit. */
   FDTD_FLAG_KERNEL_MASK   = 0xF,
   FDTD_FLAG_OVERLAP_ON    = 0x20, /* multi-slab: split sweeps into interior + halo-dependent plane (the default) */
   FDTD_FLAG_OVERLAP_OFF   = 0x40, /* multi-slab: one launch per sweep, after the halo has arrived */
@@ -237,8 +242,10 @@ int fdtd_run(fdtd_ctx* ctx, int nsteps);
 int fdtd_run_profiled(fdtd_ctx* ctx, int nsteps, fdtd_profile* out);
 int fdtd_get_step(fdtd_ctx* ctx, int64_t* step);
 /* The step schedule this context runs under its current flags, boundaries and transport:
- *   info[0] main-kernel launches per timestep (1: k_step, 2: update_E + update_H, 3: with Mur faces; 0: driven by
- *           fdtd_half_step / not steppable yet)
+ *   info[0] main-kernel launches per timestep (1: k_step or the resident schedule, 2: update_E + update_H (Mur faces: the post
+ *           pass inside update_E, update_H reads the candidates), 3: Mur faces with the apply pass as a launch of its own, 5: Mur faces
+ *           with the post and apply passes as launches of their own (several slabs, or a source edge on or next to a face);
+ *           0: driven by fdtd_half_step / not steppable (yet): no transport, or fdtd_run would refuse the selection)
  *   info[1] one launch per timestep only: planes the E sweep runs ahead of the H sweep (== nk: all E blocks, then all H blocks);
  *           -1: the resident schedule (FDTD_FLAG_KERNEL_RESIDENT: info[0] = 1, info[2] = strips, info[3] = tiles = workgroups,
  *           info[7] = timesteps one launch may hold)

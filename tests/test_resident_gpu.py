@@ -1,5 +1,5 @@
-"""The resident schedule (csrc/resident.hip, FDTD_FLAG_KERNEL_RESIDENT): small grids without CPML layers stepped with the whole grid
-in registers, tile halos as data-tagged granules.  HIP vs the oracle through the C ABI, fields bit for bit; and against the
+"""The resident schedule (csrc/resident.hip, FDTD_FLAG_KERNEL_RESIDENT): small grids (PEC, Mur faces or CPML layers) stepped with the whole
+grid in registers, tile halos as data-tagged granules.  HIP vs the oracle through the C ABI, fields bit for bit; and against the
 two-launch schedule of the HIP library itself (probe series and NF2FF spectra identical: same reduction trees)."""
 import numpy as np
 import pytest

@@ -229,6 +229,34 @@ def test_schedule_info_tells_the_schedule(hip_lib, monkeypatch):
     monkeypatch.setenv("FDTD_RESIDENT", "0")
     s = patch_sim(48, 44, 30, boundary="PEC", nr_ts=10)
     assert s.build(hip_lib).schedule_info()["launches_per_timestep"] == 2     # small grid without CPML: two launches
+    # the report is the schedule the step loop runs: one launch per timestep as the profiled run counts it ...
+    e = patch_sim(64, 60, 36, nr_ts=10).build(hip_lib)
+    prof = e.run_profiled(4)
+    assert e.schedule_info()["launches_per_timestep"] == 1 and prof.fused == 1 and 1 <= prof.launches_e <= 4
+    # ... a voltage probe on a Mur face keeps the apply pass (the post pass rides in update_E: three launches) ...
+    s = patch_sim(48, 44, 30, boundary="MUR", nr_ts=10)
+    e = s.build(hip_lib)
+    e.add_probe(capi.KIND_V, [(15 * 44 + 20) * 48], [1], [1.0])     # node (0, 20, 15): on the x-low face
+    assert e.schedule_info()["launches_per_timestep"] == 3 and e.run_profiled(4).fused == 0
+    # ... a grid 5 nodes wide cannot take the post pass inside update_E (E, post, apply, H: 5) ...
+    const, eco = pkg("constants"), pkg("ecoperator")
+    from opbuild_cases import random_scene
+    grid, eps, kap, pec, _ = random_scene(5, (5, 20, 18), False, 3, n_lumped=0, pec_frac=0.0)
+    dt = grid.courant_dt()
+    e = capi.Engine(hip_lib, *grid.shape, dt, max_steps=16)
+    emet, hmet = eco.pack_metric_tables(*eco.metric_lists(grid, dt), grid)
+    e.build_operator(grid.d, eps, kap, pec, const.EPS0, eco.lumped_overrides(grid, eps, kap, pec, dt, []), emet, hmet)
+    e.set_mur([1] * 6, [0.5] * 6)
+    assert e.schedule_info()["launches_per_timestep"] == 5 and e.run_profiled(4).fused == 0
+    # ... as do slabs with Mur faces linked in one process ...
+    engs = [patch_sim(48, 44, 30, boundary="MUR", nr_ts=10).build(hip_lib, rank=r, world=2) for r in range(2)]
+    capi.link(engs[0], engs[1])
+    assert [e.schedule_info()["launches_per_timestep"] for e in engs] == [5, 5] and engs[0].schedule_info()["transport"] == "linked"
+    # ... conducting sheets take two launches, and a selection the step loop refuses reports none
+    from test_sheet_model_cpu import cavity_sim
+    s = cavity_sim(3e5, 1e-3, nr_ts=10)
+    assert s.build(hip_lib).schedule_info()["launches_per_timestep"] == 2
+    assert s.build(hip_lib, flags=capi.FLAG_KERNEL_WAVEFRONT).schedule_info()["launches_per_timestep"] == 0
 
 
 def test_measured_xcd_shares_leave_the_results_alone(hip_lib, oracle_lib, monkeypatch):
