@@ -28,6 +28,10 @@ ABI_SYMBOLS = [
 # include/fdtd_hip_sheet.h: conducting sheets, exported by libfdtd_hip.so only (not part of ABI_SYMBOLS / FDTD_ABI_VERSION)
 SHEET_SYMBOLS = ["fdtd_sheet_set", "fdtd_sheet_get"]
 SHEET_MAX_K = 8
+# include/fdtd_hip_dispersion.h: Debye media, likewise
+DEBYE_SYMBOLS = ["fdtd_debye_set", "fdtd_debye_get"]
+DEBYE_MAX_K = 8
+DEBYE_MAX_MEDIA = 8
 
 
 class FdtdDesc(C.Structure):
@@ -116,7 +120,22 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    debye_sig = {
+        "fdtd_debye_set": (C.c_int, [p, C.c_int, C.c_int, p, p, p, p, p, p, p]),
+        "fdtd_debye_get": (C.c_int, [p, C.c_int, p, p, p]),
+    }
+    assert sorted(debye_sig) == sorted(DEBYE_SYMBOLS)
+    for name, (res, args) in debye_sig.items():     # optional, as the sheets' entry points are
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_dispersion(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the Debye-media entry points (include/fdtd_hip_dispersion.h)."""
+    return all(hasattr(lib, n) for n in DEBYE_SYMBOLS)
 
 
 def has_sheets(lib: C.CDLL) -> bool:
@@ -471,6 +490,42 @@ class Engine:
         ib = np.zeros((K, n), np.float32)
         self._ck(self.lib.fdtd_sheet_get(self._ctx, _ptr(v), _ptr(ib)), "sheet_get")
         return v, ib
+
+    # -- Debye media (include/fdtd_hip_dispersion.h) -------------------------------------------------
+    def _debye_lib(self):
+        if not has_dispersion(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no Debye media (fdtd_debye_set / fdtd_debye_get)")
+
+    def set_debye(self, alpha, oma, beta, lo, hi, w, med=None):
+        """Media tables alpha, oma = 1 - alpha, beta: float32 [nmedia][K]; per component c the box lo[c] <= (x, y, z) < hi[c] of
+        edges with the weights w[c] and medium ids med[c] over it, [z][y][x] (an empty box: the component has no dispersive edge)."""
+        self._debye_lib()
+        alpha, oma, beta = _arr(alpha, np.float32), _arr(oma, np.float32), _arr(beta, np.float32)
+        if alpha.ndim != 2 or alpha.shape != oma.shape or alpha.shape != beta.shape:
+            raise ValueError("Debye tables must be [nmedia][K]")
+        nmedia, K = alpha.shape
+        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
+        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
+        shapes = [tuple(int(max(0, hi_a[c, a] - lo_a[c, a])) for a in (2, 1, 0)) for c in range(3)]
+        ws = [_arr(np.zeros(shapes[c], np.float32) if 0 in shapes[c] else w[c], np.float32) for c in range(3)]
+        ms = [_arr(np.zeros(shapes[c], np.uint8) if (0 in shapes[c] or med is None) else med[c], np.uint8) for c in range(3)]
+        for c in range(3):
+            if ws[c].shape != shapes[c] or ms[c].shape != shapes[c]:
+                raise ValueError(f"Debye component {c}: weights / medium ids must be [z][y][x] over the box, {shapes[c]}")
+        wp = (C.c_void_p * 3)(*[x.ctypes.data for x in ws])
+        mp = (C.c_void_p * 3)(*[x.ctypes.data for x in ms])
+        self._ck(self.lib.fdtd_debye_set(self._ctx, int(nmedia), int(K), _ptr(alpha), _ptr(oma), _ptr(beta), _ptr(lo_a), _ptr(hi_a),
+                                         C.cast(wp, C.c_void_p), C.cast(mp, C.c_void_p)), "debye_set")
+        self.debye_K, self.debye_shapes = int(K), shapes
+
+    def debye_state(self, comp: int):
+        """(v_prev [z][y][x], u [K][z][y][x], vi [z][y][x]) float32 over component comp's box."""
+        self._debye_lib()
+        shp = getattr(self, "debye_shapes", [(0, 0, 0)] * 3)[comp]
+        K = getattr(self, "debye_K", 0)
+        v, u, vi = np.zeros(shp, np.float32), np.zeros((K,) + shp, np.float32), np.zeros(shp, np.float32)
+        self._ck(self.lib.fdtd_debye_get(self._ctx, int(comp), _ptr(v), _ptr(u), _ptr(vi)), "debye_get")
+        return v, u, vi
 
     # -- fields -------------------------------------------------------------------------------
     def get_field(self, kind: int, comp: int) -> np.ndarray:

@@ -273,6 +273,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   hipFree(c->d_probe); hipFree(c->d_box); hipFree(c->tw_v); hipFree(c->tw_i);
   hipFree(c->d_energy); hipFree(c->src_rng); hipFree(c->src_ids);
   sheet_free(c);
+  debye_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
   hipFree(c->mbox);
@@ -846,6 +847,7 @@ static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
 // whose fields fit the Infinity Cache (all E blocks, then all H blocks), and strips of at most 28 blocks (wf_wait_mur polls 9 * nbs flags, one thread each).
 static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
   if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
+  if (c->debye_nmedia > 0) return false;   // Debye media: likewise
   const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
                                       wf_lag_for(c) >= c->d.nk);
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
@@ -883,7 +885,7 @@ static bool wavefront_active(const fdtd_ctx* c, bool fused) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0) return false;
   if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -963,6 +965,11 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
       return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: the two-launch schedule only (their correction runs between the E phase and the H update)");
     if (multi || c->p.p2p) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: single slab only (world = 1)");
+  }
+  if (c->debye_nmedia > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: the two-launch schedule only (their correction runs between the E phase and the H update)");
+    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: single slab only (world = 1, no p2p transport, no linked contexts)");
   }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";
@@ -1056,6 +1063,8 @@ static int phase_E(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   if (!post_in_E) launch_mur(c, 1, s);          // post pass (a no-op without Mur faces)
   if (pl.mur != MUR_DIRECT) launch_mur(c, 2, s);   // apply pass, unless update_H takes the candidates itself
   if (!pl.fused) launch_post(c, FDTD_KIND_V, step, true, s);
+  // Debye media: their correction follows the V-probes, so these cannot wait for the probe blocks of update_H (phase_H leaves them out)
+  else if (c->debye_nmedia > 0 && c->nprobe > 0) launch_post(c, FDTD_KIND_V, step, false, s);
   launch_dft(c, FDTD_KIND_V, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_E, s));
   return FDTD_OK;
@@ -1077,7 +1086,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   };
   if (!split) { int r = wait_halo(); if (r) return r; }
   // Mur scenes: the pre pass of step + 1 rides in this launch (it reads V only, which is final and not written here)
-  launch_update_H(c, 0, split ? nk - 1 : nk, step, pl.fused, s, pl.fused ? pl.mur : MUR_NONE);
+  launch_update_H(c, 0, split ? nk - 1 : nk, step, pl.fused, s, pl.fused ? pl.mur : MUR_NONE, c->debye_nmedia == 0);
   if (pl.fused && c->any_mur && (c->p.mur_nb > 0 || c->p.mur_direct)) c->mur_pre_step = step + 1;   // (mur_direct: the main blocks ran the pre pass)
   c->kev0 = c->kev1 = nullptr;
   if (split) {
@@ -1241,6 +1250,7 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
   }
   for (int n = 0; n < nsteps; ++n) {
     if ((r = phase_E(c, pl, pe, n))) return r;
+    launch_debye(c, c->stream);   // Debye media: after the whole E phase, before the sheets' correction and the H update (no-op without media)
     launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
     if (multi && (r = exchange(c, FDTD_HALO_E_DOWN, pl.rccl_inline))) return r;
     if ((r = phase_H(c, pl, pe, n))) return r;
@@ -1361,6 +1371,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_mur(c, 2, s);
     launch_post(c, FDTD_KIND_V, c->step, true, s);
     launch_dft(c, FDTD_KIND_V, c->step, s);
+    launch_debye(c, s);
     launch_sheet(c, s);
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);

@@ -255,6 +255,18 @@ struct fdtd_ctx {
   int sheet_n = 0, sheet_K = 0, sheet_ncls = 0;
   int* sheet_off = nullptr; int8_t* sheet_comp = nullptr; float* sheet_vi = nullptr; int* sheet_cls = nullptr;
   float* sheet_vprev = nullptr; float* sheet_ib = nullptr; float* sheet_alpha = nullptr; float* sheet_b = nullptr;
+  // Debye media (dispersion.hip, include/fdtd_hip_dispersion.h): per component one dense box of edges, x range widened to
+  // multiples of 4; w, vi, v_prev [n] and u [K][n] over the widened box, medium ids when there are several media; the per-medium
+  // tables alpha, 1 - alpha, beta as [3][MAX_MEDIA * MAX_K] floats on the device
+  struct DebyeBox {
+    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the caller's box
+    int x0w = 0, nxw = 0;                       // widened x range: first node, length (a multiple of 4)
+    size_t n = 0;                               // edges of the widened box (0: the component has none)
+    float* w = nullptr; float* vi = nullptr; float* vprev = nullptr; float* u = nullptr; uint8_t* med = nullptr;
+  };
+  int debye_nmedia = 0, debye_K = 0;
+  DebyeBox debye_box[3];
+  float* debye_tab = nullptr;
   std::string err;
 };
 
@@ -277,7 +289,8 @@ enum MurStep { MUR_NONE, MUR_DIRECT, MUR_POST_IN_E, MUR_PASSES };
 // (update_E: I-probes of step-1, update_H: V-probes of step) so a step is exactly two launches.
 int upload_metric_tables(fdtd_ctx* c, const float* emet, const float* hmet);
 void launch_update_E(fdtd_ctx* c, int k_begin, int k_end, long long step, bool fused, bool probe_block, hipStream_t s, bool mur_post = false);
-void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, MurStep mur = MUR_NONE);
+void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, MurStep mur = MUR_NONE,
+                     bool v_probes = true);
 // one launch = E and H half-step of all planes (single slab or p2p slab, fusable sources; Mur faces where the planner admits them);
 // nsteps > 1: that many timesteps in ONE launch; lag: wf_lag_for
 int launch_step_wf(fdtd_ctx* c, long long step, hipStream_t s, int nsteps, int lag);
@@ -301,6 +314,9 @@ void res_free(fdtd_ctx* c);
 // sheet.hip: conducting sheets — the sparse correction after the E phase (no-op without sheets)
 void launch_sheet(fdtd_ctx* c, hipStream_t s);
 void sheet_free(fdtd_ctx* c);
+// dispersion.hip: Debye media — the dense correction after the E phase, in front of launch_sheet (no-op without media)
+void launch_debye(fdtd_ctx* c, hipStream_t s);
+void debye_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

@@ -1362,7 +1362,7 @@ static void launch_H2(fdtd_ctx* c, int k_begin, int nkr, long long step, int ext
   else launch_main(c, k_update_H<RAW, PML, false>, grid, pad, cap, s, c->p, k_begin, fd_ps, step, extra, 0u, c->h_murh);
 }
 
-void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, MurStep mur) {
+void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool probe_block, hipStream_t s, MurStep mur, bool v_probes) {
   const int nkr = k_end - k_begin;
   if (nkr <= 0) return;
   // extra blocks behind the main ones: [Mur pre pass of the next step (12 rows of mur_nbx blocks)] [probe block]; the Mur
@@ -1371,7 +1371,8 @@ void launch_update_H(fdtd_ctx* c, int k_begin, int k_end, long long step, bool p
   const bool pre = mur != MUR_NONE && probe_block && c->any_mur && c->d_mur;
   c->p.mur_direct = (pre && mur == MUR_DIRECT) ? 1 : 0;
   c->p.mur_nb = (pre && mur != MUR_DIRECT) ? 12 * c->p.mur_nbx : 0;
-  const int extra = (probe_block ? c->nprobe : 0) + c->p.mur_nb;
+  // (v_probes false: the V-probes of this step have been sampled already — Debye media, whose correction comes after them)
+  const int extra = (probe_block && v_probes ? c->nprobe : 0) + c->p.mur_nb;
   if (c->raw_op) {
     if (c->have_cpml) launch_H2<true, true>(c, k_begin, nkr, step, extra, s);
     else launch_H2<true, false>(c, k_begin, nkr, step, extra, s);

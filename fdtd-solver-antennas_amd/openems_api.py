@@ -173,6 +173,36 @@ class ContinuousStructure:
         self.properties.append(p)
         return p
 
+    def AddDebyeMaterial(self, name, **kw):
+        """A multi-pole Debye medium (dispersion.py), mirroring CSXCAD's Debye material property: ``order`` = K poles, ``epsilon``
+        = eps_inf, ``kappa``, and per pole the permittivity step and the relaxation time [s] — as sequences (``eps_delta``,
+        ``eps_relax_time``) or numbered from 1 (``eps_delta_1``, ``eps_relaxtime_1`` ...).  Aliases: ``eps_inf``; ``delta_eps``,
+        ``epsDelta``; ``tau``, ``eps_relaxtime``, ``epsRelaxTime``.  (The keyword spelling is not pinned against a CSXCAD install.)"""
+        kw = dict(kw)
+
+        def take(names, numbered):
+            for n in names:
+                if n in kw:
+                    return [float(v) for v in np.atleast_1d(kw.pop(n))]
+            out, q = [], 1
+            while any(f"{n}_{q}" in kw for n in numbered):
+                out.append(float(next(kw.pop(f"{n}_{q}") for n in numbered if f"{n}_{q}" in kw)))
+                q += 1
+            return out
+
+        deps = take(("eps_delta", "delta_eps", "epsDelta"), ("eps_delta", "delta_eps", "epsDelta"))
+        tau = take(("eps_relax_time", "eps_relaxtime", "tau", "epsRelaxTime"), ("eps_relaxtime", "eps_relax_time", "tau", "epsRelaxTime"))
+        order = int(kw.pop("order", len(deps)))
+        eps_inf = float(kw.pop("epsilon", kw.pop("eps_inf", 1.0)))
+        kappa = float(kw.pop("kappa", 0.0))
+        if kw:
+            raise TypeError(f"AddDebyeMaterial: unknown keyword(s) {sorted(kw)}")
+        if not (1 <= order <= 8) or len(deps) != order or len(tau) != order:
+            raise ValueError(f"AddDebyeMaterial: order {order} needs {order} permittivity steps and relaxation times (1..8 poles), got {len(deps)} and {len(tau)}")
+        p = CSProperty(self._log, "DebyeMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_delta=deps, eps_relax_time=tau)
+        self.properties.append(p)
+        return p
+
 
 # ---------------------------------------------------------------------------------------------------
 # openEMS side
@@ -385,8 +415,11 @@ class openEMS:
         grid = RectGrid(*lines)
         sc = Scene(unit=unit)
         for p in csx.properties:
-            if p.kind == "Material":
-                m = sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0))
+            if p.kind in ("Material", "DebyeMaterial"):
+                m = (sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0)) if p.kind == "Material" else
+                     sc.add_debye_material(p.name, p.params["epsilon"], p.params["kappa"], p.params["eps_delta"], p.params["eps_relax_time"]))
+                if p.kind == "DebyeMaterial":
+                    m.medium.fit_info = getattr(p, "fit_info", None)
                 for b in p.boxes:
                     m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
             else:

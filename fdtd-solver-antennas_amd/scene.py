@@ -21,6 +21,7 @@ import numpy as np
 from .grid import RectGrid
 from .ecoperator import LumpedEdge
 from . import sheet as _sheet
+from . import dispersion as _disp
 
 
 @dataclass
@@ -41,6 +42,12 @@ class Material:
     def add_box(self, start, stop, priority=0):
         self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
         return self
+
+
+@dataclass
+class DebyeMaterial(Material):
+    """add_debye_material(name, eps_inf, kappa, delta_eps, tau): a multi-pole Debye medium (dispersion.py).  eps_r holds eps_inf."""
+    medium: Optional[_disp.DebyeMedium] = None
 
 
 @dataclass
@@ -82,6 +89,14 @@ class Scene:
 
     def add_material(self, name, eps_r=1.0, kappa=0.0) -> Material:
         m = Material(name, float(eps_r), float(kappa))
+        self.materials.append(m)
+        return m
+
+    def add_debye_material(self, name, eps_inf, kappa=0.0, delta_eps=(), tau=()) -> DebyeMaterial:
+        """A dispersive dielectric eps(w) = eps_inf + sum_k delta_eps[k] / (1 + j w tau[k]) - j kappa / (w eps0), 1..8 poles.
+        Boxes, rotations and priorities work as for add_material; the highest priority owns a cell."""
+        med = _disp.DebyeMedium(eps_inf, kappa, delta_eps, tau)
+        m = DebyeMaterial(name, med.eps_inf, med.kappa, medium=med)
         self.materials.append(m)
         return m
 
@@ -127,6 +142,9 @@ class VoxelScene:
     pec: np.ndarray           # bool [3][nz][ny][nx]
     ports: List[PortOnGrid]
     sheets: Optional[_sheet.SheetEdges] = None   # conducting-sheet edges (None: the scene has no conducting sheet)
+    # Debye media (None: the scene has none): eps_r / kappa hold eps_inf / kappa of their cells — the timestep-dependent part of
+    # the fold (kappa += sum_k beta_k) is Simulation's, which knows dt
+    debye: Optional[_disp.DebyeEdges] = None
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -182,7 +200,21 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
     kap = np.zeros_like(eps)
     prio = np.full(eps.shape, -(1 << 30), dtype=np.int64)
     centers = [grid.centers(a) for a in range(3)]
+    # Debye materials with identical parameters are one medium (as sheets of one metal are one surface)
+    media, media_names, medium_of = [], [], {}
     for mat in scene.materials:
+        if isinstance(mat, DebyeMaterial):
+            k = mat.medium.key()
+            if k not in medium_of:
+                medium_of[k] = len(media)
+                media.append(mat.medium)
+                media_names.append([])
+            media_names[medium_of[k]].append(mat.name)
+    if len(media) > _disp.MAX_MEDIA:
+        raise ValueError(f"{len(media)} different Debye media: at most {_disp.MAX_MEDIA}")
+    cmed = np.full(eps.shape, -1, dtype=np.int8) if media else None
+    for mat in scene.materials:
+        mid = medium_of[mat.medium.key()] if isinstance(mat, DebyeMaterial) else -1
         for bx in mat.boxes:
             r = _inside_mask(bx, u, -tol, centers)     # strict: a cell centre on the surface is outside
             if r is None:
@@ -192,8 +224,13 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
             win = mask & (prio[sl] <= bx.priority)
             e = eps[sl]; k = kap[sl]; p = prio[sl]
             e[win] = mat.eps_r; k[win] = mat.kappa; p[win] = bx.priority
+            if cmed is not None:
+                cmed[sl][win] = mid
+    debye = _disp.make_edges(grid, media, media_names, cmed) if media and np.any(cmed >= 0) else None
     if any(isinstance(m, ConductingSheet) for m in scene.metals):
-        return _voxelize_with_sheets(scene, grid, eps, kap)
+        vs = _voxelize_with_sheets(scene, grid, eps, kap)
+        vs.debye = debye
+        return vs
     pec = np.zeros((3, nz, ny, nx), dtype=bool)
     for met in scene.metals:
         for bx in met.boxes:
@@ -212,7 +249,7 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
                       slice(off[0], off[0] + edge.shape[2])]
                 pec[c][tuple(sl)] |= edge
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
-    return VoxelScene(eps, kap, pec, ports)
+    return VoxelScene(eps, kap, pec, ports, debye=debye)
 
 
 def _box_edges(node: np.ndarray, c: int):

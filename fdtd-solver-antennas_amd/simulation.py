@@ -17,6 +17,7 @@ from .grid import RectGrid
 from .scene import VoxelScene
 from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_tables, lumped_overrides, LumpedEdge
 from . import sheet as _sheet
+from . import dispersion as _disp
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox
@@ -130,6 +131,7 @@ class RunStats:
     sheet_edges: int = 0                      # conducting-sheet edges stepped by the engine (sheet.py)
     sheet_fit_error: Optional[float] = None   # largest band error of the sheets' admittance fits (relative)
     schedule: Optional[dict] = None           # the schedule the engine ran (Engine.schedule_info)
+    dispersion: Optional[dict] = None         # Debye media stepped by the engine (dispersion.py): media, K, poles, fit errors, edges
 
 
 class Simulation:
@@ -228,6 +230,17 @@ class Simulation:
             j, i = np.divmod(r, nx)
             self.sheet_lumped = [LumpedEdge(int(c), int(a), int(b), int(q), float(sc * gimp[m]))
                                  for c, a, b, q, sc, m in zip(self.sheets.comp, i, j, k, self.sheets.scale, self.sheets.metal)]
+        # Debye media: discretised with the run's dt; the part of the branch currents proportional to the mean edge voltage folded
+        # into the cells' kappa (exact: linear in per-cell values), the rest stepped by the engine (fdtd_debye_set)
+        self.debye = vox.debye if getattr(vox, "debye", None) is not None and len(vox.debye) else None
+        self.kappa_cells = vox.kappa
+        if self.debye is not None:
+            _disp.check_placement(grid, self.debye.cell_medium, cells, [" / ".join(n) for n in self.debye.names])
+            self.kappa_cells = vox.kappa.copy()
+            for q, m in enumerate(self.debye.media):
+                on = self.debye.cell_medium == q
+                assert np.all(vox.eps_r[on] == m.eps_inf)
+                self.kappa_cells[on] = m.folded(self.dt)[1]
         self.engine: Optional[Engine] = None
         self.lib = None
         self.external_transport = None     # distributed.SlabComm when halos travel through the host
@@ -239,7 +252,7 @@ class Simulation:
         """The operator in its host (numpy) formulation — built on first use; the default product path never asks."""
         if self._op is None:
             v = self.vox
-            self._op = build_operator(self.grid, v.eps_r, v.kappa, v.pec, self.dt, v.lumped + self.sheet_lumped)
+            self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped)
         return self._op
 
     # ---------------------------------------------------------------------------------------------
@@ -263,13 +276,15 @@ class Simulation:
             raise ValueError(f"slab of rank {rank} has {nk} planes; need >= 2")
         if self.sheets is not None and world > 1:
             raise _capi.FdtdError("conducting sheets need a single slab (world = 1): a decomposed lossy-metal run is not supported")
+        if self.debye is not None and world > 1:
+            raise _capi.FdtdError("Debye media need a single slab (world = 1): a decomposed run with dispersive media is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
             v = self.vox
             emet, hmet = pack_metric_tables(*metric_lists(g, self.dt), g, k0, nk)
-            e.build_operator(g.d, v.eps_r, v.kappa, v.pec, EPS0,
-                             lumped_overrides(g, v.eps_r, v.kappa, v.pec, self.dt, v.lumped + self.sheet_lumped), emet, hmet,
+            e.build_operator(g.d, v.eps_r, self.kappa_cells, v.pec, EPS0,
+                             lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped), emet, hmet,
                              prefer_classes=self.use_classes)
             self.operator_form = "raw" if e.operator_form()[0] == "raw" else "classes"
         else:
@@ -281,6 +296,8 @@ class Simulation:
             else:
                 e.set_operator_raw(*self.op.raw(k0, nk))
                 self.operator_form = "raw"
+        if self.debye is not None:
+            e.set_debye(*self.debye_tables())
         if self.sheets is not None:
             e.set_sheets(*self.sheet_tables())
         if self.cpml is not None:
@@ -319,7 +336,7 @@ class Simulation:
         metric ex[i] * (ey[j] * ez[k]) in float32 — the association of ECOperator.raw, which the raw and class forms share.  Evaluated
         for the sheet edges alone (no download of the expanded operator)."""
         sh, g, v = self.sheets, self.grid, self.vox
-        m = lumped_overrides(g, v.eps_r, v.kappa, v.pec, self.dt, self.sheet_lumped)[3]
+        m = lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, self.sheet_lumped)[3]
         nx, ny, _ = g.shape
         k, r = np.divmod(sh.idx, nx * ny)
         j, i = np.divmod(r, nx)
@@ -336,6 +353,25 @@ class Simulation:
         sh = self.sheets
         cls, alpha, b = _sheet.class_tables(sh, self.sheet_fits, self.dt, self.sheet_K)
         return sh.idx, sh.comp, self.sheet_vi(), cls, alpha, b
+
+    def debye_tables(self):
+        """(alpha, oma, beta, lo, hi, w, med) of fdtd_debye_set (Engine.set_debye)."""
+        d = self.debye
+        alpha, oma, beta = _disp.tables(d.media, self.dt)
+        return alpha, oma, beta, d.lo, d.hi, [w.astype(np.float32) for w in d.w], d.med
+
+    def dispersion_info(self) -> Optional[dict]:
+        """What RunStats.dispersion reports: per medium the poles and, for fitted media, the fit's errors."""
+        if self.debye is None:
+            return None
+        d = self.debye
+        return {"media": [{"names": list(n), "eps_inf": m.eps_inf, "kappa": m.kappa, "delta_eps": m.delta_eps.tolist(),
+                           "tau": m.tau.tolist(), "relaxation_hz": (1.0 / (2 * np.pi * m.tau)).tolist(), "fit": m.fit_info}
+                          for m, n in zip(d.media, d.names)],
+                "K": d.K, "poles": int(sum(m.K for m in d.media)), "edges": len(d),
+                "fit_errors": {"tan_delta": max([m.fit_info["tan_delta_error"] for m in d.media if m.fit_info] or [None], key=lambda v: v or 0),
+                               "eps": max([m.fit_info["eps_error"] for m in d.media if m.fit_info] or [None], key=lambda v: v or 0)},
+                "box_edges": [int(np.prod(w.shape)) for w in d.w]}
 
     # ---------------------------------------------------------------------------------------------
     def run(self, *, max_steps: Optional[int] = None, check_every: int = 200, verbose: int = 0,
@@ -428,6 +464,7 @@ class Simulation:
         stats.seconds = time.perf_counter() - t0
         stats.sheet_edges = 0 if self.sheets is None else len(self.sheets)
         stats.sheet_fit_error = self.sheet_fit_error
+        stats.dispersion = self.dispersion_info()
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
         return stats

@@ -22,6 +22,13 @@ Functions never raise: failures come back as ``ok=False`` + message, like upstre
 openEMS/CSXCAD calls the reference makes) and are pinned call-for-call against the reference by
 tests/test_plugin_surface_cpu.py with fixtures captured from it.
 
+``metal_loss=True`` (every variant but the legacy one) models the metals with finite conductivity (sheet.py).
+``substrate_dispersion=True`` replaces the substrate's single conductivity — the requested loss tangent at f0 only, falling as
+f0 / f — by a Debye medium fitted to a CONSTANT loss tangent over the excitation band (dispersion.py), with Re eps(f0) = eps_r.
+The fixed variant's deliberate 1e-3 factor on kappa is part of the default path only: with substrate_dispersion the substrate has the
+loss tangent the user typed.  A loss tangent of 0 gives a plain loss-free material.  The legacy variant's substrate reaches into
+its absorbing layers, where dispersive cells are refused: its run reports that.  Both options compose.
+
 Additions over the reference's result type (compatible: extra optional fields): port time series,
 S11(f) and the resonance pick specified by the reference's dead S11 block (microstrip.py:407-426),
 run statistics (Mcells/s).
@@ -43,6 +50,7 @@ from .params import PatchAntennaParams
 from .patch_design import design_patch_for_frequency, calculate_microstrip_width
 from . import openems_api as oa
 from . import _capi
+from . import dispersion as _disp
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -148,6 +156,22 @@ def _add_metal(csx, name, params, metal_loss: bool):
     return csx.AddMetal(name)
 
 
+def _add_substrate(csx, name, eps_r, loss_tangent, kappa, f0, fc, substrate_dispersion: bool):
+    """The substrate material.  Default: eps_r and the ONE conductivity `kappa` the variant derives from the loss tangent (the requested
+    tan delta at f0 only, tan delta * f0 / f elsewhere).  substrate_dispersion: a Debye medium fitted to a CONSTANT loss tangent over
+    the excitation band (dispersion.fit_constant_loss_tangent, Re eps(f0) = eps_r) — the tan delta the user typed, whatever quirk
+    the variant's kappa carries; a loss tangent of 0 is then a plain loss-free material."""
+    if not substrate_dispersion:
+        return csx.AddMaterial(name, epsilon=eps_r, kappa=kappa)
+    if not loss_tangent or loss_tangent <= 0:
+        return csx.AddMaterial(name, epsilon=eps_r, kappa=0.0)
+    med = _disp.fit_constant_loss_tangent(float(eps_r), float(loss_tangent), float(f0), *_disp.substrate_band(float(f0), float(fc)))
+    prop = csx.AddDebyeMaterial(name, order=med.K, epsilon=med.eps_inf, kappa=med.kappa, eps_delta=med.delta_eps.tolist(),
+                                eps_relax_time=med.tau.tolist())
+    prop.fit_info = med.fit_info       # target, band and errors of the fit: reported in the run's stats["dispersion"]
+    return prop
+
+
 def _patch_dims_mm(p) -> tuple:
     """(W on x, L on y) in mm; designed for resonance unless both are given (fixed.py:141-149)."""
     if p.patch_length_m and p.patch_width_m:
@@ -219,7 +243,8 @@ probe_hip_fixed = probe_hip_microstrip = probe_hip
 # prepare: single patch, lumped port at x = -6 mm  (fixed.py:113-254)
 # ---------------------------------------------------------------------------------------------------
 def prepare_hip_patch_fixed(params, *, dll_dir: Optional[str] = None, work_dir: str = "fdtd_hip_out_fixed",
-                            cleanup: bool = True, verbose: int = 0, metal_loss: bool = False, **backend) -> FDTDPrepared:
+                            cleanup: bool = True, verbose: int = 0, metal_loss: bool = False, substrate_dispersion: bool = False,
+                            **backend) -> FDTDPrepared:
     try:
         lib = _load(dll_dir, backend)
         f0 = params.frequency_hz
@@ -237,7 +262,7 @@ def prepare_hip_patch_fixed(params, *, dll_dir: Optional[str] = None, work_dir: 
         patch = _add_metal(csx, "patch", params, metal_loss)
         patch.AddBox(priority=10, start=[-pw / 2, -pl / 2, h], stop=[pw / 2, pl / 2, h])
         fdtd.AddEdges2Grid(dirs="xy", properties=patch, metal_edge_res=res / 2)
-        sub = csx.AddMaterial("substrate", epsilon=params.eps_r, kappa=kappa)
+        sub = _add_substrate(csx, "substrate", params.eps_r, params.loss_tangent, kappa, f0, fc, substrate_dispersion)
         sub.AddBox(priority=0, start=[-30.0, -30.0, 0], stop=[30.0, 30.0, h])
         mesh.AddLine("z", np.linspace(0, h, 5))
         gnd = _add_metal(csx, "gnd", params, metal_loss)
@@ -258,7 +283,8 @@ def prepare_hip_patch_fixed(params, *, dll_dir: Optional[str] = None, work_dir: 
 # ---------------------------------------------------------------------------------------------------
 # prepare: microstrip-fed patch (microstrip.py:134-366) and its 3-D sampling sibling (microstrip_3d.py:19-196)
 # ---------------------------------------------------------------------------------------------------
-def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, ppw, extra_feed_lines, lib, backend, metal_loss=False):
+def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, ppw, extra_feed_lines, lib, backend, metal_loss=False,
+                      substrate_dispersion=False):
     f0 = params.frequency_hz
     fc = 0.5 * f0
     pw, pl = _patch_dims_mm(params)
@@ -275,7 +301,7 @@ def _microstrip_scene(params, feed_direction, feed_len, boundary, air_margin, pp
     mesh.AddLine("y", [-by / 2, by / 2])
     mesh.AddLine("z", [-bz / 3, bz * 2 / 3])
     kappa = 2 * np.pi * f0 * EPS0 * params.eps_r * params.loss_tangent
-    sub = csx.AddMaterial("substrate", epsilon=params.eps_r, kappa=kappa)
+    sub = _add_substrate(csx, "substrate", params.eps_r, params.loss_tangent, kappa, f0, fc, substrate_dispersion)
     sub.AddBox(priority=0, start=[-sw / 2, -sl / 2, 0], stop=[sw / 2, sl / 2, h])
     mesh.AddLine("z", np.linspace(0, h, 5))
     gnd = _add_metal(csx, "ground", params, metal_loss)
@@ -309,11 +335,12 @@ def prepare_hip_microstrip_patch(params, *, dll_dir: Optional[str] = None,
                                  feed_direction: FeedDirection = FeedDirection.NEG_X,
                                  feed_line_length_mm: float = 20.0, boundary: str = "MUR",
                                  theta_step_deg: float = 2.0, work_dir: str = "fdtd_hip_out_microstrip",
-                                 cleanup: bool = True, verbose: int = 0, metal_loss: bool = False, **backend) -> FDTDPrepared:
+                                 cleanup: bool = True, verbose: int = 0, metal_loss: bool = False, substrate_dispersion: bool = False,
+                            **backend) -> FDTDPrepared:
     try:
         lib = _load(dll_dir, backend)
         fdtd, nf, port, h, fd = _microstrip_scene(params, feed_direction, feed_line_length_mm, boundary, 50.0, 20,
-                                                  True, lib, backend, metal_loss)
+                                                  True, lib, backend, metal_loss, substrate_dispersion)
         theta = np.arange(0.0, 181.0, max(0.5, float(theta_step_deg)))
         return FDTDPrepared(True, f"Microstrip patch prepared (feed: {fd}, fdtd-hip backend)", FDTD=fdtd, nf=nf,
                             sim_path=_unique_sim_path(work_dir), theta=theta, phi=np.array([0.0, 90.0]),
@@ -327,12 +354,12 @@ def prepare_hip_microstrip_patch_3d(params, *, dll_dir: Optional[str] = None,
                                     feed_line_length_mm: float = 20.0, boundary: str = "MUR",
                                     theta_step_deg: float = 2.0, phi_step_deg: float = 5.0, mesh_quality: int = 3,
                                     work_dir: str = "fdtd_hip_out_microstrip", cleanup: bool = True, verbose: int = 0,
-                                    metal_loss: bool = False, **backend) -> FDTDPrepared:
+                                    metal_loss: bool = False, substrate_dispersion: bool = False, **backend) -> FDTDPrepared:
     try:
         lib = _load(dll_dir, backend)
         ppw = _PPW_5[_quality(mesh_quality, 5)]
         fdtd, nf, port, h, fd = _microstrip_scene(params, feed_direction, feed_line_length_mm, boundary, 80.0, ppw,
-                                                  False, lib, backend, metal_loss)
+                                                  False, lib, backend, metal_loss, substrate_dispersion)
         theta = np.arange(0.0, 181.0, max(0.5, float(theta_step_deg)))
         phi = np.arange(0.0, 361.0, max(1.0, float(phi_step_deg)))
         return FDTDPrepared(True, "Microstrip 3D prepared", FDTD=fdtd, nf=nf, sim_path=_unique_sim_path(work_dir),
@@ -371,7 +398,7 @@ def prepare_hip_microstrip_multi_3d(patches: Sequence, *, dll_dir: Optional[str]
                                     feed_line_length_mm: float = 20.0, port_mode: str = "lumped",
                                     end_criteria_db: float = -25.0, work_dir: str = "fdtd_hip_out_multi",
                                     cleanup: bool = True, verbose: int = 0, log_cb: Optional[Callable] = None,
-                                    metal_loss: bool = False, **backend) -> FDTDPrepared:
+                                    metal_loss: bool = False, substrate_dispersion: bool = False, **backend) -> FDTDPrepared:
     try:
         if not patches:
             return FDTDPrepared(False, "No patch instances provided.")
@@ -441,7 +468,7 @@ def prepare_hip_microstrip_multi_3d(patches: Sequence, *, dll_dir: Optional[str]
             p = inst.params
             fw = calculate_microstrip_width(p.frequency_hz, p.eps_r, p.h_m) * 1e3
             kappa = 2 * np.pi * p.frequency_hz * EPS0 * p.eps_r * p.loss_tangent
-            sub = csx.AddMaterial(f"substrate_{idx}", epsilon=p.eps_r, kappa=kappa)
+            sub = _add_substrate(csx, f"substrate_{idx}", p.eps_r, p.loss_tangent, kappa, p.frequency_hz, fc, substrate_dispersion)
             m_gnd, m_patch, m_feed = (_add_metal(csx, f"{n}_{idx}", p, metal_loss) for n in ("ground", "patch", "feed"))
             t = max(0.02, float(p.metal.thickness_m) * 1e3)
             _placed(sub.AddBox(priority=0, start=[-sw / 2, -sl / 2, -h / 2], stop=[sw / 2, sl / 2, h / 2]), *rot, T)
@@ -503,7 +530,7 @@ def prepare_hip_microstrip_multi_3d(patches: Sequence, *, dll_dir: Optional[str]
 # prepare: legacy full-3D variant (openems.py:140-268)
 # ---------------------------------------------------------------------------------------------------
 def prepare_hip_patch(params, *, dll_dir: Optional[str] = None, work_dir: str = "fdtd_hip_out", cleanup: bool = True,
-                      verbose: int = 0, metal_loss: bool = False, **backend) -> FDTDPrepared:
+                      verbose: int = 0, metal_loss: bool = False, substrate_dispersion: bool = False, **backend) -> FDTDPrepared:
     if metal_loss:   # (the NF2FF box records voltages on the ground plane where it crosses the box: conducting-sheet edges may not lie there)
         return FDTDPrepared(False, "prepare failed: metal_loss=True is not available for this variant: its ground plane crosses the NF2FF "
                                    "box, where conducting-sheet edges may not lie (use the fixed or microstrip variants)")
@@ -519,7 +546,7 @@ def prepare_hip_patch(params, *, dll_dir: Optional[str] = None, work_dir: str = 
         mesh.AddLine("y", [-100.0, 100.0])
         mesh.AddLine("z", [-50.0, 100.0])
         kappa = 2.0 * np.pi * f0 * 8.854187817e-12 * params.eps_r * max(0.0, params.loss_tangent)   # openems.py:199-200
-        sub = csx.AddMaterial("substrate", epsilon=params.eps_r, kappa=kappa)
+        sub = _add_substrate(csx, "substrate", params.eps_r, params.loss_tangent, kappa, f0, fc, substrate_dispersion)
         sub.AddBox([-100.0, -100.0, 0.0], [100.0, 100.0, h])
         mesh.AddLine("z", np.linspace(0.0, h, 5).tolist())
         gnd = _add_metal(csx, "gnd", params, metal_loss)
@@ -717,6 +744,8 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
                      "mesh_lines_merged": _merged_lines(fdtd),
                      "sheet_edges": getattr(st, "sheet_edges", 0), "sheet_fit_error": getattr(st, "sheet_fit_error", None),
                      "schedule": getattr(st, "schedule", None)}
+        if getattr(st, "dispersion", None) is not None:     # Debye media stepped by the engine (substrate_dispersion / AddDebyeMaterial)
+            out.stats["dispersion"] = st.dispersion
         if verbose:
             print(f"[fdtd-hip] done: {st.steps} steps, {st.mcells_per_s:.0f} MC/s, Dmax {10 * np.log10(Dmax):.2f} dBi", flush=True)
         return out
