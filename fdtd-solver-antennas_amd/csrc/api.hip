@@ -812,8 +812,13 @@ static bool mur_post_fusable(const fdtd_ctx* c, bool multi, bool fused) {
 // voltages in memory are then the E update's own, and inside update_H they are being overwritten: whoever reads V there —
 // V-probes (sampled by update_H's extra block), NF2FF / DFT boxes (sampled between the two launches) — must not hold a
 // node of a Mur face.  (The reference's probes and boxes sit inside the grid.)  Needs the post pass inside update_E.
+// k_sheet runs between the two launches and reads and writes V: a sheet edge on the node plane of an enabled face takes the apply pass
+// too (the header's order: Mur passes, then the correction).  k_debye needs no such rule: the operator holds vi = 0 on every edge of a
+// grid face, and fdtd_debye_set leaves those edges out (their V is never the correction's to change, their states never act).
 static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
   if (!c->mur_no_apply || !mur_post_fusable(c, multi, fused)) return false;
+  for (int f = 0; f < 6; ++f)
+    if (c->mur[f].on && c->sheet_n > 0 && ((c->sheet_faces >> f) & 1u)) return false;
   const int dim[3] = {c->d.nx, c->d.ny, c->d.nk};
   auto on_face = [&](const int lo[3], const int hi[3]) {
     for (int f = 0; f < 6; ++f) {
@@ -949,7 +954,24 @@ struct StepPlan {
   bool rccl_inline = false;    // two launches on RCCL: the exchange in stream order on the compute stream (no split sweeps, no events)
   int lag = 0, multi_max = 0;  // one launch: wf_lag_for, wf_multi_max; RESIDENT: timesteps per launch at most in multi_max
   unsigned pinned = 0, slots = 0;   // p2p: workgroups this slab's launches may pin (p2p_pinned_blocks), the chip's slots (chip_slots)
+  bool probes_first = false;   // two launches, fused: the V-probes in a launch of their own in front of the corrections (probes_first)
 };
+
+// The corrections of the Debye media and the conducting sheets follow the V-probes (the headers' order).  With fused sources the V-probes
+// of a timestep are otherwise sampled by the probe blocks of update_H, i.e. after the corrections: wrong as soon as a correction changes
+// a voltage a probe reads.  Debye media are volumes (ports sit inside substrates): always.  Sheet edges are few and the scene layer keeps
+// them off the probe lines: only when a V-probe cell sits on the node of a sheet edge (whatever the components: cheap and on the safe side).
+static bool probes_first(const fdtd_ctx* c) {
+  if (c->nprobe == 0) return false;
+  if (c->debye_nmedia > 0) return true;
+  if (c->sheet_n <= 0) return false;
+  for (int q = 0; q < c->nprobe; ++q) {
+    if (c->probe[q].kind != FDTD_KIND_V) continue;
+    for (int off : c->h_prb_off[q])
+      if (std::binary_search(c->h_sheet_off.begin(), c->h_sheet_off.end(), off)) return true;
+  }
+  return false;
+}
 
 // What this context runs, or the code and message of why it cannot run.  Every decision and refusal of the step loops is here, in
 // the order callers have always seen them (the message prefixes matter: simulation.Simulation.run sorts failures by them).  `linked`:
@@ -1005,6 +1027,7 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
   }
   pl.kind = StepPlan::TWO_LAUNCH;
   pl.rccl_inline = rccl_inline(c);
+  pl.probes_first = probes_first(c);
   if (c->any_mur) pl.mur = mur_direct_possible(c, multi, fused) ? MUR_DIRECT : mur_post_fusable(c, multi, fused) ? MUR_POST_IN_E : MUR_PASSES;
   return FDTD_OK;
 }
@@ -1063,8 +1086,9 @@ static int phase_E(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   if (!post_in_E) launch_mur(c, 1, s);          // post pass (a no-op without Mur faces)
   if (pl.mur != MUR_DIRECT) launch_mur(c, 2, s);   // apply pass, unless update_H takes the candidates itself
   if (!pl.fused) launch_post(c, FDTD_KIND_V, step, true, s);
-  // Debye media: their correction follows the V-probes, so these cannot wait for the probe blocks of update_H (phase_H leaves them out)
-  else if (c->debye_nmedia > 0 && c->nprobe > 0) launch_post(c, FDTD_KIND_V, step, false, s);
+  // Debye media, a sheet edge under a V-probe: the correction follows the V-probes, so these cannot wait for the probe blocks of update_H
+  // (phase_H leaves them out)
+  else if (pl.probes_first) launch_post(c, FDTD_KIND_V, step, false, s);
   launch_dft(c, FDTD_KIND_V, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_E, s));
   return FDTD_OK;
@@ -1086,7 +1110,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   };
   if (!split) { int r = wait_halo(); if (r) return r; }
   // Mur scenes: the pre pass of step + 1 rides in this launch (it reads V only, which is final and not written here)
-  launch_update_H(c, 0, split ? nk - 1 : nk, step, pl.fused, s, pl.fused ? pl.mur : MUR_NONE, c->debye_nmedia == 0);
+  launch_update_H(c, 0, split ? nk - 1 : nk, step, pl.fused, s, pl.fused ? pl.mur : MUR_NONE, !pl.probes_first);
   if (pl.fused && c->any_mur && (c->p.mur_nb > 0 || c->p.mur_direct)) c->mur_pre_step = step + 1;   // (mur_direct: the main blocks ran the pre pass)
   c->kev0 = c->kev1 = nullptr;
   if (split) {

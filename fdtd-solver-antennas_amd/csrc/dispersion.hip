@@ -224,8 +224,10 @@ int fdtd_debye_set(fdtd_ctx* c, int nmedia, int K, const float* alpha, const flo
         const size_t src = ((size_t)z * nyb + y) * nxb, dst = ((size_t)z * nyb + y) * b.nxw + (b.lo[0] - b.x0w);
         const size_t g = (size_t)ci * ncell + ((size_t)(b.lo[2] + z) * c->d.ny + (b.lo[1] + y)) * c->d.nx + b.lo[0];
         for (int x = 0; x < nxb; ++x) {
-          ww[dst + x] = w[ci][src + x];
+          // an edge the operator holds at zero (vi == 0: a grid face, metal) is no dispersive edge: the correction could never change its
+          // voltage, so its states could never act — and on a Mur face the voltage between the two launches is not the timestep's final one
           vv[dst + x] = op[1][g + x];
+          ww[dst + x] = vv[dst + x] == 0.0f ? 0.0f : w[ci][src + x];
           if (nmedia > 1) mm[dst + x] = med[ci][src + x];
         }
       }

@@ -255,6 +255,8 @@ struct fdtd_ctx {
   int sheet_n = 0, sheet_K = 0, sheet_ncls = 0;
   int* sheet_off = nullptr; int8_t* sheet_comp = nullptr; float* sheet_vi = nullptr; int* sheet_cls = nullptr;
   float* sheet_vprev = nullptr; float* sheet_ib = nullptr; float* sheet_alpha = nullptr; float* sheet_b = nullptr;
+  std::vector<int> h_sheet_off;   // the sheet edges' local offsets, sorted (host copy): does a V-probe cell sit on a sheet edge's node?
+  unsigned sheet_faces = 0;       // bit f: a sheet edge lies on the node plane of grid face f (x-, x+, y-, y+, z-, z+)
   // Debye media (dispersion.hip, include/fdtd_hip_dispersion.h): per component one dense box of edges, x range widened to
   // multiples of 4; w, vi, v_prev [n] and u [K][n] over the widened box, medium ids when there are several media; the per-medium
   // tables alpha, 1 - alpha, beta as [3][MAX_MEDIA * MAX_K] floats on the device

@@ -54,6 +54,8 @@ void sheet_free(fdtd_ctx* c) {
   c->sheet_off = nullptr; c->sheet_comp = nullptr; c->sheet_vi = nullptr; c->sheet_cls = nullptr;
   c->sheet_vprev = nullptr; c->sheet_ib = nullptr; c->sheet_alpha = nullptr; c->sheet_b = nullptr;
   c->sheet_n = c->sheet_K = c->sheet_ncls = 0;
+  c->h_sheet_off.clear();
+  c->sheet_faces = 0;
 }
 
 void launch_sheet(fdtd_ctx* c, hipStream_t s) {
@@ -81,6 +83,7 @@ int fdtd_sheet_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, c
   std::vector<int8_t> cp(n);
   std::vector<float> v(vi, vi + n);
   std::vector<int64_t> keys(n);
+  unsigned faces = 0;
   for (int e = 0; e < n; ++e) {
     const int64_t g = idx[e];
     if (g < 0 || g >= gplane * c->d.nz || comp[e] < 0 || comp[e] > 2 || cls[e] < 0 || cls[e] >= ncls)
@@ -89,6 +92,7 @@ int fdtd_sheet_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, c
     const int64_t pos[3] = {i, j, k};
     if (pos[comp[e]] >= nn[comp[e]] - 1) return fdtd_fail(c, FDTD_E_ARG, "fdtd_sheet_set: edge %d does not exist", e);
     keys[e] = g * 3 + comp[e];
+    for (int a = 0; a < 3; ++a) faces |= (pos[a] == 0 ? 1u : 0u) << (2 * a) | (pos[a] == nn[a] - 1 ? 1u : 0u) << (2 * a + 1);
     off[e] = (int)((k - c->d.k0) * c->plane + j * c->P + i);
     cp[e] = comp[e];
     cl[e] = cls[e];
@@ -114,6 +118,10 @@ int fdtd_sheet_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, c
     return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "fdtd_sheet_set: %s", hipGetErrorString(e));
   }
   c->sheet_n = n; c->sheet_K = K; c->sheet_ncls = ncls;
+  // what the planner asks (api.hip: mur_direct_possible, probes_first): the faces the edges touch, their offsets for the V-probes
+  c->sheet_faces = faces;
+  c->h_sheet_off = off;
+  std::sort(c->h_sheet_off.begin(), c->h_sheet_off.end());
   return FDTD_OK;
 }
 

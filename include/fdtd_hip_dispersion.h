@@ -24,7 +24,11 @@
  *
  * alpha, oma = 1 - alpha and beta arrive as fp32 tables (rounded from the host's float64 values; oma is a table of its own so
  * that short relaxation times keep their digits).  Edges with w_e == 0 inside a box are left alone: V, u_k and v_prev keep
- * their bits.
+ * their bits.  Edges the operator holds at zero (vi_e == 0: the tangential edges of every grid face, edges in metal) are left
+ * alone too, whatever their w_e: fdtd_debye_set treats them as w_e = 0.  q is 0 there, so no voltage depends on it; their
+ * states stay at rest instead of following a voltage they can never act on.  That is also what lets a medium run into a Mur
+ * face under every schedule: the face's voltages between update_E and update_H are final only when the apply pass is a
+ * launch of its own, and every edge of a face node plane is such an edge.
  *
  * Storage: per field component one dense box [z0, z1) x [y0, y1) x [x0, x1) of edges (node indices of the edges' lower ends),
  * laid out like the field arrays (x fastest); the library widens x0 down and x1 up to multiples of 4, so one thread owns four

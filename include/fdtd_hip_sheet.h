@@ -19,6 +19,12 @@
  * forcing FDTD_FLAG_KERNEL_WAVEFRONT or FDTD_FLAG_KERNEL_RESIDENT returns FDTD_E_UNSUPPORTED, and so does world > 1.
  * fdtd_half_step(ctx, FDTD_PHASE_E) applies the correction too.  Branch currents and v_prev start at zero (the fields are
  * zero before the first step); fdtd_set_field does not touch them.
+ *
+ * The order above holds for any edge set this call accepts, under fdtd_run as under fdtd_half_step: a V-probe whose cell sits
+ * on the node of a sheet edge is sampled in a launch of its own in front of the correction (k_post) instead of in the probe
+ * blocks of update_H, and a sheet edge on the node plane of an enabled Mur face makes the Mur apply pass a launch of its own
+ * (three launches per timestep), so that the correction reads the face's final voltage.  (The scene layer places sheets off
+ * probe lines and two planes inside Mur faces; neither case costs a context built by it anything.)
  */
 #ifndef FDTD_HIP_SHEET_H
 #define FDTD_HIP_SHEET_H

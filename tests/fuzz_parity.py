@@ -12,6 +12,9 @@ the energy to 1e-12, the NF2FF face spectra to 1e-6 of their largest entry (floa
     python tests/fuzz_parity.py [--cases 60] [--seed 1] [--only N]     # on a GPU box; prints one line per case, exits 1 on a mismatch
     python tests/fuzz_parity.py --slabs ...     # decomposed runs: 2 ... 6 z-slabs of drawn partition and schedules, coupled through their P2P
                                                 # mailboxes in one process (fdtd_run_linked), against ONE slab on the oracle ("lag" column: planes per slab)
+    python tests/fuzz_parity.py --media ...     # scenes with Debye media and / or conducting sheets (k_debye, k_sheet and their place in the step
+                                                # loop) against the oracle's half-steps plus the numpy restatement of the two corrections
+                                                # (draw_media_case / run_media_case below); tests/test_media_fuzz_cpu.py guards what the draw covers
 
 Lives under tests/ because it loads the oracle (test infrastructure); tests/test_round3_gpu.py::test_randomised_cases_equal_the_oracle
 runs a fixed-seed batch of it in the -m gpu suite.
@@ -230,6 +233,279 @@ def run_slab_case(case, hip, oracle):
     return problems, info
 
 
+# ---- scenes with Debye media and / or conducting sheets -----------------------------------------------------------------------------
+MEDIA_F0, MEDIA_FC, MEDIA_H = 9e9, 5e9, 1e-3
+MEDIA_BATCH = (36, 3)        # (cases, seed) of the batch in the -m gpu suite (tests/test_dispersion_gpu.py); test_media_fuzz_cpu.py guards its coverage
+MEDIA_BANDS = {3: (5e9, 15e9), 4: (3e9, 20e9), 5: (2e9, 25e9), 8: (0.1e9, 30e9)}     # bands over which K poles hold tan delta within 2 %
+
+
+def _pick_mod4(rng, lo, hi):
+    """A value of lo ... hi (inclusive) whose residue mod 4 is drawn first, so that the residues come out uniform."""
+    r = int(rng.integers(0, 4))
+    c = [v for v in range(lo, hi + 1) if v % 4 == r] or list(range(lo, hi + 1))
+    return int(c[int(rng.integers(0, len(c)))])
+
+
+def draw_media_case(rng):
+    """One scene with 0 ... 8 Debye media and 0 ... 3 conducting sheets (at least one of the two) as a plain dict.  All positions are node
+    indices; a medium owns the cells [lo, hi) of its box.  What each item is there for: see the table in docs/HISTORY.md (randomised media)."""
+    big = rng.random() < 0.12              # a box of >= 20 blocks of k_debye per component (>= 5 120 groups of four x-edges)
+    if big:
+        n = [int(rng.integers(62, 91)), int(rng.integers(46, 61)), int(rng.integers(30, 41))]
+    else:
+        n = [int(rng.choice([rng.integers(14, 40), rng.integers(40, 91)])), int(rng.choice([rng.integers(12, 30), rng.integers(30, 61)])),
+             int(rng.integers(12, 41))]
+    if rng.random() < 0.3:
+        kinds = [str(rng.choice(["PEC", "MUR", "CPML"]))] * 6
+    else:
+        kinds = [str(rng.choice(["PEC", "MUR", "CPML"])) for _ in range(6)]
+    cells = int(rng.integers(2, max(2, min(4 if big else 8, (min(n) - 8) // 2)) + 1))
+    layer = [cells if k == "CPML" else 0 for k in kinds]
+    L = [layer[2 * a] for a in range(3)]                       # cells [L, H) per axis lie outside the CPML layers
+    H = [n[a] - 1 - layer[2 * a + 1] for a in range(3)]
+    nmedia = int(rng.choice([0, 1, 2, 3, 4, 5, 6, 7, 8], p=[0.14, 0.28, 0.14, 0.1, 0.05, 0.05, 0.05, 0.05, 0.14]))
+    if big:
+        nmedia = int(rng.integers(1, 3))
+    # the region the media fill: now and then up to a face (never into a CPML layer), else a few cells inside
+    touch = [bool(rng.random() < 0.35) and kinds[f] != "CPML" for f in range(6)] if rng.random() < 0.3 else [False] * 6
+    rlo, rhi = [], []
+    for a in range(3):
+        span = H[a] - L[a]
+        room = 3 if big else max(3, span // 4)
+        lo_min = L[a] if kinds[2 * a] == "CPML" else 1
+        hi_max = H[a] if kinds[2 * a + 1] == "CPML" else n[a] - 2
+        lo = 0 if touch[2 * a] else _pick_mod4(rng, lo_min, lo_min + room) if a == 0 else int(rng.integers(lo_min, lo_min + room + 1))
+        hi = n[a] - 1 if touch[2 * a + 1] else _pick_mod4(rng, hi_max - room, hi_max) if a == 0 else int(rng.integers(hi_max - room, hi_max + 1))
+        if hi - lo < 2:
+            lo, hi = min(lo, lo_min + 1), max(hi, hi_max - 1)
+        rlo.append(int(lo)); rhi.append(int(hi))
+    split = int(np.argmax([rhi[a] - rlo[a] for a in range(3)]))       # the media stand behind each other along this axis, a cell apart
+    nmedia = min(nmedia, (rhi[split] - rlo[split] + 1) // 2)
+    media = []
+    if nmedia:
+        lens = np.ones(nmedia, int)
+        for _ in range(rhi[split] - rlo[split] - (2 * nmedia - 1)):
+            lens[int(rng.integers(0, nmedia))] += 1
+        pos = rlo[split]
+        for q in range(nmedia):
+            lo, hi = list(rlo), list(rhi)
+            lo[split], hi[split] = pos, pos + int(lens[q])
+            pos = hi[split] + 1
+            for a in range(3):
+                if a != split and q > 0 and rng.random() < 0.6:      # (medium 0 spans the region, so the bounding box is the region)
+                    lo[a] = int(rng.integers(rlo[a], rhi[a]))
+                    hi[a] = int(rng.integers(lo[a] + 1, rhi[a] + 1))
+            K = int(rng.choice([1, 3, 4, 5, 8], p=[0.2, 0.3, 0.15, 0.1, 0.25]))
+            kappa = float(rng.choice([0.0, 0.0, round(float(rng.uniform(0.005, 0.05)), 4)]))
+            if K == 1:
+                par = ("poles", round(float(rng.uniform(1.5, 4.0)), 3), kappa, [round(float(rng.uniform(0.2, 1.5)), 3)],
+                       [round(float(rng.uniform(5.0, 40.0)), 2) * 1e-12])
+            else:
+                par = ("fit", round(float(rng.uniform(2.0, 6.0)), 3), round(float(rng.uniform(0.005, 0.05)), 4), K, kappa)
+            hole = None
+            if all(hi[a] - lo[a] >= 4 for a in range(3)) and rng.random() < 0.5:      # plain dielectric of higher priority inside: w = 0 groups
+                h0 = [int(rng.integers(lo[a] + 1, hi[a] - 2)) for a in range(3)]
+                hole = (h0, [int(min(hi[a] - 1, h0[a] + rng.integers(2, 6))) for a in range(3)], round(float(rng.uniform(1.5, 3.0)), 2))
+            media.append({"medium": par, "lo": lo, "hi": hi, "hole": hole})
+    nf = str(rng.choice(["none", "dft", "record"]))
+    nsheets = int(rng.choice([0, 1, 2, 3], p=[0.45, 0.25, 0.2, 0.1])) if nmedia else int(rng.integers(1, 4))
+
+    def sheet_range(with_nf):     # nodes a sheet may use: two planes inside every face, outside the CPML layers, strictly inside the NF2FF box
+        lo = [max(2, L[a] + 1, (max(layer[2 * a] + 2, 3) + 1) if with_nf else 0) for a in range(3)]
+        hi = [min(n[a] - 3, H[a] - 1, (n[a] - 1 - max(layer[2 * a + 1] + 2, 3) - 1) if with_nf else n[a]) for a in range(3)]
+        return lo, hi
+
+    slo, shi = sheet_range(nf != "none")
+    if nsheets and any(shi[a] - slo[a] < 2 for a in range(3)):
+        nf = "none"
+        slo, shi = sheet_range(False)
+    # one lumped port along z, half of the time inside a medium
+    plo, phi_ = [max(2, L[a] + 1) for a in range(3)], [min(n[a] - 3, H[a] - 1) for a in range(3)]
+    port = None
+    if media and rng.random() < 0.6:
+        m = media[int(rng.integers(0, len(media)))]
+        lo = [max(plo[0], m["lo"][0] + 1), max(plo[1], m["lo"][1] + 1), max(plo[2], m["lo"][2])]
+        hi = [min(phi_[0], m["hi"][0] - 1), min(phi_[1], m["hi"][1] - 1), min(phi_[2], m["hi"][2])]
+        if lo[0] <= hi[0] and lo[1] <= hi[1] and lo[2] < hi[2]:
+            z0 = int(rng.integers(lo[2], hi[2]))
+            port = (int(rng.integers(lo[0], hi[0] + 1)), int(rng.integers(lo[1], hi[1] + 1)), z0, int(min(hi[2], z0 + rng.integers(1, 5))))
+    if port is None:
+        z0 = int(rng.integers(plo[2], phi_[2]))
+        port = (int(rng.integers(plo[0], phi_[0] + 1)), int(rng.integers(plo[1], phi_[1] + 1)), z0, int(min(phi_[2], z0 + rng.integers(1, 5))))
+    sheets = []
+    for q in range(nsheets):
+        for _ in range(8):
+            a = int(rng.integers(0, 3))
+            lo = [int(rng.integers(slo[b], shi[b] - 1)) for b in range(3)]
+            hi = [int(rng.integers(lo[b] + 2, shi[b] + 1)) for b in range(3)]
+            resolved = bool(rng.random() < 0.35)
+            if q == 0 and media and rng.random() < 0.6:      # on a medium's face: its edges are dispersive edges too
+                m = media[int(rng.integers(0, len(media)))]
+                side = m["hi"][a] if rng.random() < 0.5 else m["lo"][a]
+                if slo[a] <= side <= shi[a]:
+                    lo[a], resolved = int(side), False
+                    for b in range(3):
+                        if b != a and max(slo[b], m["lo"][b]) + 2 <= min(shi[b], m["hi"][b]):
+                            lo[b], hi[b] = max(slo[b], m["lo"][b]), min(shi[b], m["hi"][b])
+            hi[a] = min(lo[a] + 2, shi[a]) if resolved else lo[a]
+            # (the scene refuses a sheet edge that is a port edge or lies on the port's voltage line: z-edges at the port's x, y)
+            zhit = min(hi[2], port[3]) - max(lo[2], port[2]) >= 1
+            if lo[0] <= port[0] <= hi[0] and lo[1] <= port[1] <= hi[1] and zhit:
+                continue
+            sigma = float(rng.choice([5.8e7, 9.1e6, 3e5, 1e5]))
+            sheets.append((sigma, 2e-3 if resolved else float(rng.choice([5e-6, 35e-6, 1e-3])), lo, hi))
+            break
+    if not media and not sheets:      # (eight placements in a row hit the port: a medium instead)
+        media.append({"medium": ("fit", 4.3, 0.02, 3, 0.0), "lo": list(rlo), "hi": list(rhi), "hole": None})
+    env = {}
+    if "MUR" in kinds and rng.random() < 0.4:
+        env["FDTD_MUR_APPLY_PASS"] = "1"
+    if rng.random() < 0.25:
+        env["FDTD_TYS"] = str(int(rng.choice([1, 2, 3, 5, 7, 16])))
+    calls = [int(rng.integers(1, 61)) for _ in range(int(rng.integers(1, 6)))]
+    if big:
+        calls = calls[:3]
+    return {"shape": tuple(n), "graded": int(rng.integers(1, 1 << 20)) if rng.random() < 0.6 else 0, "kinds": kinds, "cells": cells,
+            "classes": bool(rng.random() < 0.7), "media": media, "sheets": sheets, "port": port, "nf2ff": nf,
+            "sched": str(rng.choice(["auto", "direct"])), "env": env, "calls": calls, "seed": int(rng.integers(1, 1 << 30))}
+
+
+def media_case_medium(par):
+    d = _mod("dispersion")
+    if par[0] == "poles":
+        return d.DebyeMedium(par[1], par[2], par[3], par[4])
+    _, eps_r, tan_delta, K, kappa = par
+    m = d.fit_constant_loss_tangent(eps_r, tan_delta, MEDIA_F0, *MEDIA_BANDS[K], K=K)
+    return m if kappa == 0 else d.DebyeMedium(m.eps_inf, kappa, m.delta_eps, m.tau)
+
+
+def media_case_sim(case):
+    """The Simulation of a drawn case (ValueError: a set-up the host layer refuses)."""
+    sc, simm, gr = _mod("scene"), _mod("simulation"), _mod("grid")
+    n = case["shape"]
+    if case["graded"]:
+        g = np.random.default_rng(case["graded"])
+        lines = [np.concatenate([[0.0], np.cumsum(MEDIA_H * g.uniform(0.7, 1.4, k - 1))]) for k in n]
+    else:
+        lines = [np.arange(k) * MEDIA_H for k in n]
+    grid = gr.RectGrid(*lines)
+    at = lambda p: [float(lines[a][p[a]]) * 1e3 for a in range(3)]
+    s = sc.Scene(unit=1e-3)
+    for q, m in enumerate(case["media"]):
+        med = media_case_medium(m["medium"])
+        s.add_debye_material(f"m{q}", med.eps_inf, med.kappa, med.delta_eps, med.tau).add_box(at(m["lo"]), at(m["hi"]), priority=1)
+        if m["hole"] is not None:
+            s.add_material(f"hole{q}", eps_r=m["hole"][2]).add_box(at(m["hole"][0]), at(m["hole"][1]), priority=2)
+    for q, (sigma, t, lo, hi) in enumerate(case["sheets"]):
+        s.add_conducting_sheet(f"s{q}", sigma, t).add_box(at(lo), at(hi))
+    px, py, z0, z1 = case["port"]
+    s.add_lumped_port(1, 50.0, at((px, py, z0)), at((px, py, z1)), "z", 1.0)
+    vox = sc.voxelize(s, grid)
+    total = sum(case["calls"])
+    return simm.Simulation(grid, vox, f0=MEDIA_F0, fc=MEDIA_FC, boundary=case["kinds"], cpml_cells=case["cells"], nr_ts=total + 8,
+                           end_criteria=0.0, nf2ff_freqs=None if case["nf2ff"] == "none" else [MEDIA_F0, 1.3 * MEDIA_F0],
+                           use_classes=case["classes"], nf2ff_mode="dft" if case["nf2ff"] == "none" else case["nf2ff"])
+
+
+def _restated(sim, oracle, seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_dispersion_model_cpu import Restated
+    return Restated(sim, oracle, seed=seed)
+
+
+def media_reference_problems(r):
+    """What the reference side must show by itself, so that a medium or a sheet the wave never reached cannot pass silently: finite and
+    non-zero fields and states, every branch state of every dispersive edge the operator does not hold (w != 0, vi != 0) and the
+    branch currents of every sheet edge off zero — at one of Restated's checkpoints (the first step, every eighth, the end of a run():
+    a single state update cancels to exactly 0.0f about once in 2^24, which a few of 1e8 final values do)."""
+    r.note_moved()
+    problems = []
+    fo = r.e.fields()
+    if not np.isfinite(fo).all() or not np.abs(fo).max() > 0:
+        problems.append("reference fields not finite / all zero")
+    for c in range(len(r.w)):
+        if not r.w[c].size:
+            continue
+        if not (np.isfinite(r.u[c]).all() and np.isfinite(r.vprev[c]).all()):
+            problems.append(f"reference states of component {c} not finite")
+        live = (r.w[c] != 0) & (r.vi[c] != 0)
+        need = live[None] & (r.tab[c][1] != 0)           # (oma == 0: the padding poles of a shorter medium, which stay at rest)
+        if not live.any() or not np.all(r.u_moved[c][need]) or not np.all(r.vprev_moved[c][live]):
+            problems.append(f"component {c}: {np.count_nonzero(~r.u_moved[c][need])} branch states of {np.count_nonzero(need)} on dispersive edges never left zero")
+        if np.any(r.u[c][:, ~live] != 0) or np.any(r.vprev[c][~live] != 0):
+            problems.append(f"component {c}: states of edges that are not dispersive edges moved")
+    if r.sheet is not None and not (np.isfinite(r.sheet["ib"]).all() and np.all(r.ib_moved.any(axis=0))):
+        problems.append("reference: a sheet edge without branch current")
+    return problems
+
+
+def run_media_case(case, hip, oracle):
+    """hip = None: the reference side alone (what tests/test_media_fuzz_cpu.py steps without a GPU)."""
+    capi = _mod("_capi")
+    flags = {"auto": 0, "direct": capi.FLAG_KERNEL_DIRECT}[case["sched"]]
+    saved = {k: os.environ.pop(k, None) for k in ENV_KNOBS}
+    os.environ.update(case["env"])
+    try:
+        so = media_case_sim(case)
+        ref = _restated(so, oracle, case["seed"])
+        sh = eh = None
+        if hip is not None:
+            sh = media_case_sim(case)
+            eh = sh.build(hip, flags=flags)
+            rng = np.random.default_rng(case["seed"])
+            for kind in (0, 1):
+                for c in range(3):
+                    eh.set_field(kind, c, (1e-3 * rng.standard_normal(eh.local_shape)).astype(np.float32))
+        for nsteps in case["calls"]:
+            ref.run(nsteps)
+            if eh is not None:
+                eh.run(nsteps)
+    finally:
+        for k in ENV_KNOBS:
+            os.environ.pop(k, None)
+            if saved[k] is not None:
+                os.environ[k] = saved[k]
+    problems = media_reference_problems(ref)
+    if eh is None:
+        return problems, {"launches_per_timestep": 0, "lag_planes": 0, "timesteps_per_launch_max": 0}
+    fh, fo = eh.fields(), ref.e.fields()
+    if not np.array_equal(fh, fo):
+        bad = np.argwhere(fh != fo)
+        problems.append(f"fields differ at {len(bad)} of {fo.size} entries, first {tuple(bad[0])}: {fh[tuple(bad[0])]!r} vs {fo[tuple(bad[0])]!r}")
+    else:
+        nzm = fo != 0
+        if not np.array_equal(fh[nzm].view(np.uint32), fo[nzm].view(np.uint32)):
+            problems.append("fields equal as values but not as bits where the reference is non-zero")
+    for c in range(len(ref.w)):
+        hv, hu, hvi = eh.debye_state(c)
+        for name, a, b in (("v_prev", hv, ref.vprev[c]), ("u", hu, ref.u[c]), ("vi", hvi, ref.vi[c])):
+            if not np.array_equal(a, b):
+                bad = np.argwhere(a != b)
+                problems.append(f"Debye {name} of component {c} differs at {len(bad)} of {b.size} entries, first {tuple(bad[0])}: "
+                                f"{a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}")
+    if ref.sheet is not None:
+        hv, hib = eh.sheet_state()
+        if not np.array_equal(hv, ref.sheet["vprev"]) or not np.array_equal(hib, ref.sheet["ib"]):
+            problems.append(f"sheet states differ ({np.count_nonzero(hv != ref.sheet['vprev'])} v_prev, {np.count_nonzero(hib != ref.sheet['ib'])} branch currents)")
+    uh, uo = sh.port_series()[0], so.port_series()[0]
+    for q, name in ((0, "port voltage"), (1, "port current")):
+        a, b = np.asarray(uh[q], float), np.asarray(uo[q], float)
+        if a.shape != b.shape or not np.abs(b).max() > 0 or np.linalg.norm(a - b) > 1e-12 * np.linalg.norm(b):
+            problems.append(f"{name} series differs")
+    ea, eb = np.array(eh.energy()), np.array(ref.e.energy())
+    if np.abs(ea - eb).max() > 1e-12 * np.abs(eb).max():
+        problems.append(f"energy {ea!r} vs {eb!r}")
+    if case["nf2ff"] != "none":
+        bh, bo = sh.nf2ff_boxes(), so.nf2ff_boxes()
+        worst = max(float(np.abs(np.asarray(a) - np.asarray(b)).max()) / max(float(np.abs(b).max()), 1e-300) for a, b in zip(bh, bo))
+        if len(bh) != len(bo) or not worst <= 1e-6:
+            problems.append(f"NF2FF face spectra differ ({worst:.2e} of the largest entry)")
+    info = eh.schedule_info()
+    if info["resident"] or info["launches_per_timestep"] not in (2, 3):
+        problems.append(f"schedule {info}: media and sheets step under two or three launches per timestep")
+    return problems, info
+
+
 def load_libs():
     capi = _mod("_capi")
     so = os.path.join(ROOT, "oracle", "libfdtd_oracle.so")
@@ -240,24 +516,26 @@ def load_libs():
     return capi.load_hip_library(), capi.bind(ctypes.CDLL(so))
 
 
-def run_batch(ncases, seed, hip, oracle, only=None, log=print, slabs=False, mur=False):
+def run_batch(ncases, seed, hip, oracle, only=None, log=print, slabs=False, mur=False, media=False):
     rng = np.random.default_rng(seed)
     failed = []
     for n in range(ncases):
-        case = draw_slab_case(rng) if slabs else draw_case(rng, mur)
+        case = draw_media_case(rng) if media else draw_slab_case(rng) if slabs else draw_case(rng, mur)
         if only is not None and n != only:
             continue
         t0 = time.perf_counter()
         try:
-            problems, info = (run_slab_case if slabs else run_case)(case, hip, oracle)
+            problems, info = (run_media_case if media else run_slab_case if slabs else run_case)(case, hip, oracle)
         except ValueError as exc:      # a drawn set-up the host layer refuses (e.g. layers that leave no room for the NF2FF box)
             log(f"case {n}: skipped ({exc}) {case}")
             continue
         except _mod("_capi").FdtdError as exc:      # an error from the library (a bounded wait that ran out, ...) is a failing case
-            if "(-5): resident schedule" in str(exc) or "(-5): wavefront schedule" in str(exc):    # ... or a grid the schedule asked for by name cannot hold
+            if media:      # ... always with --media: no schedule is forced there that the library may refuse
+                pass
+            elif "(-5): resident schedule" in str(exc) or "(-5): wavefront schedule" in str(exc):    # ... or a grid the schedule asked for by name cannot hold
                 log(f"case {n}: refused ({str(exc)[:120]}) {case}")
                 continue
-            if "not starvation-free" in str(exc):    # ... except a drawn decomposition the library REFUSES: slabs sharing the test GPU that could pin every workgroup slot
+            if not media and "not starvation-free" in str(exc):    # ... except a drawn decomposition the library REFUSES: slabs sharing the test GPU that could pin every workgroup slot
                 log(f"case {n}: refused ({str(exc)[:150]}...) {case}")
                 continue
             log(f"case {n}: FAIL (library error) {case}  -> {exc}")
@@ -278,9 +556,10 @@ def main():
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--slabs", action="store_true", help="decomposed runs: 2 ... 6 P2P slabs in one process against one slab on the oracle")
     ap.add_argument("--mur", action="store_true", help="every case with Mur faces, mostly on the two / three launches per timestep")
+    ap.add_argument("--media", action="store_true", help="scenes with Debye media and / or conducting sheets against the numpy restatement of their corrections")
     args = ap.parse_args()
     hip, oracle = load_libs()
-    failed = run_batch(args.cases, args.seed, hip, oracle, args.only, log=lambda s: print(s, flush=True), slabs=args.slabs, mur=args.mur)
+    failed = run_batch(args.cases, args.seed, hip, oracle, args.only, log=lambda s: print(s, flush=True), slabs=args.slabs, mur=args.mur, media=args.media)
     print(f"{len(failed)} failing case(s) of {args.cases} (seed {args.seed})", flush=True)
     sys.exit(1 if failed else 0)
 

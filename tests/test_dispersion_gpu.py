@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg
-from helpers import patch_sim
+from helpers import patch_sim, seeded_fields
 from test_dispersion_model_cpu import Restated, _fr4, _graded, _grid, restating_build
 
 
@@ -61,7 +61,73 @@ def _sim(name, nr_ts):
         v = _media_scene(g, [("sub", hi_band, (6, 6, 8), (19, 17, 12))], port=(50.0, (12, 11, 8), (12, 11, 12)),
                          sheets=[("cu", 5.8e7, 2e-3, (7, 7, 6), (18, 16, 8)), ("tin", 9.1e6, 5e-6, (9, 8, 12), (16, 15, 12))])
         return sim.Simulation(g, v, boundary="MUR", **kw)
+    if name == "multi-k8-three":
+        # three media with K = 8 / 3 / 1: k_debye<true, 8>, two media padded
+        g = _graded((45, 30, 22), seed=11)
+        v = _media_scene(g, [("a", wide, (3, 3, 3), (17, 26, 18)), ("b", hi_band, (18, 5, 4), (30, 24, 17)), ("c", one, (31, 2, 2), (42, 27, 19))],
+                         port=(50.0, (9, 14, 6), (9, 14, 11)))
+        return sim.Simulation(g, v, boundary="MUR", **kw)
+    if name == "multi-k8-eight":
+        # the most media a context holds, every one with the most poles: medium ids 0 ... 7 in the lanes' bytes
+        g = _graded((76, 20, 16), seed=12)
+        boxes = [(f"m{q}", d.fit_constant_loss_tangent(3.0 + 0.4 * q, 0.01 + 0.004 * q, 9e9, 0.1e9, 30e9, K=8), (2 + 9 * q, 2 + q % 3, 2), (10 + 9 * q, 17 - q % 2, 13))
+                 for q in range(8)]
+        v = _media_scene(g, boxes, port=(50.0, (32, 9, 4), (32, 9, 9)))
+        return sim.Simulation(g, v, boundary="PEC", **kw)
+    if name == "many-blocks":
+        # 41 x 30 x 20 cells of medium: 11 groups of four per row, 27-28 blocks of k_debye per component, the second and third component
+        # start at a non-zero block, the last block of each is partial
+        g = _graded((70, 50, 38), seed=13)
+        v = _media_scene(g, [("m", hi_band, (14, 10, 9), (55, 40, 29))], port=(50.0, (30, 25, 12), (30, 25, 18)),
+                         plain=[("p", 2.2, (10, 9, 6), (60, 42, 32))])
+        return sim.Simulation(g, v, boundary="CPML", cpml_cells=8, **kw)
+    if name in ("slab-to-four-mur", "slab-to-four-pec", "filled-mur", "filled-pec"):
+        # a substrate slab that runs into the four side faces / a medium that fills the grid up to all six: dispersive cells on face nodes
+        g = _graded((23, 21, 19), seed=14)
+        box = ("m", hi_band, (0, 0, 6), (22, 20, 10)) if name.startswith("slab") else ("m", hi_band, (0, 0, 0), (22, 20, 18))
+        v = _media_scene(g, [box], port=(50.0, (11, 10, 6), (11, 10, 10)))
+        return sim.Simulation(g, v, boundary="MUR" if name.endswith("mur") else "PEC", **kw)
     raise KeyError(name)
+
+
+def _x_aligned_sim(x0, x1, nx, nr_ts):
+    """A medium over the cells [x0, x1) of a small PEC grid of nx nodes along x (a hole of plain dielectric inside when there is room)."""
+    sim = pkg("simulation")
+    g = _grid((nx, 11, 10))
+    plain = [("hole", 2.0, (x0 + 2, 4, 3), (x0 + 5, 7, 7))] if x1 - x0 >= 7 else []
+    sc = pkg("scene")
+    x, y, z = (l * 1e3 for l in g.lines)
+    s = sc.Scene(unit=1e-3)
+    m = _fr4(9e9, 5e9, 15e9)
+    s.add_debye_material("m", m.eps_inf, m.kappa, m.delta_eps, m.tau).add_box([x[x0], y[2], z[2]], [x[x1], y[8], z[7]], priority=1)
+    for name, eps, lo, hi in plain:
+        s.add_material(name, eps_r=eps).add_box([x[lo[0]], y[lo[1]], z[lo[2]]], [x[hi[0]], y[hi[1]], z[hi[2]]], priority=2)
+    px = min(max(x0 + 1, 2), nx - 3)
+    s.add_lumped_port(1, 50.0, [x[px], y[5], z[3]], [x[px], y[5], z[6]], "z", 1.0)
+    return sim.Simulation(g, sc.voxelize(s, g), f0=9e9, fc=5e9, boundary="PEC", nr_ts=nr_ts, end_criteria=0.0)
+
+
+def _same_as_restatement(s, e, ref_sim, ref):
+    """Fields, Debye and sheet states and port series of the HIP context `e` (of `s`) against the restatement `ref` (of `ref_sim`), bit
+    for bit; the reference side alone finite, moving, and with every live branch state off zero."""
+    import fuzz_parity
+    assert fuzz_parity.media_reference_problems(ref) == []
+    fo = ref.e.fields()
+    fh = e.fields()
+    assert np.array_equal(fh, fo), f"fields differ at {np.count_nonzero(fh != fo)} entries, first {tuple(np.argwhere(fh != fo)[0])}"
+    assert np.array_equal(fh[fo != 0].view(np.uint32), fo[fo != 0].view(np.uint32))
+    for c in range(len(ref.w)):
+        hv, hu, hvi = e.debye_state(c)
+        assert np.array_equal(hvi, ref.vi[c])
+        assert np.array_equal(hv, ref.vprev[c]), (c, np.count_nonzero(hv != ref.vprev[c]))
+        assert np.array_equal(hu, ref.u[c]), (c, np.count_nonzero(hu != ref.u[c]))
+        off = ref.w[c] == 0
+        assert np.all(hv[off] == 0) and np.all(hu[:, off] == 0)
+    if ref.sheet is not None:
+        hv, hib = e.sheet_state()
+        assert np.array_equal(hv, ref.sheet["vprev"]) and np.array_equal(hib, ref.sheet["ib"])
+    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
+        assert np.abs(qu).max() > 0 and np.abs(qi).max() > 0 and np.array_equal(pu, qu) and np.array_equal(pi, qi)
 
 
 CASES = ["pec-uniform", "pec-uniform-raw", "pec-graded-k8", "mur-graded", "cpml8-graded", "two-media-mur", "media-and-sheets-mur"]
@@ -101,6 +167,121 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name):
         assert min(on) > 0
     if name == "pec-uniform":
         assert s.debye.lo[0][0] == 3 and s.debye.hi[0][0] == 9 and s.grid.shape[0] % 4 != 0
+
+
+# ---- directed cases: what the randomised batch below reaches by chance, by name ---------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,nsteps", [("multi-k8-three", 150), ("multi-k8-eight", 150), ("many-blocks", 80)])
+def test_every_instantiation_and_many_blocks(hip_lib, oracle_lib, name, nsteps):
+    """k_debye<true, 8> (three media of 8 / 3 / 1 poles; eight media of 8 poles) and a launch of 83 blocks whose components start at
+    non-zero blocks, from seeded fields."""
+    ref_sim, s = _sim(name, nsteps), _sim(name, nsteps)
+    ref = Restated(ref_sim, oracle_lib, seed=21)
+    e = s.build(hip_lib)
+    seeded_fields(e, 21)
+    ref.run(nsteps)
+    e.run(nsteps)
+    d = s.debye
+    if name == "many-blocks":
+        blocks = [-(-(w.shape[0] * w.shape[1] * (-(-hi[0] // 4) - lo[0] // 4)) // 256) for w, lo, hi in zip(d.w, d.lo, d.hi)]
+        assert min(blocks) >= 20 and all((w.shape[0] * w.shape[1] * (-(-hi[0] // 4) - lo[0] // 4)) % 256 for w, lo, hi in zip(d.w, d.lo, d.hi)), blocks
+    else:
+        assert d.K == 8 and len(d.media) == (3 if name == "multi-k8-three" else 8)
+        assert all(set(np.unique(d.med[c][d.w[c] != 0])) == set(range(len(d.media))) for c in range(3))
+    _same_as_restatement(s, e, ref_sim, ref)
+
+
+X_ALIGN = [(4 + r0, 12 + r1, 20 + (r0 + 2 * r1 + r0 * r1) % 4) for r0 in range(4) for r1 in range(4)] + \
+          [(0, 9, 18)] + [(5, nx - 1, nx) for nx in (17, 18, 19, 20)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("x0,x1,nx", X_ALIGN, ids=[f"x{a}-{b}-nx{n}" for a, b, n in X_ALIGN])
+def test_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
+    """The library widens every box to multiples of 4 in x: all 16 (x0 mod 4, x1 mod 4), every nx mod 4, the box that starts at x = 0 and
+    the box whose x-edges end at nx - 2 and whose y- / z-edges sit on the last column.  Whole-grid field equality also pins that the
+    widened columns outside the caller's box keep their bits."""
+    nsteps = 60
+    ref_sim, s = _x_aligned_sim(x0, x1, nx, nsteps), _x_aligned_sim(x0, x1, nx, nsteps)
+    assert s.debye.lo[0][0] == x0 and s.debye.hi[0][0] == x1 and s.debye.lo[1][0] == x0 and s.debye.hi[1][0] == min(x1 + 1, nx)
+    ref = Restated(ref_sim, oracle_lib, seed=x0 + 100 * x1)
+    e = s.build(hip_lib)
+    seeded_fields(e, x0 + 100 * x1)
+    ref.run(nsteps)
+    e.run(nsteps)
+    _same_as_restatement(s, e, ref_sim, ref)
+
+
+def test_box_alignment_cases_cover_every_residue():
+    assert {(a % 4, b % 4) for a, b, _ in X_ALIGN[:16]} == {(p, q) for p in range(4) for q in range(4)}
+    assert {n % 4 for _, _, n in X_ALIGN[:16]} == {0, 1, 2, 3} and {n % 4 for _, _, n in X_ALIGN[17:]} == {0, 1, 2, 3}
+
+
+@pytest.mark.gpu
+def test_run_in_chunks(hip_lib, oracle_lib):
+    """fdtd_run in calls of 1, 2, 97 and 100 timesteps (the V-probe launch in front of the corrections, the I-probe flush per call) on
+    media + sheets + a port inside the medium: against ONE restatement run, and against fdtd_half_step on the library itself."""
+    chunks = (1, 2, 97, 100)
+    n = sum(chunks)
+    ref_sim, s, h = (_sim("media-and-sheets-mur", n) for _ in range(3))
+    ref = Restated(ref_sim, oracle_lib, seed=3)
+    e, eh = s.build(hip_lib), h.build(hip_lib)
+    seeded_fields(e, 3)
+    seeded_fields(eh, 3)
+    ref.run(n)
+    for k in chunks:
+        e.run(k)
+        for _ in range(k):
+            eh.half_step(0)
+            eh.half_step(1)
+    _same_as_restatement(s, e, ref_sim, ref)
+    _same_as_restatement(h, eh, ref_sim, ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["slab-to-four-mur", "filled-mur", "slab-to-four-pec", "filled-pec"])
+def test_media_on_grid_faces_under_both_mur_schedules(hip_lib, oracle_lib, monkeypatch, name):
+    """Dispersive cells on the node planes of Mur (and PEC) faces.  Without an apply pass (two launches) the face voltages in memory
+    between update_E and update_H are not the timestep's final ones, and k_debye runs exactly there; with FDTD_MUR_APPLY_PASS=1 (three
+    launches) they are.  Every edge of a face node plane is held by the operator (vi = 0), and such edges are no dispersive edges
+    (fdtd_hip_dispersion.h): fields, probe series and the states of EVERY edge agree among both schedules and the restatement."""
+    nsteps = 120
+    ref_sim = _sim(name, nsteps)
+    ref = Restated(ref_sim, oracle_lib, seed=8)
+    ref.run(nsteps)
+    held = sum(int(np.count_nonzero((ref_sim.debye.w[c] != 0) & (ref.vi[c] == 0))) for c in range(3))
+    assert held > 300, held                      # the edges in question exist, in numbers
+    mur = name.endswith("mur")
+    for apply_pass, want in ((None, 2), ("1", 3 if mur else 2)):
+        if apply_pass is None:
+            monkeypatch.delenv("FDTD_MUR_APPLY_PASS", raising=False)
+        else:
+            monkeypatch.setenv("FDTD_MUR_APPLY_PASS", apply_pass)
+        s = _sim(name, nsteps)
+        e = s.build(hip_lib)
+        assert e.schedule_info()["launches_per_timestep"] == want, e.schedule_info()
+        seeded_fields(e, 8)
+        e.run(nsteps)
+        _same_as_restatement(s, e, ref_sim, ref)
+        for c in range(3):
+            hv, hu, hvi = e.debye_state(c)
+            rest = hvi == 0
+            assert np.all(hv[rest] == 0) and np.all(hu[:, rest] == 0)
+        e.close()
+
+
+@pytest.mark.gpu
+def test_randomised_media_cases_equal_the_restatement(hip_lib, oracle_lib):
+    """The fixed-seed batch of tests/fuzz_parity.py --media (what it covers: tests/test_media_fuzz_cpu.py): drawn grids, boundaries,
+    0 ... 8 media, holes, sheets, a port, NF2FF modes, Mur schedules, tilings and run() calls — fields and all states bit for bit, port
+    series, energy and NF2FF face spectra.  (Further seeds: profiles/dispersion/randomised_media_parity.txt.)"""
+    import fuzz_parity
+    lines = []
+    failed = fuzz_parity.run_batch(fuzz_parity.MEDIA_BATCH[0], fuzz_parity.MEDIA_BATCH[1], hip_lib, oracle_lib, log=lines.append, media=True)
+    ran = [l for l in lines if ": ok " in l or ": FAIL" in l]
+    assert 6 * len(ran) >= 5 * fuzz_parity.MEDIA_BATCH[0], "\n".join(lines)
+    assert not failed, "\n".join(l for l in lines if "FAIL" in l)
+    assert any("launches/ts 3" in l for l in ran) and any("launches/ts 2" in l for l in ran)
 
 
 @pytest.mark.gpu

@@ -31,10 +31,13 @@ def _graded(n=(15, 13, 14), h=1e-3, seed=3):
 
 # ---- the restatement: oracle half-steps + dispersion.correction (+ sheet.correction) ------------------------------------------
 class Restated:
-    """An engine of `lib` (no Debye entry points needed) stepped by half-steps, with the corrections of the Debye media and — after
-    them, as the header orders — of the conducting sheets applied in numpy between the E phase and the H update."""
+    """An engine of `lib` (no Debye / sheet entry points needed) stepped by half-steps, with the corrections of the Debye media and —
+    after them, as the header orders — of the conducting sheets applied in numpy between the E phase and the H update.  A simulation
+    with sheets and no media skips the Debye part (test_sheet_model_cpu.restated_run is this class).  Edges the operator holds at zero
+    (vi == 0: grid faces, metal) are no dispersive edges, as in fdtd_debye_set: their w is taken as 0.  `seed`: seeded noise in all six
+    field components before the first step (helpers.seeded_fields); the states start at zero either way."""
 
-    def __init__(self, sim, lib, flags=0):
+    def __init__(self, sim, lib, flags=0, seed=None):
         saved = sim.debye, sim.sheets
         sim.debye = sim.sheets = None            # the folded operator only: kappa_cells / sheet_lumped stay what they are
         try:
@@ -42,16 +45,18 @@ class Restated:
         finally:
             sim.debye, sim.sheets = saved
         self.sim, d = sim, sim.debye
-        alpha, oma, beta = _disp().tables(d.media, sim.dt)
-        vi_all = self.e.get_operator()[1]
-        self.K = alpha.shape[1]
+        self.K = 0
         self.sl, self.vi, self.w, self.tab, self.u, self.vprev = [], [], [], [], [], []
-        for c in range(3):
+        if d is not None:
+            alpha, oma, beta = _disp().tables(d.media, sim.dt)
+            vi_all = self.e.get_operator()[1]
+            self.K = alpha.shape[1]
+        for c in range(3 if d is not None else 0):
             (i0, j0, k0), (i1, j1, k1) = d.lo[c], d.hi[c]
             sl = (slice(k0, k1), slice(j0, j1), slice(i0, i1))
             self.sl.append(sl)
             self.vi.append(vi_all[c][sl].copy())
-            self.w.append(d.w[c].astype(np.float32))
+            self.w.append(np.where(self.vi[c] == 0, np.float32(0), d.w[c].astype(np.float32)))
             m = d.med[c].astype(np.int64)
             self.tab.append(tuple(np.moveaxis(t[m], -1, 0).copy() for t in (alpha, oma, beta)))     # [K] + box shape
             self.u.append(np.zeros((self.K,) + self.w[c].shape, np.float32))
@@ -61,12 +66,31 @@ class Restated:
             idx, comp, vi, cls, al, b = sim.sheet_tables()
             self.sheet = dict(idx=idx, vi=vi, al=al[cls].T.copy(), b=b[cls].T.copy(), vprev=np.zeros(idx.size, np.float32),
                               ib=np.zeros((al.shape[1], idx.size), np.float32), by_c=[np.nonzero(comp == c)[0] for c in range(3)])
+        if seed is not None:
+            from helpers import seeded_fields
+            seeded_fields(self.e, seed)
+        # which states have been off zero at a checkpoint (after the first step, every eighth, the end of every run()): "the wave reached
+        # this edge".  Asked at checkpoints and not of the final values alone because a + b of the u_k update cancels to exactly 0.0f
+        # about once in 2^24 state updates — twice in 800 drawn cases of ~5e7 states (one step earlier and later the state was ~5e-6).
+        self.nstep = 0
+        self.u_moved = [np.zeros(u.shape, bool) for u in self.u]
+        self.vprev_moved = [np.zeros(v.shape, bool) for v in self.vprev]
+        self.ib_moved = None if self.sheet is None else np.zeros(self.sheet["ib"].shape, bool)
+
+    def note_moved(self):
+        for c in range(len(self.u)):
+            self.u_moved[c] |= self.u[c] != 0
+            self.vprev_moved[c] |= self.vprev[c] != 0
+        if self.sheet is not None:
+            if self.ib_moved is None or self.ib_moved.shape != self.sheet["ib"].shape:      # (a test put its own edge set in)
+                self.ib_moved = np.zeros(self.sheet["ib"].shape, bool)
+            self.ib_moved |= self.sheet["ib"] != 0
 
     def step(self):
         e = self.e
         e.half_step(0)
         Vs = [e.get_field(0, c) for c in range(3)]
-        for c in range(3):
+        for c in range(len(self.w)):
             if self.w[c].size:
                 al, om, be = self.tab[c]
                 Vs[c][self.sl[c]] = _disp().correction(Vs[c][self.sl[c]], self.vi[c], self.w[c], self.vprev[c], self.u[c], al, om, be)
@@ -83,10 +107,14 @@ class Restated:
             e.set_field(0, c, Vs[c])
         self.V = Vs
         e.half_step(1)
+        self.nstep += 1
+        if self.nstep == 1 or self.nstep % 8 == 0:
+            self.note_moved()
 
     def run(self, n):
         for _ in range(int(n)):
             self.step()
+        self.note_moved()
 
 
 def restating_build(monkeypatch):

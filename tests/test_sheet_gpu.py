@@ -53,6 +53,100 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, cl
         assert np.array_equal(pu, qu) and np.array_equal(pi, qi)
 
 
+def _raw_sheet_tables(e, edges):
+    """(idx, comp, vi, cls, alpha, b) of fdtd_sheet_set for hand-picked edges [(comp, i, j, k)]: two poles, one class, vi the operator's."""
+    nz, ny, nx = e.local_shape
+    vi_all = e.get_operator()[1]
+    idx = np.array([(k * ny + j) * nx + i for _, i, j, k in edges], np.int64)
+    comp = np.array([c for c, _, _, _ in edges], np.int8)
+    vi = np.array([vi_all[c][k, j, i] for c, i, j, k in edges], np.float32)
+    return idx, comp, vi, np.zeros(idx.size, np.int32), np.array([[0.9, 0.5]], np.float32), np.array([[2e-5, 1e-4]], np.float32)
+
+
+def _restated_with_raw_sheets(sim, lib, tables, seed):
+    from test_dispersion_model_cpu import Restated
+    r = Restated(sim, lib, seed=seed)
+    idx, comp, vi, cls, al, b = tables
+    r.sheet = dict(idx=idx, vi=vi, al=al[cls].T.copy(), b=b[cls].T.copy(), vprev=np.zeros(idx.size, np.float32),
+                   ib=np.zeros((al.shape[1], idx.size), np.float32), by_c=[np.nonzero(comp == c)[0] for c in range(3)])
+    return r
+
+
+@pytest.mark.gpu
+def test_v_probe_on_a_sheet_edge_is_sampled_before_the_correction(hip_lib, oracle_lib):
+    """fdtd_hip_sheet.h: the correction follows the V-probes.  The scene layer keeps sheet edges off probe lines; the C ABI states no
+    such restriction, so a probe added there must read the voltage BEFORE k_sheet changed it, under fdtd_run as under fdtd_half_step
+    and in the restatement (with fused sources fdtd_run used to sample it in update_H's probe block, after the correction)."""
+    from helpers import seeded_fields
+    from test_dispersion_model_cpu import Restated
+    capi = pkg("_capi")
+    nsteps = 150
+    sims = [cavity_sim(3e5, 1e-3, nr_ts=nsteps) for _ in range(3)]
+    sh = sims[0].sheets
+    on = [int(q) for q in np.nonzero(sims[0].sheet_vi() != 0)[0][[3, 40, 77]]]                  # three sheet edges, live ones
+    idx, comp, w = sh.idx[on], sh.comp[on], np.array([1.0, -0.5, 2.0], np.float32)
+    ref = Restated(sims[0], oracle_lib, seed=4)
+    e_run, e_half = sims[1].build(hip_lib), sims[2].build(hip_lib)
+    pids = [e.add_probe(capi.KIND_V, idx, comp, w) for e in (ref.e, e_run, e_half)]
+    for e in (e_run, e_half):
+        seeded_fields(e, 4)
+    ref.run(nsteps)
+    e_run.run(70)
+    e_run.run(80)
+    for _ in range(nsteps):
+        e_half.half_step(0)
+        e_half.half_step(1)
+    want = ref.e.get_probe(pids[0])[:nsteps]
+    assert np.abs(want).max() > 0 and np.abs(ref.sheet["ib"]).max() > 0
+    # (the correction does change what the probe would read: sampled after it, the series differs)
+    after = sum(float(wq) * float(ref.V[c].reshape(-1)[g]) for wq, c, g in zip(w, comp, idx))
+    assert after != want[-1]
+    assert np.array_equal(e_half.get_probe(pids[2])[:nsteps], want)
+    assert np.array_equal(e_run.get_probe(pids[1])[:nsteps], want)
+    assert np.array_equal(e_run.fields(), ref.e.fields()) and np.array_equal(e_run.sheet_state()[1], ref.sheet["ib"])
+    for (pu, pi), (qu, qi) in zip(sims[1].port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in sims[0]._port_probe_ids]):
+        assert np.array_equal(pu, qu) and np.array_equal(pi, qi)
+
+
+@pytest.mark.gpu
+def test_sheet_edges_on_a_mur_face_node_plane(hip_lib, oracle_lib, monkeypatch):
+    """The scene layer keeps sheets two planes inside Mur faces; fdtd_sheet_set takes any edge.  Edges on the node plane of a Mur face
+    (the operator holds them: vi = 0, so only their states can tell) and live ones inside: k_sheet must read the face's FINAL voltage, so
+    such a context takes the apply pass as a launch of its own — fields and states equal the restatement with the environment asking
+    for either schedule."""
+    from helpers import seeded_fields
+    nsteps = 120
+    edges = [(1, 0, j, k) for j in range(3, 9) for k in range(3, 9)] + [(2, 5, 0, k) for k in range(3, 8)] + \
+            [(1, 6, j, k) for j in range(3, 9) for k in range(4, 7)] + [(0, i, 5, 5) for i in range(3, 9)]
+    mk = lambda: cavity_sim(1.0, 1.0, sheet=False, boundary="MUR", nr_ts=nsteps)
+    ref_sim = mk()
+    from test_dispersion_model_cpu import Restated
+    probe = Restated(ref_sim, oracle_lib)
+    tables = _raw_sheet_tables(probe.e, edges)
+    assert np.count_nonzero(tables[2] == 0) == 36 + 5 and np.count_nonzero(tables[2]) == 18 + 6
+    ref = _restated_with_raw_sheets(mk(), oracle_lib, tables, seed=6)
+    ref.run(nsteps)
+    assert np.all(np.abs(ref.sheet["ib"]).max(axis=0) > 0)
+    for apply_pass in (None, "1"):
+        if apply_pass is None:
+            monkeypatch.delenv("FDTD_MUR_APPLY_PASS", raising=False)
+        else:
+            monkeypatch.setenv("FDTD_MUR_APPLY_PASS", apply_pass)
+        s = mk()
+        e = s.build(hip_lib)
+        e.set_sheets(*[t[41:] if q < 4 else t for q, t in enumerate(tables)])      # the live edges alone: the environment decides
+        assert e.schedule_info()["launches_per_timestep"] == (2 if apply_pass is None else 3)
+        e.set_sheets(*tables)
+        info = e.schedule_info()
+        assert info["launches_per_timestep"] == 3 and not info["resident"], info
+        seeded_fields(e, 6)
+        e.run(nsteps)
+        assert np.array_equal(e.fields(), ref.e.fields())
+        hv, hib = e.sheet_state()
+        assert np.array_equal(hv, ref.sheet["vprev"]) and np.array_equal(hib, ref.sheet["ib"])
+        e.close()
+
+
 @pytest.mark.gpu
 def test_schedules_with_sheets(hip_lib, oracle_lib):
     capi = pkg("_capi")

@@ -232,37 +232,17 @@ def cavity_sim(sigma, t, *, n=(14, 13, 12), boundary="PEC", nr_ts=2000, sheet=Tr
 
 
 def restated_run(sim, lib, nsteps, *, flags=0, energy_every=0):
-    """Oracle half-steps + the numpy correction: (engine, v_prev, branch currents, energies)."""
-    sh = sim.sheets
-    saved, sim.sheets = sim.sheets, None     # the oracle has no sheet entry points: build the (folded) operator only
-    try:
-        e = sim.build(lib, flags=flags)
-    finally:
-        sim.sheets = saved
-    idx, comp, vi, cls, alpha, b = sim.sheet_tables()
-    K = alpha.shape[1]
-    al, bb = alpha[cls].T.copy(), b[cls].T.copy()
-    vprev = np.zeros(idx.size, np.float32)
-    ib = np.zeros((K, idx.size), np.float32)
-    by_c = [np.nonzero(comp == c)[0] for c in range(3)]
+    """Oracle half-steps + the numpy correction: (engine, v_prev, branch currents, energies).  The stepping is the one checker the
+    Debye tests use too (test_dispersion_model_cpu.Restated, which skips the media a simulation does not have)."""
+    from test_dispersion_model_cpu import Restated
+    r = Restated(sim, lib, flags=flags)
     energies = []
     for n in range(nsteps):
-        e.half_step(0)
-        Vs = [e.get_field(0, c) for c in range(3)]
-        V = np.empty(idx.size, np.float32)
-        for c in range(3):
-            V[by_c[c]] = Vs[c].reshape(-1)[idx[by_c[c]]]
-        vnew = _sheet().correction(V, vi, vprev, ib, al, bb)
-        vprev = vnew
-        for c in range(3):
-            if by_c[c].size:
-                Vs[c].reshape(-1)[idx[by_c[c]]] = vnew[by_c[c]]
-                e.set_field(0, c, Vs[c])
-        e.half_step(1)
+        r.step()
         if energy_every and (n + 1) % energy_every == 0:
-            sv, si = e.energy()
+            sv, si = r.e.energy()
             energies.append(8.854187817e-12 * sv + MU0 * si)
-    return e, vprev, ib, np.array(energies)
+    return r.e, r.sheet["vprev"], r.sheet["ib"], np.array(energies)
 
 
 def test_high_conductivity_matches_pec(oracle_lib):
