@@ -32,6 +32,8 @@ SHEET_MAX_K = 8
 DEBYE_SYMBOLS = ["fdtd_debye_set", "fdtd_debye_get"]
 DEBYE_MAX_K = 8
 DEBYE_MAX_MEDIA = 8
+# include/fdtd_hip_lumped.h: lumped R-L-C elements, likewise
+LUMPED_SYMBOLS = ["fdtd_lumped_set", "fdtd_lumped_get"]
 
 
 class FdtdDesc(C.Structure):
@@ -130,7 +132,22 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    lumped_sig = {
+        "fdtd_lumped_set": (C.c_int, [p, C.c_int, p, p, p, p, C.c_int, p, p, p]),
+        "fdtd_lumped_get": (C.c_int, [p, p, p]),
+    }
+    assert sorted(lumped_sig) == sorted(LUMPED_SYMBOLS)
+    for name, (res, args) in lumped_sig.items():    # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_lumped(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the lumped-element entry points (include/fdtd_hip_lumped.h)."""
+    return all(hasattr(lib, n) for n in LUMPED_SYMBOLS)
 
 
 def has_dispersion(lib: C.CDLL) -> bool:
@@ -490,6 +507,34 @@ class Engine:
         ib = np.zeros((K, n), np.float32)
         self._ck(self.lib.fdtd_sheet_get(self._ctx, _ptr(v), _ptr(ib)), "sheet_get")
         return v, ib
+
+    # -- lumped R-L-C elements (include/fdtd_hip_lumped.h) -------------------------------------------
+    def _lumped_lib(self):
+        if not has_lumped(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no lumped elements (fdtd_lumped_set / fdtd_lumped_get)")
+
+    def set_lumped(self, idx, comp, vi, cls, phi, gam, h):
+        """Element edges: global flat node index, component, full vi coefficient, class; phi [ncls][2][2], gam / h [ncls][2]."""
+        self._lumped_lib()
+        idx, comp, vi, cls = _arr(idx, np.int64), _arr(comp, np.int8), _arr(vi, np.float32), _arr(cls, np.int32)
+        phi, gam, h = _arr(phi, np.float32), _arr(gam, np.float32), _arr(h, np.float32)
+        if idx.size == 0:
+            phi, gam, h = phi.reshape(-1, 2, 2), gam.reshape(-1, 2), h.reshape(-1, 2)
+        if (not (idx.size == comp.size == vi.size == cls.size) or phi.ndim != 3 or phi.shape[1:] != (2, 2)
+                or gam.shape != (phi.shape[0], 2) or h.shape != gam.shape):
+            raise ValueError("lumped arrays differ in length / class tables must be phi [ncls][2][2], gam [ncls][2], h [ncls][2]")
+        self._ck(self.lib.fdtd_lumped_set(self._ctx, int(idx.size), _ptr(idx), _ptr(comp), _ptr(vi), _ptr(cls), int(phi.shape[0]),
+                                          _ptr(phi), _ptr(gam), _ptr(h)), "lumped_set")
+        self.lumped_n = int(idx.size)
+
+    def lumped_state(self):
+        """(v_prev float32 [n], states float32 [2][n]) of the element edges."""
+        self._lumped_lib()
+        n = getattr(self, "lumped_n", 0)
+        v = np.zeros(n, np.float32)
+        x = np.zeros((2, n), np.float32)
+        self._ck(self.lib.fdtd_lumped_get(self._ctx, _ptr(v), _ptr(x)), "lumped_get")
+        return v, x
 
     # -- Debye media (include/fdtd_hip_dispersion.h) -------------------------------------------------
     def _debye_lib(self):

@@ -273,6 +273,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   hipFree(c->d_probe); hipFree(c->d_box); hipFree(c->tw_v); hipFree(c->tw_i);
   hipFree(c->d_energy); hipFree(c->src_rng); hipFree(c->src_ids);
   sheet_free(c);
+  lumped_free(c);
   debye_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
@@ -815,10 +816,15 @@ static bool mur_post_fusable(const fdtd_ctx* c, bool multi, bool fused) {
 // k_sheet runs between the two launches and reads and writes V: a sheet edge on the node plane of an enabled face takes the apply pass
 // too (the header's order: Mur passes, then the correction).  k_debye needs no such rule: the operator holds vi = 0 on every edge of a
 // grid face, and fdtd_debye_set leaves those edges out (their V is never the correction's to change, their states never act).
+// k_lumped is a sparse correction as k_sheet is: the two questions the planner has are asked of "a sheet or lumped edge".
+static bool correction_on_face(const fdtd_ctx* c, int f) { return ((c->sheet_faces | c->lumped_faces) >> f) & 1u; }   // (0 without edges)
+static bool correction_at(const fdtd_ctx* c, int off) {   // an edge of a sparse correction on the node at local offset `off`
+  return std::binary_search(c->h_sheet_off.begin(), c->h_sheet_off.end(), off) || std::binary_search(c->h_lumped_off.begin(), c->h_lumped_off.end(), off);
+}
 static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
   if (!c->mur_no_apply || !mur_post_fusable(c, multi, fused)) return false;
   for (int f = 0; f < 6; ++f)
-    if (c->mur[f].on && c->sheet_n > 0 && ((c->sheet_faces >> f) & 1u)) return false;
+    if (c->mur[f].on && correction_on_face(c, f)) return false;
   const int dim[3] = {c->d.nx, c->d.ny, c->d.nk};
   auto on_face = [&](const int lo[3], const int hi[3]) {
     for (int f = 0; f < 6; ++f) {
@@ -853,6 +859,7 @@ static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
 static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
   if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
   if (c->debye_nmedia > 0) return false;   // Debye media: likewise
+  if (c->lumped_n > 0) return false;       // lumped elements: likewise
   const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
                                       wf_lag_for(c) >= c->d.nk);
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
@@ -890,7 +897,7 @@ static bool wavefront_active(const fdtd_ctx* c, bool fused) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lumped_n > 0) return false;
   if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -961,14 +968,15 @@ struct StepPlan {
 // of a timestep are otherwise sampled by the probe blocks of update_H, i.e. after the corrections: wrong as soon as a correction changes
 // a voltage a probe reads.  Debye media are volumes (ports sit inside substrates): always.  Sheet edges are few and the scene layer keeps
 // them off the probe lines: only when a V-probe cell sits on the node of a sheet edge (whatever the components: cheap and on the safe side).
+// Lumped-element edges: as the sheets'.
 static bool probes_first(const fdtd_ctx* c) {
   if (c->nprobe == 0) return false;
   if (c->debye_nmedia > 0) return true;
-  if (c->sheet_n <= 0) return false;
+  if (c->sheet_n <= 0 && c->lumped_n <= 0) return false;
   for (int q = 0; q < c->nprobe; ++q) {
     if (c->probe[q].kind != FDTD_KIND_V) continue;
     for (int off : c->h_prb_off[q])
-      if (std::binary_search(c->h_sheet_off.begin(), c->h_sheet_off.end(), off)) return true;
+      if (correction_at(c, off)) return true;
   }
   return false;
 }
@@ -992,6 +1000,11 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
       return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: the two-launch schedule only (their correction runs between the E phase and the H update)");
     if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: single slab only (world = 1, no p2p transport, no linked contexts)");
+  }
+  if (c->lumped_n > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: the two-launch schedule only (their correction runs between the E phase and the H update)");
+    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: single slab only (world = 1, no p2p transport, no linked contexts)");
   }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";
@@ -1276,6 +1289,7 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     if ((r = phase_E(c, pl, pe, n))) return r;
     launch_debye(c, c->stream);   // Debye media: after the whole E phase, before the sheets' correction and the H update (no-op without media)
     launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
+    launch_lumped(c, c->stream);  // lumped elements: behind the sheets' correction, before the H update (no-op without elements)
     if (multi && (r = exchange(c, FDTD_HALO_E_DOWN, pl.rccl_inline))) return r;
     if ((r = phase_H(c, pl, pe, n))) return r;
     if (multi && (r = exchange(c, FDTD_HALO_H_UP, pl.rccl_inline))) return r;
@@ -1397,6 +1411,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_dft(c, FDTD_KIND_V, c->step, s);
     launch_debye(c, s);
     launch_sheet(c, s);
+    launch_lumped(c, s);
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);

@@ -257,6 +257,13 @@ struct fdtd_ctx {
   float* sheet_vprev = nullptr; float* sheet_ib = nullptr; float* sheet_alpha = nullptr; float* sheet_b = nullptr;
   std::vector<int> h_sheet_off;   // the sheet edges' local offsets, sorted (host copy): does a V-probe cell sit on a sheet edge's node?
   unsigned sheet_faces = 0;       // bit f: a sheet edge lies on the node plane of grid face f (x-, x+, y-, y+, z-, z+)
+  // lumped R-L-C elements (lumped.hip, include/fdtd_hip_lumped.h): per edge offset, component, vi, class, v_prev and the two states
+  // [2][n]; per class phi [ncls][2][2], gam and h [ncls][2]
+  int lumped_n = 0;
+  int* lumped_off = nullptr; int8_t* lumped_comp = nullptr; float* lumped_vi = nullptr; int* lumped_cls = nullptr;
+  float* lumped_vprev = nullptr; float* lumped_x = nullptr; float* lumped_phi = nullptr; float* lumped_gam = nullptr; float* lumped_h = nullptr;
+  std::vector<int> h_lumped_off;  // as h_sheet_off
+  unsigned lumped_faces = 0;      // as sheet_faces
   // Debye media (dispersion.hip, include/fdtd_hip_dispersion.h): per component one dense box of edges, x range widened to
   // multiples of 4; w, vi, v_prev [n] and u [K][n] over the widened box, medium ids when there are several media; the per-medium
   // tables alpha, 1 - alpha, beta as [3][MAX_MEDIA * MAX_K] floats on the device
@@ -316,6 +323,17 @@ void res_free(fdtd_ctx* c);
 // sheet.hip: conducting sheets — the sparse correction after the E phase (no-op without sheets)
 void launch_sheet(fdtd_ctx* c, hipStream_t s);
 void sheet_free(fdtd_ctx* c);
+int sparse_edges_check(fdtd_ctx* c, const char* who, int n, const int64_t* idx, const int8_t* comp, const int32_t* cls, int ncls,
+                       std::vector<int>* off, std::vector<int8_t>* comp_out, std::vector<int>* cls_out, unsigned* faces);
+template <class T>
+inline hipError_t sparse_upload(T** dst, const std::vector<T>& v) {   // the arrays of a sparse correction: allocate and fill
+  hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T));
+  if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+  return e;
+}
+// lumped.hip: lumped R-L-C elements — the sparse correction after the E phase, behind launch_sheet (no-op without elements)
+void launch_lumped(fdtd_ctx* c, hipStream_t s);
+void lumped_free(fdtd_ctx* c);
 // dispersion.hip: Debye media — the dense correction after the E phase, in front of launch_sheet (no-op without media)
 void launch_debye(fdtd_ctx* c, hipStream_t s);
 void debye_free(fdtd_ctx* c);

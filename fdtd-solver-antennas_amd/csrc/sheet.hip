@@ -39,14 +39,38 @@ __global__ __launch_bounds__(256) void k_sheet(SheetArgs a) {
   a.vprev[e] = v;
 }
 
-template <class T>
-hipError_t upload(T** dst, const std::vector<T>& v) {
-  hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T));
-  if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  return e;
-}
-
 }  // namespace
+
+// The edge list of a sparse correction (conducting sheets here, lumped elements in lumped.hip): every edge inside the grid and
+// existing, classes in range, no edge twice.  Out: local offsets, components and classes as the kernels take them, and the grid
+// faces whose node plane holds an edge (bit f: x-, x+, y-, y+, z-, z+) — what the planner asks (api.hip).
+int sparse_edges_check(fdtd_ctx* c, const char* who, int n, const int64_t* idx, const int8_t* comp, const int32_t* cls, int ncls,
+                       std::vector<int>* off_out, std::vector<int8_t>* comp_out, std::vector<int>* cls_out, unsigned* faces_out) {
+  const int64_t gplane = (int64_t)c->d.nx * c->d.ny;
+  const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
+  std::vector<int> off(n), cl(n);
+  std::vector<int8_t> cp(n);
+  std::vector<int64_t> keys(n);
+  unsigned faces = 0;
+  for (int e = 0; e < n; ++e) {
+    const int64_t g = idx[e];
+    if (g < 0 || g >= gplane * c->d.nz || comp[e] < 0 || comp[e] > 2 || cls[e] < 0 || cls[e] >= ncls)
+      return fdtd_fail(c, FDTD_E_ARG, "%s: edge %d out of range", who, e);
+    const int64_t k = g / gplane, r = g - k * gplane, j = r / c->d.nx, i = r - j * c->d.nx;
+    const int64_t pos[3] = {i, j, k};
+    if (pos[comp[e]] >= nn[comp[e]] - 1) return fdtd_fail(c, FDTD_E_ARG, "%s: edge %d does not exist", who, e);
+    keys[e] = g * 3 + comp[e];
+    for (int a = 0; a < 3; ++a) faces |= (pos[a] == 0 ? 1u : 0u) << (2 * a) | (pos[a] == nn[a] - 1 ? 1u : 0u) << (2 * a + 1);
+    off[e] = (int)((k - c->d.k0) * c->plane + j * c->P + i);
+    cp[e] = comp[e];
+    cl[e] = cls[e];
+  }
+  std::sort(keys.begin(), keys.end());
+  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fdtd_fail(c, FDTD_E_ARG, "%s: an edge given twice", who);
+  off_out->swap(off); comp_out->swap(cp); cls_out->swap(cl);
+  *faces_out = faces;
+  return FDTD_OK;
+}
 
 void sheet_free(fdtd_ctx* c) {
   hipFree(c->sheet_off); hipFree(c->sheet_comp); hipFree(c->sheet_vi); hipFree(c->sheet_cls);
@@ -77,42 +101,25 @@ int fdtd_sheet_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, c
   if (c->d.world > 1) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: single slab only (world = 1)");
   if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_sheet_set: set the operator first");
   if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_sheet_set: before the first timestep");
-  const int64_t gplane = (int64_t)c->d.nx * c->d.ny;
-  const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
-  std::vector<int> off(n), cl(n);
-  std::vector<int8_t> cp(n);
-  std::vector<float> v(vi, vi + n);
-  std::vector<int64_t> keys(n);
+  std::vector<int> off, cl;
+  std::vector<int8_t> cp;
   unsigned faces = 0;
-  for (int e = 0; e < n; ++e) {
-    const int64_t g = idx[e];
-    if (g < 0 || g >= gplane * c->d.nz || comp[e] < 0 || comp[e] > 2 || cls[e] < 0 || cls[e] >= ncls)
-      return fdtd_fail(c, FDTD_E_ARG, "fdtd_sheet_set: edge %d out of range", e);
-    const int64_t k = g / gplane, r = g - k * gplane, j = r / c->d.nx, i = r - j * c->d.nx;
-    const int64_t pos[3] = {i, j, k};
-    if (pos[comp[e]] >= nn[comp[e]] - 1) return fdtd_fail(c, FDTD_E_ARG, "fdtd_sheet_set: edge %d does not exist", e);
-    keys[e] = g * 3 + comp[e];
-    for (int a = 0; a < 3; ++a) faces |= (pos[a] == 0 ? 1u : 0u) << (2 * a) | (pos[a] == nn[a] - 1 ? 1u : 0u) << (2 * a + 1);
-    off[e] = (int)((k - c->d.k0) * c->plane + j * c->P + i);
-    cp[e] = comp[e];
-    cl[e] = cls[e];
-  }
-  std::sort(keys.begin(), keys.end());
-  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fdtd_fail(c, FDTD_E_ARG, "fdtd_sheet_set: an edge given twice");
+  if (int r = sparse_edges_check(c, "fdtd_sheet_set", n, idx, comp, cls, ncls, &off, &cp, &cl, &faces)) return r;
+  std::vector<float> v(vi, vi + n);
   HIPCK(c, hipSetDevice(c->d.device));
   HIPCK(c, hipStreamSynchronize(c->stream));
   sheet_free(c);
   if (n == 0) return FDTD_OK;
   std::vector<float> al(alpha, alpha + (size_t)ncls * K), bb(b, b + (size_t)ncls * K);
   std::vector<float> zero((size_t)K * n, 0.f);
-  hipError_t e = upload(&c->sheet_off, off);
-  if (e == hipSuccess) e = upload(&c->sheet_comp, cp);
-  if (e == hipSuccess) e = upload(&c->sheet_vi, v);
-  if (e == hipSuccess) e = upload(&c->sheet_cls, cl);
-  if (e == hipSuccess) e = upload(&c->sheet_vprev, std::vector<float>(zero.begin(), zero.begin() + n));
-  if (e == hipSuccess) e = upload(&c->sheet_ib, zero);
-  if (e == hipSuccess) e = upload(&c->sheet_alpha, al);
-  if (e == hipSuccess) e = upload(&c->sheet_b, bb);
+  hipError_t e = sparse_upload(&c->sheet_off, off);
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_comp, cp);
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_vi, v);
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_cls, cl);
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_vprev, std::vector<float>(zero.begin(), zero.begin() + n));
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_ib, zero);
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_alpha, al);
+  if (e == hipSuccess) e = sparse_upload(&c->sheet_b, bb);
   if (e != hipSuccess) {
     sheet_free(c);
     return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "fdtd_sheet_set: %s", hipGetErrorString(e));

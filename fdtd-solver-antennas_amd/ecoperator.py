@@ -38,6 +38,7 @@ class LumpedEdge:
     j: int
     k: int
     G: float  # conductance added to this edge [S]
+    C: float = 0.0  # capacitance added to this edge [F] (a lumped element's capacitor, lumped.py)
 
 
 @dataclass
@@ -217,8 +218,8 @@ def pack_metric_tables(emet, hmet, grid: RectGrid, k0: int = 0, nk: Optional[int
 
 def lumped_overrides(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np.ndarray, dt: float,
                      lumped: Sequence[LumpedEdge], dtype=np.float32):
-    """(global edge index int64, comp int8, vv float32, m float32) of the edges that carry a lumped conductance —
-    the few coefficients the host fixes itself when the operator is built on the device (fdtd_build_operator)."""
+    """(global edge index int64, comp int8, vv float32, m float32) of the edges that carry a lumped conductance (and,
+    for a lumped element's capacitor, a capacitance: eps_e gains C l / A~) — the few coefficients the host fixes itself when the operator is built on the device (fdtd_build_operator)."""
     nx, ny, nz = grid.shape
     edge, comp, o_vv, o_m = [], [], [], []
     for le in lumped:
@@ -230,6 +231,8 @@ def lumped_overrides(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: 
         l = grid.d[c][pos[c]]
         A = grid.dd[a1][pos[a1]] * grid.dd[a2][pos[a2]]
         eps_e = _edge_scalar(eps_r, grid, c, pos) * EPS0
+        if le.C:
+            eps_e = eps_e + le.C * l / A
         kap_e = _edge_scalar(kappa, grid, c, pos)
         C = eps_e * A / l
         G = kap_e * A / l + le.G

@@ -173,6 +173,20 @@ class ContinuousStructure:
         self.properties.append(p)
         return p
 
+    def AddLumpedElement(self, name, ny, caps=True, R=None, C=None, L=None, LEtype=0):
+        """A lumped R-L-C element along direction ``ny`` (lumped.py), CSXCAD's call: ``LEtype`` 0 = R, L, C in parallel, 1 = in
+        series; an absent part is None or NaN.  ``caps``: the two end planes of a box with a cross-section become PEC.  ``AddBox``
+        on the returned property places it."""
+        from .lumped import Element
+        spec = Element(str(name), R, L, C, int(LEtype))          # validates (negative, non-finite, shorts)
+
+        def val(v):
+            return None if v is None else float(v)
+        R, L, C = spec.R, spec.L, spec.C
+        p = CSProperty(self._log, "LumpedElement", name, ny=_AX[ny], caps=bool(caps), R=val(R), C=val(C), L=val(L), LEtype=int(LEtype))
+        self.properties.append(p)
+        return p
+
     def AddDebyeMaterial(self, name, **kw):
         """A multi-pole Debye medium (dispersion.py), mirroring CSXCAD's Debye material property: ``order`` = K poles, ``epsilon``
         = eps_inf, ``kappa``, and per pole the permittivity step and the relaxation time [s] — as sequences (``eps_delta``,
@@ -422,6 +436,13 @@ class openEMS:
                     m.medium.fit_info = getattr(p, "fit_info", None)
                 for b in p.boxes:
                     m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
+            elif p.kind == "LumpedElement":
+                m = sc.add_lumped_element(p.name, p.params["ny"], R=p.params["R"], C=p.params["C"], L=p.params["L"],
+                                          kind=p.params["LEtype"], caps=p.params["caps"])
+                for b in p.boxes:
+                    if not np.allclose(b.matrix, np.eye(4)):
+                        raise ValueError(f"lumped element '{p.name}': transforms of its boxes are not supported")
+                    m.add_box(b.start, b.stop, b.priority)
             else:
                 m = (sc.add_conducting_sheet(p.name, p.params["conductivity"], p.params["thickness"]) if p.kind == "ConductingSheet"
                      else sc.add_metal(p.name))

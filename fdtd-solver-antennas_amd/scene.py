@@ -8,7 +8,9 @@ Yee grid (what [EXT] openEMS does when ``FDTD.Run`` sets up its operator):
   * conducting-sheet boxes (``add_conducting_sheet``: finite conductivity and thickness, sheet.py) -> the edges on the metal's
     surface become sheet edges (surface impedance, stepped by the engine); interior edges stay PEC.  Where metals overlap, the
     highest box priority wins, as for materials;
-  * lumped port  -> per-edge conductance, soft-source edges, voltage line and current loop.
+  * lumped port  -> per-edge conductance, soft-source edges, voltage line and current loop;
+  * lumped element (``add_lumped_element``: R, L, C in parallel or in series, lumped.py) -> the edges of its box along its
+    direction, each with its share of the element; with ``caps`` the two end planes of a box with a cross-section become PEC.
 
 Coordinates are in drawing units (``unit`` metres per unit, 1e-3 in every reference scene).
 """
@@ -22,6 +24,7 @@ from .grid import RectGrid
 from .ecoperator import LumpedEdge
 from . import sheet as _sheet
 from . import dispersion as _disp
+from . import lumped as _lumped
 
 
 @dataclass
@@ -81,11 +84,26 @@ class LumpedPort:
 
 
 @dataclass
+class LumpedElement:
+    """AddLumpedElement(name, ny, caps, R, C, L, LEtype) as plain data: `spec` holds the values and the kind (lumped.Element)."""
+    name: str
+    direction: int            # 0,1,2
+    spec: _lumped.Element = None
+    caps: bool = True
+    boxes: List[Box] = field(default_factory=list)
+
+    def add_box(self, start, stop, priority=0):
+        self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
+        return self
+
+
+@dataclass
 class Scene:
     unit: float = 1e-3
     materials: List[Material] = field(default_factory=list)
     metals: List[Metal] = field(default_factory=list)
     ports: List[LumpedPort] = field(default_factory=list)
+    elements: List[LumpedElement] = field(default_factory=list)
 
     def add_material(self, name, eps_r=1.0, kappa=0.0) -> Material:
         m = Material(name, float(eps_r), float(kappa))
@@ -120,6 +138,17 @@ class Scene:
         return p
 
 
+    def add_lumped_element(self, name, direction, R=None, C=None, L=None, kind="parallel", caps=True) -> LumpedElement:
+        """R [ohm], L [H], C [F] in parallel (kind "parallel" / 0: Y = 1/R + sC + 1/(sL)) or in series ("series" / 1:
+        Z = R + sL + 1/(sC)) between the two ends of its boxes along `direction`; None: the part is absent (lumped.py)."""
+        d = {"x": 0, "y": 1, "z": 2}.get(direction, direction)
+        if d not in (0, 1, 2):
+            raise ValueError(f"lumped element '{name}': direction must be 0..2 or 'x', 'y', 'z'")
+        el = LumpedElement(str(name), int(d), _lumped.Element(str(name), R, L, C, kind), bool(caps))
+        self.elements.append(el)
+        return el
+
+
 @dataclass
 class PortOnGrid:
     port: LumpedPort
@@ -145,6 +174,7 @@ class VoxelScene:
     # Debye media (None: the scene has none): eps_r / kappa hold eps_inf / kappa of their cells — the timestep-dependent part of
     # the fold (kappa += sum_k beta_k) is Simulation's, which knows dt
     debye: Optional[_disp.DebyeEdges] = None
+    elements: Optional[_lumped.LumpedEdges] = None   # lumped-element edges (None: the scene has no lumped element)
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -230,6 +260,7 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
     if any(isinstance(m, ConductingSheet) for m in scene.metals):
         vs = _voxelize_with_sheets(scene, grid, eps, kap)
         vs.debye = debye
+        vs.elements = _elements_on_grid(scene, grid, vs.pec, vs.ports, vs.sheets)
         return vs
     pec = np.zeros((3, nz, ny, nx), dtype=bool)
     for met in scene.metals:
@@ -249,7 +280,7 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
                       slice(off[0], off[0] + edge.shape[2])]
                 pec[c][tuple(sl)] |= edge
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
-    return VoxelScene(eps, kap, pec, ports, debye=debye)
+    return VoxelScene(eps, kap, pec, ports, debye=debye, elements=_elements_on_grid(scene, grid, pec, ports, None))
 
 
 def _box_edges(node: np.ndarray, c: int):
@@ -397,3 +428,89 @@ def _port_on_grid(port: LumpedPort, grid: RectGrid, u: float) -> PortOnGrid:
         v_idx=np.array(v_idx, np.int64), v_comp=np.full(len(v_idx), d, np.int8),
         v_w=np.full(len(v_idx), -sign, np.float32),
         i_idx=i_idx, i_comp=i_comp, i_w=i_w)
+
+
+def _elements_on_grid(scene: Scene, grid: RectGrid, pec: np.ndarray, ports, sheets) -> Optional[_lumped.LumpedEdges]:
+    """The lumped elements' boxes on the mesh, as a port's box: n_ser edges along the direction, n_par parallel lines; one
+    lumped.Element per box with these split factors.  `caps`: the transverse edges of the two end planes inside the cross-section
+    become PEC (`pec` is updated in place, sheet edges among them leave `sheets`) — a line element has none.  Refused (ValueError): a box of zero length, an edge that is
+    PEC, a sheet edge, a port's source edge or voltage-probe line (for the element's edges and for its cap edges), two elements on
+    one edge."""
+    if not scene.elements:
+        return None
+    nx, ny, nz = grid.shape
+    u = scene.unit
+    out = _lumped.LumpedEdges()
+    idx, comp, elem = [], [], []
+    caps = np.zeros_like(pec)
+    cap_of = {}                                   # cap edge key (flat node index * 3 + component) -> element name
+    for el in scene.elements:
+        d = el.direction
+        a1, a2 = (d + 1) % 3, (d + 2) % 3
+        for bx in el.boxes:
+            lo = [grid.snap(a, min(bx.start[a], bx.stop[a]) * u) for a in range(3)]
+            hi = [grid.snap(a, max(bx.start[a], bx.stop[a]) * u) for a in range(3)]
+            if hi[d] <= lo[d]:
+                raise ValueError(f"lumped element '{el.name}': the box at node {tuple(lo)} has zero length along "
+                                 f"{'xyz'[d]} on this mesh")
+            n_ser = hi[d] - lo[d]
+            n_par = (hi[a1] - lo[a1] + 1) * (hi[a2] - lo[a2] + 1)
+            q = len(out.elements)
+            out.elements.append(el.spec.split(n_ser, n_par))
+            for p1 in range(lo[a1], hi[a1] + 1):
+                for p2 in range(lo[a2], hi[a2] + 1):
+                    for s in range(lo[d], hi[d]):
+                        pos = [0, 0, 0]
+                        pos[d], pos[a1], pos[a2] = s, p1, p2
+                        idx.append(grid.flat(*pos)); comp.append(d); elem.append(q)
+            if el.caps:
+                for end in (lo[d], hi[d]):
+                    for t, o in ((a1, a2), (a2, a1)):            # t-directed edges, both end nodes inside the cross-section
+                        for pt in range(lo[t], hi[t]):
+                            for po in range(lo[o], hi[o] + 1):
+                                pos = [0, 0, 0]
+                                pos[d], pos[t], pos[o] = end, pt, po
+                                caps[t, pos[2], pos[1], pos[0]] = True
+                                cap_of.setdefault(grid.flat(*pos) * 3 + t, el.name)
+    out.idx, out.comp, out.elem = np.array(idx, np.int64), np.array(comp, np.int8), np.array(elem, np.int32)
+
+    def where(e):
+        k, r = divmod(int(out.idx[e]), nx * ny)
+        return (f"lumped element '{out.elements[out.elem[e]].name}': the edge at node {(r % nx, r // nx, k)} "
+                f"({'xyz'[out.comp[e]]})")
+
+    key = out.idx * 3 + out.comp
+    uniq, first, count = np.unique(key, return_index=True, return_counts=True)
+    if np.any(count > 1):
+        e = int(np.min(first[count > 1]))
+        other = [int(q) for q in np.nonzero(key == key[e])[0] if q != e][0]
+        raise ValueError(f"{where(e)} also belongs to lumped element '{out.elements[out.elem[other]].name}': two elements on one edge")
+    # cap edges are metal: a port they would short is refused, a conducting-sheet edge among them becomes PEC and leaves the sheets
+    if cap_of:
+        ckey = np.fromiter(cap_of, np.int64, len(cap_of))
+        for p in ports:
+            for what, pidx, pcomp in (("voltage-probe line", p.v_idx, p.v_comp), ("source edge", p.src_idx, p.src_comp)):
+                pk = np.asarray(pidx, np.int64) * 3 + np.asarray(pcomp, np.int64)
+                hit = np.isin(pk, ckey)
+                if hit.any():
+                    kk = int(pk[int(np.argmax(hit))])
+                    k, r = divmod(kk // 3, nx * ny)
+                    raise ValueError(f"lumped element '{cap_of[kk]}': its cap edge at node {(r % nx, r // nx, k)} ({'xyz'[kk % 3]}) is a "
+                                     f"{what} of lumped port {p.port.number}: the port would be shorted (caps=False leaves the end planes open)")
+        if sheets is not None and len(sheets):
+            keep = ~np.isin(sheets.idx * 3 + sheets.comp, ckey)
+            sheets.idx, sheets.comp, sheets.scale, sheets.metal = sheets.idx[keep], sheets.comp[keep], sheets.scale[keep], sheets.metal[keep]
+    pec |= caps
+    hit = pec.reshape(3, -1)[out.comp.astype(np.int64), out.idx]
+    if hit.any():
+        raise ValueError(f"{where(int(np.argmax(hit)))} is PEC: the element would be shorted")
+    if sheets is not None and len(sheets):
+        hit = np.isin(key, sheets.idx * 3 + sheets.comp)
+        if hit.any():
+            raise ValueError(f"{where(int(np.argmax(hit)))} is a conducting-sheet edge")
+    for p in ports:
+        for what, pidx, pcomp in (("voltage-probe line", p.v_idx, p.v_comp), ("source edge", p.src_idx, p.src_comp)):
+            hit = np.isin(key, np.asarray(pidx, np.int64) * 3 + np.asarray(pcomp, np.int64))
+            if hit.any():
+                raise ValueError(f"{where(int(np.argmax(hit)))} is a {what} of lumped port {p.port.number}")
+    return out

@@ -17,6 +17,7 @@ from .grid import RectGrid
 from .scene import VoxelScene
 from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_tables, lumped_overrides, LumpedEdge
 from . import sheet as _sheet
+from . import lumped as _lumped
 from . import dispersion as _disp
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
@@ -132,6 +133,7 @@ class RunStats:
     sheet_fit_error: Optional[float] = None   # largest band error of the sheets' admittance fits (relative)
     schedule: Optional[dict] = None           # the schedule the engine ran (Engine.schedule_info)
     dispersion: Optional[dict] = None         # Debye media stepped by the engine (dispersion.py): media, K, poles, fit errors, edges
+    lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
 
 
 class Simulation:
@@ -241,6 +243,19 @@ class Simulation:
                 on = self.debye.cell_medium == q
                 assert np.all(vox.eps_r[on] == m.eps_inf)
                 self.kappa_cells[on] = m.folded(self.dt)[1]
+        # lumped elements: a plain 1/R and the implicit part g0 of the stepped branch folded into the edges' conductance, a plain C
+        # into their capacitance (lumped-edge overrides); the edges that carry states are stepped by the engine (fdtd_lumped_set)
+        self.elements = vox.elements if getattr(vox, "elements", None) is not None and len(vox.elements) else None
+        self.element_lumped, self.element_stepped = [], np.zeros(0, np.int64)
+        if self.elements is not None:
+            el = self.elements
+            nx, ny, _ = grid.shape
+            fold = [m.discretise(self.dt)[3:] for m in el.elements]
+            k, r = np.divmod(el.idx, nx * ny)
+            j, i = np.divmod(r, nx)
+            self.element_lumped = [LumpedEdge(int(c), int(a), int(b), int(q), float(fold[m][0] + fold[m][1]), float(fold[m][2]))
+                                   for c, a, b, q, m in zip(el.comp, i, j, k, el.elem)]
+            self.element_stepped = el.stepped()
         self.engine: Optional[Engine] = None
         self.lib = None
         self.external_transport = None     # distributed.SlabComm when halos travel through the host
@@ -252,7 +267,7 @@ class Simulation:
         """The operator in its host (numpy) formulation — built on first use; the default product path never asks."""
         if self._op is None:
             v = self.vox
-            self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped)
+            self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped)
         return self._op
 
     # ---------------------------------------------------------------------------------------------
@@ -276,6 +291,8 @@ class Simulation:
             raise ValueError(f"slab of rank {rank} has {nk} planes; need >= 2")
         if self.sheets is not None and world > 1:
             raise _capi.FdtdError("conducting sheets need a single slab (world = 1): a decomposed lossy-metal run is not supported")
+        if self.element_stepped.size and world > 1:
+            raise _capi.FdtdError("lumped elements need a single slab (world = 1): a decomposed run with stepped R-L-C elements is not supported")
         if self.debye is not None and world > 1:
             raise _capi.FdtdError("Debye media need a single slab (world = 1): a decomposed run with dispersive media is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
@@ -284,7 +301,7 @@ class Simulation:
             v = self.vox
             emet, hmet = pack_metric_tables(*metric_lists(g, self.dt), g, k0, nk)
             e.build_operator(g.d, v.eps_r, self.kappa_cells, v.pec, EPS0,
-                             lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped), emet, hmet,
+                             lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped), emet, hmet,
                              prefer_classes=self.use_classes)
             self.operator_form = "raw" if e.operator_form()[0] == "raw" else "classes"
         else:
@@ -300,6 +317,8 @@ class Simulation:
             e.set_debye(*self.debye_tables())
         if self.sheets is not None:
             e.set_sheets(*self.sheet_tables())
+        if self.element_stepped.size:
+            e.set_lumped(*self.lumped_tables())
         if self.cpml is not None:
             e.set_cpml(*self.cpml.for_slab(k0, nk))
         if self.mur_enable.any():
@@ -335,18 +354,43 @@ class Simulation:
         """float32 vi of the sheet edges, as the engine expands it: m (the edge's lumped-edge override, float32) times the separable
         metric ex[i] * (ey[j] * ez[k]) in float32 — the association of ECOperator.raw, which the raw and class forms share.  Evaluated
         for the sheet edges alone (no download of the expanded operator)."""
-        sh, g, v = self.sheets, self.grid, self.vox
-        m = lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, self.sheet_lumped)[3]
+        return self._override_vi(self.sheet_lumped, self.sheets.idx, self.sheets.comp)
+
+    def _override_vi(self, lumped, idx, comp) -> np.ndarray:
+        g, v = self.grid, self.vox
+        m = lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, lumped)[3]
         nx, ny, _ = g.shape
-        k, r = np.divmod(sh.idx, nx * ny)
+        k, r = np.divmod(idx, nx * ny)
         j, i = np.divmod(r, nx)
         emet, _ = metric_lists(g, self.dt)
-        vi = np.empty(len(sh), np.float32)
+        vi = np.empty(idx.size, np.float32)
         for c in range(3):
-            q = np.nonzero(sh.comp == c)[0]
+            q = np.nonzero(comp == c)[0]
             ex, ey, ez = emet[c]
             vi[q] = m[q] * (ex[i[q]] * (ey[j[q]] * ez[k[q]]))
         return vi
+
+    def lumped_vi(self) -> np.ndarray:
+        """float32 vi of the stepped element edges, from the operator this simulation builds (as sheet_vi)."""
+        st, el = self.element_stepped, self.elements
+        return self._override_vi([self.element_lumped[q] for q in st], el.idx[st], el.comp[st])
+
+    def lumped_tables(self):
+        """(idx, comp, vi, cls, phi, gam, h) of fdtd_lumped_set: the element edges that carry states."""
+        st, el = self.element_stepped, self.elements
+        cls, phi, gam, h = _lumped.tables(el.elements, el.elem[st], self.dt)
+        return el.idx[st], el.comp[st], self.lumped_vi(), cls, phi, gam, h
+
+    def lumped_info(self) -> Optional[list]:
+        """What RunStats.lumped reports: per element (box) its values, its edges and split, and for an L-C element the analytic
+        resonance and the one the stepped branch has at this dt (bilinear warping)."""
+        if self.elements is None:
+            return None
+        el = self.elements
+        return [{"name": m.name, "kind": m.kind, "R": m.R, "L": m.L, "C": m.C, "edges": int(np.count_nonzero(el.elem == q)),
+                 "n_ser": m.n_ser, "n_par": m.n_par, "states": m.nstates,
+                 "resonance_hz": m.resonance(), "resonance_warped_hz": m.resonance(self.dt)}
+                for q, m in enumerate(el.elements)]
 
     def sheet_tables(self):
         """(idx, comp, vi, cls, alpha, b) of fdtd_sheet_set."""
@@ -465,6 +509,7 @@ class Simulation:
         stats.sheet_edges = 0 if self.sheets is None else len(self.sheets)
         stats.sheet_fit_error = self.sheet_fit_error
         stats.dispersion = self.dispersion_info()
+        stats.lumped = self.lumped_info()
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
         return stats

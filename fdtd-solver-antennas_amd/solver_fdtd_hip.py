@@ -746,6 +746,8 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
                      "schedule": getattr(st, "schedule", None)}
         if getattr(st, "dispersion", None) is not None:     # Debye media stepped by the engine (substrate_dispersion / AddDebyeMaterial)
             out.stats["dispersion"] = st.dispersion
+        if getattr(st, "lumped", None) is not None:         # lumped R-L-C elements (AddLumpedElement)
+            out.stats["lumped"] = st.lumped
         if verbose:
             print(f"[fdtd-hip] done: {st.steps} steps, {st.mcells_per_s:.0f} MC/s, Dmax {10 * np.log10(Dmax):.2f} dBi", flush=True)
         return out

@@ -25,6 +25,8 @@
  * blocks of update_H, and a sheet edge on the node plane of an enabled Mur face makes the Mur apply pass a launch of its own
  * (three launches per timestep), so that the correction reads the face's final voltage.  (The scene layer places sheets off
  * probe lines and two planes inside Mur faces; neither case costs a context built by it anything.)
+ *
+ * Lumped R-L-C elements — a two-state branch per edge, complex pole pairs included — are fdtd_hip_lumped.h.
  */
 #ifndef FDTD_HIP_SHEET_H
 #define FDTD_HIP_SHEET_H
