@@ -34,6 +34,9 @@ DEBYE_MAX_K = 8
 DEBYE_MAX_MEDIA = 8
 # include/fdtd_hip_lumped.h: lumped R-L-C elements, likewise
 LUMPED_SYMBOLS = ["fdtd_lumped_set", "fdtd_lumped_get"]
+# include/fdtd_hip_magnetic.h: magnetic materials, likewise
+MAGNETIC_SYMBOLS = ["fdtd_magnetic_set", "fdtd_magnetic_get"]
+MAGNETIC_MAX_CLASSES = 255
 
 
 class FdtdDesc(C.Structure):
@@ -142,7 +145,22 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    magnetic_sig = {
+        "fdtd_magnetic_set": (C.c_int, [p, C.c_int, p, p, p, p, p]),
+        "fdtd_magnetic_get": (C.c_int, [p, C.c_int, p, p]),
+    }
+    assert sorted(magnetic_sig) == sorted(MAGNETIC_SYMBOLS)
+    for name, (res, args) in magnetic_sig.items():  # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_magnetic(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the magnetic-material entry points (include/fdtd_hip_magnetic.h)."""
+    return all(hasattr(lib, n) for n in MAGNETIC_SYMBOLS)
 
 
 def has_lumped(lib: C.CDLL) -> bool:
@@ -571,6 +589,39 @@ class Engine:
         v, u, vi = np.zeros(shp, np.float32), np.zeros((K,) + shp, np.float32), np.zeros(shp, np.float32)
         self._ck(self.lib.fdtd_debye_get(self._ctx, int(comp), _ptr(v), _ptr(u), _ptr(vi)), "debye_get")
         return v, u, vi
+
+    # -- magnetic materials (include/fdtd_hip_magnetic.h) --------------------------------------------
+    def _magnetic_lib(self):
+        if not has_magnetic(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no magnetic materials (fdtd_magnetic_set / fdtd_magnetic_get)")
+
+    def set_magnetic(self, a, b, lo, hi, cls):
+        """Class tables a, b: float32 [ncls] of the live classes 1..ncls; per component c the box lo[c] <= (x, y, z) < hi[c] of
+        faces with the class bytes cls[c] over it, [z][y][x] (0: not magnetic; an empty box: the component has no magnetic face).
+        An empty table removes the set."""
+        self._magnetic_lib()
+        a, b = _arr(a, np.float32).ravel(), _arr(b, np.float32).ravel()
+        if a.shape != b.shape:
+            raise ValueError("magnetic tables must be a [ncls], b [ncls]")
+        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
+        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
+        shapes = [tuple(int(max(0, hi_a[c, q] - lo_a[c, q])) for q in (2, 1, 0)) for c in range(3)]
+        cs = [_arr(np.zeros(shapes[c], np.uint8) if 0 in shapes[c] else cls[c], np.uint8) for c in range(3)]
+        for c in range(3):
+            if cs[c].shape != shapes[c]:
+                raise ValueError(f"magnetic component {c}: class bytes must be [z][y][x] over the box, {shapes[c]}")
+        cp = (C.c_void_p * 3)(*[x.ctypes.data for x in cs])
+        self._ck(self.lib.fdtd_magnetic_set(self._ctx, int(a.size), _ptr(a), _ptr(b), _ptr(lo_a), _ptr(hi_a), C.cast(cp, C.c_void_p)),
+                 "magnetic_set")
+        self.magnetic_shapes = shapes if a.size else [(0, 0, 0)] * 3
+
+    def magnetic_state(self, comp: int):
+        """(i_prev [z][y][x], iv0 [z][y][x]) float32 over component comp's box."""
+        self._magnetic_lib()
+        shp = getattr(self, "magnetic_shapes", [(0, 0, 0)] * 3)[comp]
+        ip, iv = np.zeros(shp, np.float32), np.zeros(shp, np.float32)
+        self._ck(self.lib.fdtd_magnetic_get(self._ctx, int(comp), _ptr(ip), _ptr(iv)), "magnetic_get")
+        return ip, iv
 
     # -- fields -------------------------------------------------------------------------------
     def get_field(self, kind: int, comp: int) -> np.ndarray:

@@ -275,6 +275,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   sheet_free(c);
   lumped_free(c);
   debye_free(c);
+  magnetic_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
   hipFree(c->mbox);
@@ -860,6 +861,7 @@ static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
   if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
   if (c->debye_nmedia > 0) return false;   // Debye media: likewise
   if (c->lumped_n > 0) return false;       // lumped elements: likewise
+  if (c->mag_ncls > 0) return false;       // magnetic faces: their correction runs between the H update and whatever reads I next
   const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
                                       wf_lag_for(c) >= c->d.nk);
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
@@ -897,7 +899,7 @@ static bool wavefront_active(const fdtd_ctx* c, bool fused) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lumped_n > 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lumped_n > 0 || c->mag_ncls > 0) return false;
   if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -1005,6 +1007,11 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
       return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: the two-launch schedule only (their correction runs between the E phase and the H update)");
     if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: single slab only (world = 1, no p2p transport, no linked contexts)");
+  }
+  if (c->mag_ncls > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: the two-launch schedule only (their correction runs between the H update and the next E phase)");
+    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: single slab only (world = 1, no p2p transport, no linked contexts)");
   }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";
@@ -1131,6 +1138,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
     if (r) return r;
     launch_update_H(c, nk - 1, nk, step, false, s);
   }
+  launch_magnetic(c, s);   // magnetic faces: after the whole H update, before anything samples I (no-op without faces)
   if (!pl.fused) launch_post(c, FDTD_KIND_I, step, false, s);
   launch_dft(c, FDTD_KIND_I, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_H, s));
@@ -1414,6 +1422,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_lumped(c, s);
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);
+    launch_magnetic(c, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);
     launch_dft(c, FDTD_KIND_I, c->step, s);
     c->step++;
@@ -1943,6 +1952,7 @@ int fdtd_set_field(fdtd_ctx* c, int kind, int comp, const float* in) {
   float* dst = kind == FDTD_KIND_V ? c->p.V[comp] : c->p.I[comp];
   HIPCK(c, hipMemcpy2D(dst, (size_t)c->P * 4, in, (size_t)c->d.nx * 4, (size_t)c->d.nx * 4, (size_t)c->d.nk * c->d.ny,
                        hipMemcpyHostToDevice));
+  if (kind == FDTD_KIND_I) return magnetic_prime(c, comp);   // magnetic faces: i_prev is the I the next H update starts from
   return FDTD_OK;
 }
 

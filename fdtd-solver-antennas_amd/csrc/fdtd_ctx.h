@@ -276,6 +276,17 @@ struct fdtd_ctx {
   int debye_nmedia = 0, debye_K = 0;
   DebyeBox debye_box[3];
   float* debye_tab = nullptr;
+  // magnetic materials (magnetic.hip, include/fdtd_hip_magnetic.h): per component one dense box of faces, x range widened to
+  // multiples of 4; i_prev and one class byte per face over the widened box; the (a, b) pairs of the classes as 256 float2 on the device
+  struct MagBox {
+    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the caller's box
+    int x0w = 0, nxw = 0;                       // widened x range: first node, length (a multiple of 4)
+    size_t n = 0;                               // faces of the widened box (0: the component has none)
+    float* iprev = nullptr; uint8_t* cls = nullptr;
+  };
+  int mag_ncls = 0;                             // live classes (0: no magnetic faces)
+  MagBox mag_box[3];
+  float2* mag_tab = nullptr;
   std::string err;
 };
 
@@ -337,6 +348,10 @@ void lumped_free(fdtd_ctx* c);
 // dispersion.hip: Debye media — the dense correction after the E phase, in front of launch_sheet (no-op without media)
 void launch_debye(fdtd_ctx* c, hipStream_t s);
 void debye_free(fdtd_ctx* c);
+// magnetic.hip: magnetic materials — the dense correction after the H update, in front of everything that samples I (no-op without faces)
+void launch_magnetic(fdtd_ctx* c, hipStream_t s);
+int magnetic_prime(fdtd_ctx* c, int comp);   // i_prev <- the component's I array (fdtd_magnetic_set, fdtd_set_field)
+void magnetic_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

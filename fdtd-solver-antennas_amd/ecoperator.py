@@ -140,8 +140,8 @@ def _edge_average(cellval: np.ndarray, grid: RectGrid, comp: int) -> np.ndarray:
 
 
 def build_operator(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np.ndarray,
-                   dt: float, lumped: Sequence[LumpedEdge] = ()) -> ECOperator:
-    """eps_r, kappa: per cell [nz-1][ny-1][nx-1]; pec: bool [3][nz][ny][nx] (True = PEC edge)."""
+                   dt: float, lumped: Sequence[LumpedEdge] = (), pmc: Optional[Sequence[bool]] = None) -> ECOperator:
+    """eps_r, kappa: per cell [nz-1][ny-1][nx-1]; pec: bool [3][nz][ny][nx] (True = PEC edge); pmc: metric_lists' argument."""
     nx, ny, nz = grid.shape
     if eps_r.shape != (nz - 1, ny - 1, nx - 1) or kappa.shape != eps_r.shape:
         raise ValueError("cell arrays must be [nz-1][ny-1][nx-1]")
@@ -174,7 +174,7 @@ def build_operator(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np
         m_c[dead] = 0.0
         vv[c] = vv_c
         m[c] = m_c
-    emet, hmet = metric_lists(grid, dt)
+    emet, hmet = metric_lists(grid, dt, pmc=pmc)
     op = ECOperator(grid=grid, dt=dt, vv=vv, m=m, emet=emet, hmet=hmet)
     # lumped conductances: (vv, m) of those edges with G_total = kappa*A~/l + G
     edge, comp, o_vv, o_m = lumped_overrides(grid, eps_r, kappa, pec, dt, lumped)
@@ -183,10 +183,15 @@ def build_operator(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np
     return op
 
 
-def metric_lists(grid: RectGrid, dt: float, dtype=np.float32):
+def metric_lists(grid: RectGrid, dt: float, dtype=np.float32, pmc: Optional[Sequence[bool]] = None):
     """Separable metric of the EC operator: vi = m * l[c] / (dd[a1] * dd[a2]);  iv = (dt/mu0) * dd[c] / (d[a1] * d[a2]).
     emet[c][axis], hmet[c][axis] -> 1-D float32 tables over the whole grid (`dtype`: the C ABI takes float32; float64 is what
-    the double-precision checker of the fp32 error budget is handed, tests/helpers.py)."""
+    the double-precision checker of the fp32 error budget is handed, tests/helpers.py).
+
+    `pmc`: six flags (x-, x+, y-, y+, z-, z+), True = a magnetic wall (PMC) on that face.  A PMC face of axis a zeroes the face
+    currents tangential to it on the first dual plane inside the face — index 0 on the low side, n_a - 2 on the high side — by
+    zeroing the axis-a entry of the two tangential components' H tables there (the device of `inv[-1] = 0`).  The wall therefore
+    sits ON that dual plane, half a cell inside the outer node plane; the edges behind it (on the outer node plane) stay dead."""
     emet, hmet = [], []
     for c in range(3):
         et, ht = [None] * 3, [None] * 3
@@ -200,6 +205,10 @@ def metric_lists(grid: RectGrid, dt: float, dtype=np.float32):
                 et[a] = (1.0 / grid.dd[a]).astype(dtype)
                 inv = 1.0 / grid.d[a]
                 inv[-1] = 0.0
+                if pmc is not None and pmc[2 * a]:
+                    inv[0] = 0.0
+                if pmc is not None and pmc[2 * a + 1]:
+                    inv[-2] = 0.0
                 ht[a] = inv.astype(dtype)
         emet.append(et)
         hmet.append(ht)

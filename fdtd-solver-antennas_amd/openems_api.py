@@ -430,7 +430,8 @@ class openEMS:
         sc = Scene(unit=unit)
         for p in csx.properties:
             if p.kind in ("Material", "DebyeMaterial"):
-                m = (sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0)) if p.kind == "Material" else
+                m = (sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0),
+                                     mu_r=p.params.get("mue", 1.0), sigma_m=p.params.get("sigma", 0.0)) if p.kind == "Material" else
                      sc.add_debye_material(p.name, p.params["epsilon"], p.params["kappa"], p.params["eps_delta"], p.params["eps_relax_time"]))
                 if p.kind == "DebyeMaterial":
                     m.medium.fit_info = getattr(p, "fit_info", None)

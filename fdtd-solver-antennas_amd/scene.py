@@ -3,7 +3,8 @@
 antenna_sim/solver_fdtd_openems_fixed.py:176-220) kept as plain data, and its mapping onto the
 Yee grid (what [EXT] openEMS does when ``FDTD.Run`` sets up its operator):
 
-  * material boxes -> per-cell eps_r / kappa (highest priority box containing the cell centre);
+  * material boxes -> per-cell eps_r / kappa and mu_r / sigma_m (highest priority box containing the cell centre; the magnetic
+    pair is turned into face coefficients by magnetic.py);
   * metal boxes (PEC, any thickness incl. zero) -> every edge with both end nodes inside is PEC;
   * conducting-sheet boxes (``add_conducting_sheet``: finite conductivity and thickness, sheet.py) -> the edges on the metal's
     surface become sheet edges (surface impedance, stepped by the engine); interior edges stay PEC.  Where metals overlap, the
@@ -25,6 +26,7 @@ from .ecoperator import LumpedEdge
 from . import sheet as _sheet
 from . import dispersion as _disp
 from . import lumped as _lumped
+from . import magnetic as _magnetic
 
 
 @dataclass
@@ -41,6 +43,8 @@ class Material:
     eps_r: float = 1.0
     kappa: float = 0.0
     boxes: List[Box] = field(default_factory=list)
+    mu_r: float = 1.0        # relative permeability (>= 1) and magnetic loss sigma* [ohm/m]: magnetic.py
+    sigma_m: float = 0.0
 
     def add_box(self, start, stop, priority=0):
         self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
@@ -105,8 +109,11 @@ class Scene:
     ports: List[LumpedPort] = field(default_factory=list)
     elements: List[LumpedElement] = field(default_factory=list)
 
-    def add_material(self, name, eps_r=1.0, kappa=0.0) -> Material:
-        m = Material(name, float(eps_r), float(kappa))
+    def add_material(self, name, eps_r=1.0, kappa=0.0, mu_r=1.0, sigma_m=0.0) -> Material:
+        """mu_r >= 1 and sigma_m >= 0 (magnetic loss sigma* [ohm/m]) make the material magnetic (magnetic.py); anisotropic
+        (sequence), negative or non-finite values and mu_r < 1 are refused."""
+        _magnetic.check_material(name, mu_r, sigma_m)
+        m = Material(name, float(eps_r), float(kappa), mu_r=float(mu_r), sigma_m=float(sigma_m))
         self.materials.append(m)
         return m
 
@@ -175,6 +182,12 @@ class VoxelScene:
     # the fold (kappa += sum_k beta_k) is Simulation's, which knows dt
     debye: Optional[_disp.DebyeEdges] = None
     elements: Optional[_lumped.LumpedEdges] = None   # lumped-element edges (None: the scene has no lumped element)
+    # magnetic materials (None: mu_r = 1, sigma_m = 0 everywhere): per cell, same priority rule as eps_r; cell_material indexes
+    # material_names (-1: background) so that a refusal can name the material
+    mu_r: Optional[np.ndarray] = None
+    sigma_m: Optional[np.ndarray] = None
+    cell_material: Optional[np.ndarray] = None
+    material_names: Optional[List[str]] = None
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -228,6 +241,9 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
     tol = _tol(grid)
     eps = np.ones((nz - 1, ny - 1, nx - 1))
     kap = np.zeros_like(eps)
+    mur = np.ones_like(eps)
+    sgm = np.zeros_like(eps)
+    cmat = np.full(eps.shape, -1, dtype=np.int32)
     prio = np.full(eps.shape, -(1 << 30), dtype=np.int64)
     centers = [grid.centers(a) for a in range(3)]
     # Debye materials with identical parameters are one medium (as sheets of one metal are one surface)
@@ -243,7 +259,7 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
     if len(media) > _disp.MAX_MEDIA:
         raise ValueError(f"{len(media)} different Debye media: at most {_disp.MAX_MEDIA}")
     cmed = np.full(eps.shape, -1, dtype=np.int8) if media else None
-    for mat in scene.materials:
+    for qm, mat in enumerate(scene.materials):
         mid = medium_of[mat.medium.key()] if isinstance(mat, DebyeMaterial) else -1
         for bx in mat.boxes:
             r = _inside_mask(bx, u, -tol, centers)     # strict: a cell centre on the surface is outside
@@ -254,12 +270,15 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
             win = mask & (prio[sl] <= bx.priority)
             e = eps[sl]; k = kap[sl]; p = prio[sl]
             e[win] = mat.eps_r; k[win] = mat.kappa; p[win] = bx.priority
+            mur[sl][win] = mat.mu_r; sgm[sl][win] = mat.sigma_m; cmat[sl][win] = qm
             if cmed is not None:
                 cmed[sl][win] = mid
     debye = _disp.make_edges(grid, media, media_names, cmed) if media and np.any(cmed >= 0) else None
+    magnetic = dict(mu_r=mur, sigma_m=sgm, cell_material=cmat, material_names=[m.name for m in scene.materials])
     if any(isinstance(m, ConductingSheet) for m in scene.metals):
         vs = _voxelize_with_sheets(scene, grid, eps, kap)
         vs.debye = debye
+        vs.mu_r, vs.sigma_m, vs.cell_material, vs.material_names = mur, sgm, cmat, magnetic["material_names"]
         vs.elements = _elements_on_grid(scene, grid, vs.pec, vs.ports, vs.sheets)
         return vs
     pec = np.zeros((3, nz, ny, nx), dtype=bool)
@@ -280,7 +299,7 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
                       slice(off[0], off[0] + edge.shape[2])]
                 pec[c][tuple(sl)] |= edge
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
-    return VoxelScene(eps, kap, pec, ports, debye=debye, elements=_elements_on_grid(scene, grid, pec, ports, None))
+    return VoxelScene(eps, kap, pec, ports, debye=debye, elements=_elements_on_grid(scene, grid, pec, ports, None), **magnetic)
 
 
 def _box_edges(node: np.ndarray, c: int):

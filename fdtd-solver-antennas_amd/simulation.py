@@ -19,6 +19,7 @@ from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_ta
 from . import sheet as _sheet
 from . import lumped as _lumped
 from . import dispersion as _disp
+from . import magnetic as _magnetic
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox
@@ -89,8 +90,12 @@ def slab_partition(costs: Sequence[float], world: int, min_planes: int = 2):
 
 @dataclass
 class BoundarySpec:
-    """Per face (x-,x+,y-,y+,z-,z+): 'PEC', 'MUR' or 'CPML' (reference strings 'MUR' / 'PML_8',
-    solver_fdtd_openems_microstrip_3d.py:84)."""
+    """Per face (x-,x+,y-,y+,z-,z+): 'PEC', 'PMC', 'MUR' or 'CPML' (reference strings 'MUR' / 'PML_8',
+    solver_fdtd_openems_microstrip_3d.py:84; openEMS numbers 0 = PEC, 1 = PMC, 2 = MUR, 3 = PML_8).
+
+    A 'PMC' face is a magnetic wall: the tangential face currents of the first dual plane inside the face are held at zero
+    (ecoperator.metric_lists), so the wall sits half a cell inside the outer node plane — a symmetry plane of a mirror-symmetric
+    scene lies midway between the first two node lines of that side.  The edges on the outer node plane stay dead."""
     kinds: Sequence[str] = ("CPML",) * 6
     cpml_cells: int = 10
     cpml: CPMLSpec = field(default_factory=CPMLSpec)
@@ -111,12 +116,19 @@ class BoundarySpec:
                     cells = int(s.split("_")[1])
             elif s in ("PEC", "0"):
                 kinds.append("PEC")
+            elif s in ("PMC", "1"):
+                kinds.append("PMC")
             else:
                 raise ValueError(f"unsupported boundary '{b}'")
         return cls(tuple(kinds), 8 if cells is None else cells)
 
     def face_cells(self):
         return tuple(self.cpml_cells if k == "CPML" else 0 for k in self.kinds)
+
+    def pmc_faces(self):
+        """Six flags for ecoperator.metric_lists, or None without a PMC face."""
+        f = tuple(k == "PMC" for k in self.kinds)
+        return f if any(f) else None
 
 
 @dataclass
@@ -134,6 +146,7 @@ class RunStats:
     schedule: Optional[dict] = None           # the schedule the engine ran (Engine.schedule_info)
     dispersion: Optional[dict] = None         # Debye media stepped by the engine (dispersion.py): media, K, poles, fit errors, edges
     lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
+    magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
 
 
 class Simulation:
@@ -154,6 +167,10 @@ class Simulation:
         self.device_operator = device_operator
         self._op: Optional[ECOperator] = None
         cells = self.bc.face_cells()
+        self.pmc = self.bc.pmc_faces()
+        if self.pmc is not None and nf2ff_freqs is not None:
+            raise ValueError("an NF2FF box together with a PMC face is not supported: the far field of the mirror image is not added "
+                             "— run the whole structure, or leave the NF2FF box out")
         self.cpml = None
         if any(cells):
             spec = CPMLSpec(**{**self.bc.cpml.__dict__, "cells": cells})
@@ -243,6 +260,17 @@ class Simulation:
                 on = self.debye.cell_medium == q
                 assert np.all(vox.eps_r[on] == m.eps_inf)
                 self.kappa_cells[on] = m.folded(self.dt)[1]
+        # magnetic materials: per-cell mu_r / sigma_m -> face coefficients at this dt -> classes and boxes; the operator stays the
+        # base one (ii = 1, iv0), the faces are corrected by the engine after every H update (fdtd_magnetic_set)
+        self.magnetic = None
+        sgm = None if getattr(vox, "mu_r", None) is None else vox.sigma_m if vox.sigma_m is not None else np.zeros_like(vox.mu_r)
+        if sgm is not None and (np.any(vox.mu_r != 1.0) or np.any(sgm != 0.0)):
+            _magnetic.check_cells(grid, vox.mu_r, sgm, cells, vox.cell_material, vox.material_names)
+            media = []
+            if vox.cell_material is not None and vox.material_names is not None:
+                on = (vox.mu_r != 1.0) | (sgm != 0.0)
+                media = [vox.material_names[q] for q in np.unique(vox.cell_material[on]) if q >= 0]
+            self.magnetic = _magnetic.make_faces(grid, vox.mu_r, sgm, self.dt, media)
         # lumped elements: a plain 1/R and the implicit part g0 of the stepped branch folded into the edges' conductance, a plain C
         # into their capacitance (lumped-edge overrides); the edges that carry states are stepped by the engine (fdtd_lumped_set)
         self.elements = vox.elements if getattr(vox, "elements", None) is not None and len(vox.elements) else None
@@ -267,7 +295,8 @@ class Simulation:
         """The operator in its host (numpy) formulation — built on first use; the default product path never asks."""
         if self._op is None:
             v = self.vox
-            self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped)
+            walls = {} if self.pmc is None else {"pmc": self.pmc}
+            self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, **walls)
         return self._op
 
     # ---------------------------------------------------------------------------------------------
@@ -295,11 +324,13 @@ class Simulation:
             raise _capi.FdtdError("lumped elements need a single slab (world = 1): a decomposed run with stepped R-L-C elements is not supported")
         if self.debye is not None and world > 1:
             raise _capi.FdtdError("Debye media need a single slab (world = 1): a decomposed run with dispersive media is not supported")
+        if self.magnetic is not None and world > 1:
+            raise _capi.FdtdError("magnetic materials need a single slab (world = 1): a decomposed run with magnetic media is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
             v = self.vox
-            emet, hmet = pack_metric_tables(*metric_lists(g, self.dt), g, k0, nk)
+            emet, hmet = pack_metric_tables(*metric_lists(g, self.dt, pmc=self.pmc), g, k0, nk)
             e.build_operator(g.d, v.eps_r, self.kappa_cells, v.pec, EPS0,
                              lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped), emet, hmet,
                              prefer_classes=self.use_classes)
@@ -319,6 +350,8 @@ class Simulation:
             e.set_sheets(*self.sheet_tables())
         if self.element_stepped.size:
             e.set_lumped(*self.lumped_tables())
+        if self.magnetic is not None:
+            e.set_magnetic(*self.magnetic.tables())
         if self.cpml is not None:
             e.set_cpml(*self.cpml.for_slab(k0, nk))
         if self.mur_enable.any():
@@ -403,6 +436,14 @@ class Simulation:
         d = self.debye
         alpha, oma, beta = _disp.tables(d.media, self.dt)
         return alpha, oma, beta, d.lo, d.hi, [w.astype(np.float32) for w in d.w], d.med
+
+    def magnetic_info(self) -> Optional[dict]:
+        """What RunStats.magnetic reports: the magnetic media, the (a, b) classes, the faces per component and their boxes."""
+        if self.magnetic is None:
+            return None
+        m = self.magnetic
+        return {"media": list(m.media), "classes": m.ncls, "faces": m.faces(), "lo": [list(map(int, v)) for v in m.lo],
+                "hi": [list(map(int, v)) for v in m.hi], "box_faces": [int(c.size) for c in m.cls]}
 
     def dispersion_info(self) -> Optional[dict]:
         """What RunStats.dispersion reports: per medium the poles and, for fitted media, the fit's errors."""
@@ -510,6 +551,7 @@ class Simulation:
         stats.sheet_fit_error = self.sheet_fit_error
         stats.dispersion = self.dispersion_info()
         stats.lumped = self.lumped_info()
+        stats.magnetic = self.magnetic_info()
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
         return stats
