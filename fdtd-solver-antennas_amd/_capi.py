@@ -37,6 +37,8 @@ LUMPED_SYMBOLS = ["fdtd_lumped_set", "fdtd_lumped_get"]
 # include/fdtd_hip_magnetic.h: magnetic materials, likewise
 MAGNETIC_SYMBOLS = ["fdtd_magnetic_set", "fdtd_magnetic_get"]
 MAGNETIC_MAX_CLASSES = 255
+# include/fdtd_hip_traffic.h: which memory-traffic shortcuts a context took, likewise
+TRAFFIC_SYMBOLS = ["fdtd_traffic_info"]
 
 
 class FdtdDesc(C.Structure):
@@ -155,7 +157,19 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    traffic_sig = {"fdtd_traffic_info": (C.c_int, [p, p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)])}
+    assert sorted(traffic_sig) == sorted(TRAFFIC_SYMBOLS)
+    for name, (res, args) in traffic_sig.items():   # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_traffic_info(lib: C.CDLL) -> bool:
+    """Whether `lib` exports fdtd_traffic_info (include/fdtd_hip_traffic.h)."""
+    return all(hasattr(lib, n) for n in TRAFFIC_SYMBOLS)
 
 
 def has_magnetic(lib: C.CDLL) -> bool:
@@ -487,6 +501,17 @@ class Engine:
                 "blocks_per_sweep": int(a[3]),
                 "transport": ("none", "p2p", "rccl", "linked", "external")[int(a[4])] if 0 <= a[4] <= 4 else None,
                 "xcd_shares_weighted": bool(a[5]), "xcd_adaptations": int(a[6]), "timesteps_per_launch_max": int(a[7])}
+
+    def traffic_info(self) -> dict:
+        """Inert CPML indices skipped per axis and side, distinct class rows (0: per-cell bytes) and the estimate of bytes per
+        timestep saved (fdtd_traffic_info, include/fdtd_hip_traffic.h; libfdtd_hip.so only)."""
+        if not has_traffic_info(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no fdtd_traffic_info")
+        a = np.zeros(6, np.int32)
+        rows, saved = C.c_int32(0), C.c_int64(0)
+        self._ck(self.lib.fdtd_traffic_info(self._ctx, _ptr(a), C.byref(rows), C.byref(saved)), "traffic_info")
+        return {"psi_skipped": {ax: {"E": int(a[2 * n]), "H": int(a[2 * n + 1])} for n, ax in enumerate("xyz")},
+                "class_rows": int(rows.value), "bytes_saved_per_timestep": int(saved.value)}
 
     def comm_nranks(self) -> int:
         """Ranks of the RCCL communicator attached to this context (0: none)."""

@@ -12,6 +12,8 @@
 #include <chrono>
 #include <vector>
 
+#include "host_tables.hpp"
+#include "../../include/fdtd_hip_traffic.h"
 #include "kernel_common.hpp"   // fdtd_ctx.h + the device helpers of the mailbox protocol (self-test kernels below)
 
 static thread_local std::string g_err;
@@ -229,6 +231,8 @@ int fdtd_create(const fdtd_desc* d, fdtd_ctx** out) {
   if (const char* v = getenv("FDTD_RESIDENT")) c->res_mode = atoi(v) ? 1 : 0;          // 1: the resident schedule whenever it is possible, 0: never
   if (const char* v = getenv("FDTD_RES_CHUNK")) c->res_chunk = std::max(1, std::min(4096, atoi(v)));
   if (const char* v = getenv("FDTD_WF_MULTI")) c->wf_multi = std::max(1, std::min(4096, atoi(v)));   // timesteps per launch at most (1: one launch per timestep)
+  if (const char* v = getenv("FDTD_CLASS_ROWS")) c->class_rows_on = atoi(v) != 0;     // 0 = per-cell class bytes (A/B, tests)
+  if (const char* v = getenv("FDTD_PSI_ACTIVE")) c->psi_trim_on = atoi(v) != 0;       // 0 = the whole psi storage ranges stay active (A/B)
   if (const char* v = getenv("FDTD_OCC_H")) c->occ_h = std::max(0, std::min(16, atoi(v)));
   if (const char* v = getenv("FDTD_P2P_FAULT_STEP")) c->p2p_fault_step = atoll(v);   // test hook: see fdtd_run
   if (const char* v = getenv("FDTD_WF_FAULT_STEP")) c->wf_fault_step = atoll(v);   // test hook: the H blocks of that step wait for flags nobody sets (bounded wait -> error word)
@@ -256,8 +260,8 @@ void fdtd_destroy(fdtd_ctx* c) {
   if (c->comm_stream) hipStreamSynchronize(c->comm_stream);
   if (c->comm) ncclCommDestroy((ncclComm_t)c->comm);
   for (int n = 0; n < 6; ++n) hipFree(c->fieldbase[n]);
-  hipFree(c->vv); hipFree(c->vi); hipFree(c->ii); hipFree(c->iv); hipFree(c->ecls); hipFree(c->lut); hipFree(c->met);
-  hipFree(c->cpcoef); hipFree(c->xc_tab);
+  hipFree(c->vv); hipFree(c->vi); hipFree(c->ii); hipFree(c->iv); hipFree(c->ecls); hipFree(c->erow); hipFree(c->epat); hipFree(c->lut); hipFree(c->met);
+  hipFree(c->cpcoef); hipFree(c->xc_tab); hipFree(c->pml_act);
   hipFree(c->xstamp);
   res_free(c);
   hipFree(c->wf_flags); hipFree(c->wf_err); hipFree(c->wf_flagsH); hipFree(c->wf_prb_sp); hipFree(c->wf_prb_blk); hipFree(c->wf_prb_rng);
@@ -303,7 +307,30 @@ int fdtd_set_operator_raw(fdtd_ctx* c, const float* vv, const float* vi, const f
     HIPCK(c, upload_rows(*dst[n], c->P, src[n], c->d.nx, rows));
   }
   c->p.vv = c->vv; c->p.vi = c->vi; c->p.ii = c->ii; c->p.iv = c->iv;
-  c->have_op = true; c->raw_op = true; c->op_nclasses = 0;
+  c->have_op = true; c->raw_op = true; c->packed_op = false; c->op_nclasses = 0;
+  return build_class_rows(c);
+}
+
+// Row form of the packed class bytes (DevParams::erow / epat): the bytes come back from the device once — whoever wrote them,
+// fdtd_set_operator_classes or fdtd_build_operator —, the rows of P bytes are deduplicated on the host (host_tables.hpp) and the row
+// offsets and patterns go up.  Per-cell form when the operator is not packed, the patterns exceed 1 MiB or $FDTD_CLASS_ROWS=0.
+extern "C++" int build_class_rows(fdtd_ctx* c) {
+  hipFree(c->erow); hipFree(c->epat);
+  c->erow = nullptr; c->epat = nullptr; c->class_rows = 0;
+  c->p.erow = nullptr; c->p.epat = nullptr;
+  if (!c->have_op || c->raw_op || !c->packed_op || !c->class_rows_on) return FDTD_OK;
+  const size_t nrows = (size_t)c->d.nk * c->d.ny, P = (size_t)c->P;
+  std::vector<uint8_t> bytes(nrows * P);
+  HIPCK(c, hipMemcpy(bytes.data(), c->ecls, bytes.size(), hipMemcpyDeviceToHost));
+  std::vector<int32_t> ids;
+  std::vector<uint8_t> pats;
+  if (!host_tables::dedup_rows(bytes.data(), nrows, P, P, (size_t)1 << 20, &ids, &pats)) return FDTD_OK;
+  for (auto& v : ids) v *= (int32_t)P;   // byte offset of the pattern
+  pats.resize(pats.size() + 64, 0);      // slack, as ecls has
+  HIPCK(c, to_device(&c->erow, ids));
+  HIPCK(c, to_device(&c->epat, pats));
+  c->class_rows = (int)((pats.size() - 64) / P);
+  c->p.erow = c->erow; c->p.epat = c->epat;
   return FDTD_OK;
 }
 
@@ -366,7 +393,7 @@ int fdtd_set_operator_classes(fdtd_ctx* c, const uint8_t* ecls, int ncls, const 
   c->p.ecls = c->ecls; c->p.lut = c->lut;
   c->have_op = true; c->raw_op = false;
   c->op_nclasses = ncls;
-  return FDTD_OK;
+  return build_class_rows(c);
 }
 
 int fdtd_set_cpml(fdtd_ctx* c, const int32_t* sx, const int32_t* sy, const int32_t* sz, int nsx, int nsy, int nsz,
@@ -463,6 +490,20 @@ int fdtd_set_cpml(fdtd_ctx* c, const int32_t* sx, const int32_t* sy, const int32
         c->psi[(eh * 3 + comp) * 2 + w] = ptr;
         (eh ? c->p.psiH : c->p.psiE)[comp][w] = ptr;
       }
+  // active sub-ranges per (axis, side), from the tables as handed in: the inert ends of the storage ranges are skipped along y and z
+  // (kernel_common.hpp pml_slot_act); the storage slots, nslot and the psi layout above stay what they are
+  std::vector<int4> act(6);
+  for (int a = 0; a < 3; ++a)
+    for (int eh = 0; eh < 2; ++eh) {
+      const float* t[3] = {host.data() + tab_off[a][eh][0], host.data() + tab_off[a][eh][1], host.data() + tab_off[a][eh][2]};
+      const int lo = c->p.pml_lo[a], hi = std::min(c->p.pml_hi[a], nn[a]);
+      const host_tables::ActiveRanges full = host_tables::full_ranges(nn[a], lo, hi);
+      const host_tables::ActiveRanges r = (a == 0 || !c->psi_trim_on) ? full : host_tables::trim_active(t[0], t[1], t[2], nn[a], lo, hi);
+      act[2 * a + eh] = make_int4(r.a0, r.a1 - r.a0, r.b0, r.b1 - r.b0);
+      c->psi_skipped[a][eh] = full.count() - r.count();
+    }
+  HIPCK(c, to_device(&c->pml_act, act));
+  c->p.pml_act = c->pml_act;
   c->have_cpml = (nsx + nsy + nsz) > 0;
   xcd_shares_reset(c);   // the layers decide what a block costs
   return FDTD_OK;
@@ -1760,6 +1801,23 @@ int fdtd_p2p_link_info(fdtd_ctx* c, int which, int32_t info[8]) {
   if (!c || !info || (which != 0 && which != 1)) return fdtd_fail(c, FDTD_E_ARG, "bad link query");
   const bool attached = which == 0 ? c->peer_lo != nullptr : c->peer_hi != nullptr;
   for (int q = 0; q < 8; ++q) info[q] = attached ? c->link_info[which][q] : -1;
+  return FDTD_OK;
+}
+
+int fdtd_traffic_info(fdtd_ctx* c, int32_t skipped[6], int32_t* class_rows, int64_t* bytes_saved) {
+  if (!c || !skipped || !class_rows || !bytes_saved) return fdtd_fail(c, FDTD_E_ARG, "null argument");
+  const int64_t nx4 = c->P, ny = c->d.ny, nk = c->d.nk;
+  int64_t saved = 0;
+  for (int a = 0; a < 3; ++a)
+    for (int eh = 0; eh < 2; ++eh) {
+      const int n = c->have_cpml ? c->psi_skipped[a][eh] : 0;
+      skipped[2 * a + eh] = n;
+      // two psi arrays per (axis, side), each read and written once per timestep: 16 B per cell of a skipped plane (z) or row (y)
+      saved += (int64_t)n * 16 * nx4 * (a == 2 ? ny : a == 1 ? nk : 0);
+    }
+  *class_rows = c->class_rows;
+  if (c->class_rows > 0) saved += nk * ny * nx4 - nk * ny * 4;   // one byte per cell became one row offset per (k, j); the patterns stay on chip
+  *bytes_saved = saved;
   return FDTD_OK;
 }
 

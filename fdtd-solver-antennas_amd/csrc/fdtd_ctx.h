@@ -76,11 +76,20 @@ struct DevParams {
   const uint8_t* ecls;       // class mode: [3][nloc] one byte per edge; packed mode: [nloc] one byte per cell
   const float2* lut;         // class mode: [256] (vv, m); packed mode: [256][3] (vv, m) per component
   int lut_n;                 // entries actually used (only these are staged in LDS)
+  // packed mode, row form (null: per-cell bytes): the rows of ecls are almost all copies of a few — erow[k * ny + j] is the byte offset
+  // of row (k, j)'s pattern in epat (distinct rows of P bytes, at most 1 MiB: L1 / L2 resident instead of 1 B per cell from the fabric)
+  const int* erow; const uint8_t* epat;
   const float* emet[3][3];   // [comp][axis], x tables padded to P with zeros
   const float* hmet[3][3];
   // CPML: index q along axis a is in a layer iff q < pml_lo[a] (slot q) or q >= pml_hi[a]
   // (slot q - pml_hi[a] + pml_hi_slot[a]); pml_hi[a] >= n_a disables the upper layer.
   int pml_lo[3], pml_hi[3], pml_hi_slot[3], nslot[3];
+  // ... and does something there only inside the ACTIVE sub-ranges of the side (E-located / H-located tables): pml_act[2 * axis + side] =
+  // {begin, length} of the low and of the high one.  The slot ranges above are storage; the indices trimmed off their ends have b = 0,
+  // c = 0, 1 / kappa = 1 (fdtd_set_cpml, host_tables.hpp) and are treated as "no layer here" along y and z.  The x axis pays by line, not
+  // by cell: not trimmed.  A device table read through the scalar cache where it is used (pml_slot_act): k_step holds the E and the H
+  // body, and sixteen more kernel-argument scalars live across both cost its Mur variants their registers (the parameter block went to scratch).
+  const int4* pml_act;
   // x-directed psi: element offset of (k, j, i0) = k * xplane + j * xrs + (i0 < pml_lo[0] ? xlo_off + i0 : xhi_off + i0 - pml_hi[0])
   int xrs, xplane, xlo_off, xhi_off;
   const float* cp[3][2][3];  // [axis][E-loc/H-loc][b, c, 1/kappa]
@@ -202,6 +211,12 @@ struct fdtd_ctx {
   std::map<std::pair<int, int>, XcdShare> xcd_cache;   // (first plane, planes) of a launch -> its shares
   float *vv = nullptr, *vi = nullptr, *ii = nullptr, *iv = nullptr;
   uint8_t* ecls = nullptr;
+  int* erow = nullptr; uint8_t* epat = nullptr;   // row form of the packed class bytes (build_class_rows)
+  int class_rows = 0;            // distinct rows (0: per-cell form)
+  bool class_rows_on = true;     // $FDTD_CLASS_ROWS=0 keeps the per-cell form
+  bool psi_trim_on = true;       // $FDTD_PSI_ACTIVE=0 keeps the whole storage ranges active
+  int4* pml_act = nullptr;       // device table DevParams::pml_act
+  int psi_skipped[3][2] = {};    // inert indices trimmed per (axis, E / H side)
   float2* lut = nullptr;
   float* met = nullptr;          // packed metric tables
   bool have_op = false, raw_op = false, packed_op = false;
@@ -291,6 +306,7 @@ struct fdtd_ctx {
 };
 
 int fdtd_fail(fdtd_ctx* c, int code, const char* fmt, ...);
+int build_class_rows(fdtd_ctx* c);   // api.hip: after the class bytes changed — the row form of the packed bytes, or back to per-cell
 #define HIPCK(c, expr)                                                                       \
   do {                                                                                       \
     hipError_t e_ = (expr);                                                                  \

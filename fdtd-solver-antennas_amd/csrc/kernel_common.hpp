@@ -387,6 +387,22 @@ __device__ __forceinline__ void add_elem(float4& v, int e, float a) {
 __device__ __forceinline__ int pml_slot(const DevParams& p, int a, int q) {
   return q < p.pml_lo[a] ? q : (q >= p.pml_hi[a] ? q - p.pml_hi[a] + p.pml_hi_slot[a] : -1);
 }
+// ... of the indices where the layer DOES something (DevParams::pml_act), -1 elsewhere.  The storage ranges hold indices whose
+// coefficients are the identity (b = 0, c = 0, 1 / kappa = 1: PEC-backed boundary nodes, the node where the layer begins, the last
+// H index); there psi <- 0 * psi + 0 * d = +-0 and d <- 1 * d + psi = d for finite fields, so leaving out the psi loads, the arithmetic
+// and the psi stores changes at most the SIGN OF AN EXACT ZERO (d = -0, psi = +0 gives +0), which no == comparison sees and which
+// cannot change a non-zero value downstream.  The four bounds come by one scalar load where they are needed (an immutable 96-byte table,
+// scalar-cache hits) and live in SGPRs for the two compares only: scalar compares for z (k is block-uniform), SGPR operands for y.
+__device__ __forceinline__ int4 sload_int4(const int4* q) {
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  v4i v;
+  asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(q));
+  return make_int4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ int pml_slot_act(const DevParams& p, int a, int eh, int q) {
+  const int4 r = sload_int4(p.pml_act + (2 * a + eh));
+  return (unsigned)(q - r.x) < (unsigned)r.y ? q : ((unsigned)(q - r.z) < (unsigned)r.w ? q - p.pml_hi[a] + p.pml_hi_slot[a] : -1);
+}
 
 // psi <- b*psi + c*d ; d <- d/kappa + psi   for the four cells of a thread (row-uniform coefficients)
 __device__ __forceinline__ void cpml_row4(float4& d, float* base, const unsigned o, float b, float c, float ik) {
@@ -544,10 +560,19 @@ __device__ __forceinline__ int psi_off_y(const DevParams& p, const int k, const 
   const int sy = pml_slot(p, 1, j);
   return sy < 0 ? -1 : (k * p.nslot[1] + sy) * p.P + i0;
 }
+// The same for the update kernels, which skip the inert ends of the storage ranges (pml_slot_act); eh: E-located (0) / H-located (1) side
+__device__ __forceinline__ int psi_off_z(const DevParams& p, const int eh, const int k, const int j, const int i0) {
+  const int sz = pml_slot_act(p, 2, eh, k);
+  return sz < 0 ? -1 : (sz * p.ny + j) * p.P + i0;
+}
+__device__ __forceinline__ int psi_off_y(const DevParams& p, const int eh, const int k, const int j, const int i0) {
+  const int sy = pml_slot_act(p, 1, eh, j);
+  return sy < 0 ? -1 : (k * p.nslot[1] + sy) * p.P + i0;
+}
 // Slots 2,3 take the z-directed pair in the z-layer planes (block-uniform: a block lies in one plane) and the y-directed
 // pair elsewhere; where both layers meet (edges, corners) the y pair is loaded directly, after the differences, as before.
 template <bool DEV = false>
-__device__ __forceinline__ void psi_stage_issue(const DevParams& p, float* const (&psi)[3][2], const unsigned stage, const bool valid,
+__device__ __forceinline__ void psi_stage_issue(const DevParams& p, float* const (&psi)[3][2], const int eh, const unsigned stage, const bool valid,
                                                 const int k, const int j, const int i0) {
   if (!valid) return;
   const int ox = psi_off_x(p, k, j, i0);
@@ -555,12 +580,12 @@ __device__ __forceinline__ void psi_stage_issue(const DevParams& p, float* const
     glds16o_t<DEV>(psi[1][1], (unsigned)ox, stage);
     glds16o_t<DEV>(psi[2][0], (unsigned)ox, stage + 1024u);
   }
-  const int oz = psi_off_z(p, k, j, i0);   // >= 0 for the whole block or for none of it (a block lies in one plane)
+  const int oz = psi_off_z(p, eh, k, j, i0);   // >= 0 for the whole block or for none of it (a block lies in one plane)
   if (oz >= 0) {
     glds16o_t<DEV>(psi[0][1], (unsigned)oz, stage + 2048u);
     glds16o_t<DEV>(psi[1][0], (unsigned)oz, stage + 3072u);
-  } else {                                  // outside the z layers the same two slots take the y-directed pair
-    const int oy = psi_off_y(p, k, j, i0);
+  } else {                                  // outside the (active) z layers the same two slots take the y-directed pair
+    const int oy = psi_off_y(p, eh, k, j, i0);
     if (oy >= 0) {
       glds16o_t<DEV>(psi[0][0], (unsigned)oy, stage + 2048u);
       glds16o_t<DEV>(psi[2][1], (unsigned)oy, stage + 3072u);
@@ -572,7 +597,7 @@ template <bool DEV = false>
 __device__ __forceinline__ void psi_stage_apply(const DevParams& p, float* const (&psi)[3][2], const int eh, const float4* s_psi, const float* s_xc,
                                                 const bool xc_lds, const int k, const int j, const int i0,
                                                 float4& dzA, float4& dzB, float4& dxA, float4& dxB, float4& dyA, float4& dyB) {
-  const int ox = psi_off_x(p, k, j, i0), oz = psi_off_z(p, k, j, i0);   // recomputed, not carried: registers
+  const int ox = psi_off_x(p, k, j, i0), oz = psi_off_z(p, eh, k, j, i0);   // recomputed, not carried: registers
   const float4* mine = s_psi + (threadIdx.x >> 6) * (PSI_SLOTS * 64) + (threadIdx.x & 63u);
   // one psi array at a time, fenced: the scheduler would otherwise keep all four staged values and the coefficient vectors
   // live at once, and this kernel has no registers to spare
@@ -588,7 +613,7 @@ __device__ __forceinline__ void psi_stage_apply(const DevParams& p, float* const
       sto4_t<DEV>(psi[1][0], (unsigned)oz, ps);
     }
     __builtin_amdgcn_sched_barrier(0);
-    const int oy = psi_off_y(p, k, j, i0);
+    const int oy = psi_off_y(p, eh, k, j, i0);
     if (oy >= 0) {
       const float b = p.cp[1][eh][0][j], c = p.cp[1][eh][1][j], ik = p.cp[1][eh][2][j];
       cpml_row4_t<DEV>(dyA, psi[0][0], (unsigned)oy, b, c, ik);
@@ -596,7 +621,7 @@ __device__ __forceinline__ void psi_stage_apply(const DevParams& p, float* const
       cpml_row4_t<DEV>(dyB, psi[2][1], (unsigned)oy, b, c, ik);
     }
   } else {         // elsewhere the stage holds the y pair
-    const int oy = psi_off_y(p, k, j, i0);
+    const int oy = psi_off_y(p, eh, k, j, i0);
     if (oy >= 0) {
       const float b = p.cp[1][eh][0][j], c = p.cp[1][eh][1][j], ik = p.cp[1][eh][2][j];
       float4 ps = mine[2 * 64];

@@ -184,7 +184,7 @@ __device__ __forceinline__ void body_E(const DevParams& p, const int strip, cons
     if (srng.y > srng.x && !dense) stage_sources(p, p.src_ids, srng.x, srng.y - srng.x, step, s_src);
   }
   if (PML && FDTD_PSI_STAGE)   // psi of the x / z layers: LDS-DMA right behind the field loads (kernel_common.hpp)
-    psi_stage_issue<MULTI>(p, p.psiE, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
+    psi_stage_issue<MULTI>(p, p.psiE, 0, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
   if (dep_in) {   // H halo of step-1 (tag = step + 1; for step 0 the neighbour's INITIAL top plane, pushed by k_p2p_prime); slot of the parity of the step that produced it
     const float* mb = p.mb_in_H + (size_t)((step + 1) & 1) * 2 * mb_slot_words(p);
     mb_pull2(mb, mb + mb_slot_words(p), (unsigned)(j * p.P + i0), (unsigned)step + 1u + p.p2p_tag_bias, ix_km, iy_km, p.p2p_err, p.p2p_limit,
@@ -217,14 +217,14 @@ __device__ __forceinline__ void body_E(const DevParams& p, const int strip, cons
     if (FDTD_PSI_STAGE) {
       psi_stage_apply<MULTI>(p, p.psiE, 0, s_psi, s_xc, xc_lds, k, j, i0, dx2, dy1, dy2, dz1, dx1, dz2);
     } else {
-      const int sy = pml_slot(p, 1, j);
+      const int sy = pml_slot_act(p, 1, 0, j);
       if (sy >= 0) {
         const float b = p.cp[1][0][0][j], c = p.cp[1][0][1][j], ik = p.cp[1][0][2][j];
         const int o = (k * p.nslot[1] + sy) * p.P + i0;
         cpml_row4(dx1, p.psiE[0][0], (unsigned)o, b, c, ik);
         cpml_row4(dz2, p.psiE[2][1], (unsigned)o, b, c, ik);
       }
-      const int sz = pml_slot(p, 2, k);
+      const int sz = pml_slot_act(p, 2, 0, k);
       if (sz >= 0) {
         const float b = p.cp[2][0][0][k], c = p.cp[2][0][1][k], ik = p.cp[2][0][2][k];
         const int o = (sz * p.ny + j) * p.P + i0;
@@ -266,7 +266,10 @@ __device__ __forceinline__ void body_E(const DevParams& p, const int strip, cons
   // at once), which costs the variant without CPML branches more registers than its occupancy target has (it spilled).
   const int nsrc_t = (FUSE && !dense) ? srng.y - srng.x : 0;
   uchar4 cc = make_uchar4(0, 0, 0, 0);
-  if (COEF == 2) cc = *reinterpret_cast<const uchar4*>(p.ecls + off);
+  if (COEF == 2) {   // row form: the row's pattern by its offset (plain loads of immutable data, L1 / L2 hits), else one byte per cell
+    if (p.erow != nullptr) cc = *reinterpret_cast<const uchar4*>(p.epat + (unsigned)(p.erow[k * p.ny + j] + i0));
+    else cc = *reinterpret_cast<const uchar4*>(p.ecls + off);
+  }
 #pragma unroll
   for (int comp = 0; comp < 3; ++comp) {
     float4& v = comp == 0 ? vx : (comp == 1 ? vy : vz);
@@ -554,7 +557,7 @@ __device__ __forceinline__ void body_H(const DevParams& p, const int strip, cons
     }
     ix = ldo4(p.I[0], uo); iy = ldo4(p.I[1], uo); iz = ldo4(p.I[2], uo);
     if (staged)
-      psi_stage_issue(p, p.psiH, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
+      psi_stage_issue(p, p.psiH, 1, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
   } else {
     // wavefront block: everything that does not depend on this launch's E blocks first (I, psi), then the flags of the E
     // blocks this block reads from, then V with device-scope (sc1) loads — they bypass this CU's L1, which no other CU's
@@ -562,7 +565,7 @@ __device__ __forceinline__ void body_H(const DevParams& p, const int strip, cons
     if (!MULTI) {
       ix = ldo4(p.I[0], uo); iy = ldo4(p.I[1], uo); iz = ldo4(p.I[2], uo);
       if (staged)
-        psi_stage_issue(p, p.psiH, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
+        psi_stage_issue(p, p.psiH, 1, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
     }
     // MUR: the E blocks whose CANDIDATES this block loads, too.  Away from the y and z faces these are E blocks it waits for anyway — a candidate
     // it reads was written by the thread of the same cells (x faces; the row / plane in front of an upper face) —; a block that holds a row or a
@@ -588,7 +591,7 @@ __device__ __forceinline__ void body_H(const DevParams& p, const int strip, cons
       if (back_target && p.wf_prb_sp != nullptr && sload_int(p.wf_prb_sp + (k * p.nstrips + strip)) != 0) wf_wait_probes(p, FDTD_KIND_I, back_target);
       ix = ldb4_dev(dev_buf(p.I[0]), uo << 2, 0u); iy = ldb4_dev(dev_buf(p.I[1]), uo << 2, 0u); iz = ldb4_dev(dev_buf(p.I[2]), uo << 2, 0u);
       if (staged)
-        psi_stage_issue<true>(p, p.psiH, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
+        psi_stage_issue<true>(p, p.psiH, 1, __builtin_amdgcn_readfirstlane(lds_off(s_psi) + (threadIdx.x >> 6) * (PSI_SLOTS * 1024u)), valid, k, j, i0);
     }
     if (MUR) {
       mx = mur_load_V<true>(p, k, j, i0, uo, ip_load, vx, vy, vz, vz_jp, vx_jp, vy_kp, vx_kp, vz_ip, vy_ip, *mh, (int)(step & 1));
@@ -637,14 +640,14 @@ __device__ __forceinline__ void body_H(const DevParams& p, const int strip, cons
     if (FDTD_PSI_STAGE) {
       psi_stage_apply<MULTI>(p, p.psiH, 1, s_psi, s_xc, xc_lds, k, j, i0, dx2, dy1, dy2, dz1, dx1, dz2);
     } else {
-      const int sy = pml_slot(p, 1, j);
+      const int sy = pml_slot_act(p, 1, 1, j);
       if (sy >= 0) {
         const float b = p.cp[1][1][0][j], c = p.cp[1][1][1][j], ik = p.cp[1][1][2][j];
         const int o = (k * p.nslot[1] + sy) * p.P + i0;
         cpml_row4(dx1, p.psiH[0][0], (unsigned)o, b, c, ik);
         cpml_row4(dz2, p.psiH[2][1], (unsigned)o, b, c, ik);
       }
-      const int sz = pml_slot(p, 2, k);
+      const int sz = pml_slot_act(p, 2, 1, k);
       if (sz >= 0) {
         const float b = p.cp[2][1][0][k], c = p.cp[2][1][1][k], ik = p.cp[2][1][2][k];
         const int o = (sz * p.ny + j) * p.P + i0;

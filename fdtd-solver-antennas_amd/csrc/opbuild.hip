@@ -367,7 +367,7 @@ int fdtd_build_operator(fdtd_ctx* c, const double* dx, const double* dy, const d
     c->op_nclasses = 0;
   }
   HIPCK(c, hipGetLastError());
-  return FDTD_OK;
+  return build_class_rows(c);
 }
 
 int fdtd_operator_form(fdtd_ctx* c, int* form, int* nclasses) {

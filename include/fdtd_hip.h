@@ -193,7 +193,11 @@ int fdtd_get_operator(fdtd_ctx* ctx, float* vv, float* vi, float* ii, float* iv)
 /* CPML.  slot_a[idx] >= 0 gives the psi storage slot of index idx along axis a (-1: no psi).
  * coef: [3 axes][2 (0: E-located = node, 1: H-located = half node)][3 (b, c, 1/kappa)][n_a]
  * stored axis after axis with n_x = nx, n_y = ny, n_z = nk (LOCAL).  Outside the layers b=c=0, 1/kappa=1.
- *   psi = b*psi + c*d ;  term = (1/kappa)*d + psi     for every difference d along that axis. */
+ *   psi = b*psi + c*d ;  term = (1/kappa)*d + psi     for every difference d along that axis.
+ * A slot is storage, not a promise of work: libfdtd_hip.so trims, per axis and per side, both ends of the two slot ranges
+ * while b == 0, c == 0 (either sign of zero) and 1/kappa == 1.0f in the tables it is handed, and along y and z its update
+ * kernels treat a trimmed index as one without psi (there psi = +-0 and term = d for finite fields: at most the sign of an
+ * exact zero differs).  Slots, nslot and the psi layout stay as declared; fdtd_hip_traffic.h tells what was trimmed. */
 int fdtd_set_cpml(fdtd_ctx* ctx, const int32_t* slot_x, const int32_t* slot_y, const int32_t* slot_z,
                   int nslot_x, int nslot_y, int nslot_z, const float* coef);
 /* First-order Mur on faces {x-,x+,y-,y+,z-,z+}; coeff = (c*dt - d)/(c*dt + d). z faces apply on the
