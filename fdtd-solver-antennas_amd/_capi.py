@@ -32,6 +32,10 @@ SHEET_MAX_K = 8
 DEBYE_SYMBOLS = ["fdtd_debye_set", "fdtd_debye_get"]
 DEBYE_MAX_K = 8
 DEBYE_MAX_MEDIA = 8
+# include/fdtd_hip_lorentz.h: Lorentz / Drude media, likewise
+LORENTZ_SYMBOLS = ["fdtd_lorentz_set", "fdtd_lorentz_get"]
+LORENTZ_MAX_K = 4
+LORENTZ_MAX_MEDIA = 8
 # include/fdtd_hip_lumped.h: lumped R-L-C elements, likewise
 LUMPED_SYMBOLS = ["fdtd_lumped_set", "fdtd_lumped_get"]
 # include/fdtd_hip_magnetic.h: magnetic materials, likewise
@@ -137,6 +141,16 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    lorentz_sig = {
+        "fdtd_lorentz_set": (C.c_int, [p, C.c_int, C.c_int, p, p, p, p, p, p, p]),
+        "fdtd_lorentz_get": (C.c_int, [p, C.c_int, p, p, p]),
+    }
+    assert sorted(lorentz_sig) == sorted(LORENTZ_SYMBOLS)
+    for name, (res, args) in lorentz_sig.items():   # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     lumped_sig = {
         "fdtd_lumped_set": (C.c_int, [p, C.c_int, p, p, p, p, C.c_int, p, p, p]),
         "fdtd_lumped_get": (C.c_int, [p, p, p]),
@@ -185,6 +199,11 @@ def has_lumped(lib: C.CDLL) -> bool:
 def has_dispersion(lib: C.CDLL) -> bool:
     """Whether `lib` exports the Debye-media entry points (include/fdtd_hip_dispersion.h)."""
     return all(hasattr(lib, n) for n in DEBYE_SYMBOLS)
+
+
+def has_lorentz(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the Lorentz-media entry points (include/fdtd_hip_lorentz.h)."""
+    return all(hasattr(lib, n) for n in LORENTZ_SYMBOLS)
 
 
 def has_sheets(lib: C.CDLL) -> bool:
@@ -614,6 +633,43 @@ class Engine:
         v, u, vi = np.zeros(shp, np.float32), np.zeros((K,) + shp, np.float32), np.zeros(shp, np.float32)
         self._ck(self.lib.fdtd_debye_get(self._ctx, int(comp), _ptr(v), _ptr(u), _ptr(vi)), "debye_get")
         return v, u, vi
+
+    # -- Lorentz / Drude media (include/fdtd_hip_lorentz.h) ------------------------------------------
+    def _lorentz_lib(self):
+        if not has_lorentz(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no Lorentz media (fdtd_lorentz_set / fdtd_lorentz_get)")
+
+    def set_lorentz(self, phi, gam, h, lo, hi, w, med=None):
+        """Media tables phi: float32 [nmedia][K][2][2], gam, h: [nmedia][K][2]; per component c the box lo[c] <= (x, y, z) < hi[c] of
+        edges with the weights w[c] and medium ids med[c] over it, [z][y][x] (an empty box: the component has no dispersive edge).
+        No media (phi of length 0) removes the set."""
+        self._lorentz_lib()
+        phi, gam, h = _arr(phi, np.float32), _arr(gam, np.float32), _arr(h, np.float32)
+        if phi.ndim != 4 or phi.shape[2:] != (2, 2) or gam.shape != phi.shape[:2] + (2,) or h.shape != gam.shape:
+            raise ValueError("Lorentz tables must be phi [nmedia][K][2][2], gam and h [nmedia][K][2]")
+        nmedia, K = phi.shape[:2]
+        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
+        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
+        shapes = [tuple(max(int(hi_a[c][a] - lo_a[c][a]), 0) for a in (2, 1, 0)) for c in range(3)]
+        ws = [_arr(np.zeros(shapes[c], np.float32) if 0 in shapes[c] else w[c], np.float32) for c in range(3)]
+        ms = [_arr(np.zeros(shapes[c], np.uint8) if (0 in shapes[c] or med is None) else med[c], np.uint8) for c in range(3)]
+        for c in range(3):
+            if ws[c].shape != shapes[c] or ms[c].shape != shapes[c]:
+                raise ValueError(f"Lorentz component {c}: weights / medium ids must be [z][y][x] over the box, {shapes[c]}")
+        wp = (C.c_void_p * 3)(*[x.ctypes.data for x in ws])
+        mp = (C.c_void_p * 3)(*[x.ctypes.data for x in ms])
+        self._ck(self.lib.fdtd_lorentz_set(self._ctx, int(nmedia), int(K), _ptr(phi), _ptr(gam), _ptr(h), _ptr(lo_a), _ptr(hi_a),
+                                           C.cast(wp, C.c_void_p), C.cast(mp, C.c_void_p)), "lorentz_set")
+        self.lorentz_K, self.lorentz_shapes = (int(K), shapes) if nmedia else (0, [(0, 0, 0)] * 3)
+
+    def lorentz_state(self, comp: int):
+        """(v_prev [z][y][x], x [K][2][z][y][x] (j_k, u_k), vi [z][y][x]) float32 over component comp's box."""
+        self._lorentz_lib()
+        shp = getattr(self, "lorentz_shapes", [(0, 0, 0)] * 3)[comp]
+        K = getattr(self, "lorentz_K", 0)
+        v, x, vi = np.zeros(shp, np.float32), np.zeros((K, 2) + shp, np.float32), np.zeros(shp, np.float32)
+        self._ck(self.lib.fdtd_lorentz_get(self._ctx, int(comp), _ptr(v), _ptr(x), _ptr(vi)), "lorentz_get")
+        return v, x, vi
 
     # -- magnetic materials (include/fdtd_hip_magnetic.h) --------------------------------------------
     def _magnetic_lib(self):

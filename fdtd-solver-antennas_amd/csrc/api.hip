@@ -279,6 +279,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   sheet_free(c);
   lumped_free(c);
   debye_free(c);
+  lorentz_free(c);
   magnetic_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
@@ -901,6 +902,7 @@ static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
 static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
   if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
   if (c->debye_nmedia > 0) return false;   // Debye media: likewise
+  if (c->lorentz_nmedia > 0) return false; // Lorentz / Drude media: likewise
   if (c->lumped_n > 0) return false;       // lumped elements: likewise
   if (c->mag_ncls > 0) return false;       // magnetic faces: their correction runs between the H update and whatever reads I next
   const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
@@ -940,7 +942,7 @@ static bool wavefront_active(const fdtd_ctx* c, bool fused) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lumped_n > 0 || c->mag_ncls > 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lorentz_nmedia > 0 || c->lumped_n > 0 || c->mag_ncls > 0) return false;
   if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -1014,7 +1016,7 @@ struct StepPlan {
 // Lumped-element edges: as the sheets'.
 static bool probes_first(const fdtd_ctx* c) {
   if (c->nprobe == 0) return false;
-  if (c->debye_nmedia > 0) return true;
+  if (c->debye_nmedia > 0 || c->lorentz_nmedia > 0) return true;   // (Lorentz / Drude media are volumes as well)
   if (c->sheet_n <= 0 && c->lumped_n <= 0) return false;
   for (int q = 0; q < c->nprobe; ++q) {
     if (c->probe[q].kind != FDTD_KIND_V) continue;
@@ -1043,6 +1045,11 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
       return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: the two-launch schedule only (their correction runs between the E phase and the H update)");
     if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: single slab only (world = 1, no p2p transport, no linked contexts)");
+  }
+  if (c->lorentz_nmedia > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Lorentz media: the two-launch schedule only (their correction runs between the E phase and the H update)");
+    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Lorentz media: single slab only (world = 1, no p2p transport, no linked contexts)");
   }
   if (c->lumped_n > 0) {
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
@@ -1337,6 +1344,7 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
   for (int n = 0; n < nsteps; ++n) {
     if ((r = phase_E(c, pl, pe, n))) return r;
     launch_debye(c, c->stream);   // Debye media: after the whole E phase, before the sheets' correction and the H update (no-op without media)
+    launch_lorentz(c, c->stream); // Lorentz / Drude media: behind the Debye media's correction (no-op without media)
     launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
     launch_lumped(c, c->stream);  // lumped elements: behind the sheets' correction, before the H update (no-op without elements)
     if (multi && (r = exchange(c, FDTD_HALO_E_DOWN, pl.rccl_inline))) return r;
@@ -1459,6 +1467,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_post(c, FDTD_KIND_V, c->step, true, s);
     launch_dft(c, FDTD_KIND_V, c->step, s);
     launch_debye(c, s);
+    launch_lorentz(c, s);
     launch_sheet(c, s);
     launch_lumped(c, s);
   } else if (phase == FDTD_PHASE_H) {

@@ -291,6 +291,11 @@ struct fdtd_ctx {
   int debye_nmedia = 0, debye_K = 0;
   DebyeBox debye_box[3];
   float* debye_tab = nullptr;
+  // Lorentz / Drude media (lorentz.hip, include/fdtd_hip_lorentz.h): boxes as the Debye media's, u holding the state planes
+  // [2 K][n] (j_k, u_k per pole); the per-(medium, pole) rows phi, gam, h as [MAX_MEDIA][MAX_K][8] floats on the device
+  int lorentz_nmedia = 0, lorentz_K = 0;
+  DebyeBox lorentz_box[3];
+  float* lorentz_tab = nullptr;
   // magnetic materials (magnetic.hip, include/fdtd_hip_magnetic.h): per component one dense box of faces, x range widened to
   // multiples of 4; i_prev and one class byte per face over the widened box; the (a, b) pairs of the classes as 256 float2 on the device
   struct MagBox {
@@ -364,6 +369,9 @@ void lumped_free(fdtd_ctx* c);
 // dispersion.hip: Debye media — the dense correction after the E phase, in front of launch_sheet (no-op without media)
 void launch_debye(fdtd_ctx* c, hipStream_t s);
 void debye_free(fdtd_ctx* c);
+// lorentz.hip: Lorentz / Drude media — the dense correction behind launch_debye, in front of launch_sheet (no-op without media)
+void launch_lorentz(fdtd_ctx* c, hipStream_t s);
+void lorentz_free(fdtd_ctx* c);
 // magnetic.hip: magnetic materials — the dense correction after the H update, in front of everything that samples I (no-op without faces)
 void launch_magnetic(fdtd_ctx* c, hipStream_t s);
 int magnetic_prime(fdtd_ctx* c, int comp);   // i_prev <- the component's I array (fdtd_magnetic_set, fdtd_set_field)

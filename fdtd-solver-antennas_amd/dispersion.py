@@ -173,10 +173,11 @@ class DebyeEdges:
         return max(m.K for m in self.media)
 
 
-def edge_weights(grid, cell_medium: np.ndarray, nmedia: int, names: Optional[Sequence[str]] = None):
+def edge_weights(grid, cell_medium: np.ndarray, nmedia: int, names: Optional[Sequence[str]] = None, kind: str = "Debye"):
     """Per component (w [nz][ny][nx] float64, medium id [nz][ny][nx] uint8): w_e = A~/l times the area-weighted four-cell share of
     the edge that lies in its medium (ecoperator._edge_average of the medium's indicator); 0 where no cell around the edge is
-    dispersive and on the edges that do not exist.  An edge whose cells belong to two different media is refused."""
+    dispersive and on the edges that do not exist.  An edge whose cells belong to two different media is refused (`kind`: what the
+    message calls the media — lorentz.py shares this function)."""
     from .ecoperator import _edge_average
     nx, ny, nz = grid.shape
     out = []
@@ -202,7 +203,7 @@ def edge_weights(grid, cell_medium: np.ndarray, nmedia: int, names: Optional[Seq
                 k, j, i = (int(v[0]) for v in np.nonzero(clash))
                 other = int(med[k, j, i])
                 nm = (lambda q: names[q] if names else str(q))
-                raise ValueError(f"the {'xyz'[c]}-edge at node {(i, j, k)} is shared by two different Debye media "
+                raise ValueError(f"the {'xyz'[c]}-edge at node {(i, j, k)} is shared by two different {kind} media "
                                  f"('{nm(other)}' and '{nm(m)}'): give them the same parameters or separate them by a cell")
             w[on] = (share * geo)[on]
             med[on] = m
@@ -233,7 +234,7 @@ def make_edges(grid, media: Sequence[DebyeMedium], names, cell_medium: np.ndarra
     return DebyeEdges(list(media), [list(n) for n in names], cell_medium, lo, hi, w, med)
 
 
-def check_placement(grid, cell_medium: np.ndarray, cpml_cells: Sequence[int], names: Optional[Sequence[str]] = None):
+def check_placement(grid, cell_medium: np.ndarray, cpml_cells: Sequence[int], names: Optional[Sequence[str]] = None, kind: str = "Debye"):
     """Refuse (ValueError) dispersive cells inside CPML layers (`cpml_cells`: layer thickness in cells per face, x-, x+, y-, ...):
     the layers' psi recursion assumes the folded eps / kappa only."""
     n = grid.shape
@@ -247,7 +248,7 @@ def check_placement(grid, cell_medium: np.ndarray, cpml_cells: Sequence[int], na
         sub = cell_medium[tuple(sl)]
         if np.any(sub >= 0):
             m = int(sub[sub >= 0][0])
-            raise ValueError(f"Debye medium '{names[m] if names else m}' reaches into the CPML layer {'xyz'[a]}{'+' if f % 2 else '-'} "
+            raise ValueError(f"{kind} medium '{names[m] if names else m}' reaches into the CPML layer {'xyz'[a]}{'+' if f % 2 else '-'} "
                              f"({t} cells): dispersive cells inside absorbing layers are not supported — end the medium before the "
                              f"layer or use Mur faces")
 

@@ -148,6 +148,19 @@ class CSProperty:
         return b
 
 
+def _take(kw, names, numbered):
+    """Per-pole values out of the keywords `kw` (popped): the first of `names` present, as a sequence — else the keywords of
+    `numbered` with the suffixes _1, _2, ... as far as they go."""
+    for n in names:
+        if n in kw:
+            return [float(v) for v in np.atleast_1d(kw.pop(n))]
+    out, q = [], 1
+    while any(f"{n}_{q}" in kw for n in numbered):
+        out.append(float(next(kw.pop(f"{n}_{q}") for n in numbered if f"{n}_{q}" in kw)))
+        q += 1
+    return out
+
+
 class ContinuousStructure:
     def __init__(self, log: Optional[_CallLog] = None):
         self._log = log or _CallLog()
@@ -193,17 +206,7 @@ class ContinuousStructure:
         ``eps_relax_time``) or numbered from 1 (``eps_delta_1``, ``eps_relaxtime_1`` ...).  Aliases: ``eps_inf``; ``delta_eps``,
         ``epsDelta``; ``tau``, ``eps_relaxtime``, ``epsRelaxTime``.  (The keyword spelling is not pinned against a CSXCAD install.)"""
         kw = dict(kw)
-
-        def take(names, numbered):
-            for n in names:
-                if n in kw:
-                    return [float(v) for v in np.atleast_1d(kw.pop(n))]
-            out, q = [], 1
-            while any(f"{n}_{q}" in kw for n in numbered):
-                out.append(float(next(kw.pop(f"{n}_{q}") for n in numbered if f"{n}_{q}" in kw)))
-                q += 1
-            return out
-
+        take = lambda names, numbered: _take(kw, names, numbered)
         deps = take(("eps_delta", "delta_eps", "epsDelta"), ("eps_delta", "delta_eps", "epsDelta"))
         tau = take(("eps_relax_time", "eps_relaxtime", "tau", "epsRelaxTime"), ("eps_relaxtime", "eps_relax_time", "tau", "epsRelaxTime"))
         order = int(kw.pop("order", len(deps)))
@@ -214,6 +217,37 @@ class ContinuousStructure:
         if not (1 <= order <= 8) or len(deps) != order or len(tau) != order:
             raise ValueError(f"AddDebyeMaterial: order {order} needs {order} permittivity steps and relaxation times (1..8 poles), got {len(deps)} and {len(tau)}")
         p = CSProperty(self._log, "DebyeMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_delta=deps, eps_relax_time=tau)
+        self.properties.append(p)
+        return p
+
+    def AddLorentzMaterial(self, name, **kw):
+        """Lorentz and Drude poles (lorentz.py), mirroring CSXCAD's Lorentz material property with openEMS's keywords: ``order`` =
+        K poles (1..4), ``epsilon`` = eps_inf (the prefactor of the pole sum as well), ``kappa``, and per pole the plasma frequency
+        ``eps_plasma`` [Hz], the pole frequency ``eps_pole_freq`` [Hz] (0 or absent: a Drude pole) and the relaxation time
+        ``eps_relax`` [s] (0 or absent: a loss-free pole).  Further poles: each keyword as a sequence, or the first pole bare and the
+        others numbered from 1 (``eps_plasma_1`` ...).  Magnetic poles (``mue_plasma`` ...) and ``mue`` != 1 are refused."""
+        kw = dict(kw)
+        mag = sorted(k for k in kw if k.startswith(("mue_plasma", "mue_pole_freq", "mue_relax")))
+        if mag:
+            raise ValueError(f"AddLorentzMaterial '{name}': magnetic poles ({', '.join(mag)}) are not supported: magnetic dispersion is out of scope")
+        mue = kw.pop("mue", 1.0)
+        if np.ndim(mue) != 0 or float(mue) != 1.0:
+            raise ValueError(f"AddLorentzMaterial '{name}': mue = {mue!r} is not supported on a Lorentz material (mue must be 1)")
+        per_pole = lambda n: _take(kw, (n,), ()) + _take(kw, (), (n,))
+        fp, f0, relax = per_pole("eps_plasma"), per_pole("eps_pole_freq"), per_pole("eps_relax")
+        order = int(kw.pop("order", len(fp)))
+        eps_inf = float(kw.pop("epsilon", 1.0))
+        kappa = float(kw.pop("kappa", 0.0))
+        if kw:
+            raise TypeError(f"AddLorentzMaterial: unknown keyword(s) {sorted(kw)}")
+        if not (1 <= order <= 4) or len(fp) != order or len(f0) not in (0, order) or len(relax) not in (0, order):
+            raise ValueError(f"AddLorentzMaterial: order {order} needs {order} plasma frequencies and, where given, as many pole frequencies "
+                             f"and relaxation times (1..4 poles), got {len(fp)}, {len(f0)} and {len(relax)}")
+        f0, relax = f0 or [0.0] * order, relax or [0.0] * order
+        if any(t < 0 for t in relax):
+            raise ValueError(f"AddLorentzMaterial '{name}': eps_relax must be >= 0 (0: a loss-free pole)")
+        p = CSProperty(self._log, "LorentzMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_plasma=fp, eps_pole_freq=f0,
+                       eps_relax=relax)
         self.properties.append(p)
         return p
 
@@ -429,7 +463,13 @@ class openEMS:
         grid = RectGrid(*lines)
         sc = Scene(unit=unit)
         for p in csx.properties:
-            if p.kind in ("Material", "DebyeMaterial"):
+            if p.kind == "LorentzMaterial":
+                q = p.params
+                m = sc.add_lorentz_material(p.name, q["epsilon"], q["kappa"], wp=[2 * np.pi * f for f in q["eps_plasma"]],
+                                            w0=[2 * np.pi * f for f in q["eps_pole_freq"]], gamma=[1.0 / t if t else 0.0 for t in q["eps_relax"]])
+                for b in p.boxes:
+                    m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
+            elif p.kind in ("Material", "DebyeMaterial"):
                 m = (sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0),
                                      mu_r=p.params.get("mue", 1.0), sigma_m=p.params.get("sigma", 0.0)) if p.kind == "Material" else
                      sc.add_debye_material(p.name, p.params["epsilon"], p.params["kappa"], p.params["eps_delta"], p.params["eps_relax_time"]))

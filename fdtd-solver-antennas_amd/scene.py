@@ -25,6 +25,7 @@ from .grid import RectGrid
 from .ecoperator import LumpedEdge
 from . import sheet as _sheet
 from . import dispersion as _disp
+from . import lorentz as _lorentz
 from . import lumped as _lumped
 from . import magnetic as _magnetic
 
@@ -55,6 +56,12 @@ class Material:
 class DebyeMaterial(Material):
     """add_debye_material(name, eps_inf, kappa, delta_eps, tau): a multi-pole Debye medium (dispersion.py).  eps_r holds eps_inf."""
     medium: Optional[_disp.DebyeMedium] = None
+
+
+@dataclass
+class LorentzMaterial(Material):
+    """add_lorentz_material(name, eps_inf, kappa, wp, w0, gamma): Lorentz / Drude poles (lorentz.py).  eps_r holds eps_inf."""
+    medium: Optional[_lorentz.LorentzMedium] = None
 
 
 @dataclass
@@ -125,6 +132,15 @@ class Scene:
         self.materials.append(m)
         return m
 
+    def add_lorentz_material(self, name, eps_inf, kappa=0.0, wp=(), w0=(), gamma=()) -> LorentzMaterial:
+        """A resonant dielectric eps(w) = eps_inf (1 + sum_k wp[k]^2 / (w0[k]^2 - w^2 + j w gamma[k])) - j kappa / (w eps0), 1..4
+        poles, all in rad/s; w0[k] = 0 (or w0 left out) is a Drude pole, gamma left out a loss-free one.  Boxes, rotations and
+        priorities work as for add_material; the highest priority owns a cell."""
+        med = _lorentz.LorentzMedium(eps_inf, kappa, wp, w0, gamma)
+        m = LorentzMaterial(name, med.eps_inf, med.kappa, medium=med)
+        self.materials.append(m)
+        return m
+
     def add_metal(self, name) -> Metal:
         m = Metal(name)
         self.metals.append(m)
@@ -181,6 +197,7 @@ class VoxelScene:
     # Debye media (None: the scene has none): eps_r / kappa hold eps_inf / kappa of their cells — the timestep-dependent part of
     # the fold (kappa += sum_k beta_k) is Simulation's, which knows dt
     debye: Optional[_disp.DebyeEdges] = None
+    lorentz: Optional[_lorentz.LorentzEdges] = None  # Lorentz / Drude media, a sibling of debye (the fold kappa += sum_k g0_k is Simulation's too)
     elements: Optional[_lumped.LumpedEdges] = None   # lumped-element edges (None: the scene has no lumped element)
     # magnetic materials (None: mu_r = 1, sigma_m = 0 everywhere): per cell, same priority rule as eps_r; cell_material indexes
     # material_names (-1: background) so that a refusal can name the material
@@ -235,6 +252,20 @@ def _inside_mask(bx: Box, u: float, tol: float, coords: Sequence[np.ndarray]):
     return mask, off
 
 
+def _merged_media(materials, kind):
+    """(media, the material names merged into each, key -> medium id) of the materials of class `kind`, in order of appearance."""
+    media, names, medium_of = [], [], {}
+    for mat in materials:
+        if isinstance(mat, kind):
+            k = mat.medium.key()
+            if k not in medium_of:
+                medium_of[k] = len(media)
+                media.append(mat.medium)
+                names.append([])
+            names[medium_of[k]].append(mat.name)
+    return media, names, medium_of
+
+
 def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
     nx, ny, nz = grid.shape
     u = scene.unit
@@ -246,21 +277,18 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
     cmat = np.full(eps.shape, -1, dtype=np.int32)
     prio = np.full(eps.shape, -(1 << 30), dtype=np.int64)
     centers = [grid.centers(a) for a in range(3)]
-    # Debye materials with identical parameters are one medium (as sheets of one metal are one surface)
-    media, media_names, medium_of = [], [], {}
-    for mat in scene.materials:
-        if isinstance(mat, DebyeMaterial):
-            k = mat.medium.key()
-            if k not in medium_of:
-                medium_of[k] = len(media)
-                media.append(mat.medium)
-                media_names.append([])
-            media_names[medium_of[k]].append(mat.name)
+    # Debye materials with identical parameters are one medium (as sheets of one metal are one surface), and so are Lorentz materials
+    media, media_names, medium_of = _merged_media(scene.materials, DebyeMaterial)
     if len(media) > _disp.MAX_MEDIA:
         raise ValueError(f"{len(media)} different Debye media: at most {_disp.MAX_MEDIA}")
     cmed = np.full(eps.shape, -1, dtype=np.int8) if media else None
+    lmedia, lmedia_names, lmedium_of = _merged_media(scene.materials, LorentzMaterial)
+    if len(lmedia) > _lorentz.MAX_MEDIA:
+        raise ValueError(f"{len(lmedia)} different Lorentz media: at most {_lorentz.MAX_MEDIA}")
+    clor = np.full(eps.shape, -1, dtype=np.int8) if lmedia else None
     for qm, mat in enumerate(scene.materials):
         mid = medium_of[mat.medium.key()] if isinstance(mat, DebyeMaterial) else -1
+        lid = lmedium_of[mat.medium.key()] if isinstance(mat, LorentzMaterial) else -1
         for bx in mat.boxes:
             r = _inside_mask(bx, u, -tol, centers)     # strict: a cell centre on the surface is outside
             if r is None:
@@ -273,11 +301,16 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
             mur[sl][win] = mat.mu_r; sgm[sl][win] = mat.sigma_m; cmat[sl][win] = qm
             if cmed is not None:
                 cmed[sl][win] = mid
+            if clor is not None:
+                clor[sl][win] = lid
     debye = _disp.make_edges(grid, media, media_names, cmed) if media and np.any(cmed >= 0) else None
+    lorentz = _lorentz.make_edges(grid, lmedia, lmedia_names, clor) if lmedia and np.any(clor >= 0) else None
+    if lorentz is not None:
+        _lorentz.check_disjoint(lorentz, debye)
     magnetic = dict(mu_r=mur, sigma_m=sgm, cell_material=cmat, material_names=[m.name for m in scene.materials])
     if any(isinstance(m, ConductingSheet) for m in scene.metals):
         vs = _voxelize_with_sheets(scene, grid, eps, kap)
-        vs.debye = debye
+        vs.debye, vs.lorentz = debye, lorentz
         vs.mu_r, vs.sigma_m, vs.cell_material, vs.material_names = mur, sgm, cmat, magnetic["material_names"]
         vs.elements = _elements_on_grid(scene, grid, vs.pec, vs.ports, vs.sheets)
         return vs
@@ -299,7 +332,7 @@ def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
                       slice(off[0], off[0] + edge.shape[2])]
                 pec[c][tuple(sl)] |= edge
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
-    return VoxelScene(eps, kap, pec, ports, debye=debye, elements=_elements_on_grid(scene, grid, pec, ports, None), **magnetic)
+    return VoxelScene(eps, kap, pec, ports, debye=debye, lorentz=lorentz, elements=_elements_on_grid(scene, grid, pec, ports, None), **magnetic)
 
 
 def _box_edges(node: np.ndarray, c: int):

@@ -19,6 +19,7 @@ from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_ta
 from . import sheet as _sheet
 from . import lumped as _lumped
 from . import dispersion as _disp
+from . import lorentz as _lorentz
 from . import magnetic as _magnetic
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
@@ -145,6 +146,7 @@ class RunStats:
     sheet_fit_error: Optional[float] = None   # largest band error of the sheets' admittance fits (relative)
     schedule: Optional[dict] = None           # the schedule the engine ran (Engine.schedule_info)
     dispersion: Optional[dict] = None         # Debye media stepped by the engine (dispersion.py): media, K, poles, fit errors, edges
+    lorentz: Optional[dict] = None            # Lorentz / Drude media stepped by the engine (lorentz.py): media, K, poles, edges
     lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
     magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
 
@@ -260,6 +262,16 @@ class Simulation:
                 on = self.debye.cell_medium == q
                 assert np.all(vox.eps_r[on] == m.eps_inf)
                 self.kappa_cells[on] = m.folded(self.dt)[1]
+        # Lorentz / Drude media: the same fold with the branches' g0 (lorentz.py), the rest stepped by the engine (fdtd_lorentz_set)
+        self.lorentz = vox.lorentz if getattr(vox, "lorentz", None) is not None and len(vox.lorentz) else None
+        if self.lorentz is not None:
+            _lorentz.check_placement(grid, self.lorentz.cell_medium, cells, [" / ".join(n) for n in self.lorentz.names])
+            if self.kappa_cells is vox.kappa:
+                self.kappa_cells = vox.kappa.copy()
+            for q, m in enumerate(self.lorentz.media):
+                on = self.lorentz.cell_medium == q
+                assert np.all(vox.eps_r[on] == m.eps_inf)
+                self.kappa_cells[on] = m.folded(self.dt)[1]
         # magnetic materials: per-cell mu_r / sigma_m -> face coefficients at this dt -> classes and boxes; the operator stays the
         # base one (ii = 1, iv0), the faces are corrected by the engine after every H update (fdtd_magnetic_set)
         self.magnetic = None
@@ -324,6 +336,8 @@ class Simulation:
             raise _capi.FdtdError("lumped elements need a single slab (world = 1): a decomposed run with stepped R-L-C elements is not supported")
         if self.debye is not None and world > 1:
             raise _capi.FdtdError("Debye media need a single slab (world = 1): a decomposed run with dispersive media is not supported")
+        if self.lorentz is not None and world > 1:
+            raise _capi.FdtdError("Lorentz media need a single slab (world = 1): a decomposed run with dispersive media is not supported")
         if self.magnetic is not None and world > 1:
             raise _capi.FdtdError("magnetic materials need a single slab (world = 1): a decomposed run with magnetic media is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
@@ -346,6 +360,8 @@ class Simulation:
                 self.operator_form = "raw"
         if self.debye is not None:
             e.set_debye(*self.debye_tables())
+        if self.lorentz is not None:
+            e.set_lorentz(*self.lorentz_tables())
         if self.sheets is not None:
             e.set_sheets(*self.sheet_tables())
         if self.element_stepped.size:
@@ -436,6 +452,23 @@ class Simulation:
         d = self.debye
         alpha, oma, beta = _disp.tables(d.media, self.dt)
         return alpha, oma, beta, d.lo, d.hi, [w.astype(np.float32) for w in d.w], d.med
+
+    def lorentz_tables(self):
+        """(phi, gam, h, lo, hi, w, med) of fdtd_lorentz_set (Engine.set_lorentz)."""
+        d = self.lorentz
+        phi, gam, h = _lorentz.tables(d.media, self.dt)
+        return phi, gam, h, d.lo, d.hi, [w.astype(np.float32) for w in d.w], d.med
+
+    def lorentz_info(self) -> Optional[dict]:
+        """What RunStats.lorentz reports: per medium the poles; the dispersive edges per component and their boxes."""
+        if self.lorentz is None:
+            return None
+        d = self.lorentz
+        return {"media": [{"names": list(n), "eps_inf": m.eps_inf, "kappa": m.kappa, "plasma_hz": (m.wp / (2 * np.pi)).tolist(),
+                           "pole_hz": (m.w0 / (2 * np.pi)).tolist(), "gamma": m.gamma.tolist(), "kappa_cell": m.folded(self.dt)[1]}
+                          for m, n in zip(d.media, d.names)],
+                "K": d.K, "poles": int(sum(m.K for m in d.media)), "edges": [int(np.count_nonzero(w)) for w in d.w],
+                "box_edges": [int(np.prod(w.shape)) for w in d.w]}
 
     def magnetic_info(self) -> Optional[dict]:
         """What RunStats.magnetic reports: the magnetic media, the (a, b) classes, the faces per component and their boxes."""
@@ -550,6 +583,7 @@ class Simulation:
         stats.sheet_edges = 0 if self.sheets is None else len(self.sheets)
         stats.sheet_fit_error = self.sheet_fit_error
         stats.dispersion = self.dispersion_info()
+        stats.lorentz = self.lorentz_info()
         stats.lumped = self.lumped_info()
         stats.magnetic = self.magnetic_info()
         stats.schedule = e.schedule_info()

@@ -746,6 +746,8 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
                      "schedule": getattr(st, "schedule", None)}
         if getattr(st, "dispersion", None) is not None:     # Debye media stepped by the engine (substrate_dispersion / AddDebyeMaterial)
             out.stats["dispersion"] = st.dispersion
+        if getattr(st, "lorentz", None) is not None:        # Lorentz / Drude media (AddLorentzMaterial)
+            out.stats["lorentz"] = st.lorentz
         if getattr(st, "lumped", None) is not None:         # lumped R-L-C elements (AddLumpedElement)
             out.stats["lumped"] = st.lumped
         if getattr(st, "magnetic", None) is not None:       # magnetic materials (AddMaterial(mue=, sigma=))
