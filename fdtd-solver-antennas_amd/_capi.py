@@ -43,6 +43,8 @@ MAGNETIC_SYMBOLS = ["fdtd_magnetic_set", "fdtd_magnetic_get"]
 MAGNETIC_MAX_CLASSES = 255
 # include/fdtd_hip_traffic.h: which memory-traffic shortcuts a context took, likewise
 TRAFFIC_SYMBOLS = ["fdtd_traffic_info"]
+# include/fdtd_hip_voxel.h: primitives rasterised on the device, likewise
+VOXEL_SYMBOLS = ["fdtd_voxelize"]
 
 
 class FdtdDesc(C.Structure):
@@ -178,7 +180,21 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    voxel_sig = {
+        "fdtd_voxelize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, C.c_int, p, C.c_int, p, C.c_double, p, p]),
+    }
+    assert sorted(voxel_sig) == sorted(VOXEL_SYMBOLS)
+    for name, (res, args) in voxel_sig.items():     # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_voxelize(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the device rasteriser (include/fdtd_hip_voxel.h)."""
+    return all(hasattr(lib, n) for n in VOXEL_SYMBOLS)
 
 
 def has_traffic_info(lib: C.CDLL) -> bool:
@@ -764,3 +780,40 @@ def farfield(lib: C.CDLL, pos, Js, Ms, k_wave: float, theta, phi, device: int = 
         msg = lib.fdtd_last_error(None)
         raise FdtdError(f"fdtd_farfield failed ({rc}): {msg.decode() if msg else ''}")
     return eth[:, 0] + 1j * eth[:, 1], eph[:, 0] + 1j * eph[:, 1]
+
+
+def voxelize_raw(lib: C.CDLL, grid, table, device: int = 0, cells: bool = True, edges: bool = True):
+    """fdtd_voxelize on a primitives.Table: (cell_owner int32 [nz-1][ny-1][nx-1] or None, edge_owner int32 [3][nz][ny][nx] or None)."""
+    if not has_voxelize(lib):
+        raise FdtdError("this library has no device rasteriser (fdtd_voxelize)")
+    nx, ny, nz = grid.shape
+    lines = _arr(np.concatenate(grid.lines), np.float64)
+    rec = np.ascontiguousarray(table.rec)
+    verts = _arr(table.verts, np.float64)
+    if rec.dtype.itemsize != 248:
+        raise ValueError("the table's records must be primitives.RECORD")
+    cown = np.empty((nz - 1, ny - 1, nx - 1), np.int32) if cells else None
+    eown = np.empty((3, nz, ny, nx), np.int32) if edges else None
+    rc = lib.fdtd_voxelize(int(device), nx, ny, nz, _ptr(lines), int(rec.size), _ptr(rec) if rec.size else None, int(verts.size),
+                           _ptr(verts) if verts.size else None, float(table.tol), _ptr(cown), _ptr(eown))
+    if rc != 0:
+        msg = lib.fdtd_last_error(None)
+        raise FdtdError(f"fdtd_voxelize failed ({rc}): {msg.decode() if msg else ''}")
+    return cown, eown
+
+
+def voxelize_device(lib: C.CDLL, device: int = 0):
+    """A `rasteriser` for scene.voxelize(scene, grid, rasteriser): primitives.rasterise_spec's result, computed by csrc/voxel.hip."""
+    def rasteriser(grid, table):
+        return voxelize_raw(lib, grid, table, device)
+    return rasteriser
+
+
+def default_rasteriser(lib: C.CDLL, device: int = 0):
+    """What openEMS.Run hands to scene.voxelize (the package's one caller of voxelize; the plugin's scenes reach it through Run): the
+    device rasteriser when `lib` exports fdtd_voxelize and FDTD_VOXELIZE is not "host", else None (the numpy specification).  No
+    size threshold: the whole device call was 2.7 to 4.6 times faster than the specification on every grid timed, from 50 x 50 x 7 to
+    800 x 800 x 120 nodes, and 49 times on a 1000-segment wire (profiles/primitives/timing.txt)."""
+    if os.environ.get("FDTD_VOXELIZE", "").lower() == "host" or not has_voxelize(lib):
+        return None
+    return voxelize_device(lib, device)

@@ -18,3 +18,5 @@ class CSProperties:            # names probed by probe_openems_fixed (fixed.py:1
 
 class CSPrimitives:
     CSPrimBox = _api.CSPrimBox
+    CSPrimCylinder = CSPrimCylindricalShell = CSPrimSphere = CSPrimSphericalShell = _api.CSPrimCurved
+    CSPrimPolygon = CSPrimLinPoly = CSPrimCurve = CSPrimWire = _api.CSPrimCurved

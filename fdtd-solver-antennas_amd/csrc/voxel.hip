@@ -1,0 +1,393 @@
+// voxel.hip — rasterise the primitive table of include/fdtd_hip_voxel.h onto the Yee grid (what scene.voxelize did in numpy over
+// whole-grid temporaries).  One kernel, templated on the pass: the cell pass tests cell centres against the material records and
+// keeps the winner; the edge pass tests every node and its +x, +y, +z neighbours against the metal records and keeps the winner
+// per component.  float64 throughout, in the operation order the header spells (primitives._inside is the same text in numpy;
+// -ffp-contract=off keeps the compiler from fusing), so the owners are those of primitives.rasterise_spec bit for bit.
+//
+// A block of 256 threads owns a tile of one z-plane: VX_TY rows of VX_TX threads, four consecutive x points per thread.  The table
+// is staged through LDS in chunks of VX_CHUNK records; a record whose index box misses the block's tile is skipped before any
+// arithmetic (block-uniform: the record's integers go through readfirstlane, so the skip is a scalar branch) — N primitives x M
+// points becomes about M.  Every output word has exactly one writer and is always written (-1: no owner): no atomics, no memset.
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "fdtd_ctx.h"
+#include "../../include/fdtd_hip_voxel.h"
+
+static_assert(sizeof(fdtd_voxel_prim) == 248, "fdtd_voxel_prim is 248 bytes (primitives.RECORD)");
+
+namespace {
+constexpr int VX_BLOCK = 256, VX_TX = 32, VX_TY = 8, VX_PTS = 4;
+constexpr int VX_CHUNK = 48;                                  // records per LDS chunk: 48 * 248 B = 11.6 KiB
+constexpr int VX_WORDS = (int)(sizeof(fdtd_voxel_prim) / 8);  // 31
+enum { PASS_CELL = 0, PASS_EDGE = 1 };
+
+struct VoxArgs {
+  int nx, ny, nz;             // node counts
+  const double* lines;        // x lines, y lines, z lines
+  int nprim;
+  const fdtd_voxel_prim* table;
+  const double* verts;
+  double tol;
+  int32_t* out;               // cell pass: [nz-1][ny-1][nx-1]; edge pass: [3][nz][ny][nx]
+};
+
+// the points of one thread: cell pass 4 (x + q); edge pass 13: q 0..4 at x + q, 5..8 at (x + q - 5, y + 1), 9..12 at (x + q - 9, z + 1)
+template <int PASS> struct PtMap {
+  static constexpr int N = PASS == PASS_CELL ? 4 : 13;
+  static constexpr __host__ __device__ int xi(int q) { return q < 5 ? q : (q < 9 ? q - 5 : q - 9); }
+  static constexpr __host__ __device__ int yi(int q) { return (q >= 5 && q < 9) ? 1 : 0; }
+  static constexpr __host__ __device__ int zi(int q) { return q >= 9 ? 1 : 0; }
+};
+
+// point-to-segment distance^2 <= lim2 (w = p - a, g = p - b, d = b - a), division-free
+__device__ __forceinline__ bool seg_near(double wx, double wy, double wz, double gx, double gy, double gz, double dx, double dy,
+                                         double dz, double lim2) {
+  const double L = (dx * dx + dy * dy) + dz * dz;
+  const double s = (wx * dx + wy * dy) + wz * dz;
+  const double ww = (wx * wx + wy * wy) + wz * wz;
+  const double gg = (gx * gx + gy * gy) + gz * gz;
+  return s <= 0.0 ? ww <= lim2 : (s >= L ? gg <= lim2 : ww * L - s * s <= lim2 * L);
+}
+
+// Bit q of the result: point q is inside record r (in LDS) under its role's rule.  `gate` masks the points outside the index box.
+template <int N>
+__device__ __forceinline__ unsigned vx_test(const fdtd_voxel_prim* r, const int type, const bool metal, const int norm_dir,
+                                            const int vert0, const int nvert, const bool has_matrix,
+                                            const double* __restrict__ verts, const double tol, const double (&wx)[N],
+                                            const double (&wy)[N], const double (&wz)[N], const unsigned gate) {
+  const double t = metal ? tol : -tol;
+  double x[N], y[N], z[N];
+  if (has_matrix) {
+    const double m0 = r->m[0], m1 = r->m[1], m2 = r->m[2], m3 = r->m[3], m4 = r->m[4], m5 = r->m[5], m6 = r->m[6], m7 = r->m[7],
+                 m8 = r->m[8], m9 = r->m[9], m10 = r->m[10], m11 = r->m[11];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      x[q] = ((m0 * wx[q] + m1 * wy[q]) + m2 * wz[q]) + m3;
+      y[q] = ((m4 * wx[q] + m5 * wy[q]) + m6 * wz[q]) + m7;
+      z[q] = ((m8 * wx[q] + m9 * wy[q]) + m10 * wz[q]) + m11;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < N; ++q) { x[q] = wx[q]; y[q] = wy[q]; z[q] = wz[q]; }
+  }
+  const double p0 = r->par[0], p1 = r->par[1], p2 = r->par[2], p3 = r->par[3], p4 = r->par[4], p5 = r->par[5], p6 = r->par[6],
+               p7 = r->par[7];
+  unsigned in = 0u;
+  switch (type) {
+    case FDTD_VOXEL_BOX: {
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const bool b = ((x[q] >= p0 - t) && (x[q] <= p3 + t)) && ((y[q] >= p1 - t) && (y[q] <= p4 + t)) &&
+                       ((z[q] >= p2 - t) && (z[q] <= p5 + t));
+        in |= (b ? 1u : 0u) << q;
+      }
+    } break;
+    case FDTD_VOXEL_SPHERE:
+    case FDTD_VOXEL_SPHERICAL_SHELL: {
+      const bool shell = type == FDTD_VOXEL_SPHERICAL_SHELL;
+      const double ro = shell ? (p3 + 0.5 * p4) + t : p3 + t;
+      const double ri = shell ? (p3 - 0.5 * p4) - t : 0.0;
+      const double ro2 = ro * ro, ri2 = ri * ri;
+      if (ro >= 0.0) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+          const double dx = x[q] - p0, dy = y[q] - p1, dz = z[q] - p2;
+          const double d2 = (dx * dx + dy * dy) + dz * dz;
+          const bool b = (d2 <= ro2) && (ri <= 0.0 || d2 >= ri2);
+          in |= (b ? 1u : 0u) << q;
+        }
+      }
+    } break;
+    case FDTD_VOXEL_CYLINDER:
+    case FDTD_VOXEL_CYLINDRICAL_SHELL: {
+      const bool shell = type == FDTD_VOXEL_CYLINDRICAL_SHELL;
+      const double dx = p3 - p0, dy = p4 - p1, dz = p5 - p2;
+      const double L = (dx * dx + dy * dy) + dz * dz;
+      const double tt = (tol * tol) * L;
+      const double ro = shell ? (p6 + 0.5 * p7) + t : p6 + t;
+      const double ri = shell ? (p6 - 0.5 * p7) - t : 0.0;
+      const double ro2L = (ro * ro) * L, ri2L = (ri * ri) * L;
+      if (ro >= 0.0) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+          const double ax = x[q] - p0, ay = y[q] - p1, az = z[q] - p2;
+          const double s = (ax * dx + ay * dy) + az * dz;
+          const double ww = (ax * ax + ay * ay) + az * az;
+          const double qq = ww * L - s * s;
+          const double e = s - L;
+          const bool axial = metal ? ((s >= 0.0 || s * s <= tt) && (e <= 0.0 || e * e <= tt))
+                                   : ((s >= 0.0 && s * s >= tt) && (e <= 0.0 && e * e >= tt));
+          const bool b = axial && (qq <= ro2L) && (ri <= 0.0 || qq >= ri2L);
+          in |= (b ? 1u : 0u) << q;
+        }
+      }
+    } break;
+    case FDTD_VOXEL_DISC: {
+      if (metal) {
+        const double re = p6 + t;
+        const double re2 = re * re;
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+          const double dx = x[q] - p0, dy = y[q] - p1, dz = z[q] - p2;
+          const bool b = ((dz <= tol) && (dz >= -tol)) && (dx * dx + dy * dy <= re2);
+          in |= (b ? 1u : 0u) << q;
+        }
+      }
+    } break;
+    case FDTD_VOXEL_POLYGON:
+    case FDTD_VOXEL_LINPOLY: {
+      const bool flat = type == FDTD_VOXEL_POLYGON;
+      if (flat && !metal) break;
+      const double tol2 = tol * tol;
+      unsigned nrm = 0u, par = 0u, near = 0u;
+      double pu[N], pv[N];
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const double pn = norm_dir == 0 ? x[q] : (norm_dir == 1 ? y[q] : z[q]);
+        pu[q] = norm_dir == 0 ? y[q] : (norm_dir == 1 ? z[q] : x[q]);
+        pv[q] = norm_dir == 0 ? z[q] : (norm_dir == 1 ? x[q] : y[q]);
+        const double dn = pn - p0;
+        const bool b = flat ? ((dn <= tol) && (dn >= -tol)) : ((pn >= p0 - t) && (pn <= p1 + t));
+        nrm |= (b ? 1u : 0u) << q;
+      }
+      const double* V = verts + vert0;
+      for (int e = 0; e < nvert; ++e) {
+        const int f = e + 1 == nvert ? 0 : e + 1;
+        const double au = V[2 * e], av = V[2 * e + 1], bu = V[2 * f], bv = V[2 * f + 1];
+        const double du = bu - au, dv = bv - av;
+        const double L = du * du + dv * dv;
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+          const double wu = pu[q] - au, wv = pv[q] - av;
+          const double lhs = wu * dv, rhs = wv * du;
+          const bool straddle = (av > pv[q]) != (bv > pv[q]);
+          const bool c = straddle && (dv > 0.0 ? lhs < rhs : lhs > rhs);
+          par ^= (c ? 1u : 0u) << q;
+          const double eu = pu[q] - bu, ev = pv[q] - bv;
+          const double s = wu * du + wv * dv;
+          const double ww = wu * wu + wv * wv;
+          const double ee = eu * eu + ev * ev;
+          const bool nr = s <= 0.0 ? ww <= tol2 : (s >= L ? ee <= tol2 : ww * L - s * s <= tol2 * L);
+          near |= (nr ? 1u : 0u) << q;
+        }
+      }
+      in = nrm & (metal ? (par | near) : (par & ~near));
+    } break;
+    case FDTD_VOXEL_WIRE: {
+      const double re = p0 + t;
+      if (!metal || re < 0.0) break;
+      const double re2 = re * re;
+      const double* V = verts + vert0;
+      const int nseg = nvert > 1 ? nvert - 1 : 1;
+      for (int e = 0; e < nseg; ++e) {
+        const int f = e + 1 < nvert ? e + 1 : nvert - 1;
+        const double a0 = V[3 * e], a1 = V[3 * e + 1], a2 = V[3 * e + 2], b0 = V[3 * f], b1 = V[3 * f + 1], b2 = V[3 * f + 2];
+        const double dx = b0 - a0, dy = b1 - a1, dz = b2 - a2;
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+          const bool b = seg_near(x[q] - a0, y[q] - a1, z[q] - a2, x[q] - b0, y[q] - b1, z[q] - b2, dx, dy, dz, re2);
+          in |= (b ? 1u : 0u) << q;
+        }
+      }
+    } break;
+    default: break;
+  }
+  return in & gate;
+}
+
+template <int PASS>
+__global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
+  using M = PtMap<PASS>;
+  constexpr int N = M::N;
+  constexpr int NOUT = PASS == PASS_CELL ? VX_PTS : 3 * VX_PTS;
+  __shared__ unsigned long long s_tab[VX_CHUNK * VX_WORDS];
+
+  // point counts of this pass and the block's tile
+  const int px = PASS == PASS_CELL ? a.nx - 1 : a.nx, py = PASS == PASS_CELL ? a.ny - 1 : a.ny;
+  const int pz = PASS == PASS_CELL ? a.nz - 1 : a.nz;
+  const int tx = threadIdx.x % VX_TX, ty = threadIdx.x / VX_TX;
+  const int bx0 = blockIdx.x * (VX_TX * VX_PTS), by0 = blockIdx.y * VX_TY, k = blockIdx.z;
+  const int i0 = bx0 + tx * VX_PTS, j = by0 + ty;
+  const int ext = PASS == PASS_EDGE ? 1 : 0;                      // the edge pass reads one node beyond the tile
+  const int tx1 = min(bx0 + VX_TX * VX_PTS - 1 + ext, px - 1), ty1 = min(by0 + VX_TY - 1 + ext, py - 1), tz1 = min(k + ext, pz - 1);
+
+  // coordinates (indices clamped to the grid: a clamped point is never inside an index box at its own index)
+  const double* lx = a.lines;
+  const double* ly = a.lines + a.nx;
+  const double* lz = a.lines + a.nx + a.ny;
+  double xs[VX_PTS + 1], ys[2], zs[2];
+#pragma unroll
+  for (int q = 0; q < VX_PTS + 1; ++q) {
+    const int i = min(i0 + q, px - 1);
+    xs[q] = PASS == PASS_CELL ? 0.5 * (lx[i] + lx[i + 1]) : lx[i];
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int jj = min(j + q, py - 1), kk = min(k + q, pz - 1);
+    ys[q] = PASS == PASS_CELL ? 0.5 * (ly[jj] + ly[jj + 1]) : ly[jj];
+    zs[q] = PASS == PASS_CELL ? 0.5 * (lz[kk] + lz[kk + 1]) : lz[kk];
+  }
+  double wx[N], wy[N], wz[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) { wx[q] = xs[M::xi(q)]; wy[q] = ys[M::yi(q)]; wz[q] = zs[M::zi(q)]; }
+
+  int best[NOUT], own[NOUT];
+#pragma unroll
+  for (int q = 0; q < NOUT; ++q) { best[q] = INT32_MIN; own[q] = -1; }
+
+  for (int c0 = 0; c0 < a.nprim; c0 += VX_CHUNK) {
+    const int cn = min(VX_CHUNK, a.nprim - c0);
+    __syncthreads();                                              // the previous chunk is no longer read
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(a.table + c0);
+    for (int w = threadIdx.x; w < cn * VX_WORDS; w += VX_BLOCK) s_tab[w] = src[w];
+    __syncthreads();
+    for (int p = 0; p < cn; ++p) {
+      const fdtd_voxel_prim* r = reinterpret_cast<const fdtd_voxel_prim*>(s_tab + p * VX_WORDS);
+      const int role = __builtin_amdgcn_readfirstlane(r->role);
+      if (role != (PASS == PASS_CELL ? FDTD_VOXEL_MATERIAL : FDTD_VOXEL_METAL)) continue;
+      const int32_t* box = PASS == PASS_CELL ? r->cbox : r->nbox;
+      const int b0 = __builtin_amdgcn_readfirstlane(box[0]), b1 = __builtin_amdgcn_readfirstlane(box[1]);
+      const int b2 = __builtin_amdgcn_readfirstlane(box[2]), b3 = __builtin_amdgcn_readfirstlane(box[3]);
+      const int b4 = __builtin_amdgcn_readfirstlane(box[4]), b5 = __builtin_amdgcn_readfirstlane(box[5]);
+      if (b3 < bx0 || b0 > tx1 || b4 < by0 || b1 > ty1 || b5 < k || b2 > tz1) continue;   // misses the tile: block-uniform
+      const int type = __builtin_amdgcn_readfirstlane(r->type);
+      const int prio = __builtin_amdgcn_readfirstlane(r->priority);
+      const int norm_dir = __builtin_amdgcn_readfirstlane(r->norm_dir);
+      const int vert0 = __builtin_amdgcn_readfirstlane(r->vert0), nvert = __builtin_amdgcn_readfirstlane(r->nvert);
+      const bool has_matrix = __builtin_amdgcn_readfirstlane(r->has_matrix) != 0;
+      unsigned gate = 0u;
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const int i = i0 + M::xi(q), jj = j + M::yi(q), kk = k + M::zi(q);
+        const bool g = i >= b0 && i <= b3 && jj >= b1 && jj <= b4 && kk >= b2 && kk <= b5;
+        gate |= (g ? 1u : 0u) << q;
+      }
+      const unsigned in = vx_test<N>(r, type, PASS == PASS_EDGE, norm_dir, vert0, nvert, has_matrix, a.verts, a.tol, wx, wy, wz, gate);
+      const int idx = c0 + p;
+      if (PASS == PASS_CELL) {
+#pragma unroll
+        for (int q = 0; q < VX_PTS; ++q) {
+          const bool w = ((in >> q) & 1u) && prio >= best[q];     // records are in drawing order: >= lets the later one win a tie
+          best[q] = w ? prio : best[q];
+          own[q] = w ? idx : own[q];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < VX_PTS; ++q) {
+          const bool n0 = (in >> q) & 1u;
+          const bool ex = n0 && ((in >> (q + 1)) & 1u), ey = n0 && ((in >> (q + 5)) & 1u), ez = n0 && ((in >> (q + 9)) & 1u);
+          const bool w0 = ex && prio >= best[q], w1 = ey && prio >= best[VX_PTS + q], w2 = ez && prio >= best[2 * VX_PTS + q];
+          best[q] = w0 ? prio : best[q];                       own[q] = w0 ? idx : own[q];
+          best[VX_PTS + q] = w1 ? prio : best[VX_PTS + q];         own[VX_PTS + q] = w1 ? idx : own[VX_PTS + q];
+          best[2 * VX_PTS + q] = w2 ? prio : best[2 * VX_PTS + q]; own[2 * VX_PTS + q] = w2 ? idx : own[2 * VX_PTS + q];
+        }
+      }
+    }
+  }
+
+  // stores: int4 where the row length keeps every group of four 16-byte aligned (hipMalloc aligns the base)
+  if (j >= py || i0 >= px) return;
+  const size_t plane = (size_t)px * (size_t)py;
+  const size_t row = ((size_t)k * (size_t)py + (size_t)j) * (size_t)px + (size_t)i0;
+  const size_t comp_stride = plane * (size_t)pz;
+  const bool wide = (px % 4 == 0) && (comp_stride % 4 == 0);     // block-uniform; i0 is a multiple of 4, so i0 + 3 < px
+#pragma unroll
+  for (int c = 0; c < (PASS == PASS_CELL ? 1 : 3); ++c) {
+    int32_t* dst = a.out + (size_t)c * comp_stride + row;
+    if (wide) {
+      *reinterpret_cast<int4*>(dst) = make_int4(own[c * VX_PTS], own[c * VX_PTS + 1], own[c * VX_PTS + 2], own[c * VX_PTS + 3]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < VX_PTS; ++q)
+        if (i0 + q < px) dst[q] = own[c * VX_PTS + q];
+    }
+  }
+}
+// The host part of fdtd_voxelize: validates the table and copies it to out[nprim] with its index boxes clipped to the grid.
+int vx_check_table(int nx, int ny, int nz, int nprim, const void* table, int nvert, fdtd_voxel_prim* out) {
+  if (nx < 2 || ny < 2 || nz < 2 || nprim < 0 || nvert < 0 || (nprim > 0 && (!table || !out)))
+    return fdtd_fail(nullptr, FDTD_E_ARG, "bad voxelize argument");
+  const int nn[3] = {nx, ny, nz};
+  for (int p = 0; p < nprim; ++p) {
+    fdtd_voxel_prim r;
+    memcpy(&r, (const char*)table + (size_t)p * sizeof(r), sizeof(r));
+    if (r.type < 0 || r.type >= FDTD_VOXEL_NTYPES || (r.role != FDTD_VOXEL_MATERIAL && r.role != FDTD_VOXEL_METAL))
+      return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d has type %d, role %d", p, r.type, r.role);
+    const bool poly = r.type == FDTD_VOXEL_POLYGON || r.type == FDTD_VOXEL_LINPOLY, wire = r.type == FDTD_VOXEL_WIRE;
+    if (poly || wire) {
+      const long long need = (long long)r.vert0 + (long long)(poly ? 2 : 3) * (long long)r.nvert;
+      if (r.vert0 < 0 || r.nvert < 1 || need > (long long)nvert)
+        return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d reads vertices %d + %d of %d", p, r.vert0, r.nvert, nvert);
+      if (poly && (r.norm_dir < 0 || r.norm_dir > 2))
+        return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d has norm_dir %d", p, r.norm_dir);
+    }
+    for (int ax = 0; ax < 3; ++ax) {                              // clip the index boxes to the grid
+      if (r.cbox[ax] < 0) r.cbox[ax] = 0;
+      if (r.cbox[3 + ax] > nn[ax] - 2) r.cbox[3 + ax] = nn[ax] - 2;
+      if (r.nbox[ax] < 0) r.nbox[ax] = 0;
+      if (r.nbox[3 + ax] > nn[ax] - 1) r.nbox[3 + ax] = nn[ax] - 1;
+    }
+    out[p] = r;
+  }
+  return FDTD_OK;
+}
+}  // namespace
+
+extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
+                             const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner) {
+  if (!lines || (nvert > 0 && !verts) || !(tol >= 0.0)) return fdtd_fail(nullptr, FDTD_E_ARG, "bad voxelize argument");
+  std::vector<fdtd_voxel_prim> tab;
+  try {
+    tab.resize((size_t)(nprim > 0 ? nprim : 0));
+  } catch (...) {
+    return fdtd_fail(nullptr, FDTD_E_NOMEM, "voxelize: no host memory for %d records", nprim);
+  }
+  int rc = vx_check_table(nx, ny, nz, nprim, table, nvert, tab.data());
+  if (rc != FDTD_OK) return rc;
+  const size_t ncell = (size_t)(nx - 1) * (size_t)(ny - 1) * (size_t)(nz - 1), nedge = 3 * (size_t)nx * (size_t)ny * (size_t)nz;
+  if (nprim == 0) {                                               // nothing drawn: no device work
+    if (cell_owner) for (size_t q = 0; q < ncell; ++q) cell_owner[q] = -1;
+    if (edge_owner) for (size_t q = 0; q < nedge; ++q) edge_owner[q] = -1;
+    return FDTD_OK;
+  }
+  if (!cell_owner && !edge_owner) return FDTD_OK;
+  HIPCK(nullptr, hipSetDevice(device));
+  double *d_lines = nullptr, *d_verts = nullptr;
+  fdtd_voxel_prim* d_tab = nullptr;
+  int32_t *d_cell = nullptr, *d_edge = nullptr;
+  const size_t nl = (size_t)nx + (size_t)ny + (size_t)nz;
+#define VX(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess && rc == FDTD_OK) rc = fdtd_fail(nullptr, e_ == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+  VX(hipMalloc(&d_lines, nl * sizeof(double)));
+  VX(hipMalloc(&d_verts, (size_t)(nvert > 0 ? nvert : 1) * sizeof(double)));
+  VX(hipMalloc(&d_tab, (size_t)nprim * sizeof(fdtd_voxel_prim)));
+  if (cell_owner) VX(hipMalloc(&d_cell, ncell * sizeof(int32_t)));
+  if (edge_owner) VX(hipMalloc(&d_edge, nedge * sizeof(int32_t)));
+  if (rc == FDTD_OK) {
+    VX(hipMemcpy(d_lines, lines, nl * sizeof(double), hipMemcpyHostToDevice));
+    if (nvert > 0) VX(hipMemcpy(d_verts, verts, (size_t)nvert * sizeof(double), hipMemcpyHostToDevice));
+    VX(hipMemcpy(d_tab, tab.data(), (size_t)nprim * sizeof(fdtd_voxel_prim), hipMemcpyHostToDevice));
+  }
+  if (rc == FDTD_OK) {
+    VoxArgs a{nx, ny, nz, d_lines, nprim, d_tab, d_verts, tol, nullptr};
+    const int per_x = VX_TX * VX_PTS;
+    if (cell_owner) {
+      a.out = d_cell;
+      hipLaunchKernelGGL(k_voxel<PASS_CELL>, dim3((nx - 1 + per_x - 1) / per_x, (ny - 1 + VX_TY - 1) / VX_TY, nz - 1), dim3(VX_BLOCK), 0, 0, a);
+      VX(hipGetLastError());
+    }
+    if (edge_owner) {
+      a.out = d_edge;
+      hipLaunchKernelGGL(k_voxel<PASS_EDGE>, dim3((nx + per_x - 1) / per_x, (ny + VX_TY - 1) / VX_TY, nz), dim3(VX_BLOCK), 0, 0, a);
+      VX(hipGetLastError());
+    }
+    VX(hipDeviceSynchronize());
+    if (rc == FDTD_OK && cell_owner) VX(hipMemcpy(cell_owner, d_cell, ncell * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (rc == FDTD_OK && edge_owner) VX(hipMemcpy(edge_owner, d_edge, nedge * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+#undef VX
+  hipFree(d_lines); hipFree(d_verts); hipFree(d_tab); hipFree(d_cell); hipFree(d_edge);
+  return rc;
+}

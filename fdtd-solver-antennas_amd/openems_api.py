@@ -31,6 +31,7 @@ from . import constants
 from .grid import RectGrid
 from .mesher import mesh_hint_from_box, smooth_mesh_lines, unique_lines
 from .scene import Scene, Box as SceneBox, voxelize
+from . import primitives as _prims
 from .simulation import Simulation, BoundarySpec
 from .nf2ff import calc_nf2ff, NF2FFResult
 
@@ -100,11 +101,11 @@ class CSRectGrid:
             self._lines[a] = unique_lines(self._lines[a]).tolist()
 
 
-class CSPrimBox:
-    def __init__(self, entry: dict, start, stop, priority):
+class _CSPrimitive:
+    """What every primitive shares: its call-log entry, priority and transform."""
+
+    def __init__(self, entry: dict, priority):
         self._entry = entry
-        self.start = np.asarray(start, dtype=float)
-        self.stop = np.asarray(stop, dtype=float)
         self.priority = int(priority)
         self.matrix = np.eye(4)
 
@@ -124,11 +125,66 @@ class CSPrimBox:
         self.matrix = M @ self.matrix      # applied in the order given, column-vector convention
         return self
 
+    def GetPriority(self):
+        return self.priority
+
+
+class CSPrimBox(_CSPrimitive):
+    def __init__(self, entry: dict, start, stop, priority):
+        super().__init__(entry, priority)
+        self.start = np.asarray(start, dtype=float)
+        self.stop = np.asarray(stop, dtype=float)
+
     def GetStart(self):
         return self.start
 
     def GetStop(self):
         return self.stop
+
+
+class CSPrimCurved(_CSPrimitive):
+    """AddCylinder, AddCylindricalShell, AddSphere, AddSphericalShell, AddPolygon, AddLinPoly, AddCurve, AddWire: `kind` is the
+    primitives.py class name, `prim` the validated primitive (drawing units, without the transform)."""
+
+    def __init__(self, entry: dict, kind: str, priority, **kw):
+        super().__init__(entry, priority)
+        self.kind = kind
+        self.prim = _prims.make(kind, priority, **kw)
+
+    def to_scene(self):
+        import copy
+        pr = copy.copy(self.prim)
+        pr.matrix = self.matrix.copy()
+        return pr
+
+    def bounding_box(self):
+        """(start, stop) of the world-space bounding box, drawing units (what AddEdges2Grid takes the primitive by)."""
+        pr = self.prim
+        if self.kind in ("Sphere", "SphericalShell"):
+            ext = pr.radius + 0.5 * getattr(pr, "shell_width", 0.0)
+            lo, hi = np.asarray(pr.center) - ext, np.asarray(pr.center) + ext
+        elif self.kind in ("Cylinder", "CylindricalShell"):
+            # exact for an axis along a coordinate direction: the radius extends the two transverse axes only
+            a, b = np.asarray(pr.start), np.asarray(pr.stop)
+            ext = (pr.radius + 0.5 * getattr(pr, "shell_width", 0.0)) * np.ones(3)
+            d = np.nonzero(a != b)[0]
+            if d.size == 1 or (d.size == 0):
+                ext[d[0] if d.size else 2] = 0.0
+            lo, hi = np.minimum(a, b) - ext, np.maximum(a, b) + ext
+        elif self.kind in ("Polygon", "LinPoly"):
+            n = pr.norm_dir
+            lo, hi = np.zeros(3), np.zeros(3)
+            e1 = pr.elevation + getattr(pr, "length", 0.0)
+            lo[n], hi[n] = min(pr.elevation, e1), max(pr.elevation, e1)
+            for q, ax in enumerate(((n + 1) % 3, (n + 2) % 3)):
+                lo[ax], hi[ax] = pr.points[q].min(), pr.points[q].max()
+        else:
+            r = getattr(pr, "radius", 0.0)
+            lo, hi = pr.points.min(axis=1) - r, pr.points.max(axis=1) + r
+        if not np.allclose(self.matrix, np.eye(4)):
+            c = np.array([[x, y, z, 1.0] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])]) @ self.matrix.T
+            lo, hi = c[:, :3].min(axis=0), c[:, :3].max(axis=0)
+        return lo, hi
 
 
 class CSProperty:
@@ -146,6 +202,54 @@ class CSProperty:
         b = CSPrimBox(self._log.calls[-1], start, stop, priority)
         self.boxes.append(b)
         return b
+
+    # -- the curved and polygonal primitives (primitives.py), CSXCAD's argument names; `boxes` keeps the drawing order of all ------
+    def _add(self, kind, priority, **kw):
+        if kind in ("Curve", "Wire") and self.kind != "Metal":
+            raise ValueError(f"Add{kind} on {self.kind} '{self.name}': curves and wires are for metals (AddMetal) only")
+        if self.kind == "LumpedElement":
+            raise ValueError(f"Add{kind} on lumped element '{self.name}': lumped elements take boxes only")
+        self._log.add("Add" + kind, prop=self.name, priority=priority, **kw)
+        b = CSPrimCurved(self._log.calls[-1], kind, priority, **kw)
+        self.boxes.append(b)
+        return b
+
+    def AddCylinder(self, start, stop, radius, priority=0, **kw):
+        return self._add("Cylinder", priority, start=list(start), stop=list(stop), radius=radius)
+
+    def AddCylindricalShell(self, start, stop, radius, shell_width, priority=0, **kw):
+        return self._add("CylindricalShell", priority, start=list(start), stop=list(stop), radius=radius, shell_width=shell_width)
+
+    def AddSphere(self, center, radius, priority=0, **kw):
+        return self._add("Sphere", priority, center=list(center), radius=radius)
+
+    def AddSphericalShell(self, center, radius, shell_width, priority=0, **kw):
+        return self._add("SphericalShell", priority, center=list(center), radius=radius, shell_width=shell_width)
+
+    def AddPolygon(self, points, norm_dir, elevation, priority=0, **kw):
+        return self._add("Polygon", priority, points=np.asarray(points, float), norm_dir=_AX[norm_dir], elevation=elevation)
+
+    def AddLinPoly(self, points, norm_dir, elevation, length, priority=0, **kw):
+        return self._add("LinPoly", priority, points=np.asarray(points, float), norm_dir=_AX[norm_dir], elevation=elevation, length=length)
+
+    def AddCurve(self, points, priority=0, **kw):
+        return self._add("Curve", priority, points=np.asarray(points, float))
+
+    def AddWire(self, points, radius, priority=0, **kw):
+        return self._add("Wire", priority, points=np.asarray(points, float), radius=radius)
+
+    def _out_of_scope(self, what):
+        raise ValueError(f"{what} is not supported by the HIP backend: out of scope (boxes, cylinders, spheres, shells, polygons, "
+                         f"curves and wires are)")
+
+    def AddRotPoly(self, *a, **kw):
+        self._out_of_scope("AddRotPoly")
+
+    def AddPolyhedron(self, *a, **kw):
+        self._out_of_scope("AddPolyhedron")
+
+    def AddMultiBox(self, *a, **kw):
+        self._out_of_scope("AddMultiBox")
 
 
 def _take(kw, names, numbered):
@@ -428,9 +532,13 @@ class openEMS:
             boxes.extend(primitives if isinstance(primitives, (list, tuple)) else [primitives])
         grid = self._csx.GetGrid()
         for b in boxes:
-            if not np.allclose(b.matrix, np.eye(4)):
+            if isinstance(b, CSPrimCurved):
+                start, stop = b.bounding_box()      # a curved primitive is taken by its world-space bounding box
+            elif not np.allclose(b.matrix, np.eye(4)):
                 continue   # as upstream: edge hints cannot be derived for transformed primitives
-            hint = mesh_hint_from_box(b.start, b.stop, d, mer)
+            else:
+                start, stop = b.start, b.stop
+            hint = mesh_hint_from_box(start, stop, d, mer)
             for a in range(3):
                 if hint[a]:
                     grid._lines[a].extend(hint[a])
@@ -456,6 +564,10 @@ class openEMS:
         return self._nf2ff
 
     # -- run ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _draw(m, b):
+        m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()) if isinstance(b, CSPrimBox) else b.to_scene())
+
     def _build_scene(self):
         csx = self._csx
         unit = csx.GetGrid().GetDeltaUnit()
@@ -468,7 +580,7 @@ class openEMS:
                 m = sc.add_lorentz_material(p.name, q["epsilon"], q["kappa"], wp=[2 * np.pi * f for f in q["eps_plasma"]],
                                             w0=[2 * np.pi * f for f in q["eps_pole_freq"]], gamma=[1.0 / t if t else 0.0 for t in q["eps_relax"]])
                 for b in p.boxes:
-                    m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
+                    self._draw(m, b)
             elif p.kind in ("Material", "DebyeMaterial"):
                 m = (sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0),
                                      mu_r=p.params.get("mue", 1.0), sigma_m=p.params.get("sigma", 0.0)) if p.kind == "Material" else
@@ -476,11 +588,13 @@ class openEMS:
                 if p.kind == "DebyeMaterial":
                     m.medium.fit_info = getattr(p, "fit_info", None)
                 for b in p.boxes:
-                    m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
+                    self._draw(m, b)
             elif p.kind == "LumpedElement":
                 m = sc.add_lumped_element(p.name, p.params["ny"], R=p.params["R"], C=p.params["C"], L=p.params["L"],
                                           kind=p.params["LEtype"], caps=p.params["caps"])
                 for b in p.boxes:
+                    if not isinstance(b, CSPrimBox):
+                        raise ValueError(f"lumped element '{p.name}': {b.kind} is not supported, lumped elements take boxes only")
                     if not np.allclose(b.matrix, np.eye(4)):
                         raise ValueError(f"lumped element '{p.name}': transforms of its boxes are not supported")
                     m.add_box(b.start, b.stop, b.priority)
@@ -488,7 +602,7 @@ class openEMS:
                 m = (sc.add_conducting_sheet(p.name, p.params["conductivity"], p.params["thickness"]) if p.kind == "ConductingSheet"
                      else sc.add_metal(p.name))
                 for b in p.boxes:
-                    m.boxes.append(SceneBox(tuple(b.start), tuple(b.stop), b.priority, b.matrix.copy()))
+                    self._draw(m, b)
         for port in self._ports:
             sc.add_lumped_port(port.number, port.R, port.start, port.stop, port.exc_ny, port.excite, port.priority)
         return grid, sc
@@ -506,7 +620,7 @@ class openEMS:
     def Run(self, sim_path, cleanup=False, setup_only=False, verbose=None, **kw):
         """Time-step on the GPU.  Blocks; ctypes releases the GIL so a GUI thread stays live
         (the reference calls this from one background thread, gui_app.py:2688-2690)."""
-        from ._capi import load_hip_library
+        from ._capi import load_hip_library, default_rasteriser
         self.calls_log.add("Run", verbose=verbose, cleanup=cleanup)
         if self._csx is None or self._f0 is None:
             raise RuntimeError("SetCSX and SetGaussExcite must be called before Run")
@@ -514,7 +628,7 @@ class openEMS:
             self._wipe_sim_path(sim_path)
         lib = self._lib or load_hip_library()
         grid, sc = self._build_scene()
-        vox = voxelize(sc, grid)
+        vox = voxelize(sc, grid, rasteriser=default_rasteriser(lib, self._device))
         bc = BoundarySpec.parse(self._bc, self._cpml_cells)
         freqs = None
         if self._nf2ff is not None:

@@ -28,6 +28,7 @@ from . import dispersion as _disp
 from . import lorentz as _lorentz
 from . import lumped as _lumped
 from . import magnetic as _magnetic
+from . import primitives as _prims
 
 
 @dataclass
@@ -38,8 +39,34 @@ class Box:
     matrix: Optional[np.ndarray] = None   # 4x4 local->world (drawing units), None = identity
 
 
+class _Drawable:
+    """The drawing calls beyond add_box (primitives.py); `boxes` holds every primitive of the property in drawing order."""
+
+    def _add(self, kind, priority, **kw):
+        self.boxes.append(_prims.make(kind, priority, **kw))
+        return self
+
+    def add_cylinder(self, start, stop, radius, priority=0):
+        return self._add("Cylinder", priority, start=start, stop=stop, radius=radius)
+
+    def add_cylindrical_shell(self, start, stop, radius, shell_width, priority=0):
+        return self._add("CylindricalShell", priority, start=start, stop=stop, radius=radius, shell_width=shell_width)
+
+    def add_sphere(self, center, radius, priority=0):
+        return self._add("Sphere", priority, center=center, radius=radius)
+
+    def add_spherical_shell(self, center, radius, shell_width, priority=0):
+        return self._add("SphericalShell", priority, center=center, radius=radius, shell_width=shell_width)
+
+    def add_polygon(self, points, norm_dir, elevation, priority=0):
+        return self._add("Polygon", priority, points=points, norm_dir=norm_dir, elevation=elevation)
+
+    def add_lin_poly(self, points, norm_dir, elevation, length, priority=0):
+        return self._add("LinPoly", priority, points=points, norm_dir=norm_dir, elevation=elevation, length=length)
+
+
 @dataclass
-class Material:
+class Material(_Drawable):
     name: str
     eps_r: float = 1.0
     kappa: float = 0.0
@@ -65,13 +92,25 @@ class LorentzMaterial(Material):
 
 
 @dataclass
-class Metal:
+class Metal(_Drawable):
     name: str
     boxes: List[Box] = field(default_factory=list)
 
     def add_box(self, start, stop, priority=0):
         self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
         return self
+
+    def _no_sheet(self, what):
+        if isinstance(self, ConductingSheet):
+            raise ValueError(f"conducting sheet '{self.name}': {what} is for plain metals (add_metal) only")
+
+    def add_curve(self, points, priority=0):
+        self._no_sheet("a curve")
+        return self._add("Curve", priority, points=points)
+
+    def add_wire(self, points, radius, priority=0):
+        self._no_sheet("a wire")
+        return self._add("Wire", priority, points=points, radius=radius)
 
 
 @dataclass
@@ -266,7 +305,11 @@ def _merged_media(materials, kind):
     return media, names, medium_of
 
 
-def voxelize(scene: Scene, grid: RectGrid) -> VoxelScene:
+def voxelize(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
+    """A scene drawn with boxes only takes the box path below; any other primitive sends every primitive, boxes included, through
+    the owner arrays of `rasteriser` (default: primitives.rasterise_spec; _capi.voxelize_device gives the device one)."""
+    if _prims.has_new(scene):
+        return voxelize_owners(scene, grid, rasteriser)
     nx, ny, nz = grid.shape
     u = scene.unit
     tol = _tol(grid)
@@ -374,6 +417,25 @@ def _voxelize_with_sheets(scene: Scene, grid: RectGrid, eps, kap) -> VoxelScene:
                 win = edge & (eprio[c][sl] <= bx.priority)
                 eprio[c][sl][win] = bx.priority
                 eown[c][sl][win] = mi
+    def filled_of(members):
+        filled = np.zeros((nz, ny, nx), bool)
+        for mi in members:
+            for bx in scene.metals[mi].boxes:
+                r = _inside_mask(bx, u, -tol, centers)
+                if r is None:
+                    continue
+                mask, off = r
+                sl = tuple(slice(off[a], off[a] + mask.shape[2 - a]) for a in (2, 1, 0))
+                filled[sl] |= mask
+        return filled
+    return _sheets_from_owners(scene, grid, eps, kap, eown, node_masks, filled_of)
+
+
+def _sheets_from_owners(scene: Scene, grid: RectGrid, eps, kap, eown, node_masks, filled_of) -> VoxelScene:
+    """The sheet edges from eown (int32 [3][nz][ny][nx]: the metal that owns the edge, -1 none), node_masks (sheet metal -> the node
+    masks of its primitives) and filled_of(members) (the cells a group of sheet metals fills, at the lowest node)."""
+    nx, ny, nz = grid.shape
+    u = scene.unit
     pec = eown >= 0
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
     sh = _sheet.SheetEdges()
@@ -384,15 +446,7 @@ def _voxelize_with_sheets(scene: Scene, grid: RectGrid, eps, kap) -> VoxelScene:
     for mi in node_masks:
         groups.setdefault((scene.metals[mi].conductivity, scene.metals[mi].thickness), []).append(mi)
     for members in groups.values():
-        filled = np.zeros((nz, ny, nx), bool)
-        for mi in members:
-            for bx in scene.metals[mi].boxes:
-                r = _inside_mask(bx, u, -tol, centers)
-                if r is None:
-                    continue
-                mask, off = r
-                sl = tuple(slice(off[a], off[a] + mask.shape[2 - a]) for a in (2, 1, 0))
-                filled[sl] |= mask
+        filled = filled_of(members)
         S = _sheet.surface_faces([m for mi in members for m in node_masks[mi]], filled)
         for mi in members:
             met = scene.metals[mi]
@@ -566,3 +620,83 @@ def _elements_on_grid(scene: Scene, grid: RectGrid, pec: np.ndarray, ports, shee
             if hit.any():
                 raise ValueError(f"{where(int(np.argmax(hit)))} is a {what} of lumped port {p.port.number}")
     return out
+
+
+def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
+    """voxelize() through the owner arrays (primitives.pack_table -> rasteriser(grid, table) -> (cell_owner, edge_owner)): every
+    VoxelScene field is filled from the owners, by the ownership rules of the box path (highest priority, later wins ties; an edge
+    is metal when one primitive holds both its end nodes).  Curves and wire centre lines are snapped to grid edges on the host."""
+    import warnings
+    nx, ny, nz = grid.shape
+    u = scene.unit
+    table = _prims.pack_table(scene, grid)
+    cown, eown = (rasteriser or _prims.rasterise_spec)(grid, table)
+    rec = table.rec
+    shape = (nz - 1, ny - 1, nx - 1)
+    if cown.shape != shape or eown.shape != (3, nz, ny, nx):
+        raise ValueError("the rasteriser returned owner arrays of the wrong shape")
+    media, media_names, medium_of = _merged_media(scene.materials, DebyeMaterial)
+    if len(media) > _disp.MAX_MEDIA:
+        raise ValueError(f"{len(media)} different Debye media: at most {_disp.MAX_MEDIA}")
+    lmedia, lmedia_names, lmedium_of = _merged_media(scene.materials, LorentzMaterial)
+    if len(lmedia) > _lorentz.MAX_MEDIA:
+        raise ValueError(f"{len(lmedia)} different Lorentz media: at most {_lorentz.MAX_MEDIA}")
+    # per-material tables with the background in the last row, indexed by the owner's material (-1: background)
+    mats = scene.materials
+    cmat = np.where(cown >= 0, rec["prop"][np.maximum(cown, 0)] if rec.size else -1, -1).astype(np.int32)
+
+    def per_cell(values, background, dtype=np.float64):
+        return np.array(list(values) + [background], dtype)[cmat]
+    eps = per_cell((m.eps_r for m in mats), 1.0)
+    kap = per_cell((m.kappa for m in mats), 0.0)
+    mur = per_cell((m.mu_r for m in mats), 1.0)
+    sgm = per_cell((m.sigma_m for m in mats), 0.0)
+    cmed = per_cell((medium_of[m.medium.key()] if isinstance(m, DebyeMaterial) else -1 for m in mats), -1, np.int8) if media else None
+    clor = per_cell((lmedium_of[m.medium.key()] if isinstance(m, LorentzMaterial) else -1 for m in mats), -1, np.int8) if lmedia else None
+    debye = _disp.make_edges(grid, media, media_names, cmed) if media and np.any(cmed >= 0) else None
+    lorentz = _lorentz.make_edges(grid, lmedia, lmedia_names, clor) if lmedia and np.any(clor >= 0) else None
+    if lorentz is not None:
+        _lorentz.check_disjoint(lorentz, debye)
+    # metals: the metal that owns each edge; curve edges go to their metal where no volume owns the edge
+    emet = np.where(eown >= 0, rec["prop"][np.maximum(eown, 0)] if rec.size else -1, -1).astype(np.int32)
+    for mi, pts in table.curves:
+        for c, i, j, k in _prims.snap_curve(grid, pts):
+            if emet[c, k, j, i] < 0:
+                emet[c, k, j, i] = mi
+    owned = np.unique(emet)
+    metal_recs = np.nonzero(rec["role"] == _prims.ROLE_METAL)[0] if rec.size else []
+    for mi, met in enumerate(scene.metals):
+        if met.boxes and mi not in owned and not any(_prims.marks_any_edge(grid, table, q) for q in metal_recs if rec["prop"][q] == mi):
+            warnings.warn(f"metal '{met.name}' marks no edge of this mesh: it is thinner than a cell and misses every node "
+                          f"(add mesh lines through it)", RuntimeWarning, stacklevel=3)
+    names = [m.name for m in mats]
+    if any(isinstance(m, ConductingSheet) for m in scene.metals):
+        node_masks = {}
+        cells_of = {}
+        for q in metal_recs:
+            mi = int(rec["prop"][q])
+            if not isinstance(scene.metals[mi], ConductingSheet):
+                continue
+            for cells, store in ((False, node_masks), (True, cells_of)):
+                res = _prims.node_mask(grid, table, q, cells=cells, role=_prims.ROLE_MATERIAL if cells else None)
+                if res is None:
+                    continue
+                full = np.zeros((nz, ny, nx), bool)
+                full[res[1]] = res[0]
+                store.setdefault(mi, []).append(full)
+
+        def filled_of(members):
+            filled = np.zeros((nz, ny, nx), bool)
+            for mi in members:
+                for f in cells_of.get(mi, []):
+                    filled |= f
+            return filled
+        vs = _sheets_from_owners(scene, grid, eps, kap, emet, node_masks, filled_of)
+        vs.debye, vs.lorentz = debye, lorentz
+        vs.mu_r, vs.sigma_m, vs.cell_material, vs.material_names = mur, sgm, cmat, names
+        vs.elements = _elements_on_grid(scene, grid, vs.pec, vs.ports, vs.sheets)
+        return vs
+    pec = emet >= 0
+    ports = [_port_on_grid(p, grid, u) for p in scene.ports]
+    return VoxelScene(eps, kap, pec, ports, debye=debye, lorentz=lorentz, elements=_elements_on_grid(scene, grid, pec, ports, None),
+                      mu_r=mur, sigma_m=sgm, cell_material=cmat, material_names=names)
