@@ -281,6 +281,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   debye_free(c);
   lorentz_free(c);
   magnetic_free(c);
+  conformal_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
   hipFree(c->mbox);
@@ -905,6 +906,7 @@ static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
   if (c->lorentz_nmedia > 0) return false; // Lorentz / Drude media: likewise
   if (c->lumped_n > 0) return false;       // lumped elements: likewise
   if (c->mag_ncls > 0) return false;       // magnetic faces: their correction runs between the H update and whatever reads I next
+  if (c->conf_n > 0) return false;         // conformal faces: likewise
   const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
                                       wf_lag_for(c) >= c->d.nk);
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
@@ -942,7 +944,7 @@ static bool wavefront_active(const fdtd_ctx* c, bool fused) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lorentz_nmedia > 0 || c->lumped_n > 0 || c->mag_ncls > 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lorentz_nmedia > 0 || c->lumped_n > 0 || c->mag_ncls > 0 || c->conf_n > 0) return false;
   if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -1060,6 +1062,11 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
       return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: the two-launch schedule only (their correction runs between the H update and the next E phase)");
     if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: single slab only (world = 1, no p2p transport, no linked contexts)");
+  }
+  if (c->conf_n > 0) {
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conformal boundaries: the two-launch schedule only (their correction runs between the H update and the next E phase)");
+    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conformal boundaries: single slab only (world = 1, no p2p transport, no linked contexts)");
   }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";
@@ -1187,6 +1194,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
     launch_update_H(c, nk - 1, nk, step, false, s);
   }
   launch_magnetic(c, s);   // magnetic faces: after the whole H update, before anything samples I (no-op without faces)
+  launch_conformal(c, s);  // conformal faces: likewise
   if (!pl.fused) launch_post(c, FDTD_KIND_I, step, false, s);
   launch_dft(c, FDTD_KIND_I, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_H, s));
@@ -1473,6 +1481,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);
     launch_magnetic(c, s);
+    launch_conformal(c, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);
     launch_dft(c, FDTD_KIND_I, c->step, s);
     c->step++;
@@ -2019,7 +2028,10 @@ int fdtd_set_field(fdtd_ctx* c, int kind, int comp, const float* in) {
   float* dst = kind == FDTD_KIND_V ? c->p.V[comp] : c->p.I[comp];
   HIPCK(c, hipMemcpy2D(dst, (size_t)c->P * 4, in, (size_t)c->d.nx * 4, (size_t)c->d.nx * 4, (size_t)c->d.nk * c->d.ny,
                        hipMemcpyHostToDevice));
-  if (kind == FDTD_KIND_I) return magnetic_prime(c, comp);   // magnetic faces: i_prev is the I the next H update starts from
+  if (kind == FDTD_KIND_I) {   // magnetic and conformal faces: i_prev is the I the next H update starts from
+    const int r = magnetic_prime(c, comp);
+    return r ? r : conformal_prime(c, comp);
+  }
   return FDTD_OK;
 }
 

@@ -307,6 +307,12 @@ struct fdtd_ctx {
   int mag_ncls = 0;                             // live classes (0: no magnetic faces)
   MagBox mag_box[3];
   float2* mag_tab = nullptr;
+  // conformal PEC boundaries (conformal.hip, include/fdtd_hip_conformal.h): the listed faces — per face its node offset and component,
+  // its four coefficients and i_prev
+  int conf_n = 0;                               // listed faces (0: none)
+  int4* conf_face = nullptr;
+  float4* conf_coef = nullptr;
+  float* conf_iprev = nullptr;
   std::string err;
 };
 
@@ -376,6 +382,10 @@ void lorentz_free(fdtd_ctx* c);
 void launch_magnetic(fdtd_ctx* c, hipStream_t s);
 int magnetic_prime(fdtd_ctx* c, int comp);   // i_prev <- the component's I array (fdtd_magnetic_set, fdtd_set_field)
 void magnetic_free(fdtd_ctx* c);
+// conformal.hip: conformal PEC boundaries — the sparse correction after the H update, behind launch_magnetic (no-op without faces)
+void launch_conformal(fdtd_ctx* c, hipStream_t s);
+int conformal_prime(fdtd_ctx* c, int comp);  // i_prev <- the listed faces' currents (fdtd_conformal_set, fdtd_set_field; comp < 0: all)
+void conformal_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

@@ -15,6 +15,7 @@
 
 #include "fdtd_ctx.h"
 #include "../../include/fdtd_hip_voxel.h"
+#include "../../include/fdtd_hip_conformal.h"
 
 static_assert(sizeof(fdtd_voxel_prim) == 248, "fdtd_voxel_prim is 248 bytes (primitives.RECORD)");
 
@@ -306,6 +307,80 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
     }
   }
 }
+// ---- conformal fractions (include/fdtd_hip_conformal.h, conformal.fractions_spec) -----------------------------------------------
+// Both kernels call vx_test<1> on the records in global memory: the inside predicates are the rasteriser's own text, so a node's
+// or a bisection point's verdict has the bits of primitives._inside.  A cut edge costs nbisect * (records whose node box holds one
+// of its two nodes) predicates; the cut edges are a surface, a few per cent of the grid at most.
+struct FracArgs {
+  int nx, ny, nz;
+  const double* lines;
+  int nprim;
+  const fdtd_voxel_prim* table;
+  const double* verts;
+  double tol, snap;
+  int nbisect;
+  uint8_t* node_in;          // [nz][ny][nx]
+  long long ncut;
+  const uint8_t* code;       // comp | flip << 2
+  const long long* idx;
+  double* f;
+};
+
+__device__ __forceinline__ bool vx_holds(const fdtd_voxel_prim* r, const double* verts, const double tol, const double x, const double y,
+                                         const double z) {
+  const double wx[1] = {x}, wy[1] = {y}, wz[1] = {z};
+  return vx_test<1>(r, r->type, true, r->norm_dir, r->vert0, r->nvert, r->has_matrix != 0, verts, tol, wx, wy, wz, 1u) != 0u;
+}
+__device__ __forceinline__ bool vx_in_box(const fdtd_voxel_prim* r, const int i, const int j, const int k) {
+  return i >= r->nbox[0] && i <= r->nbox[3] && j >= r->nbox[1] && j <= r->nbox[4] && k >= r->nbox[2] && k <= r->nbox[5];
+}
+
+__global__ __launch_bounds__(VX_BLOCK) void k_node_in(const FracArgs a) {
+  const long long q = (long long)blockIdx.x * VX_BLOCK + threadIdx.x;
+  const long long nn = (long long)a.nx * a.ny * a.nz;
+  if (q >= nn) return;
+  const int i = (int)(q % a.nx), j = (int)((q / a.nx) % a.ny), k = (int)(q / ((long long)a.nx * a.ny));
+  const double x = a.lines[i], y = a.lines[a.nx + j], z = a.lines[a.nx + a.ny + k];
+  bool in = false;
+  for (int p = 0; p < a.nprim; ++p) {
+    const fdtd_voxel_prim* r = a.table + p;
+    if (!vx_in_box(r, i, j, k)) continue;
+    in = in || vx_holds(r, a.verts, a.tol, x, y, z);
+  }
+  a.node_in[q] = in ? 1 : 0;
+}
+
+__global__ __launch_bounds__(VX_BLOCK) void k_fractions(const FracArgs a) {
+  const long long e = (long long)blockIdx.x * VX_BLOCK + threadIdx.x;
+  if (e >= a.ncut) return;
+  const int c = a.code[e] & 3;
+  const bool flip = (a.code[e] >> 2) & 1;
+  const long long g = a.idx[e];
+  const int i = (int)(g % a.nx), j = (int)((g / a.nx) % a.ny), k = (int)(g / ((long long)a.nx * a.ny));
+  const int i1 = i + (c == 0 ? 1 : 0), j1 = j + (c == 1 ? 1 : 0), k1 = k + (c == 2 ? 1 : 0);
+  double p[3] = {a.lines[i], a.lines[a.nx + j], a.lines[a.nx + a.ny + k]};
+  const double lower = p[c];
+  const double upper = c == 0 ? a.lines[i1] : c == 1 ? a.lines[a.nx + j1] : a.lines[a.nx + a.ny + k1];
+  const double x_in = flip ? upper : lower, x_out = flip ? lower : upper;
+  const double d = x_out - x_in;
+  double ta = 0.0, tb = 1.0;
+  for (int it = 0; it < a.nbisect; ++it) {
+    const double tm = 0.5 * (ta + tb);
+    const double x = x_in + tm * d;
+    const double px = c == 0 ? x : p[0], py = c == 1 ? x : p[1], pz = c == 2 ? x : p[2];
+    bool in = false;
+    for (int q = 0; q < a.nprim && !in; ++q) {
+      const fdtd_voxel_prim* r = a.table + q;
+      if (!vx_in_box(r, i, j, k) && !vx_in_box(r, i1, j1, k1)) continue;
+      in = vx_holds(r, a.verts, a.tol, px, py, pz);
+    }
+    ta = in ? tm : ta;
+    tb = in ? tb : tm;
+  }
+  const double len = d < 0.0 ? -d : d;
+  a.f[e] = ta * len <= a.snap ? 1.0 : 1.0 - ta;
+}
+
 // The host part of fdtd_voxelize: validates the table and copies it to out[nprim] with its index boxes clipped to the grid.
 int vx_check_table(int nx, int ny, int nz, int nprim, const void* table, int nvert, fdtd_voxel_prim* out) {
   if (nx < 2 || ny < 2 || nz < 2 || nprim < 0 || nvert < 0 || (nprim > 0 && (!table || !out)))
@@ -389,5 +464,79 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
   }
 #undef VX
   hipFree(d_lines); hipFree(d_verts); hipFree(d_tab); hipFree(d_cell); hipFree(d_edge);
+  return rc;
+}
+extern "C" int fdtd_voxel_fractions(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
+                                    const double* verts, double tol, double snap, int nbisect, uint8_t* node_in, int64_t ncut,
+                                    const uint8_t* code, const int64_t* idx, double* f) {
+  if (!lines || (nvert > 0 && !verts) || !(tol >= 0.0) || !(snap >= 0.0) || nbisect < 1 || nbisect > 60 || ncut < 0 ||
+      (ncut > 0 && (!code || !idx || !f)))
+    return fdtd_fail(nullptr, FDTD_E_ARG, "bad fractions argument");
+  std::vector<fdtd_voxel_prim> tab;
+  try {
+    tab.resize((size_t)(nprim > 0 ? nprim : 0));
+  } catch (...) {
+    return fdtd_fail(nullptr, FDTD_E_NOMEM, "fractions: no host memory for %d records", nprim);
+  }
+  int rc = vx_check_table(nx, ny, nz, nprim, table, nvert, tab.data());
+  if (rc != FDTD_OK) return rc;
+  for (int p = 0; p < nprim; ++p)
+    if (tab[p].role != FDTD_VOXEL_METAL) return fdtd_fail(nullptr, FDTD_E_ARG, "fractions: record %d is no metal", p);
+  const long long nn = (long long)nx * ny * nz;
+  for (int64_t e = 0; e < ncut; ++e) {                              // every edge inside the grid and existing
+    const int c = code[e] & 3;
+    const long long g = idx[e];
+    if (c > 2 || code[e] > 7 || g < 0 || g >= nn) return fdtd_fail(nullptr, FDTD_E_ARG, "fractions: edge %lld out of range", (long long)e);
+    const int pos[3] = {(int)(g % nx), (int)((g / nx) % ny), (int)(g / ((long long)nx * ny))};
+    const int lim[3] = {nx, ny, nz};
+    if (pos[c] >= lim[c] - 1) return fdtd_fail(nullptr, FDTD_E_ARG, "fractions: edge %lld does not exist", (long long)e);
+  }
+  if (nprim == 0) {                                                 // nothing drawn: no node inside, no edge cut
+    if (node_in) memset(node_in, 0, (size_t)nn);
+    for (int64_t e = 0; e < ncut; ++e) f[e] = 1.0;
+    return FDTD_OK;
+  }
+  if (!node_in && ncut == 0) return FDTD_OK;
+  HIPCK(nullptr, hipSetDevice(device));
+  double *d_lines = nullptr, *d_verts = nullptr, *d_f = nullptr;
+  fdtd_voxel_prim* d_tab = nullptr;
+  uint8_t *d_node = nullptr, *d_code = nullptr;
+  long long* d_idx = nullptr;
+  const size_t nl = (size_t)nx + (size_t)ny + (size_t)nz;
+#define VX(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess && rc == FDTD_OK) rc = fdtd_fail(nullptr, e_ == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+  VX(hipMalloc(&d_lines, nl * sizeof(double)));
+  VX(hipMalloc(&d_verts, (size_t)(nvert > 0 ? nvert : 1) * sizeof(double)));
+  VX(hipMalloc(&d_tab, (size_t)nprim * sizeof(fdtd_voxel_prim)));
+  if (node_in) VX(hipMalloc(&d_node, (size_t)nn));
+  if (ncut > 0) {
+    VX(hipMalloc(&d_code, (size_t)ncut));
+    VX(hipMalloc(&d_idx, (size_t)ncut * sizeof(long long)));
+    VX(hipMalloc(&d_f, (size_t)ncut * sizeof(double)));
+  }
+  if (rc == FDTD_OK) {
+    VX(hipMemcpy(d_lines, lines, nl * sizeof(double), hipMemcpyHostToDevice));
+    if (nvert > 0) VX(hipMemcpy(d_verts, verts, (size_t)nvert * sizeof(double), hipMemcpyHostToDevice));
+    VX(hipMemcpy(d_tab, tab.data(), (size_t)nprim * sizeof(fdtd_voxel_prim), hipMemcpyHostToDevice));
+    if (ncut > 0) {
+      VX(hipMemcpy(d_code, code, (size_t)ncut, hipMemcpyHostToDevice));
+      VX(hipMemcpy(d_idx, idx, (size_t)ncut * sizeof(long long), hipMemcpyHostToDevice));
+    }
+  }
+  if (rc == FDTD_OK) {
+    FracArgs a{nx, ny, nz, d_lines, nprim, d_tab, d_verts, tol, snap, nbisect, d_node, (long long)ncut, d_code, d_idx, d_f};
+    if (node_in) {
+      hipLaunchKernelGGL(k_node_in, dim3((unsigned)((nn + VX_BLOCK - 1) / VX_BLOCK)), dim3(VX_BLOCK), 0, 0, a);
+      VX(hipGetLastError());
+    }
+    if (ncut > 0) {
+      hipLaunchKernelGGL(k_fractions, dim3((unsigned)((ncut + VX_BLOCK - 1) / VX_BLOCK)), dim3(VX_BLOCK), 0, 0, a);
+      VX(hipGetLastError());
+    }
+    VX(hipDeviceSynchronize());
+    if (rc == FDTD_OK && node_in) VX(hipMemcpy(node_in, d_node, (size_t)nn, hipMemcpyDeviceToHost));
+    if (rc == FDTD_OK && ncut > 0) VX(hipMemcpy(f, d_f, (size_t)ncut * sizeof(double), hipMemcpyDeviceToHost));
+  }
+#undef VX
+  hipFree(d_lines); hipFree(d_verts); hipFree(d_tab); hipFree(d_node); hipFree(d_code); hipFree(d_idx); hipFree(d_f);
   return rc;
 }

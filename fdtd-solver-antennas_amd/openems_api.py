@@ -476,16 +476,20 @@ class openEMS:
     n_gpus / rank / world (z-slab decomposition), device, cpml_cells (default: the _N of 'PML_N'),
     nf2ff_mode: 'auto' (default) records the NF2FF faces in the time domain in HBM when that fits the budget, so
     that CalcNF2FF can be asked for ANY frequency after the run, as upstream; otherwise / 'dft': running DFT at
-    nf2ff_freqs (default then: a 21-point comb over the reference's S11 band, CalcNF2FF snaps to the nearest)."""
+    nf2ff_freqs (default then: a 21-point comb over the reference's S11 band, CalcNF2FF snaps to the nearest).
+    conformal=True: conformal (Dey-Mittra) PEC boundaries on the surfaces of curved and slanted metals (conformal.py) instead of the
+    bare staircase, every g_e = f_e / a_f bounded by conformal_ratio (R, default 2); a scene with cut faces then runs at
+    courant_dt / sqrt(R).  The default False changes nothing."""
 
     def __init__(self, NrTS=1e9, EndCriteria=1e-5, *, lib=None, device=0, rank=0, world=1, cpml_cells=None,
-                 nf2ff_freqs=None, nf2ff_mode="auto", comm=None, **kw):
+                 nf2ff_freqs=None, nf2ff_mode="auto", comm=None, conformal=False, conformal_ratio=2.0, **kw):
         self.calls_log = _CallLog()
         self.NrTS, self.EndCriteria = NrTS, EndCriteria
         self.calls_log.add("openEMS", NrTS=NrTS, EndCriteria=EndCriteria)
         self._lib, self._device, self._rank, self._world = lib, device, rank, world
         self._cpml_cells, self._nf2ff_freqs, self._comm = cpml_cells, nf2ff_freqs, comm
         self._nf2ff_mode, self._nf2ff_snap, self._box_cache = nf2ff_mode, False, {}
+        self._conformal, self._conformal_ratio = bool(conformal), float(conformal_ratio)
         self._csx: Optional[ContinuousStructure] = None
         self._bc = ["PEC"] * 6
         self._f0 = self._fc = None
@@ -620,7 +624,7 @@ class openEMS:
     def Run(self, sim_path, cleanup=False, setup_only=False, verbose=None, **kw):
         """Time-step on the GPU.  Blocks; ctypes releases the GIL so a GUI thread stays live
         (the reference calls this from one background thread, gui_app.py:2688-2690)."""
-        from ._capi import load_hip_library, default_rasteriser
+        from ._capi import load_hip_library, default_rasteriser, default_fractions
         self.calls_log.add("Run", verbose=verbose, cleanup=cleanup)
         if self._csx is None or self._f0 is None:
             raise RuntimeError("SetCSX and SetGaussExcite must be called before Run")
@@ -628,7 +632,8 @@ class openEMS:
             self._wipe_sim_path(sim_path)
         lib = self._lib or load_hip_library()
         grid, sc = self._build_scene()
-        vox = voxelize(sc, grid, rasteriser=default_rasteriser(lib, self._device))
+        fractions = dict(conformal=True, device_fractions=default_fractions(lib, self._device)) if self._conformal else {}
+        vox = voxelize(sc, grid, rasteriser=default_rasteriser(lib, self._device), **fractions)
         bc = BoundarySpec.parse(self._bc, self._cpml_cells)
         freqs = None
         if self._nf2ff is not None:
@@ -636,7 +641,8 @@ class openEMS:
 
         def make(fr):
             return Simulation(grid, vox, f0=self._f0, fc=self._fc, boundary=bc, nr_ts=int(min(self.NrTS, 2**31 - 2)),
-                              end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode)
+                              end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode,
+                              conformal=self._conformal, conformal_ratio=self._conformal_ratio)
         self.sim = make(freqs)
         self._nf2ff_snap, self._box_cache = False, {}
         if self._nf2ff is not None and self.sim.nf2ff_mode == "dft" and self._nf2ff_freqs is None:

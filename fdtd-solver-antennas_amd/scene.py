@@ -28,6 +28,7 @@ from . import dispersion as _disp
 from . import lorentz as _lorentz
 from . import lumped as _lumped
 from . import magnetic as _magnetic
+from . import conformal as _conformal
 from . import primitives as _prims
 
 
@@ -244,6 +245,9 @@ class VoxelScene:
     sigma_m: Optional[np.ndarray] = None
     cell_material: Optional[np.ndarray] = None
     material_names: Optional[List[str]] = None
+    # conformal PEC boundaries (None: not asked for): the nodes inside the plain metals and the fractions of the cut edges
+    # (conformal.Fractions); Simulation(conformal=True) turns them into the face list
+    fractions: Optional["_conformal.Fractions"] = None
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -305,9 +309,18 @@ def _merged_media(materials, kind):
     return media, names, medium_of
 
 
-def voxelize(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
-    """A scene drawn with boxes only takes the box path below; any other primitive sends every primitive, boxes included, through
-    the owner arrays of `rasteriser` (default: primitives.rasterise_spec; _capi.voxelize_device gives the device one)."""
+def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = False, device_fractions=None) -> VoxelScene:
+    """A scene drawn with boxes only takes the box path; any other primitive sends every primitive, boxes included, through the
+    owner arrays of `rasteriser` (default: primitives.rasterise_spec; _capi.voxelize_device gives the device one).  `conformal`:
+    also the fractions of the edges the plain metals cut (conformal.fractions; `device_fractions`: _capi.default_fractions' callable,
+    None: numpy) — the staircase itself, every other field of the result, stays what it is."""
+    vs = _voxelize(scene, grid, rasteriser)
+    if conformal:
+        vs.fractions = _conformal.fractions(scene, grid, device_fractions)
+    return vs
+
+
+def _voxelize(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
     if _prims.has_new(scene):
         return voxelize_owners(scene, grid, rasteriser)
     nx, ny, nz = grid.shape

@@ -21,6 +21,7 @@ from . import lumped as _lumped
 from . import dispersion as _disp
 from . import lorentz as _lorentz
 from . import magnetic as _magnetic
+from . import conformal as _conformal
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox
@@ -149,6 +150,7 @@ class RunStats:
     lorentz: Optional[dict] = None            # Lorentz / Drude media stepped by the engine (lorentz.py): media, K, poles, edges
     lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
     magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
+    conformal: Optional[dict] = None          # conformal PEC boundaries (conformal.py): faces per component, R, dt factor, faces clamped
 
 
 class Simulation:
@@ -157,12 +159,21 @@ class Simulation:
                  dt: Optional[float] = None, nf2ff_freqs: Optional[Sequence[float]] = None,
                  nf2ff_inset: Optional[int] = None, dft_oversample: float = 4.0, use_classes: bool = True,
                  device_operator: bool = True, nf2ff_mode: str = "dft", rec_budget_bytes: Optional[int] = None,
-                 sheet_band: Optional[Sequence[float]] = None, sheet_K: int = _sheet.MAX_K):
+                 sheet_band: Optional[Sequence[float]] = None, sheet_K: int = _sheet.MAX_K,
+                 conformal: bool = False, conformal_ratio: float = _conformal.DEFAULT_RATIO):
         self.grid, self.vox = grid, vox
         self.f0, self.fc = float(f0), float(fc)
         self.bc = BoundarySpec.parse(boundary, cpml_cells)
         self.nr_ts, self.end_criteria = int(nr_ts), float(end_criteria)
-        self.dt = grid.courant_dt() if dt is None else float(dt)
+        # conformal PEC boundaries: the faces the metal surfaces cut, each with its four g_e = f_e / a_f <= conformal_ratio; the
+        # operator stays the base one, the faces are corrected by the engine after every H update (fdtd_conformal_set); a scene with
+        # listed faces runs at courant_dt / sqrt(conformal_ratio)
+        self.conformal = None
+        if conformal:
+            if getattr(vox, "fractions", None) is None:
+                raise ValueError("conformal=True needs the fractions of the cut edges: scene.voxelize(scene, grid, conformal=True)")
+            self.conformal = _conformal.make_faces(grid, vox.fractions, vox.pec, conformal_ratio)
+        self.dt = (grid.courant_dt() if self.conformal is None else float(grid.courant_dt() / np.sqrt(self.conformal.ratio))) if dt is None else float(dt)
         self.use_classes = use_classes
         # True: the engine builds the operator itself from materials + mesh (fdtd_build_operator: on the GPU for
         # libfdtd_hip.so); False: numpy build on the host (ecoperator.build_operator, the spec) + array upload
@@ -283,6 +294,9 @@ class Simulation:
                 on = (vox.mu_r != 1.0) | (sgm != 0.0)
                 media = [vox.material_names[q] for q in np.unique(vox.cell_material[on]) if q >= 0]
             self.magnetic = _magnetic.make_faces(grid, vox.mu_r, sgm, self.dt, media)
+        if self.conformal is not None:
+            _conformal.check_placement(grid, self.conformal, cells, tuple(self.mur_enable),
+                                       None if self.magnetic is None else self.magnetic.full_classes(grid.shape[::-1]))
         # lumped elements: a plain 1/R and the implicit part g0 of the stepped branch folded into the edges' conductance, a plain C
         # into their capacitance (lumped-edge overrides); the edges that carry states are stepped by the engine (fdtd_lumped_set)
         self.elements = vox.elements if getattr(vox, "elements", None) is not None and len(vox.elements) else None
@@ -340,6 +354,8 @@ class Simulation:
             raise _capi.FdtdError("Lorentz media need a single slab (world = 1): a decomposed run with dispersive media is not supported")
         if self.magnetic is not None and world > 1:
             raise _capi.FdtdError("magnetic materials need a single slab (world = 1): a decomposed run with magnetic media is not supported")
+        if self.conformal is not None and world > 1:
+            raise _capi.FdtdError("conformal boundaries need a single slab (world = 1): a decomposed run with cut faces is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
@@ -368,6 +384,8 @@ class Simulation:
             e.set_lumped(*self.lumped_tables())
         if self.magnetic is not None:
             e.set_magnetic(*self.magnetic.tables())
+        if self.conformal is not None:
+            e.set_conformal(*self.conformal_tables())
         if self.cpml is not None:
             e.set_cpml(*self.cpml.for_slab(k0, nk))
         if self.mur_enable.any():
@@ -469,6 +487,17 @@ class Simulation:
                           for m, n in zip(d.media, d.names)],
                 "K": d.K, "poles": int(sum(m.K for m in d.media)), "edges": [int(np.count_nonzero(w)) for w in d.w],
                 "box_edges": [int(np.prod(w.shape)) for w in d.w]}
+
+    def conformal_tables(self):
+        """(comp, idx, coef) of fdtd_conformal_set (Engine.set_conformal): coef = iv0 * g_e, iv0 from the H metric tables alone."""
+        return _conformal.tables(self.conformal, metric_lists(self.grid, self.dt, pmc=self.pmc)[1], self.grid.shape)
+
+    def conformal_info(self) -> Optional[dict]:
+        """What RunStats.conformal reports: the listed faces per component, the cut edges, R, the factor on dt, the faces clamped."""
+        if self.conformal is None:
+            return None
+        c = self.conformal
+        return {"faces": c.faces(), "cut_edges": int(c.frac.idx.size), "ratio": c.ratio, "dt_factor": c.dt_factor, "clamped": c.clamped}
 
     def magnetic_info(self) -> Optional[dict]:
         """What RunStats.magnetic reports: the magnetic media, the (a, b) classes, the faces per component and their boxes."""
@@ -586,6 +615,7 @@ class Simulation:
         stats.lorentz = self.lorentz_info()
         stats.lumped = self.lumped_info()
         stats.magnetic = self.magnetic_info()
+        stats.conformal = self.conformal_info()
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
         return stats

@@ -752,6 +752,8 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
             out.stats["lumped"] = st.lumped
         if getattr(st, "magnetic", None) is not None:       # magnetic materials (AddMaterial(mue=, sigma=))
             out.stats["magnetic"] = st.magnetic
+        if getattr(st, "conformal", None) is not None:      # conformal PEC boundaries (openEMS(conformal=True))
+            out.stats["conformal"] = st.conformal
         if verbose:
             print(f"[fdtd-hip] done: {st.steps} steps, {st.mcells_per_s:.0f} MC/s, Dmax {10 * np.log10(Dmax):.2f} dBi", flush=True)
         return out
