@@ -47,6 +47,10 @@ TRAFFIC_SYMBOLS = ["fdtd_traffic_info"]
 VOXEL_SYMBOLS = ["fdtd_voxelize"]
 # include/fdtd_hip_conformal.h: conformal PEC boundaries and the cut edges' fractions on the device, likewise
 CONFORMAL_SYMBOLS = ["fdtd_conformal_set", "fdtd_conformal_get", "fdtd_voxel_fractions"]
+# include/fdtd_hip_sar.h: local and mass-averaged SAR on the device, likewise
+SAR_SYMBOLS = ["fdtd_sar_local", "fdtd_sar_average"]
+# FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
+MAX_BOXES = 64
 
 
 class FdtdDesc(C.Structure):
@@ -203,7 +207,22 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    sar_sig = {
+        "fdtd_sar_local": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p]),
+        "fdtd_sar_average": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, C.c_double, C.c_int, p, p, p, p]),
+    }
+    assert sorted(sar_sig) == sorted(SAR_SYMBOLS)
+    for name, (res, args) in sar_sig.items():        # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_sar(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the SAR entry points (include/fdtd_hip_sar.h)."""
+    return all(hasattr(lib, n) for n in SAR_SYMBOLS)
 
 
 def has_conformal(lib: C.CDLL) -> bool:
@@ -850,6 +869,55 @@ def voxelize_device(lib: C.CDLL, device: int = 0):
     def rasteriser(grid, table):
         return voxelize_raw(lib, grid, table, device)
     return rasteriser
+
+
+def sar_local_raw(lib: C.CDLL, dx, dy, dz, Vx, Vy, Vz, sigma, rho, device: int = 0):
+    """fdtd_sar_local: (p, sar_local) float64 [ncz][ncy][ncx] — sar.local_spec's result, bit for bit."""
+    if not has_sar(lib):
+        raise FdtdError("this library has no device SAR (fdtd_sar_local / fdtd_sar_average)")
+    dx, dy, dz = (_arr(a, np.float64).ravel() for a in (dx, dy, dz))
+    shape = (dz.size, dy.size, dx.size)
+    sigma, rho = _arr(sigma, np.float64), _arr(rho, np.float64)
+    V = [_arr(v, np.complex128) for v in (Vx, Vy, Vz)]
+    if sigma.shape != shape or rho.shape != shape or any(v.shape != tuple(n + 1 for n in shape) for v in V):
+        raise ValueError("SAR: per-cell arrays must be [ncz][ncy][ncx], edge voltages [ncz+1][ncy+1][ncx+1]")
+    p_out, sar_out = np.empty(shape, np.float64), np.empty(shape, np.float64)
+    rc = lib.fdtd_sar_local(int(device), dx.size, dy.size, dz.size, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(V[0]), _ptr(V[1]), _ptr(V[2]),
+                            _ptr(sigma), _ptr(rho), _ptr(p_out), _ptr(sar_out))
+    if rc != 0:
+        msg = lib.fdtd_last_error(None)
+        raise FdtdError(f"fdtd_sar_local failed ({rc}): {msg.decode() if msg else ''}")
+    return p_out, sar_out
+
+
+def sar_average_raw(lib: C.CDLL, dx, dy, dz, rho, p, mass, method="ieee", device: int = 0):
+    """fdtd_sar_average: (sar_avg, half_side float64 [ncz][ncy][ncx], status int8, counts int64 [4]) — sar.average_spec's result."""
+    from . import sar as _sar
+    if not has_sar(lib):
+        raise FdtdError("this library has no device SAR (fdtd_sar_local / fdtd_sar_average)")
+    if method not in _sar.METHODS:
+        raise ValueError(f"SAR: averaging method must be one of {sorted(_sar.METHODS)}, got {method!r}")
+    dx, dy, dz = (_arr(a, np.float64).ravel() for a in (dx, dy, dz))
+    shape = (dz.size, dy.size, dx.size)
+    rho, p = _arr(rho, np.float64), _arr(p, np.float64)
+    if rho.shape != shape or p.shape != shape:
+        raise ValueError("SAR: per-cell arrays must be [ncz][ncy][ncx]")
+    sar_avg, half = np.empty(shape, np.float64), np.empty(shape, np.float64)
+    status, counts = np.empty(shape, np.int8), np.zeros(4, np.int64)
+    rc = lib.fdtd_sar_average(int(device), dx.size, dy.size, dz.size, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(rho), _ptr(p), float(mass),
+                              int(_sar.METHODS[method]), _ptr(sar_avg), _ptr(half), _ptr(status), _ptr(counts))
+    if rc != 0:
+        msg = lib.fdtd_last_error(None)
+        raise FdtdError(f"fdtd_sar_average failed ({rc}): {msg.decode() if msg else ''}")
+    return sar_avg, half, status, counts
+
+
+def sar_device(lib: C.CDLL, device: int = 0):
+    """What Simulation.sar hands to sar.evaluate: the pair (local, average) of csrc/sar.hip when `lib` exports the SAR entry points
+    and FDTD_SAR is not "host", else None (the numpy specification, sar.local_spec / sar.average_spec)."""
+    if os.environ.get("FDTD_SAR", "").lower() == "host" or not has_sar(lib):
+        return None
+    return (lambda *a: sar_local_raw(lib, *a, device=device)), (lambda *a: sar_average_raw(lib, *a, device=device))
 
 
 def default_rasteriser(lib: C.CDLL, device: int = 0):

@@ -316,11 +316,13 @@ class ContinuousStructure:
         order = int(kw.pop("order", len(deps)))
         eps_inf = float(kw.pop("epsilon", kw.pop("eps_inf", 1.0)))
         kappa = float(kw.pop("kappa", 0.0))
+        density = kw.pop("density", None)
         if kw:
             raise TypeError(f"AddDebyeMaterial: unknown keyword(s) {sorted(kw)}")
         if not (1 <= order <= 8) or len(deps) != order or len(tau) != order:
             raise ValueError(f"AddDebyeMaterial: order {order} needs {order} permittivity steps and relaxation times (1..8 poles), got {len(deps)} and {len(tau)}")
-        p = CSProperty(self._log, "DebyeMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_delta=deps, eps_relax_time=tau)
+        p = CSProperty(self._log, "DebyeMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_delta=deps, eps_relax_time=tau,
+                       **({} if density is None else {"density": density}))
         self.properties.append(p)
         return p
 
@@ -342,6 +344,7 @@ class ContinuousStructure:
         order = int(kw.pop("order", len(fp)))
         eps_inf = float(kw.pop("epsilon", 1.0))
         kappa = float(kw.pop("kappa", 0.0))
+        density = kw.pop("density", None)
         if kw:
             raise TypeError(f"AddLorentzMaterial: unknown keyword(s) {sorted(kw)}")
         if not (1 <= order <= 4) or len(fp) != order or len(f0) not in (0, order) or len(relax) not in (0, order):
@@ -351,7 +354,28 @@ class ContinuousStructure:
         if any(t < 0 for t in relax):
             raise ValueError(f"AddLorentzMaterial '{name}': eps_relax must be >= 0 (0: a loss-free pole)")
         p = CSProperty(self._log, "LorentzMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_plasma=fp, eps_pole_freq=f0,
-                       eps_relax=relax)
+                       eps_relax=relax, **({} if density is None else {"density": density}))
+        self.properties.append(p)
+        return p
+
+    SAR_DUMP_MASS = {20: 0.0, 21: 1e-3, 22: 10e-3}      # dump_type -> averaging mass [kg] (20: local SAR)
+
+    def AddDump(self, name, dump_type=0, frequency=None, **kw):
+        """CSXCAD's dump box, for the SAR dump types only: ``dump_type`` 20 = local SAR, 21 = 1 g, 22 = 10 g averaged, at the
+        frequencies ``frequency`` [Hz]; ``AddBox`` on the returned property places it (one box), ``openEMS.GetSAR(name)`` returns the
+        result after ``Run`` (sar.SARResult; no HDF5 file is written).  ``sar_method``: "ieee" (default) or "simple".  Field dumps
+        (every other dump_type) are refused; other keywords (dump_mode, file_type ...) are logged and have no effect."""
+        if dump_type not in self.SAR_DUMP_MASS:
+            raise ValueError(f"AddDump '{name}': dump_type {dump_type!r} is not supported by the HIP backend: out of scope — field dumps are "
+                             f"not supported (the SAR dump types 20, 21 and 22 are)")
+        f = [] if frequency is None else [float(v) for v in np.atleast_1d(frequency)]
+        if not f or not all(np.isfinite(v) and v > 0 for v in f):
+            raise ValueError(f"AddDump '{name}': a SAR dump needs frequency=[...] with values > 0")
+        from .sar import METHODS
+        method = kw.pop("sar_method", "ieee")
+        if method not in METHODS:
+            raise ValueError(f"AddDump '{name}': sar_method must be one of {sorted(METHODS)}, got {method!r}")
+        p = CSProperty(self._log, "Dump", name, dump_type=int(dump_type), frequency=f, sar_method=method, **kw)
         self.properties.append(p)
         return p
 
@@ -498,6 +522,7 @@ class openEMS:
         self._nf2ff: Optional[nf2ff] = None
         self.sim: Optional[Simulation] = None
         self.stats = None
+        self._sar = {}                 # (dump name, frequency) -> sar.SARResult of the last Run
 
     @property
     def calls(self):
@@ -582,17 +607,22 @@ class openEMS:
             if p.kind == "LorentzMaterial":
                 q = p.params
                 m = sc.add_lorentz_material(p.name, q["epsilon"], q["kappa"], wp=[2 * np.pi * f for f in q["eps_plasma"]],
-                                            w0=[2 * np.pi * f for f in q["eps_pole_freq"]], gamma=[1.0 / t if t else 0.0 for t in q["eps_relax"]])
+                                            w0=[2 * np.pi * f for f in q["eps_pole_freq"]], gamma=[1.0 / t if t else 0.0 for t in q["eps_relax"]],
+                                            density=q.get("density", 0.0))
                 for b in p.boxes:
                     self._draw(m, b)
             elif p.kind in ("Material", "DebyeMaterial"):
                 m = (sc.add_material(p.name, p.params.get("epsilon", 1.0), p.params.get("kappa", 0.0),
-                                     mu_r=p.params.get("mue", 1.0), sigma_m=p.params.get("sigma", 0.0)) if p.kind == "Material" else
-                     sc.add_debye_material(p.name, p.params["epsilon"], p.params["kappa"], p.params["eps_delta"], p.params["eps_relax_time"]))
+                                     mu_r=p.params.get("mue", 1.0), sigma_m=p.params.get("sigma", 0.0),
+                                     density=p.params.get("density", 0.0)) if p.kind == "Material" else
+                     sc.add_debye_material(p.name, p.params["epsilon"], p.params["kappa"], p.params["eps_delta"], p.params["eps_relax_time"],
+                                           density=p.params.get("density", 0.0)))
                 if p.kind == "DebyeMaterial":
                     m.medium.fit_info = getattr(p, "fit_info", None)
                 for b in p.boxes:
                     self._draw(m, b)
+            elif p.kind == "Dump":
+                continue                       # no part of the scene: Run hands the SAR boxes to Simulation.add_sar_box
             elif p.kind == "LumpedElement":
                 m = sc.add_lumped_element(p.name, p.params["ny"], R=p.params["R"], C=p.params["C"], L=p.params["L"],
                                           kind=p.params["LEtype"], caps=p.params["caps"])
@@ -639,12 +669,25 @@ class openEMS:
         if self._nf2ff is not None:
             freqs = [self._f0] if self._nf2ff_freqs is None else list(self._nf2ff_freqs)
 
+        dumps = [p for p in self._csx.properties if p.kind == "Dump"]
+        dump_freqs = sorted({f for p in dumps for f in p.params["frequency"]})
+
         def make(fr):
-            return Simulation(grid, vox, f0=self._f0, fc=self._fc, boundary=bc, nr_ts=int(min(self.NrTS, 2**31 - 2)),
-                              end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode,
-                              conformal=self._conformal, conformal_ratio=self._conformal_ratio)
+            if fr is not None and dump_freqs:          # a running DFT accumulates the SAR frequencies too
+                fr = np.unique(np.concatenate([np.atleast_1d(np.asarray(fr, float)), dump_freqs]))
+            sim = Simulation(grid, vox, f0=self._f0, fc=self._fc, boundary=bc, nr_ts=int(min(self.NrTS, 2**31 - 2)),
+                             end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode,
+                             conformal=self._conformal, conformal_ratio=self._conformal_ratio)
+            for p in dumps:
+                if len(p.boxes) != 1 or not isinstance(p.boxes[0], CSPrimBox) or not np.allclose(p.boxes[0].matrix, np.eye(4)):
+                    raise ValueError(f"SAR dump '{p.name}': takes exactly one box, without a transform")
+                b = p.boxes[0]
+                sim.add_sar_box(p.name, b.start * grid_unit, b.stop * grid_unit, p.params["frequency"],
+                                ContinuousStructure.SAR_DUMP_MASS[p.params["dump_type"]], p.params["sar_method"])
+            return sim
+        grid_unit = self._csx.GetGrid().GetDeltaUnit()
         self.sim = make(freqs)
-        self._nf2ff_snap, self._box_cache = False, {}
+        self._nf2ff_snap, self._box_cache, self._sar = False, {}, {}
         if self._nf2ff is not None and self.sim.nf2ff_mode == "dft" and self._nf2ff_freqs is None:
             self.sim = make(nf2ff_comb(self._f0))     # no time-domain record: a comb, CalcNF2FF snaps to it
             self._nf2ff_snap = True
@@ -665,6 +708,8 @@ class openEMS:
             # ask for HERE, where every rank is, so that CalcNF2FF at those is local (rank 0 alone may post-process)
             f = np.asarray(freqs, float)
             self._box_cache = {tuple(float(x) for x in f): self.sim.nf2ff_boxes(allreduce, freqs=f)}
+        # the SAR dumps, as upstream writes them during the run: every dump at each of its frequencies (stats.sar: counts and time)
+        self._sar = {(p.name, f): self.sim.sar(p.name, f) for p in dumps for f in p.params["frequency"]}
         if sim_path and self._rank == 0:
             try:
                 os.makedirs(sim_path, exist_ok=True)
@@ -676,7 +721,8 @@ class openEMS:
                                "operator": self.sim.operator_form, "n_gpus": self._world,
                                "halo_transport": getattr(self._comm, "transport_used", None),
                                "halo_transports_failed": list(self.stats.transports_failed),
-                               "schedule_fallback": self.stats.schedule_fallback}, fh)
+                               "schedule_fallback": self.stats.schedule_fallback,
+                               **({"sar": self.stats.sar} if self.stats.sar else {})}, fh)
                 # the port series as upstream's probe files (text): only on request — formatting them takes 0.03 s of a
                 # 0.34 s call on the reference's default scene, and CalcPort reads the arrays, not the files
                 if int(verbose or 0) > 0 or os.environ.get("FDTD_WRITE_PORT_FILES"):
@@ -694,6 +740,19 @@ class openEMS:
             if port.number == number:
                 return u, i, self.sim.dt
         raise KeyError(number)
+
+    def GetSAR(self, name, freq=None, normalise_to=None):
+        """The result of the SAR dump `name` (AddDump, dump_type 20 / 21 / 22) at `freq` (default: its first frequency): a
+        sar.SARResult.  normalise_to=P divides the SAR values and P_abs by P (CalcPort's P_acc at that frequency: SAR per watt)."""
+        if self.sim is None or self.stats is None:
+            raise RuntimeError("Run() first")
+        dump = next((p for p in self._csx.properties if p.kind == "Dump" and p.name == name), None)
+        if dump is None:
+            raise KeyError(f"no SAR dump '{name}'")
+        f = float(dump.params["frequency"][0] if freq is None else freq)
+        if normalise_to is None and (name, f) in self._sar:
+            return self._sar[(name, f)]
+        return self.sim.sar(name, f, normalise_to=normalise_to)
 
     def _calc_nf2ff(self, freq, theta_deg, phi_deg, radius, center):
         if self.sim is None or self._nf2ff is None or self.sim.nf2ff_box is None:

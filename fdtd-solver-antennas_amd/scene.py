@@ -74,6 +74,7 @@ class Material(_Drawable):
     boxes: List[Box] = field(default_factory=list)
     mu_r: float = 1.0        # relative permeability (>= 1) and magnetic loss sigma* [ohm/m]: magnetic.py
     sigma_m: float = 0.0
+    density: float = 0.0     # [kg/m^3], 0: no tissue — what SAR divides by (sar.py)
 
     def add_box(self, start, stop, priority=0):
         self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
@@ -148,6 +149,12 @@ class LumpedElement:
         return self
 
 
+def _density(name, density) -> float:
+    if np.ndim(density) != 0 or not (np.isfinite(float(density)) and float(density) >= 0):
+        raise ValueError(f"material '{name}': density = {density!r} must be one finite value >= 0 [kg/m^3]")
+    return float(density)
+
+
 @dataclass
 class Scene:
     unit: float = 1e-3
@@ -156,28 +163,28 @@ class Scene:
     ports: List[LumpedPort] = field(default_factory=list)
     elements: List[LumpedElement] = field(default_factory=list)
 
-    def add_material(self, name, eps_r=1.0, kappa=0.0, mu_r=1.0, sigma_m=0.0) -> Material:
+    def add_material(self, name, eps_r=1.0, kappa=0.0, mu_r=1.0, sigma_m=0.0, density=0.0) -> Material:
         """mu_r >= 1 and sigma_m >= 0 (magnetic loss sigma* [ohm/m]) make the material magnetic (magnetic.py); anisotropic
-        (sequence), negative or non-finite values and mu_r < 1 are refused."""
+        (sequence), negative or non-finite values and mu_r < 1 are refused.  density [kg/m^3] > 0 makes it tissue for SAR (sar.py)."""
         _magnetic.check_material(name, mu_r, sigma_m)
-        m = Material(name, float(eps_r), float(kappa), mu_r=float(mu_r), sigma_m=float(sigma_m))
+        m = Material(name, float(eps_r), float(kappa), mu_r=float(mu_r), sigma_m=float(sigma_m), density=_density(name, density))
         self.materials.append(m)
         return m
 
-    def add_debye_material(self, name, eps_inf, kappa=0.0, delta_eps=(), tau=()) -> DebyeMaterial:
+    def add_debye_material(self, name, eps_inf, kappa=0.0, delta_eps=(), tau=(), density=0.0) -> DebyeMaterial:
         """A dispersive dielectric eps(w) = eps_inf + sum_k delta_eps[k] / (1 + j w tau[k]) - j kappa / (w eps0), 1..8 poles.
         Boxes, rotations and priorities work as for add_material; the highest priority owns a cell."""
         med = _disp.DebyeMedium(eps_inf, kappa, delta_eps, tau)
-        m = DebyeMaterial(name, med.eps_inf, med.kappa, medium=med)
+        m = DebyeMaterial(name, med.eps_inf, med.kappa, medium=med, density=_density(name, density))
         self.materials.append(m)
         return m
 
-    def add_lorentz_material(self, name, eps_inf, kappa=0.0, wp=(), w0=(), gamma=()) -> LorentzMaterial:
+    def add_lorentz_material(self, name, eps_inf, kappa=0.0, wp=(), w0=(), gamma=(), density=0.0) -> LorentzMaterial:
         """A resonant dielectric eps(w) = eps_inf (1 + sum_k wp[k]^2 / (w0[k]^2 - w^2 + j w gamma[k])) - j kappa / (w eps0), 1..4
         poles, all in rad/s; w0[k] = 0 (or w0 left out) is a Drude pole, gamma left out a loss-free one.  Boxes, rotations and
         priorities work as for add_material; the highest priority owns a cell."""
         med = _lorentz.LorentzMedium(eps_inf, kappa, wp, w0, gamma)
-        m = LorentzMaterial(name, med.eps_inf, med.kappa, medium=med)
+        m = LorentzMaterial(name, med.eps_inf, med.kappa, medium=med, density=_density(name, density))
         self.materials.append(m)
         return m
 
@@ -248,6 +255,8 @@ class VoxelScene:
     # conformal PEC boundaries (None: not asked for): the nodes inside the plain metals and the fractions of the cut edges
     # (conformal.Fractions); Simulation(conformal=True) turns them into the face list
     fractions: Optional["_conformal.Fractions"] = None
+    # mass density per cell [kg/m^3] of the material that owns it (None: no material of the scene has one): sar.py
+    density: Optional[np.ndarray] = None
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -315,6 +324,8 @@ def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = Fa
     also the fractions of the edges the plain metals cut (conformal.fractions; `device_fractions`: _capi.default_fractions' callable,
     None: numpy) — the staircase itself, every other field of the result, stays what it is."""
     vs = _voxelize(scene, grid, rasteriser)
+    if any(m.density > 0 for m in scene.materials):
+        vs.density = np.array([m.density for m in scene.materials] + [0.0])[vs.cell_material]
     if conformal:
         vs.fractions = _conformal.fractions(scene, grid, device_fractions)
     return vs

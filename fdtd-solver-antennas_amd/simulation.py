@@ -22,6 +22,7 @@ from . import dispersion as _disp
 from . import lorentz as _lorentz
 from . import magnetic as _magnetic
 from . import conformal as _conformal
+from . import sar as _sar
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox
@@ -151,6 +152,7 @@ class RunStats:
     lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
     magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
     conformal: Optional[dict] = None          # conformal PEC boundaries (conformal.py): faces per component, R, dt factor, faces clamped
+    sar: Optional[dict] = None                # SAR boxes (sar.py): per name the voxels, tissue voxels, mass, method and, once Simulation.sar has run, status counts and averaging time
 
 
 class Simulation:
@@ -208,6 +210,9 @@ class Simulation:
         self.nf2ff_warning: Optional[str] = None
         self.nf2ff_freqs = None
         self.nf2ff_mode, self.rec_bytes, self.nf2ff_fmax = "dft", 0, 0.0
+        # what add_sar_box needs to set the recorder / DFT up itself when there is no NF2FF box
+        self._mode_asked, self._dft_oversample, self._rec_budget = nf2ff_mode, float(dft_oversample), rec_budget_bytes
+        self.sar_boxes, self._sar_ids, self._sar_report = {}, {}, {}
         if nf2ff_freqs is not None:
             self.nf2ff_freqs = np.atleast_1d(np.asarray(nf2ff_freqs, float))
             n = grid.shape
@@ -356,6 +361,8 @@ class Simulation:
             raise _capi.FdtdError("magnetic materials need a single slab (world = 1): a decomposed run with magnetic media is not supported")
         if self.conformal is not None and world > 1:
             raise _capi.FdtdError("conformal boundaries need a single slab (world = 1): a decomposed run with cut faces is not supported")
+        if self.sar_boxes and world > 1:
+            raise _capi.FdtdError("SAR boxes need a single slab (world = 1): a decomposed run with SAR boxes is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
@@ -399,11 +406,11 @@ class Simulation:
             uid = e.add_probe(KIND_V, p.v_idx, p.v_comp, p.v_w)
             iid = e.add_probe(KIND_I, p.i_idx, p.i_comp, p.i_w)
             self._port_probe_ids.append((uid, iid))
-        if self.nf2ff_box is not None:
+        if self.nf2ff_box is not None or self.sar_boxes:
             if self.nf2ff_mode == "record":
                 try:
                     e.set_recorder(self.dft_every, self.dft_nsamples)
-                    self._nf_ids = self.nf2ff_box.register(e)
+                    self._register_boxes(e)
                 except _capi.FdtdError as err:
                     raise _capi.FdtdError(f"{err} — time-domain NF2FF recording needs {self.rec_bytes / 2**30:.1f} GiB; "
                                           "use nf2ff_mode='dft'") from err
@@ -411,11 +418,135 @@ class Simulation:
                 tw_v = dft_twiddles(self.nf2ff_freqs, self.dt, self.dft_every, self.dft_nsamples, 0.0)
                 tw_i = dft_twiddles(self.nf2ff_freqs, self.dt, self.dft_every, self.dft_nsamples, 0.5)
                 e.set_dft(self.dft_every, tw_v, tw_i)
-                self._nf_ids = self.nf2ff_box.register(e)
+                self._register_boxes(e)
         self.engine, self.lib = e, lib
         self.rank, self.world, self.device = rank, world, device
         self._build_flags = int(flags)
         return e
+
+    def _register_boxes(self, e: Engine):
+        """The NF2FF faces, then per SAR box its three voltage boxes (kind V, components 0..2) on the node box."""
+        if self.nf2ff_box is not None:
+            self._nf_ids = self.nf2ff_box.register(e)
+        self._sar_ids = {name: [e.add_dft_box(KIND_V, c, b["lo"], b["hi"]) for c in range(3)] for name, b in self.sar_boxes.items()}
+
+    # ---------------------------------------------------------------------------------------------
+    def add_sar_box(self, name, start, stop, freqs, mass, method: str = "ieee"):
+        """A SAR box (before build): start / stop in metres, snapped to whole cells; `freqs` the frequencies Simulation.sar may be
+        asked for; `mass` the averaging mass in kg (0: local SAR only); `method` "ieee" or "simple" (sar.py).  Its edge voltages are
+        recorded like the NF2FF faces, in the mode the run uses; without an NF2FF box the recorder / DFT is set up here, by the
+        same rules."""
+        if self.engine is not None:
+            raise ValueError(f"SAR box '{name}': add_sar_box comes before build")
+        if name in self.sar_boxes:
+            raise ValueError(f"SAR box '{name}' is defined twice")
+        if method not in _sar.METHODS:
+            raise ValueError(f"SAR box '{name}': averaging method must be one of {sorted(_sar.METHODS)}, got {method!r}")
+        mass = float(mass)
+        if not (np.isfinite(mass) and mass >= 0):
+            raise ValueError(f"SAR box '{name}': the averaging mass must be finite and >= 0 [kg]")
+        f = np.atleast_1d(np.asarray(freqs, float))
+        if f.size == 0 or not np.all(np.isfinite(f)) or np.any(f <= 0):
+            raise ValueError(f"SAR box '{name}': needs at least one frequency > 0")
+        g, n, cells = self.grid, self.grid.shape, self.bc.face_cells()
+        lo = [g.snap(a, min(start[a], stop[a])) for a in range(3)]
+        hi = [g.snap(a, max(start[a], stop[a])) for a in range(3)]
+        for a in range(3):
+            if hi[a] <= lo[a]:
+                raise ValueError(f"SAR box '{name}': holds no whole cell along {'xyz'[a]} on this mesh (nodes {lo[a]}..{hi[a]})")
+            for side, bad in ((0, lo[a] < cells[2 * a]), (1, hi[a] > n[a] - 1 - cells[2 * a + 1])):
+                if cells[2 * a + side] and bad:
+                    raise ValueError(f"SAR box '{name}' reaches into the CPML layer {'xyz'[a]}{'+' if side else '-'} ({cells[2 * a + side]} cells): "
+                                     f"SAR inside absorbing layers is not supported — end the box before the layer")
+        sl = tuple(slice(lo[a], hi[a]) for a in (2, 1, 0))
+        for kind, edges in (("Debye", self.debye), ("Lorentz", self.lorentz)):
+            if edges is not None and np.any(edges.cell_medium[sl] >= 0):
+                m = int(edges.cell_medium[sl][edges.cell_medium[sl] >= 0][0])
+                raise ValueError(f"SAR box '{name}' holds cells of the {kind} medium '{' / '.join(edges.names[m])}': the loss of a dispersive "
+                                 f"medium depends on frequency, its SAR is not supported — use a material with kappa")
+        rho = getattr(self.vox, "density", None)
+        if rho is None or not np.any(rho[sl] > 0):
+            raise ValueError(f"SAR box '{name}' holds no cell of a material with density > 0: there is no tissue to average over "
+                             f"(AddMaterial(..., density=) / Scene.add_material(..., density=))")
+        used = (0 if self.nf2ff_box is None else len(self.nf2ff_box.requests)) + 3 * len(self.sar_boxes)
+        if used + 3 > _capi.MAX_BOXES:
+            raise ValueError(f"SAR box '{name}': its three voltage boxes would make {used + 3} recording boxes, a context takes "
+                             f"{_capi.MAX_BOXES} (FDTD_MAX_BOXES)")
+        if self.nf2ff_freqs is None:          # no NF2FF box (and no SAR box yet): the rules of __init__'s NF2FF block
+            if self._mode_asked not in ("dft", "record", "auto"):
+                raise ValueError("nf2ff_mode must be 'dft', 'record' or 'auto'")
+            fmax = max(self.f0 + self.fc, float(np.max(f)))
+            self.dft_every = max(1, int(np.floor(1.0 / (2.0 * fmax * self._dft_oversample * self.dt))))
+            self.dft_nsamples = self.nr_ts // self.dft_every + 1
+            self.nf2ff_freqs, self.nf2ff_fmax = f.copy(), fmax
+            self.nf2ff_mode = self._mode_asked
+        nbytes = 4 * self.dft_nsamples * 3 * int(np.prod([hi[a] - lo[a] + 1 for a in range(3)]))
+        if self.nf2ff_mode == "auto":
+            budget = int(os.environ.get("FDTD_REC_BUDGET_BYTES", 32 << 30)) if self._rec_budget is None else int(self._rec_budget)
+            self.nf2ff_mode = "record" if nbytes <= budget else "dft"
+        if self.nf2ff_mode == "record":
+            if float(np.max(f)) > self.nf2ff_fmax * (1 + 1e-9):
+                raise ValueError(f"SAR box '{name}': frequency {float(np.max(f)):g} Hz is above the recorder's band ({self.nf2ff_fmax:g} Hz)")
+        else:
+            rec = np.asarray(self.nf2ff_freqs, float)
+            miss = [x for x in f if np.min(np.abs(rec - x)) > 1e-6 * max(x, 1.0)]
+            if miss:
+                raise ValueError(f"SAR box '{name}': frequency {miss[0]:g} Hz is not among nf2ff_freqs ({rec.tolist()}): the running DFT "
+                                 f"accumulates those only — add it to nf2ff_freqs or use nf2ff_mode='record'")
+        self.rec_bytes += nbytes
+        self.sar_boxes[name] = {"lo": tuple(lo), "hi": tuple(hi), "freqs": f, "mass": mass, "method": method}
+        self._sar_report[name] = {"voxels": int(np.prod([hi[a] - lo[a] for a in range(3)])), "tissue_voxels": int(np.count_nonzero(rho[sl] > 0)),
+                                  "mass_kg": mass, "method": method, "status_counts": None, "averaging_seconds": None, "device": None}
+
+    def sar(self, name, freq=None, normalise_to=None) -> "_sar.SARResult":
+        """Local and mass-averaged SAR of box `name` at `freq` (default: the box's first frequency), after the run: the spectra of
+        its three voltage boxes (single-sided, as nf2ff_boxes) -> csrc/sar.hip, or sar.py where the library has no SAR entry points
+        or FDTD_SAR=host.  normalise_to=P divides the SAR values and P_abs by P — with the accepted power of CalcPort at the same
+        frequency (the same single-sided pulse spectrum) that is SAR per watt."""
+        if name not in self.sar_boxes:
+            raise KeyError(f"no SAR box '{name}' (defined: {sorted(self.sar_boxes)})")
+        if self.engine is None or name not in self._sar_ids:
+            raise RuntimeError("SAR: build and run first")
+        b = self.sar_boxes[name]
+        f = float(b["freqs"][0] if freq is None else freq)
+        ids = self._sar_ids[name]
+        if self.nf2ff_mode == "record":
+            if f > self.nf2ff_fmax * (1 + 1e-9):
+                raise ValueError(f"SAR frequency {f:g} Hz is above the recorder's band ({self.nf2ff_fmax:g} Hz)")
+            tw = dft_twiddles(np.array([f]), self.dt, self.dft_every, self.dft_nsamples, 0.0)
+            V = [self.engine.rec_transform(q, tw)[0][0] for q in ids]
+        else:
+            rec = np.asarray(self.nf2ff_freqs, float)
+            row = int(np.argmin(np.abs(rec - f)))
+            if abs(rec[row] - f) > 1e-6 * max(f, 1.0):
+                raise ValueError(f"SAR frequency {f:g} Hz was not recorded (recorded: {rec.tolist()})")
+            V = [self.engine.get_dft_box(q)[0][row] for q in ids]
+        scale = 2.0 * self.dt * self.dft_every
+        V = [v * scale for v in V]
+        lo, hi = b["lo"], b["hi"]
+        g = self.grid
+        d = [g.d[a][lo[a]:hi[a]] for a in range(3)]
+        sl = tuple(slice(lo[a], hi[a]) for a in (2, 1, 0))
+        sigma, rho = np.ascontiguousarray(self.vox.kappa[sl]), np.ascontiguousarray(self.vox.density[sl])
+        calls = _capi.sar_device(self.lib, self.device)
+        p, s_loc, s_avg, half, status, counts, secs = _sar.evaluate(d[0], d[1], d[2], V[0], V[1], V[2], sigma, rho, b["mass"], b["method"], calls)
+        vol = d[2][:, None, None] * d[1][None, :, None] * d[0][None, None, :]
+        p_abs, box_mass = float(np.sum(p * vol)), float(np.sum(rho * vol))
+        if normalise_to is not None:
+            s_loc, s_avg, p_abs = s_loc / normalise_to, s_avg / normalise_to, p_abs / normalise_to
+        ctr = [g.centers(a)[lo[a]:hi[a]] for a in range(3)]
+        if np.all(np.isnan(s_avg)):
+            peak, cell = float("nan"), (-1, -1, -1)
+        else:
+            k, j, i = np.unravel_index(int(np.nanargmax(s_avg)), s_avg.shape)
+            peak, cell = float(s_avg[k, j, i]), (int(i), int(j), int(k))
+        pos = tuple(float(ctr[a][cell[a]]) for a in range(3)) if cell[0] >= 0 else (float("nan"),) * 3
+        cnt = {"valid": int(counts[0]), "used": int(counts[1]), "no_cube": int(counts[2]), "too_small": int(counts[3]),
+               "background": int(np.count_nonzero(status == _sar.STATUS_BACKGROUND))}
+        self._sar_report[name].update(status_counts=cnt, averaging_seconds=secs, device=calls is not None)
+        return _sar.SARResult(name=name, freq=f, averaging_mass=b["mass"], method=b["method"], sar_local=s_loc, sar_avg=s_avg, status=status,
+                              half_side=half, peak=peak, peak_cell=cell, peak_position=pos, P_abs=p_abs, mass=box_mass, counts=cnt,
+                              x=ctr[0], y=ctr[1], z=ctr[2], device=calls is not None, seconds=secs, normalised_to=normalise_to)
 
     def sheet_vi(self) -> np.ndarray:
         """float32 vi of the sheet edges, as the engine expands it: m (the edge's lumped-edge override, float32) times the separable
@@ -616,6 +747,7 @@ class Simulation:
         stats.lumped = self.lumped_info()
         stats.magnetic = self.magnetic_info()
         stats.conformal = self.conformal_info()
+        stats.sar = self._sar_report if self.sar_boxes else None      # Simulation.sar fills in the status counts and the averaging time
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
         return stats
