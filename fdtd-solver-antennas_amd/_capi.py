@@ -598,14 +598,44 @@ class Engine:
         buf = C.create_string_buffer(uid, 128)
         self._ck(self.lib.fdtd_comm_init(self._ctx, buf), "comm_init")
 
-    # -- conducting sheets (include/fdtd_hip_sheet.h) ------------------------------------------------
-    def _sheet_lib(self):
-        if not has_sheets(self.lib):
-            raise FdtdError(f"this library ({self.backend}) has no conducting sheets (fdtd_sheet_set / fdtd_sheet_get)")
+    # -- the corrections: what they share -----------------------------------------------------------
+    _CORRECTIONS = {   # what a library may lack: how to ask it, what to say
+        "sheet": (has_sheets, "conducting sheets (fdtd_sheet_set / fdtd_sheet_get)"),
+        "lumped": (has_lumped, "lumped elements (fdtd_lumped_set / fdtd_lumped_get)"),
+        "debye": (has_dispersion, "Debye media (fdtd_debye_set / fdtd_debye_get)"),
+        "lorentz": (has_lorentz, "Lorentz media (fdtd_lorentz_set / fdtd_lorentz_get)"),
+        "magnetic": (has_magnetic, "magnetic materials (fdtd_magnetic_set / fdtd_magnetic_get)"),
+        "conformal": (has_conformal, "conformal boundaries (fdtd_conformal_set / fdtd_conformal_get)"),
+    }
 
+    def _need(self, correction: str):
+        """Raise unless the loaded library exports the correction's entry points."""
+        has, what = self._CORRECTIONS[correction]
+        if not has(self.lib):
+            raise FdtdError(f"this library ({self.backend}) has no {what}")
+
+    @staticmethod
+    def _boxes(lo, hi, fields, who: str, what: str):
+        """The per-component boxes lo[c] <= (x, y, z) < hi[c] of a dense correction and its arrays over them, `fields` = (values per
+        component, dtype, whether None stands for zeros)...: (lo, hi as int32 [3][3]; shapes [z][y][x] per component; per field the pointer triple the C
+        side takes; the arrays behind the pointers, to be kept until the call has returned).  Empty boxes take empty arrays."""
+        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
+        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
+        shapes = [tuple(int(max(0, hi_a[c, a] - lo_a[c, a])) for a in (2, 1, 0)) for c in range(3)]
+        keep, ptrs = [], []
+        for vals, dtype, optional in fields:
+            arrs = [_arr(np.zeros(shapes[c], dtype) if (0 in shapes[c] or (optional and vals is None)) else vals[c], dtype) for c in range(3)]
+            for c in range(3):
+                if arrs[c].shape != shapes[c]:
+                    raise ValueError(f"{who} component {c}: {what} must be [z][y][x] over the box, {shapes[c]}")
+            keep.append(arrs)
+            ptrs.append(C.cast((C.c_void_p * 3)(*[x.ctypes.data for x in arrs]), C.c_void_p))
+        return lo_a, hi_a, shapes, ptrs, keep
+
+    # -- conducting sheets (include/fdtd_hip_sheet.h) ------------------------------------------------
     def set_sheets(self, idx, comp, vi, cls, alpha, b):
         """Sheet edges: global flat node index, component, full vi coefficient, class; alpha / b: [ncls][K] (b = scale * b_k)."""
-        self._sheet_lib()
+        self._need("sheet")
         idx, comp, vi, cls = _arr(idx, np.int64), _arr(comp, np.int8), _arr(vi, np.float32), _arr(cls, np.int32)
         alpha, b = _arr(alpha, np.float32), _arr(b, np.float32)
         if not (idx.size == comp.size == vi.size == cls.size) or alpha.ndim != 2 or alpha.shape != b.shape:
@@ -617,7 +647,7 @@ class Engine:
 
     def sheet_state(self):
         """(v_prev float32 [n], branch currents float32 [K][n]) of the sheet edges."""
-        self._sheet_lib()
+        self._need("sheet")
         n, K = getattr(self, "sheet_n", 0), getattr(self, "sheet_K", 0)
         v = np.zeros(n, np.float32)
         ib = np.zeros((K, n), np.float32)
@@ -625,13 +655,9 @@ class Engine:
         return v, ib
 
     # -- lumped R-L-C elements (include/fdtd_hip_lumped.h) -------------------------------------------
-    def _lumped_lib(self):
-        if not has_lumped(self.lib):
-            raise FdtdError(f"this library ({self.backend}) has no lumped elements (fdtd_lumped_set / fdtd_lumped_get)")
-
     def set_lumped(self, idx, comp, vi, cls, phi, gam, h):
         """Element edges: global flat node index, component, full vi coefficient, class; phi [ncls][2][2], gam / h [ncls][2]."""
-        self._lumped_lib()
+        self._need("lumped")
         idx, comp, vi, cls = _arr(idx, np.int64), _arr(comp, np.int8), _arr(vi, np.float32), _arr(cls, np.int32)
         phi, gam, h = _arr(phi, np.float32), _arr(gam, np.float32), _arr(h, np.float32)
         if idx.size == 0:
@@ -645,7 +671,7 @@ class Engine:
 
     def lumped_state(self):
         """(v_prev float32 [n], states float32 [2][n]) of the element edges."""
-        self._lumped_lib()
+        self._need("lumped")
         n = getattr(self, "lumped_n", 0)
         v = np.zeros(n, np.float32)
         x = np.zeros((2, n), np.float32)
@@ -653,35 +679,22 @@ class Engine:
         return v, x
 
     # -- Debye media (include/fdtd_hip_dispersion.h) -------------------------------------------------
-    def _debye_lib(self):
-        if not has_dispersion(self.lib):
-            raise FdtdError(f"this library ({self.backend}) has no Debye media (fdtd_debye_set / fdtd_debye_get)")
-
     def set_debye(self, alpha, oma, beta, lo, hi, w, med=None):
         """Media tables alpha, oma = 1 - alpha, beta: float32 [nmedia][K]; per component c the box lo[c] <= (x, y, z) < hi[c] of
         edges with the weights w[c] and medium ids med[c] over it, [z][y][x] (an empty box: the component has no dispersive edge)."""
-        self._debye_lib()
+        self._need("debye")
         alpha, oma, beta = _arr(alpha, np.float32), _arr(oma, np.float32), _arr(beta, np.float32)
         if alpha.ndim != 2 or alpha.shape != oma.shape or alpha.shape != beta.shape:
             raise ValueError("Debye tables must be [nmedia][K]")
         nmedia, K = alpha.shape
-        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
-        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
-        shapes = [tuple(int(max(0, hi_a[c, a] - lo_a[c, a])) for a in (2, 1, 0)) for c in range(3)]
-        ws = [_arr(np.zeros(shapes[c], np.float32) if 0 in shapes[c] else w[c], np.float32) for c in range(3)]
-        ms = [_arr(np.zeros(shapes[c], np.uint8) if (0 in shapes[c] or med is None) else med[c], np.uint8) for c in range(3)]
-        for c in range(3):
-            if ws[c].shape != shapes[c] or ms[c].shape != shapes[c]:
-                raise ValueError(f"Debye component {c}: weights / medium ids must be [z][y][x] over the box, {shapes[c]}")
-        wp = (C.c_void_p * 3)(*[x.ctypes.data for x in ws])
-        mp = (C.c_void_p * 3)(*[x.ctypes.data for x in ms])
-        self._ck(self.lib.fdtd_debye_set(self._ctx, int(nmedia), int(K), _ptr(alpha), _ptr(oma), _ptr(beta), _ptr(lo_a), _ptr(hi_a),
-                                         C.cast(wp, C.c_void_p), C.cast(mp, C.c_void_p)), "debye_set")
+        lo_a, hi_a, shapes, (wp, mp), _keep = self._boxes(lo, hi, [(w, np.float32, False), (med, np.uint8, True)], "Debye", "weights / medium ids")
+        self._ck(self.lib.fdtd_debye_set(self._ctx, int(nmedia), int(K), _ptr(alpha), _ptr(oma), _ptr(beta), _ptr(lo_a), _ptr(hi_a), wp, mp),
+                 "debye_set")
         self.debye_K, self.debye_shapes = int(K), shapes
 
     def debye_state(self, comp: int):
         """(v_prev [z][y][x], u [K][z][y][x], vi [z][y][x]) float32 over component comp's box."""
-        self._debye_lib()
+        self._need("debye")
         shp = getattr(self, "debye_shapes", [(0, 0, 0)] * 3)[comp]
         K = getattr(self, "debye_K", 0)
         v, u, vi = np.zeros(shp, np.float32), np.zeros((K,) + shp, np.float32), np.zeros(shp, np.float32)
@@ -689,36 +702,23 @@ class Engine:
         return v, u, vi
 
     # -- Lorentz / Drude media (include/fdtd_hip_lorentz.h) ------------------------------------------
-    def _lorentz_lib(self):
-        if not has_lorentz(self.lib):
-            raise FdtdError(f"this library ({self.backend}) has no Lorentz media (fdtd_lorentz_set / fdtd_lorentz_get)")
-
     def set_lorentz(self, phi, gam, h, lo, hi, w, med=None):
         """Media tables phi: float32 [nmedia][K][2][2], gam, h: [nmedia][K][2]; per component c the box lo[c] <= (x, y, z) < hi[c] of
         edges with the weights w[c] and medium ids med[c] over it, [z][y][x] (an empty box: the component has no dispersive edge).
         No media (phi of length 0) removes the set."""
-        self._lorentz_lib()
+        self._need("lorentz")
         phi, gam, h = _arr(phi, np.float32), _arr(gam, np.float32), _arr(h, np.float32)
         if phi.ndim != 4 or phi.shape[2:] != (2, 2) or gam.shape != phi.shape[:2] + (2,) or h.shape != gam.shape:
             raise ValueError("Lorentz tables must be phi [nmedia][K][2][2], gam and h [nmedia][K][2]")
         nmedia, K = phi.shape[:2]
-        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
-        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
-        shapes = [tuple(max(int(hi_a[c][a] - lo_a[c][a]), 0) for a in (2, 1, 0)) for c in range(3)]
-        ws = [_arr(np.zeros(shapes[c], np.float32) if 0 in shapes[c] else w[c], np.float32) for c in range(3)]
-        ms = [_arr(np.zeros(shapes[c], np.uint8) if (0 in shapes[c] or med is None) else med[c], np.uint8) for c in range(3)]
-        for c in range(3):
-            if ws[c].shape != shapes[c] or ms[c].shape != shapes[c]:
-                raise ValueError(f"Lorentz component {c}: weights / medium ids must be [z][y][x] over the box, {shapes[c]}")
-        wp = (C.c_void_p * 3)(*[x.ctypes.data for x in ws])
-        mp = (C.c_void_p * 3)(*[x.ctypes.data for x in ms])
-        self._ck(self.lib.fdtd_lorentz_set(self._ctx, int(nmedia), int(K), _ptr(phi), _ptr(gam), _ptr(h), _ptr(lo_a), _ptr(hi_a),
-                                           C.cast(wp, C.c_void_p), C.cast(mp, C.c_void_p)), "lorentz_set")
+        lo_a, hi_a, shapes, (wp, mp), _keep = self._boxes(lo, hi, [(w, np.float32, False), (med, np.uint8, True)], "Lorentz", "weights / medium ids")
+        self._ck(self.lib.fdtd_lorentz_set(self._ctx, int(nmedia), int(K), _ptr(phi), _ptr(gam), _ptr(h), _ptr(lo_a), _ptr(hi_a), wp, mp),
+                 "lorentz_set")
         self.lorentz_K, self.lorentz_shapes = (int(K), shapes) if nmedia else (0, [(0, 0, 0)] * 3)
 
     def lorentz_state(self, comp: int):
         """(v_prev [z][y][x], x [K][2][z][y][x] (j_k, u_k), vi [z][y][x]) float32 over component comp's box."""
-        self._lorentz_lib()
+        self._need("lorentz")
         shp = getattr(self, "lorentz_shapes", [(0, 0, 0)] * 3)[comp]
         K = getattr(self, "lorentz_K", 0)
         v, x, vi = np.zeros(shp, np.float32), np.zeros((K, 2) + shp, np.float32), np.zeros(shp, np.float32)
@@ -726,47 +726,31 @@ class Engine:
         return v, x, vi
 
     # -- magnetic materials (include/fdtd_hip_magnetic.h) --------------------------------------------
-    def _magnetic_lib(self):
-        if not has_magnetic(self.lib):
-            raise FdtdError(f"this library ({self.backend}) has no magnetic materials (fdtd_magnetic_set / fdtd_magnetic_get)")
-
     def set_magnetic(self, a, b, lo, hi, cls):
         """Class tables a, b: float32 [ncls] of the live classes 1..ncls; per component c the box lo[c] <= (x, y, z) < hi[c] of
         faces with the class bytes cls[c] over it, [z][y][x] (0: not magnetic; an empty box: the component has no magnetic face).
         An empty table removes the set."""
-        self._magnetic_lib()
+        self._need("magnetic")
         a, b = _arr(a, np.float32).ravel(), _arr(b, np.float32).ravel()
         if a.shape != b.shape:
             raise ValueError("magnetic tables must be a [ncls], b [ncls]")
-        lo_a = _arr(np.asarray(lo).reshape(3, 3), np.int32)
-        hi_a = _arr(np.asarray(hi).reshape(3, 3), np.int32)
-        shapes = [tuple(int(max(0, hi_a[c, q] - lo_a[c, q])) for q in (2, 1, 0)) for c in range(3)]
-        cs = [_arr(np.zeros(shapes[c], np.uint8) if 0 in shapes[c] else cls[c], np.uint8) for c in range(3)]
-        for c in range(3):
-            if cs[c].shape != shapes[c]:
-                raise ValueError(f"magnetic component {c}: class bytes must be [z][y][x] over the box, {shapes[c]}")
-        cp = (C.c_void_p * 3)(*[x.ctypes.data for x in cs])
-        self._ck(self.lib.fdtd_magnetic_set(self._ctx, int(a.size), _ptr(a), _ptr(b), _ptr(lo_a), _ptr(hi_a), C.cast(cp, C.c_void_p)),
-                 "magnetic_set")
+        lo_a, hi_a, shapes, (cp,), _keep = self._boxes(lo, hi, [(cls, np.uint8, False)], "magnetic", "class bytes")
+        self._ck(self.lib.fdtd_magnetic_set(self._ctx, int(a.size), _ptr(a), _ptr(b), _ptr(lo_a), _ptr(hi_a), cp), "magnetic_set")
         self.magnetic_shapes = shapes if a.size else [(0, 0, 0)] * 3
 
     def magnetic_state(self, comp: int):
         """(i_prev [z][y][x], iv0 [z][y][x]) float32 over component comp's box."""
-        self._magnetic_lib()
+        self._need("magnetic")
         shp = getattr(self, "magnetic_shapes", [(0, 0, 0)] * 3)[comp]
         ip, iv = np.zeros(shp, np.float32), np.zeros(shp, np.float32)
         self._ck(self.lib.fdtd_magnetic_get(self._ctx, int(comp), _ptr(ip), _ptr(iv)), "magnetic_get")
         return ip, iv
 
     # -- conformal PEC boundaries (include/fdtd_hip_conformal.h) ------------------------------------
-    def _conformal_lib(self):
-        if not has_conformal(self.lib):
-            raise FdtdError(f"this library ({self.backend}) has no conformal boundaries (fdtd_conformal_set / fdtd_conformal_get)")
-
     def set_conformal(self, comp, idx, coef):
         """The listed faces: comp int8 [n], idx int64 [n] (flat node index), coef float32 [n][4] = iv0 * g_e in the order of
         conformal.face_edges.  An empty list removes the set."""
-        self._conformal_lib()
+        self._need("conformal")
         comp, idx = _arr(comp, np.int8).ravel(), _arr(idx, np.int64).ravel()
         coef = _arr(coef, np.float32).reshape(-1, 4)
         if not (comp.size == idx.size == coef.shape[0]):
@@ -775,7 +759,7 @@ class Engine:
 
     def conformal_state(self) -> np.ndarray:
         """i_prev float32 [n] of the listed faces, in the order they were set."""
-        self._conformal_lib()
+        self._need("conformal")
         n = C.c_int(0)
         self._ck(self.lib.fdtd_conformal_get(self._ctx, None, C.byref(n)), "conformal_get")
         ip = np.zeros(n.value, np.float32)

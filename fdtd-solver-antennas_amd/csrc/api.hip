@@ -41,15 +41,6 @@ static hipError_t upload_rows(T* dst, int P, const T* src, int nx, size_t rows) 
   return hipMemcpy2D(dst, (size_t)P * sizeof(T), src, (size_t)nx * sizeof(T), (size_t)nx * sizeof(T), rows, hipMemcpyHostToDevice);
 }
 
-template <typename T>
-static hipError_t to_device(T** dst, const std::vector<T>& v) {
-  hipFree(*dst); *dst = nullptr;
-  hipError_t e = hipMalloc(dst, std::max<size_t>(v.size(), 1) * sizeof(T));
-  if (e != hipSuccess) return e;
-  if (v.empty()) return hipSuccess;
-  return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
 // Per strip-plane source lists (CSR) for a tiling of `tys` rows per strip: a source at (k, j) is listed in the
 // strip-plane that holds row j of plane k.
 static hipError_t build_source_lists(const fdtd_ctx* c, int tys, int nstrips, int2** d_rng, int** d_ids) {
@@ -278,8 +269,8 @@ void fdtd_destroy(fdtd_ctx* c) {
   hipFree(c->d_energy); hipFree(c->src_rng); hipFree(c->src_ids);
   sheet_free(c);
   lumped_free(c);
-  debye_free(c);
-  lorentz_free(c);
+  media_free(&c->debye);
+  media_free(&c->lorentz);
   magnetic_free(c);
   conformal_free(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
@@ -861,10 +852,40 @@ static bool mur_post_fusable(const fdtd_ctx* c, bool multi, bool fused) {
 // too (the header's order: Mur passes, then the correction).  k_debye needs no such rule: the operator holds vi = 0 on every edge of a
 // grid face, and fdtd_debye_set leaves those edges out (their V is never the correction's to change, their states never act).
 // k_lumped is a sparse correction as k_sheet is: the two questions the planner has are asked of "a sheet or lumped edge".
-static bool correction_on_face(const fdtd_ctx* c, int f) { return ((c->sheet_faces | c->lumped_faces) >> f) & 1u; }   // (0 without edges)
+static bool correction_on_face(const fdtd_ctx* c, int f) { return ((c->sheet.faces | c->lumped.faces) >> f) & 1u; }   // (0 without edges)
 static bool correction_at(const fdtd_ctx* c, int off) {   // an edge of a sparse correction on the node at local offset `off`
-  return std::binary_search(c->h_sheet_off.begin(), c->h_sheet_off.end(), off) || std::binary_search(c->h_lumped_off.begin(), c->h_lumped_off.end(), off);
+  for (const EdgeList* l : {&c->sheet, &c->lumped})
+    if (std::binary_search(l->h_off.begin(), l->h_off.end(), off)) return true;
+  return false;
 }
+
+// What the planner knows of the corrections (enum Correction: their launch order, and the order of the refusals): is one set, its name in
+// the messages, whether it runs behind the H update (else between the E phase and the H update: either way two launches per timestep, no
+// k_step, no k_resident), and whether linked contexts are refused besides decomposed grids and the p2p transport.
+struct CorrectionInfo { bool active; const char* name; bool after_H; bool no_links; };
+static CorrectionInfo correction(const fdtd_ctx* c, int which) {
+  switch (which) {
+    case CORR_SHEET:    return {c->sheet.n > 0, "conducting sheets", false, false};
+    case CORR_DEBYE:    return {c->debye.nmedia > 0, "Debye media", false, true};
+    case CORR_LORENTZ:  return {c->lorentz.nmedia > 0, "Lorentz media", false, true};
+    case CORR_LUMPED:   return {c->lumped.n > 0, "lumped elements", false, true};
+    case CORR_MAGNETIC: return {c->mag_ncls > 0, "magnetic materials", true, true};
+    default:            return {c->conf_n > 0, "conformal boundaries", true, true};
+  }
+}
+static bool any_correction(const fdtd_ctx* c) {
+  for (int q = 0; q < CORR_COUNT; ++q)
+    if (correction(c, q).active) return true;
+  return false;
+}
+}  // extern "C" (the *_set functions of the other files call this one)
+int correction_single_slab(fdtd_ctx* c, Correction which) {
+  const CorrectionInfo k = correction(c, which);
+  if (c->d.world > 1 || c->p.p2p || (k.no_links && (c->link_lo || c->link_hi)))
+    return fdtd_fail(c, FDTD_E_UNSUPPORTED, k.no_links ? "%s: single slab only (world = 1, no p2p transport, no linked contexts)" : "%s: single slab only (world = 1)", k.name);
+  return FDTD_OK;
+}
+extern "C" {
 static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
   if (!c->mur_no_apply || !mur_post_fusable(c, multi, fused)) return false;
   for (int f = 0; f < 6; ++f)
@@ -901,12 +922,7 @@ static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
 // Mur faces inside the one launch (k_step<..., MUR>): what the two-launch schedule without an apply pass needs (mur_direct_possible), a single slab
 // whose fields fit the Infinity Cache (all E blocks, then all H blocks), and strips of at most 28 blocks (wf_wait_mur polls 9 * nbs flags, one thread each).
 static bool wavefront_possible(const fdtd_ctx* c, bool fused) {
-  if (c->sheet_n > 0) return false;   // conducting sheets: their correction runs between the E phase and the H update (two launches)
-  if (c->debye_nmedia > 0) return false;   // Debye media: likewise
-  if (c->lorentz_nmedia > 0) return false; // Lorentz / Drude media: likewise
-  if (c->lumped_n > 0) return false;       // lumped elements: likewise
-  if (c->mag_ncls > 0) return false;       // magnetic faces: their correction runs between the H update and whatever reads I next
-  if (c->conf_n > 0) return false;         // conformal faces: likewise
+  if (any_correction(c)) return false;   // it runs between the E phase and the H update, or between the H update and whatever reads I next
   const bool mur_ok = !c->any_mur || (c->d.world == 1 && !c->p.p2p && mur_direct_possible(c, false, fused) && 9 * c->p.nbs <= FDTD_BLOCK &&
                                       wf_lag_for(c) >= c->d.nk);
   // (an H block polls at most 64 flags with one wave: 2 * (1 + P4 / 256) + 3 <= 64, i.e. rows of at most 30 720 cells)
@@ -944,7 +960,7 @@ static bool wavefront_active(const fdtd_ctx* c, bool fused) {
 // $FDTD_RESIDENT=0 never, AUTO as below.
 static bool resident_active(fdtd_ctx* c, bool fused) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
-  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || c->sheet_n > 0 || c->debye_nmedia > 0 || c->lorentz_nmedia > 0 || c->lumped_n > 0 || c->mag_ncls > 0 || c->conf_n > 0) return false;
+  if (sel == FDTD_FLAG_KERNEL_DIRECT || sel == FDTD_FLAG_KERNEL_WAVEFRONT || c->res_mode == 0 || any_correction(c)) return false;
   if (!fused || !res_possible(c, nullptr)) return false;
   if (sel == FDTD_FLAG_KERNEL_RESIDENT || c->res_mode == 1) return true;
   // Mur faces: whenever it is possible (the alternative is three latency-bound launches per timestep).  PEC / CPML: while the tiles are at most two per
@@ -1018,8 +1034,7 @@ struct StepPlan {
 // Lumped-element edges: as the sheets'.
 static bool probes_first(const fdtd_ctx* c) {
   if (c->nprobe == 0) return false;
-  if (c->debye_nmedia > 0 || c->lorentz_nmedia > 0) return true;   // (Lorentz / Drude media are volumes as well)
-  if (c->sheet_n <= 0 && c->lumped_n <= 0) return false;
+  if (correction(c, CORR_DEBYE).active || correction(c, CORR_LORENTZ).active) return true;   // (Lorentz / Drude media are volumes as well)
   for (int q = 0; q < c->nprobe; ++q) {
     if (c->probe[q].kind != FDTD_KIND_V) continue;
     for (int off : c->h_prb_off[q])
@@ -1038,35 +1053,13 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
   const bool multi = c->d.world > 1;
   const bool fused = sources_fusable(c);
-  if (c->sheet_n > 0) {
+  for (int q = 0; q < CORR_COUNT; ++q) {
+    const CorrectionInfo k = correction(c, q);
+    if (!k.active) continue;
     if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: the two-launch schedule only (their correction runs between the E phase and the H update)");
-    if (multi || c->p.p2p) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conducting sheets: single slab only (world = 1)");
-  }
-  if (c->debye_nmedia > 0) {
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: the two-launch schedule only (their correction runs between the E phase and the H update)");
-    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Debye media: single slab only (world = 1, no p2p transport, no linked contexts)");
-  }
-  if (c->lorentz_nmedia > 0) {
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Lorentz media: the two-launch schedule only (their correction runs between the E phase and the H update)");
-    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Lorentz media: single slab only (world = 1, no p2p transport, no linked contexts)");
-  }
-  if (c->lumped_n > 0) {
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: the two-launch schedule only (their correction runs between the E phase and the H update)");
-    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: single slab only (world = 1, no p2p transport, no linked contexts)");
-  }
-  if (c->mag_ncls > 0) {
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: the two-launch schedule only (their correction runs between the H update and the next E phase)");
-    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: single slab only (world = 1, no p2p transport, no linked contexts)");
-  }
-  if (c->conf_n > 0) {
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conformal boundaries: the two-launch schedule only (their correction runs between the H update and the next E phase)");
-    if (multi || c->p.p2p || c->link_lo || c->link_hi) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conformal boundaries: single slab only (world = 1, no p2p transport, no linked contexts)");
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "%s: the two-launch schedule only (their correction runs between the %s)", k.name,
+                       k.after_H ? "H update and the next E phase" : "E phase and the H update");
+    if (int r = correction_single_slab(c, (Correction)q)) return r;
   }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";

@@ -89,40 +89,37 @@ extern "C" {
 int fdtd_conformal_set(fdtd_ctx* c, int n, const int8_t* comp, const int64_t* idx, const float* coef) {
   if (!c) return FDTD_E_ARG;
   if (n < 0 || (n > 0 && (!comp || !idx || !coef))) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: bad argument");
-  if (n > 0 && (c->d.world > 1 || c->p.p2p || c->link_lo || c->link_hi))
-    return fdtd_fail(c, FDTD_E_UNSUPPORTED, "conformal boundaries: single slab only (world = 1, no p2p transport, no linked contexts)");
+  if (n > 0)
+    if (int r = correction_single_slab(c, CORR_CONFORMAL)) return r;
   if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_conformal_set: set the operator first");
   if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_conformal_set: before the first timestep");
-  const int64_t gplane = (int64_t)c->d.nx * c->d.ny;
   const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
   std::vector<int4> face((size_t)n);
   std::vector<float4> cf((size_t)n);
   std::vector<int64_t> keys((size_t)n);
   for (int f = 0; f < n; ++f) {
-    const int64_t g = idx[f];
     const int m = comp[f];
-    if (g < 0 || g >= gplane * c->d.nz || m < 0 || m > 2) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: face %d out of range", f);
-    const int64_t k = g / gplane, r = g - k * gplane, j = r / c->d.nx, i = r - j * c->d.nx;
-    const int64_t pos[3] = {i, j, k};
+    int64_t pos[3];
+    int off;
+    if (!sparse_decode(c, idx[f], m, pos, &off)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: face %d out of range", f);
     // the face spans one cell along both transverse axes: its four edges reach the nodes p + e_a1 and p + e_a2
     if (pos[(m + 1) % 3] >= nn[(m + 1) % 3] - 1 || pos[(m + 2) % 3] >= nn[(m + 2) % 3] - 1)
       return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: face %d does not exist", f);
-    keys[f] = g * 3 + m;
-    face[f] = make_int4((int)((k - c->d.k0) * c->plane + j * c->P + i), m, 0, 0);
+    keys[f] = idx[f] * 3 + m;
+    face[f] = make_int4(off, m, 0, 0);
     cf[f] = make_float4(coef[4 * (size_t)f], coef[4 * (size_t)f + 1], coef[4 * (size_t)f + 2], coef[4 * (size_t)f + 3]);
   }
-  std::sort(keys.begin(), keys.end());
-  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: a face given twice");
+  if (sparse_doubles(keys)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: a face given twice");
   HIPCK(c, hipSetDevice(c->d.device));
   HIPCK(c, hipStreamSynchronize(c->stream));
   conformal_free(c);
   if (n == 0) return FDTD_OK;
-  hipError_t e = sparse_upload(&c->conf_face, face);
-  if (e == hipSuccess) e = sparse_upload(&c->conf_coef, cf);
+  hipError_t e = to_device(&c->conf_face, face);
+  if (e == hipSuccess) e = to_device(&c->conf_coef, cf);
   if (e == hipSuccess) e = hipMalloc((void**)&c->conf_iprev, (size_t)n * sizeof(float));
   if (e != hipSuccess) {
     conformal_free(c);
-    return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "fdtd_conformal_set: %s", hipGetErrorString(e));
+    return fdtd_fail_hip(c, "fdtd_conformal_set", e);
   }
   c->conf_n = n;
   const int r = conformal_prime(c, -1);

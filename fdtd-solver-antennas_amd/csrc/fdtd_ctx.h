@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <map>
 #include <string>
 #include <utility>
@@ -162,6 +163,30 @@ struct ResHost {
   int capacity = -1, capacity_variant = -1;   // workgroups of k_resident the chip holds at once (occupancy query), for which kernel variant
 };
 
+// The edge list of a sparse correction (conducting sheets, lumped elements): per edge its local offset, component, full vi, class and
+// v_prev on the device; for the planner (api.hip correction_on_face, correction_at) the grid faces whose node plane holds an edge
+// (bit f: x-, x+, y-, y+, z-, z+) and the offsets once more, sorted, on the host (does a V-probe cell sit on an edge's node?)
+struct EdgeList {
+  int n = 0;
+  int* off = nullptr; int8_t* comp = nullptr; float* vi = nullptr; int* cls = nullptr; float* vprev = nullptr;
+  unsigned faces = 0;
+  std::vector<int> h_off;
+};
+// The box of a dense correction (Debye and Lorentz media: edges; magnetic materials: faces), per field component: laid out like the
+// field arrays, its x range widened to multiples of 4 so that a thread's four elements are one 16-byte vector (dense_box.hpp)
+struct DenseBox {
+  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the caller's box
+  int x0w = 0, nxw = 0;                       // widened x range: first node, length (a multiple of 4)
+  size_t n = 0;                               // elements of the widened box (0: the component has none)
+};
+// Debye or Lorentz media: w, vi, v_prev [n] and the state planes u over each widened box, medium ids when there are several media
+struct MediaBoxes {
+  int nmedia = 0, K = 0;
+  struct Box { DenseBox g; float* w = nullptr; float* vi = nullptr; float* vprev = nullptr; float* u = nullptr; uint8_t* med = nullptr; };
+  Box box[3];
+  float* tab = nullptr;
+};
+
 struct fdtd_ctx {
   fdtd_desc d{};
   DevParams p{};
@@ -265,45 +290,22 @@ struct fdtd_ctx {
   bool tables_dirty = true;
   int launch_failed = 0;         // a main-kernel launch the runtime refused (launch_main): the step loop returns this code, message in err
   hipEvent_t kev0 = nullptr, kev1 = nullptr;   // profiled run: start / stop events the next main launch carries
-  // conducting sheets (sheet.hip, include/fdtd_hip_sheet.h): per edge offset, component, vi, class, v_prev and K branch currents
-  // [K][n]; per class alpha and scale * b [ncls][K]
-  int sheet_n = 0, sheet_K = 0, sheet_ncls = 0;
-  int* sheet_off = nullptr; int8_t* sheet_comp = nullptr; float* sheet_vi = nullptr; int* sheet_cls = nullptr;
-  float* sheet_vprev = nullptr; float* sheet_ib = nullptr; float* sheet_alpha = nullptr; float* sheet_b = nullptr;
-  std::vector<int> h_sheet_off;   // the sheet edges' local offsets, sorted (host copy): does a V-probe cell sit on a sheet edge's node?
-  unsigned sheet_faces = 0;       // bit f: a sheet edge lies on the node plane of grid face f (x-, x+, y-, y+, z-, z+)
-  // lumped R-L-C elements (lumped.hip, include/fdtd_hip_lumped.h): per edge offset, component, vi, class, v_prev and the two states
-  // [2][n]; per class phi [ncls][2][2], gam and h [ncls][2]
-  int lumped_n = 0;
-  int* lumped_off = nullptr; int8_t* lumped_comp = nullptr; float* lumped_vi = nullptr; int* lumped_cls = nullptr;
-  float* lumped_vprev = nullptr; float* lumped_x = nullptr; float* lumped_phi = nullptr; float* lumped_gam = nullptr; float* lumped_h = nullptr;
-  std::vector<int> h_lumped_off;  // as h_sheet_off
-  unsigned lumped_faces = 0;      // as sheet_faces
-  // Debye media (dispersion.hip, include/fdtd_hip_dispersion.h): per component one dense box of edges, x range widened to
-  // multiples of 4; w, vi, v_prev [n] and u [K][n] over the widened box, medium ids when there are several media; the per-medium
-  // tables alpha, 1 - alpha, beta as [3][MAX_MEDIA * MAX_K] floats on the device
-  struct DebyeBox {
-    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the caller's box
-    int x0w = 0, nxw = 0;                       // widened x range: first node, length (a multiple of 4)
-    size_t n = 0;                               // edges of the widened box (0: the component has none)
-    float* w = nullptr; float* vi = nullptr; float* vprev = nullptr; float* u = nullptr; uint8_t* med = nullptr;
-  };
-  int debye_nmedia = 0, debye_K = 0;
-  DebyeBox debye_box[3];
-  float* debye_tab = nullptr;
-  // Lorentz / Drude media (lorentz.hip, include/fdtd_hip_lorentz.h): boxes as the Debye media's, u holding the state planes
-  // [2 K][n] (j_k, u_k per pole); the per-(medium, pole) rows phi, gam, h as [MAX_MEDIA][MAX_K][8] floats on the device
-  int lorentz_nmedia = 0, lorentz_K = 0;
-  DebyeBox lorentz_box[3];
-  float* lorentz_tab = nullptr;
-  // magnetic materials (magnetic.hip, include/fdtd_hip_magnetic.h): per component one dense box of faces, x range widened to
-  // multiples of 4; i_prev and one class byte per face over the widened box; the (a, b) pairs of the classes as 256 float2 on the device
-  struct MagBox {
-    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the caller's box
-    int x0w = 0, nxw = 0;                       // widened x range: first node, length (a multiple of 4)
-    size_t n = 0;                               // faces of the widened box (0: the component has none)
-    float* iprev = nullptr; uint8_t* cls = nullptr;
-  };
+  // conducting sheets (sheet.hip, include/fdtd_hip_sheet.h): the edge list (EdgeList above), K branch currents [K][n] per edge; per class
+  // alpha and scale * b [ncls][K]
+  EdgeList sheet;
+  int sheet_K = 0, sheet_ncls = 0;
+  float* sheet_ib = nullptr; float* sheet_alpha = nullptr; float* sheet_b = nullptr;
+  // lumped R-L-C elements (lumped.hip, include/fdtd_hip_lumped.h): the edge list, the two states [2][n] per edge; per class
+  // phi [ncls][2][2], gam and h [ncls][2]
+  EdgeList lumped;
+  float* lumped_x = nullptr; float* lumped_phi = nullptr; float* lumped_gam = nullptr; float* lumped_h = nullptr;
+  // Debye media (dispersion.hip, include/fdtd_hip_dispersion.h): u holds [K][n]; the per-medium tables alpha, 1 - alpha, beta as
+  // [3][MAX_MEDIA * MAX_K] floats on the device.  Lorentz / Drude media (lorentz.hip, include/fdtd_hip_lorentz.h): u holds the state
+  // planes [2 K][n] (j_k, u_k per pole); the per-(medium, pole) rows phi, gam, h as [MAX_MEDIA][MAX_K][8] floats on the device
+  MediaBoxes debye, lorentz;
+  // magnetic materials (magnetic.hip, include/fdtd_hip_magnetic.h): per component one dense box of faces with i_prev and one class
+  // byte per face over the widened box; the (a, b) pairs of the classes as 256 float2 on the device
+  struct MagBox { DenseBox g; float* iprev = nullptr; uint8_t* cls = nullptr; };
   int mag_ncls = 0;                             // live classes (0: no magnetic faces)
   MagBox mag_box[3];
   float2* mag_tab = nullptr;
@@ -358,26 +360,51 @@ bool res_possible(fdtd_ctx* c, const char** why);
 int res_prepare(fdtd_ctx* c, int max_chunk);
 int launch_resident(fdtd_ctx* c, long long step, int nsteps, hipStream_t s);
 void res_free(fdtd_ctx* c);
+// The corrections between the E and H phases and behind the H update, in launch order.  api.hip lists what the planner knows of each.
+enum Correction { CORR_SHEET, CORR_DEBYE, CORR_LORENTZ, CORR_LUMPED, CORR_MAGNETIC, CORR_CONFORMAL, CORR_COUNT };
+int correction_single_slab(fdtd_ctx* c, Correction which);   // api.hip: FDTD_OK, or the refusal of a decomposed / p2p / linked context
+inline int fdtd_fail_hip(fdtd_ctx* c, const char* who, hipError_t e) {   // a set function's allocation or copy failed
+  return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
+}
+// allocate and fill a device array (an earlier allocation is released)
+template <typename T>
+inline hipError_t to_device(T** dst, const std::vector<T>& v) {
+  hipFree(*dst); *dst = nullptr;
+  hipError_t e = hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(T));
+  if (e != hipSuccess) return e;
+  if (v.empty()) return hipSuccess;
+  return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
 // sheet.hip: conducting sheets — the sparse correction after the E phase (no-op without sheets)
 void launch_sheet(fdtd_ctx* c, hipStream_t s);
 void sheet_free(fdtd_ctx* c);
-int sparse_edges_check(fdtd_ctx* c, const char* who, int n, const int64_t* idx, const int8_t* comp, const int32_t* cls, int ncls,
-                       std::vector<int>* off, std::vector<int8_t>* comp_out, std::vector<int>* cls_out, unsigned* faces);
-template <class T>
-inline hipError_t sparse_upload(T** dst, const std::vector<T>& v) {   // the arrays of a sparse correction: allocate and fill
-  hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T));
-  if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  return e;
+// ... and what it shares with lumped.hip: the list's prologue (state checks, every edge inside the grid and existing, classes in range, no
+// edge twice; then the stream synchronised, `release` called, the list's arrays uploaded, the planner's facts kept) and its release
+int edge_list_set(fdtd_ctx* c, EdgeList* l, void (*release)(fdtd_ctx*), const char* who, int n, const int64_t* idx, const int8_t* comp,
+                  const float* vi, const int32_t* cls, int ncls);
+void edge_list_free(EdgeList* l);
+// ... and with conformal.hip: a listed flat node index -> (i, j, k) and the local offset (false: outside the grid, or no component), and
+// whether a key (3 * index + component) is listed twice
+inline bool sparse_decode(const fdtd_ctx* c, int64_t g, int comp, int64_t pos[3], int* off) {
+  const int64_t gplane = (int64_t)c->d.nx * c->d.ny;
+  if (g < 0 || g >= gplane * c->d.nz || comp < 0 || comp > 2) return false;
+  const int64_t k = g / gplane, r = g - k * gplane, j = r / c->d.nx, i = r - j * c->d.nx;
+  pos[0] = i; pos[1] = j; pos[2] = k;
+  *off = (int)((k - c->d.k0) * c->plane + j * c->P + i);
+  return true;
+}
+inline bool sparse_doubles(std::vector<int64_t>& keys) {
+  std::sort(keys.begin(), keys.end());
+  return std::adjacent_find(keys.begin(), keys.end()) != keys.end();
 }
 // lumped.hip: lumped R-L-C elements — the sparse correction after the E phase, behind launch_sheet (no-op without elements)
 void launch_lumped(fdtd_ctx* c, hipStream_t s);
 void lumped_free(fdtd_ctx* c);
 // dispersion.hip: Debye media — the dense correction after the E phase, in front of launch_sheet (no-op without media)
 void launch_debye(fdtd_ctx* c, hipStream_t s);
-void debye_free(fdtd_ctx* c);
+void media_free(MediaBoxes* m);   // (Debye and Lorentz media alike)
 // lorentz.hip: Lorentz / Drude media — the dense correction behind launch_debye, in front of launch_sheet (no-op without media)
 void launch_lorentz(fdtd_ctx* c, hipStream_t s);
-void lorentz_free(fdtd_ctx* c);
 // magnetic.hip: magnetic materials — the dense correction after the H update, in front of everything that samples I (no-op without faces)
 void launch_magnetic(fdtd_ctx* c, hipStream_t s);
 int magnetic_prime(fdtd_ctx* c, int comp);   // i_prev <- the component's I array (fdtd_magnetic_set, fdtd_set_field)

@@ -8,8 +8,7 @@
 // 16-byte vectors, consecutive lanes on consecutive memory, no index array.  Per edge the kernel moves 8 (V) + 4 (vi) + 4 (w) +
 // 8 (v_prev) + 16 K (j_k, u_k) bytes and does 17 K + 5 flops: it is a streaming kernel.  Every statement is one fp32 operation in the
 // order the header spells (-ffp-contract=off), so a host restatement on top of the oracle's half-steps reproduces it bit for bit.
-#include "fdtd_ctx.h"
-#include "kernel_common.hpp"
+#include "dense_box.hpp"
 #include "../../include/fdtd_hip_lorentz.h"
 
 #include <vector>
@@ -25,11 +24,7 @@ struct LorentzComp {
   float* V;                // the component's voltage array (local plane 0)
   const float* w; const float* vi; const uint8_t* med;
   float* vprev; float* x;
-  unsigned blk0;           // first block of this component in the launch
-  unsigned nq;             // threads = groups of four x-edges: nz_b * ny_b * qx
-  unsigned n;              // edges of the widened box = 4 * nq (stride of the state planes)
-  int off0;                // field offset of the box's first edge: z0 * plane + y0 * P + x0w
-  FastDiv fd_qx, fd_ny;    // groups per row, rows per plane
+  BoxLaunch l;
 };
 struct LorentzArgs { LorentzComp c[3]; int K, P, plane; const float* tab; };
 
@@ -84,17 +79,11 @@ __global__ __launch_bounds__(256) void k_lorentz(const LorentzArgs a) {
     tab[threadIdx.x] = a.tab[threadIdx.x];
     __syncthreads();
   }
-  const unsigned b = blockIdx.x;
-  const int ci = b >= a.c[2].blk0 ? 2 : b >= a.c[1].blk0 ? 1 : 0;
-  const LorentzComp& d = a.c[ci];
-  const unsigned q = (b - d.blk0) * 256u + threadIdx.x;
-  if (q >= d.nq) return;
-  const unsigned row = fd_div(q, d.fd_qx);
-  const unsigned ix = q - row * d.fd_qx.d;
-  const unsigned kz = fd_div(row, d.fd_ny);
-  const unsigned jy = row - kz * d.fd_ny.d;
-  const size_t o = (size_t)q * 4u;                                                     // in the box arrays
-  const long of = (long)d.off0 + (long)kz * a.plane + (long)jy * a.P + (long)ix * 4;   // in the field array
+  unsigned q;
+  const LorentzComp& d = box_group(a.c, q);
+  if (q >= d.l.nq) return;
+  const long of = box_field_offset(d.l, q, a.P, a.plane);         // in the field array
+  const size_t o = (size_t)q * 4u;                                // in the box arrays
   const float4 w4 = *reinterpret_cast<const float4*>(d.w + o);
   if (w4.x == 0.0f && w4.y == 0.0f && w4.z == 0.0f && w4.w == 0.0f) return;   // (padding, or cells of another material inside the box)
   const float4 vi4 = *reinterpret_cast<const float4*>(d.vi + o);
@@ -105,8 +94,8 @@ __global__ __launch_bounds__(256) void k_lorentz(const LorentzArgs a) {
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
     if (k < K) {
-      const float4 tj = *reinterpret_cast<const float4*>(d.x + (size_t)(2 * k) * d.n + o);
-      const float4 tu = *reinterpret_cast<const float4*>(d.x + (size_t)(2 * k + 1) * d.n + o);
+      const float4 tj = *reinterpret_cast<const float4*>(d.x + (size_t)(2 * k) * d.l.n + o);
+      const float4 tu = *reinterpret_cast<const float4*>(d.x + (size_t)(2 * k + 1) * d.l.n + o);
       jx[k] = tj.x; jy_[k] = tj.y; jz[k] = tj.z; jw[k] = tj.w;
       ux[k] = tu.x; uy[k] = tu.y; uz[k] = tu.z; uw[k] = tu.w;
     } else {
@@ -131,55 +120,28 @@ __global__ __launch_bounds__(256) void k_lorentz(const LorentzArgs a) {
 #pragma unroll
   for (int k = 0; k < KMAX; ++k)
     if (k < K) {
-      *reinterpret_cast<float4*>(d.x + (size_t)(2 * k) * d.n + o) = make_float4(jx[k], jy_[k], jz[k], jw[k]);
-      *reinterpret_cast<float4*>(d.x + (size_t)(2 * k + 1) * d.n + o) = make_float4(ux[k], uy[k], uz[k], uw[k]);
+      *reinterpret_cast<float4*>(d.x + (size_t)(2 * k) * d.l.n + o) = make_float4(jx[k], jy_[k], jz[k], jw[k]);
+      *reinterpret_cast<float4*>(d.x + (size_t)(2 * k + 1) * d.l.n + o) = make_float4(ux[k], uy[k], uz[k], uw[k]);
     }
 }
 
-template <class T>
-hipError_t upload(T** dst, const std::vector<T>& v) {
-  hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T));
-  if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  return e;
-}
-
-inline int floor4(int v) { return v & ~3; }
-inline int ceil4(int v) { return (v + 3) & ~3; }
-
 }  // namespace
 
-void lorentz_free(fdtd_ctx* c) {
-  for (auto& b : c->lorentz_box) {
-    hipFree(b.w); hipFree(b.vi); hipFree(b.vprev); hipFree(b.u); hipFree(b.med);
-    b = fdtd_ctx::DebyeBox{};
-  }
-  hipFree(c->lorentz_tab);
-  c->lorentz_tab = nullptr;
-  c->lorentz_nmedia = c->lorentz_K = 0;
-}
-
 void launch_lorentz(fdtd_ctx* c, hipStream_t s) {
-  if (c->lorentz_nmedia <= 0) return;
+  const MediaBoxes& m = c->lorentz;
+  if (m.nmedia <= 0) return;
   LorentzArgs a{};
-  unsigned blocks = 0;
-  for (int ci = 0; ci < 3; ++ci) {
-    const fdtd_ctx::DebyeBox& b = c->lorentz_box[ci];
-    LorentzComp& d = a.c[ci];
-    d.blk0 = blocks;
-    d.nq = (unsigned)(b.n / 4);
-    d.n = (unsigned)b.n;
-    d.fd_qx = make_fastdiv(1); d.fd_ny = make_fastdiv(1);
-    if (b.n == 0) continue;
-    d.V = c->p.V[ci]; d.w = b.w; d.vi = b.vi; d.med = b.med; d.vprev = b.vprev; d.x = b.u;
-    d.off0 = b.lo[2] * c->plane + b.lo[1] * c->P + b.x0w;
-    d.fd_qx = make_fastdiv((unsigned)(b.nxw / 4));
-    d.fd_ny = make_fastdiv((unsigned)(b.hi[1] - b.lo[1]));
-    blocks += (d.nq + 255u) / 256u;
-  }
+  const unsigned blocks = box_layout(c, m.box, a.c);
   if (blocks == 0) return;
-  a.K = c->lorentz_K; a.P = c->P; a.plane = c->plane; a.tab = c->lorentz_tab;
-  const bool multi = c->lorentz_nmedia > 1;
-  const int kb = c->lorentz_K <= 1 ? 1 : c->lorentz_K <= 2 ? 2 : 4;
+  for (int ci = 0; ci < 3; ++ci) {
+    const MediaBoxes::Box& b = m.box[ci];
+    if (b.g.n == 0) continue;
+    LorentzComp& d = a.c[ci];
+    d.V = c->p.V[ci]; d.w = b.w; d.vi = b.vi; d.med = b.med; d.vprev = b.vprev; d.x = b.u;
+  }
+  a.K = m.K; a.P = c->P; a.plane = c->plane; a.tab = m.tab;
+  const bool multi = m.nmedia > 1;
+  const int kb = m.K <= 1 ? 1 : m.K <= 2 ? 2 : 4;
   auto kern = multi ? (kb == 1 ? k_lorentz<true, 1> : kb == 2 ? k_lorentz<true, 2> : k_lorentz<true, 4>)
                     : (kb == 1 ? k_lorentz<false, 1> : kb == 2 ? k_lorentz<false, 2> : k_lorentz<false, 4>);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, a);
@@ -194,105 +156,19 @@ int fdtd_lorentz_set(fdtd_ctx* c, int nmedia, int K, const float* phi, const flo
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: at most %d media", FDTD_LORENTZ_MAX_MEDIA);
   if (nmedia > 0 && (K < 1 || K > FDTD_LORENTZ_MAX_K)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: K must be 1..%d", FDTD_LORENTZ_MAX_K);
   if (nmedia > 0 && (!phi || !gam || !h || !lo || !hi || !w)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: bad argument");
-  if (nmedia > 0 && (c->d.world > 1 || c->p.p2p || c->link_lo || c->link_hi))
-    return fdtd_fail(c, FDTD_E_UNSUPPORTED, "Lorentz media: single slab only (world = 1, no p2p transport, no linked contexts)");
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_lorentz_set: set the operator first");
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_lorentz_set: before the first timestep");
-  const int nn[3] = {c->d.nx, c->d.ny, c->d.nz};
-  size_t nbox[3] = {0, 0, 0};
-  for (int ci = 0; ci < 3 && nmedia > 0; ++ci) {
-    bool empty = false;
-    for (int a = 0; a < 3; ++a) empty = empty || hi[ci][a] <= lo[ci][a];
-    if (empty) continue;
-    for (int a = 0; a < 3; ++a)
-      if (lo[ci][a] < 0 || hi[ci][a] > (a == ci ? nn[a] - 1 : nn[a]))
-        return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: component %d: box [%d, %d) along axis %d leaves the grid's edges", ci, lo[ci][a], hi[ci][a], a);
-    if (!w[ci] || (nmedia > 1 && (!med || !med[ci]))) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: component %d: weights / medium ids missing", ci);
-    nbox[ci] = (size_t)(hi[ci][0] - lo[ci][0]) * (hi[ci][1] - lo[ci][1]) * (hi[ci][2] - lo[ci][2]);
-    if (nbox[ci] * 4 > 0x7fffffffu) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: component %d: box too large", ci);
-    if (nmedia > 1)
-      for (size_t e = 0; e < nbox[ci]; ++e)
-        if (med[ci][e] >= nmedia) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_set: component %d: medium id %d out of range", ci, (int)med[ci][e]);
-  }
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  lorentz_free(c);
-  if (nmedia == 0 || nbox[0] + nbox[1] + nbox[2] == 0) return FDTD_OK;
-  // the edges' vi, as the update kernels expand it (raw or class form): the whole operator once, cropped to the boxes
-  const size_t ncell = (size_t)c->d.nk * c->d.ny * c->d.nx;
-  std::vector<float> op[4];
-  for (auto& v : op) v.resize(3 * ncell);
-  int r = fdtd_get_operator(c, op[0].data(), op[1].data(), op[2].data(), op[3].data());
-  if (r) return r;
-  hipError_t e = hipSuccess;
-  for (int ci = 0; ci < 3 && e == hipSuccess; ++ci) {
-    if (nbox[ci] == 0) continue;
-    fdtd_ctx::DebyeBox& b = c->lorentz_box[ci];
-    for (int a = 0; a < 3; ++a) { b.lo[a] = lo[ci][a]; b.hi[a] = hi[ci][a]; }
-    b.x0w = floor4(b.lo[0]);
-    b.nxw = ceil4(b.hi[0]) - b.x0w;           // ceil4(hi) <= ceil4(nx) = P: the widened rows stay inside the field rows
-    const int nyb = b.hi[1] - b.lo[1], nzb = b.hi[2] - b.lo[2], nxb = b.hi[0] - b.lo[0];
-    b.n = (size_t)b.nxw * nyb * nzb;
-    std::vector<float> ww(b.n, 0.f), vv(b.n, 0.f);
-    std::vector<uint8_t> mm(b.n, 0);
-    for (int z = 0; z < nzb; ++z)
-      for (int y = 0; y < nyb; ++y) {
-        const size_t src = ((size_t)z * nyb + y) * nxb, dst = ((size_t)z * nyb + y) * b.nxw + (b.lo[0] - b.x0w);
-        const size_t g = (size_t)ci * ncell + ((size_t)(b.lo[2] + z) * c->d.ny + (b.lo[1] + y)) * c->d.nx + b.lo[0];
-        for (int x = 0; x < nxb; ++x) {
-          // an edge the operator holds at zero (vi == 0: a grid face, metal) is no dispersive edge (the header; fdtd_debye_set's rule)
-          vv[dst + x] = op[1][g + x];
-          ww[dst + x] = vv[dst + x] == 0.0f ? 0.0f : w[ci][src + x];
-          if (nmedia > 1) mm[dst + x] = med[ci][src + x];
-        }
-      }
-    e = upload(&b.w, ww);
-    if (e == hipSuccess) e = upload(&b.vi, vv);
-    if (e == hipSuccess && nmedia > 1) e = upload(&b.med, mm);
-    if (e == hipSuccess) e = upload(&b.vprev, std::vector<float>(b.n, 0.f));
-    if (e == hipSuccess) e = upload(&b.u, std::vector<float>((size_t)2 * K * b.n, 0.f));
-  }
-  if (e == hipSuccess) {
-    std::vector<float> tab(TAB, 0.f);
-    for (int m = 0; m < nmedia; ++m)
-      for (int k = 0; k < K; ++k) {
-        float* row = &tab[(size_t)m * MROW + k * ROW];
-        for (int q = 0; q < 4; ++q) row[q] = phi[((size_t)m * K + k) * 4 + q];
-        for (int q = 0; q < 2; ++q) { row[4 + q] = gam[((size_t)m * K + k) * 2 + q]; row[6 + q] = h[((size_t)m * K + k) * 2 + q]; }
-      }
-    e = upload(&c->lorentz_tab, tab);
-  }
-  if (e != hipSuccess) {
-    lorentz_free(c);
-    return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "fdtd_lorentz_set: %s", hipGetErrorString(e));
-  }
-  c->lorentz_nmedia = nmedia; c->lorentz_K = K;
-  return FDTD_OK;
+  std::vector<float> tab(TAB, 0.f);
+  for (int m = 0; m < nmedia; ++m)
+    for (int k = 0; k < K; ++k) {
+      float* row = &tab[(size_t)m * MROW + k * ROW];
+      for (int q = 0; q < 4; ++q) row[q] = phi[((size_t)m * K + k) * 4 + q];
+      for (int q = 0; q < 2; ++q) { row[4 + q] = gam[((size_t)m * K + k) * 2 + q]; row[6 + q] = h[((size_t)m * K + k) * 2 + q]; }
+    }
+  return media_set(c, &c->lorentz, "fdtd_lorentz_set", CORR_LORENTZ, 2, nmedia, K, tab, lo, hi, w, med);
 }
 
 int fdtd_lorentz_get(fdtd_ctx* c, int comp, float* v_prev, float* x, float* vi) {
   if (!c) return FDTD_E_ARG;
-  if (comp < 0 || comp > 2) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lorentz_get: component %d", comp);
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  const fdtd_ctx::DebyeBox& b = c->lorentz_box[comp];
-  if (c->lorentz_nmedia == 0 || b.n == 0) return FDTD_OK;
-  const int nyb = b.hi[1] - b.lo[1], nzb = b.hi[2] - b.lo[2], nxb = b.hi[0] - b.lo[0];
-  const size_t rows = (size_t)nyb * nzb;
-  const size_t x0 = (size_t)(b.lo[0] - b.x0w);
-  std::vector<float> tmp(b.n);
-  auto crop = [&](const float* dev, float* out) -> hipError_t {
-    hipError_t e = hipMemcpy(tmp.data(), dev, b.n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
-    for (size_t r = 0; r < rows; ++r)
-      for (int xx = 0; xx < nxb; ++xx) out[r * nxb + xx] = tmp[r * b.nxw + x0 + xx];
-    return hipSuccess;
-  };
-  if (v_prev) HIPCK(c, crop(b.vprev, v_prev));
-  if (vi) HIPCK(c, crop(b.vi, vi));
-  if (x)
-    for (int p = 0; p < 2 * c->lorentz_K; ++p) HIPCK(c, crop(b.u + (size_t)p * b.n, x + (size_t)p * rows * nxb));
-  return FDTD_OK;
+  return media_get(c, &c->lorentz, "fdtd_lorentz_get", 2, comp, v_prev, x, vi);
 }
 
 }  // extern "C"

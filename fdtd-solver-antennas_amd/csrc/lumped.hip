@@ -43,20 +43,16 @@ __global__ __launch_bounds__(256) void k_lumped(LumpedArgs a) {
 }  // namespace
 
 void lumped_free(fdtd_ctx* c) {
-  hipFree(c->lumped_off); hipFree(c->lumped_comp); hipFree(c->lumped_vi); hipFree(c->lumped_cls);
-  hipFree(c->lumped_vprev); hipFree(c->lumped_x); hipFree(c->lumped_phi); hipFree(c->lumped_gam); hipFree(c->lumped_h);
-  c->lumped_off = nullptr; c->lumped_comp = nullptr; c->lumped_vi = nullptr; c->lumped_cls = nullptr;
-  c->lumped_vprev = nullptr; c->lumped_x = nullptr; c->lumped_phi = nullptr; c->lumped_gam = nullptr; c->lumped_h = nullptr;
-  c->lumped_n = 0;
-  c->h_lumped_off.clear();
-  c->lumped_faces = 0;
+  edge_list_free(&c->lumped);
+  hipFree(c->lumped_x); hipFree(c->lumped_phi); hipFree(c->lumped_gam); hipFree(c->lumped_h);
+  c->lumped_x = nullptr; c->lumped_phi = nullptr; c->lumped_gam = nullptr; c->lumped_h = nullptr;
 }
 
 void launch_lumped(fdtd_ctx* c, hipStream_t s) {
-  if (c->lumped_n <= 0) return;
-  LumpedArgs a{c->p.V[0], c->p.V[1], c->p.V[2], c->lumped_off, c->lumped_comp, c->lumped_vi, c->lumped_cls,
-               c->lumped_vprev, c->lumped_x, c->lumped_phi, c->lumped_gam, c->lumped_h, c->lumped_n};
-  hipLaunchKernelGGL(k_lumped, dim3((unsigned)((c->lumped_n + 255) / 256)), dim3(256), 0, s, a);
+  const EdgeList& l = c->lumped;
+  if (l.n <= 0) return;
+  LumpedArgs a{c->p.V[0], c->p.V[1], c->p.V[2], l.off, l.comp, l.vi, l.cls, l.vprev, c->lumped_x, c->lumped_phi, c->lumped_gam, c->lumped_h, l.n};
+  hipLaunchKernelGGL(k_lumped, dim3((unsigned)((l.n + 255) / 256)), dim3(256), 0, s, a);
 }
 
 extern "C" {
@@ -67,38 +63,18 @@ int fdtd_lumped_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, 
   if (n < 0 || (n > 0 && (!idx || !comp || !vi || !cls || !phi || !gam || !h)))
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_lumped_set: bad argument");
   if (n > 0 && ncls < 1) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lumped_set: ncls must be >= 1");
+  // (this call's own wording; the planner refuses p2p and linked contexts when they step: api.hip corrections)
   if (c->d.world > 1) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: single slab only (world = 1)");
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_lumped_set: set the operator first");
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_lumped_set: before the first timestep");
-  std::vector<int> off, cl;
-  std::vector<int8_t> cp;
-  unsigned faces = 0;
-  if (int r = sparse_edges_check(c, "fdtd_lumped_set", n, idx, comp, cls, ncls, &off, &cp, &cl, &faces)) return r;
-  std::vector<float> v(vi, vi + n);
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  lumped_free(c);
-  if (n == 0) return FDTD_OK;
-  std::vector<float> ph(phi, phi + (size_t)ncls * 4), gm(gam, gam + (size_t)ncls * 2), hh(h, h + (size_t)ncls * 2);
-  std::vector<float> zero((size_t)2 * n, 0.f);
-  hipError_t e = sparse_upload(&c->lumped_off, off);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_comp, cp);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_vi, v);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_cls, cl);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_vprev, std::vector<float>(zero.begin(), zero.begin() + n));
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_x, zero);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_phi, ph);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_gam, gm);
-  if (e == hipSuccess) e = sparse_upload(&c->lumped_h, hh);
+  const int r = edge_list_set(c, &c->lumped, lumped_free, "fdtd_lumped_set", n, idx, comp, vi, cls, ncls);
+  if (r || n == 0) return r;
+  hipError_t e = to_device(&c->lumped_x, std::vector<float>((size_t)2 * n, 0.f));
+  if (e == hipSuccess) e = to_device(&c->lumped_phi, std::vector<float>(phi, phi + (size_t)ncls * 4));
+  if (e == hipSuccess) e = to_device(&c->lumped_gam, std::vector<float>(gam, gam + (size_t)ncls * 2));
+  if (e == hipSuccess) e = to_device(&c->lumped_h, std::vector<float>(h, h + (size_t)ncls * 2));
   if (e != hipSuccess) {
     lumped_free(c);
-    return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "fdtd_lumped_set: %s", hipGetErrorString(e));
+    return fdtd_fail_hip(c, "fdtd_lumped_set", e);
   }
-  c->lumped_n = n;
-  // what the planner asks (api.hip: correction_on_face, correction_at): the faces the edges touch, their offsets for the V-probes
-  c->lumped_faces = faces;
-  c->h_lumped_off = off;
-  std::sort(c->h_lumped_off.begin(), c->h_lumped_off.end());
   return FDTD_OK;
 }
 
@@ -106,9 +82,10 @@ int fdtd_lumped_get(fdtd_ctx* c, float* v_prev, float* x) {
   if (!c) return FDTD_E_ARG;
   HIPCK(c, hipSetDevice(c->d.device));
   HIPCK(c, hipStreamSynchronize(c->stream));
-  if (c->lumped_n == 0) return FDTD_OK;
-  if (v_prev) HIPCK(c, hipMemcpy(v_prev, c->lumped_vprev, (size_t)c->lumped_n * sizeof(float), hipMemcpyDeviceToHost));
-  if (x) HIPCK(c, hipMemcpy(x, c->lumped_x, (size_t)2 * c->lumped_n * sizeof(float), hipMemcpyDeviceToHost));
+  const int n = c->lumped.n;
+  if (n == 0) return FDTD_OK;
+  if (v_prev) HIPCK(c, hipMemcpy(v_prev, c->lumped.vprev, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  if (x) HIPCK(c, hipMemcpy(x, c->lumped_x, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost));
   return FDTD_OK;
 }
 

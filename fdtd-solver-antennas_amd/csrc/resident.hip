@@ -497,14 +497,6 @@ __global__ __launch_bounds__(FDTD_BLOCK) void k_res_probes(const DevParams p, co
   if (threadIdx.x == 0) pr.series[step] = red[0];
 }
 
-template <typename T>
-hipError_t res_upload(T** dst, const std::vector<T>& v) {
-  hipFree(*dst); *dst = nullptr;
-  hipError_t e = hipMalloc(dst, std::max<size_t>(v.size(), 1) * sizeof(T));
-  if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  return e;
-}
-
 template <int COEF, bool MUR, bool PML>
 const void* res_kernel() { return reinterpret_cast<const void*>(&k_resident<COEF, MUR, PML>); }
 template <int COEF>
@@ -595,8 +587,8 @@ int res_prepare(fdtd_ctx* c, int max_chunk) {
   std::vector<int> kt, jt;
   if (!res_tiling(c, kt, jt)) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: rows of more than 1024 cells");
   h.nzt = (int)kt.size() - 1; h.nstrips = (int)jt.size() - 1; h.nblocks = h.nzt * h.nstrips;
-  HIPCK(c, res_upload(&h.d_kt, kt));
-  HIPCK(c, res_upload(&h.d_jt, jt));
+  HIPCK(c, to_device(&h.d_kt, kt));
+  HIPCK(c, to_device(&h.d_jt, jt));
   auto tile_of = [&](int off, int& thread, int& elem) {
     const int k = off / c->plane, r2 = off - k * c->plane, j = r2 / c->P, i = r2 - j * c->P;
     const int zt = (int)(std::upper_bound(kt.begin(), kt.end(), k) - kt.begin()) - 1;
@@ -616,8 +608,8 @@ int res_prepare(fdtd_ctx* c, int max_chunk) {
       if ((int)lists[q].size() > RES_MAX_SRC) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "resident schedule: more than %d source edges in one tile", RES_MAX_SRC);
       rng[q].x = (int)ids.size(); ids.insert(ids.end(), lists[q].begin(), lists[q].end()); rng[q].y = (int)ids.size();
     }
-    HIPCK(c, res_upload(&h.d_src_rng, rng));
-    HIPCK(c, res_upload(&h.d_src_ids, ids));
+    HIPCK(c, to_device(&h.d_src_rng, rng));
+    HIPCK(c, to_device(&h.d_src_ids, ids));
   }
   // probe cells per tile; stage slots in (probe, cell) order
   {
@@ -643,9 +635,9 @@ int res_prepare(fdtd_ctx* c, int max_chunk) {
       std::stable_sort(lists[q].begin(), lists[q].end(), [](const int4& a, const int4& b2) { return a.w < b2.w; });   // V-probe cells (kind 0) first
       rng[q].x = (int)cells.size(); cells.insert(cells.end(), lists[q].begin(), lists[q].end()); rng[q].y = (int)cells.size();
     }
-    HIPCK(c, res_upload(&h.d_prb_rng, rng));
-    HIPCK(c, res_upload(&h.d_prb_cells, cells));
-    HIPCK(c, res_upload(&h.d_slot0, slot0));
+    HIPCK(c, to_device(&h.d_prb_rng, rng));
+    HIPCK(c, to_device(&h.d_prb_cells, cells));
+    HIPCK(c, to_device(&h.d_slot0, slot0));
     hipFree(h.stage); h.stage = nullptr;
     HIPCK(c, hipMalloc(&h.stage, (size_t)max_chunk * h.nslots * sizeof(float)));
     HIPCK(c, hipMemset(h.stage, 0, (size_t)max_chunk * h.nslots * sizeof(float)));
