@@ -49,6 +49,8 @@ VOXEL_SYMBOLS = ["fdtd_voxelize"]
 CONFORMAL_SYMBOLS = ["fdtd_conformal_set", "fdtd_conformal_get", "fdtd_voxel_fractions"]
 # include/fdtd_hip_sar.h: local and mass-averaged SAR on the device, likewise
 SAR_SYMBOLS = ["fdtd_sar_local", "fdtd_sar_average"]
+# include/fdtd_hip_planewave.h: plane-wave excitation on a total-field / scattered-field box, likewise
+PLANEWAVE_SYMBOLS = ["fdtd_planewave_set"]
 # FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
 MAX_BOXES = 64
 
@@ -207,6 +209,13 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    planewave_sig = {"fdtd_planewave_set": (C.c_int, [p, C.c_int, p, p, p, p, p, C.c_int, p, p, p, p, p, p, C.c_int])}
+    assert sorted(planewave_sig) == sorted(PLANEWAVE_SYMBOLS)
+    for name, (res, args) in planewave_sig.items():  # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     sar_sig = {
         "fdtd_sar_local": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p]),
         "fdtd_sar_average": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, C.c_double, C.c_int, p, p, p, p]),
@@ -223,6 +232,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
 def has_sar(lib: C.CDLL) -> bool:
     """Whether `lib` exports the SAR entry points (include/fdtd_hip_sar.h)."""
     return all(hasattr(lib, n) for n in SAR_SYMBOLS)
+
+
+def has_planewave(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the plane-wave entry point (include/fdtd_hip_planewave.h)."""
+    return all(hasattr(lib, n) for n in PLANEWAVE_SYMBOLS)
 
 
 def has_conformal(lib: C.CDLL) -> bool:
@@ -606,6 +620,7 @@ class Engine:
         "lorentz": (has_lorentz, "Lorentz media (fdtd_lorentz_set / fdtd_lorentz_get)"),
         "magnetic": (has_magnetic, "magnetic materials (fdtd_magnetic_set / fdtd_magnetic_get)"),
         "conformal": (has_conformal, "conformal boundaries (fdtd_conformal_set / fdtd_conformal_get)"),
+        "planewave": (has_planewave, "plane-wave excitation (fdtd_planewave_set)"),
     }
 
     def _need(self, correction: str):
@@ -767,6 +782,24 @@ class Engine:
         return ip
 
     # -- fields -------------------------------------------------------------------------------
+    # -- plane-wave excitation (include/fdtd_hip_planewave.h) ----------------------------------------
+    def set_planewave(self, idxE, compE, coefE, m0E, wE, idxH, compH, coefH, m0H, wH, sig2):
+        """The edge list and the face list of planewave.tables (per list idx int64 [n], comp int8 [n], coef float32 [n][2], m0 int32
+        [n][2], w float32 [n][2]) and the pulse at half-step resolution.  Two empty lists remove the set."""
+        self._need("planewave")
+        lists = []
+        for idx, comp, coef, m0, w in ((idxE, compE, coefE, m0E, wE), (idxH, compH, coefH, m0H, wH)):
+            idx, comp = _arr(idx, np.int64).ravel(), _arr(comp, np.int8).ravel()
+            coef, m0, w = _arr(coef, np.float32).reshape(-1, 2), _arr(m0, np.int32).reshape(-1, 2), _arr(w, np.float32).reshape(-1, 2)
+            if not (idx.size == comp.size == coef.shape[0] == m0.shape[0] == w.shape[0]):
+                raise ValueError("plane-wave lists must be idx [n], comp [n], coef [n][2], m0 [n][2], w [n][2]")
+            lists.append((idx, comp, coef, m0, w))
+        sig2 = _arr(np.zeros(0) if sig2 is None else sig2, np.float32).ravel()
+        args = []
+        for l in lists:
+            args += [int(l[0].size)] + [_ptr(a) if a.size else None for a in l]
+        self._ck(self.lib.fdtd_planewave_set(self._ctx, *args, _ptr(sig2) if sig2.size else None, int(sig2.size)), "planewave_set")
+
     def get_field(self, kind: int, comp: int) -> np.ndarray:
         out = np.empty(self.local_shape, np.float32)
         self._ck(self.lib.fdtd_get_field(self._ctx, int(kind), int(comp), _ptr(out)), "get_field")

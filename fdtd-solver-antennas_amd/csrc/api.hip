@@ -269,6 +269,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   hipFree(c->d_energy); hipFree(c->src_rng); hipFree(c->src_ids);
   sheet_free(c);
   lumped_free(c);
+  planewave_free(c);
   media_free(&c->debye);
   media_free(&c->lorentz);
   magnetic_free(c);
@@ -870,7 +871,8 @@ static CorrectionInfo correction(const fdtd_ctx* c, int which) {
     case CORR_LORENTZ:  return {c->lorentz.nmedia > 0, "Lorentz media", false, true};
     case CORR_LUMPED:   return {c->lumped.n > 0, "lumped elements", false, true};
     case CORR_MAGNETIC: return {c->mag_ncls > 0, "magnetic materials", true, true};
-    default:            return {c->conf_n > 0, "conformal boundaries", true, true};
+    case CORR_CONFORMAL: return {c->conf_n > 0, "conformal boundaries", true, true};
+    default:            return {c->pw[0].n > 0 || c->pw[1].n > 0, "plane-wave excitation", true, true};   // (its edge list runs behind the E phase as well)
   }
 }
 static bool any_correction(const fdtd_ctx* c) {
@@ -1188,6 +1190,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   }
   launch_magnetic(c, s);   // magnetic faces: after the whole H update, before anything samples I (no-op without faces)
   launch_conformal(c, s);  // conformal faces: likewise
+  launch_planewave(c, FDTD_KIND_I, step, s);   // plane wave: the faces just outside the box, last of the H side (no-op without one)
   if (!pl.fused) launch_post(c, FDTD_KIND_I, step, false, s);
   launch_dft(c, FDTD_KIND_I, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_H, s));
@@ -1348,6 +1351,7 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     launch_lorentz(c, c->stream); // Lorentz / Drude media: behind the Debye media's correction (no-op without media)
     launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
     launch_lumped(c, c->stream);  // lumped elements: behind the sheets' correction, before the H update (no-op without elements)
+    launch_planewave(c, FDTD_KIND_V, c->step, c->stream);   // plane wave: the box surface's edges, last of the E side (no-op without one)
     if (multi && (r = exchange(c, FDTD_HALO_E_DOWN, pl.rccl_inline))) return r;
     if ((r = phase_H(c, pl, pe, n))) return r;
     if (multi && (r = exchange(c, FDTD_HALO_H_UP, pl.rccl_inline))) return r;
@@ -1471,10 +1475,12 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_lorentz(c, s);
     launch_sheet(c, s);
     launch_lumped(c, s);
+    launch_planewave(c, FDTD_KIND_V, c->step, s);
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);
     launch_magnetic(c, s);
     launch_conformal(c, s);
+    launch_planewave(c, FDTD_KIND_I, c->step, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);
     launch_dft(c, FDTD_KIND_I, c->step, s);
     c->step++;

@@ -315,6 +315,11 @@ struct fdtd_ctx {
   int4* conf_face = nullptr;
   float4* conf_coef = nullptr;
   float* conf_iprev = nullptr;
+  // plane-wave excitation (planewave.hip, include/fdtd_hip_planewave.h): the edge list [0] and the face list [1] — per entry its node
+  // offset and component and two terms (coefficient, whole half-steps of delay, fraction) — and the pulse at half-step resolution
+  struct PlaneWaveList { int n = 0; int* off = nullptr; int8_t* comp = nullptr; float2* coef = nullptr; int2* m0 = nullptr; float2* w = nullptr; };
+  PlaneWaveList pw[2];
+  float* pw_sig2 = nullptr; int pw_nsig2 = 0;
   std::string err;
 };
 
@@ -361,7 +366,7 @@ int res_prepare(fdtd_ctx* c, int max_chunk);
 int launch_resident(fdtd_ctx* c, long long step, int nsteps, hipStream_t s);
 void res_free(fdtd_ctx* c);
 // The corrections between the E and H phases and behind the H update, in launch order.  api.hip lists what the planner knows of each.
-enum Correction { CORR_SHEET, CORR_DEBYE, CORR_LORENTZ, CORR_LUMPED, CORR_MAGNETIC, CORR_CONFORMAL, CORR_COUNT };
+enum Correction { CORR_SHEET, CORR_DEBYE, CORR_LORENTZ, CORR_LUMPED, CORR_MAGNETIC, CORR_CONFORMAL, CORR_PLANEWAVE, CORR_COUNT };
 int correction_single_slab(fdtd_ctx* c, Correction which);   // api.hip: FDTD_OK, or the refusal of a decomposed / p2p / linked context
 inline int fdtd_fail_hip(fdtd_ctx* c, const char* who, hipError_t e) {   // a set function's allocation or copy failed
   return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
@@ -413,6 +418,10 @@ void magnetic_free(fdtd_ctx* c);
 void launch_conformal(fdtd_ctx* c, hipStream_t s);
 int conformal_prime(fdtd_ctx* c, int comp);  // i_prev <- the listed faces' currents (fdtd_conformal_set, fdtd_set_field; comp < 0: all)
 void conformal_free(fdtd_ctx* c);
+// planewave.hip: plane-wave excitation — the sparse corrections of the box surface: kind FDTD_KIND_V after the E phase, behind
+// launch_lumped; kind FDTD_KIND_I after the H update, behind launch_conformal (no-ops without a plane wave)
+void launch_planewave(fdtd_ctx* c, int kind, long long step, hipStream_t s);
+void planewave_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

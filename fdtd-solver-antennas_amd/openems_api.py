@@ -252,6 +252,33 @@ class CSProperty:
         self._out_of_scope("AddMultiBox")
 
 
+class CSExcitation(CSProperty):
+    """What ContinuousStructure.AddExcitation returns: a plane wave (excitation type 10) on the box given with AddBox."""
+
+    def __init__(self, log: _CallLog, name: str, exc_type: int, exc_val, delay: float):
+        super().__init__(log, "Excitation", name, exc_type=int(exc_type), exc_val=[float(v) for v in exc_val], delay=float(delay))
+        self.params["prop_dir"] = None
+
+    def SetPropagationDir(self, val):
+        d = [float(v) for v in np.atleast_1d(val)]
+        if len(d) != 3:
+            raise ValueError(f"excitation '{self.name}': SetPropagationDir takes three values")
+        self._log.add("SetPropagationDir", prop=self.name, val=d)
+        self.params["prop_dir"] = d
+
+    def SetWeightFunction(self, func):
+        raise ValueError(f"excitation '{self.name}': SetWeightFunction is not supported by the HIP backend: out of scope — a plane wave has "
+                         f"one amplitude over its box")
+
+    def AddBox(self, start=None, stop=None, priority=0, **kw):
+        if self.boxes:
+            raise ValueError(f"excitation '{self.name}': one box per plane wave (several boxes are not supported)")
+        return super().AddBox(start, stop, priority, **kw)
+
+    def _add(self, kind, priority, **kw):
+        raise ValueError(f"Add{kind} on excitation '{self.name}': a plane wave takes one box only")
+
+
 def _take(kw, names, numbered):
     """Per-pole values out of the keywords `kw` (popped): the first of `names` present, as a sequence — else the keywords of
     `numbered` with the suffixes _1, _2, ... as far as they go."""
@@ -355,6 +382,25 @@ class ContinuousStructure:
             raise ValueError(f"AddLorentzMaterial '{name}': eps_relax must be >= 0 (0: a loss-free pole)")
         p = CSProperty(self._log, "LorentzMaterial", name, order=order, epsilon=eps_inf, kappa=kappa, eps_plasma=fp, eps_pole_freq=f0,
                        eps_relax=relax, **({} if density is None else {"density": density}))
+        self.properties.append(p)
+        return p
+
+    def AddExcitation(self, name, exc_type, exc_val, delay=0):
+        """CSXCAD's excitation property, for the plane wave only: ``exc_type`` 10 with ``exc_val`` = E0 [V/m]; ``SetPropagationDir``
+        and one ``AddBox`` on the returned property give the direction and the total-field box (planewave.py).  The field
+        excitations (types 0..3) are refused: a structure is fed through ``openEMS.AddLumpedPort``."""
+        if exc_type in (0, 1, 2, 3):
+            raise ValueError(f"AddExcitation '{name}': exc_type {exc_type} (a field excitation) is not supported by the HIP backend: out of scope "
+                             f"— feed the structure through a lumped port (openEMS.AddLumpedPort), or use exc_type 10 (plane wave)")
+        if exc_type != 10:
+            raise ValueError(f"AddExcitation '{name}': exc_type {exc_type!r} is not supported by the HIP backend (10, the plane wave, is)")
+        if np.size(exc_val) != 3:
+            raise ValueError(f"AddExcitation '{name}': exc_val takes the three components of E0")
+        if float(delay) != 0.0:
+            raise ValueError(f"AddExcitation '{name}': delay = {delay!r} is not supported: the plane wave starts with the run")
+        if any(p.kind == "Excitation" for p in self.properties):
+            raise ValueError(f"AddExcitation '{name}': the structure already has a plane wave (one plane-wave box per scene)")
+        p = CSExcitation(self._log, name, exc_type, np.asarray(exc_val, float).reshape(-1), delay)
         self.properties.append(p)
         return p
 
@@ -621,6 +667,12 @@ class openEMS:
                     m.medium.fit_info = getattr(p, "fit_info", None)
                 for b in p.boxes:
                     self._draw(m, b)
+            elif p.kind == "Excitation":
+                if p.params["prop_dir"] is None:
+                    raise ValueError(f"excitation '{p.name}': a plane wave needs its direction (SetPropagationDir)")
+                if len(p.boxes) != 1 or not np.allclose(p.boxes[0].matrix, np.eye(4)):
+                    raise ValueError(f"excitation '{p.name}': takes exactly one box, without a transform")
+                sc.add_plane_wave(p.name, p.params["exc_val"], p.params["prop_dir"]).add_box(p.boxes[0].start, p.boxes[0].stop)
             elif p.kind == "Dump":
                 continue                       # no part of the scene: Run hands the SAR boxes to Simulation.add_sar_box
             elif p.kind == "LumpedElement":
@@ -723,6 +775,11 @@ class openEMS:
                                "halo_transports_failed": list(self.stats.transports_failed),
                                "schedule_fallback": self.stats.schedule_fallback,
                                **({"sar": self.stats.sar} if self.stats.sar else {})}, fh)
+                # a plane wave: the excitation signal as upstream's two-column `et` file (time, value), which its RCS post-processing
+                # reads for the incident spectrum (P_rad of CalcNF2FF over the spectrum of et)
+                if self.sim.plane_wave is not None:
+                    sig = np.asarray(self.sim.signal, np.float64)
+                    np.savetxt(os.path.join(sim_path, "et"), np.c_[np.arange(sig.size) * self.sim.dt, sig])
                 # the port series as upstream's probe files (text): only on request — formatting them takes 0.03 s of a
                 # 0.34 s call on the reference's default scene, and CalcPort reads the arrays, not the files
                 if int(verbose or 0) > 0 or os.environ.get("FDTD_WRITE_PORT_FILES"):

@@ -30,6 +30,7 @@ from . import lumped as _lumped
 from . import magnetic as _magnetic
 from . import conformal as _conformal
 from . import primitives as _prims
+from . import planewave as _planewave
 
 
 @dataclass
@@ -149,6 +150,21 @@ class LumpedElement:
         return self
 
 
+@dataclass
+class PlaneWaveSource:
+    """AddExcitation(name, 10, e0) + SetPropagationDir as plain data: a plane wave on a total-field / scattered-field box
+    (planewave.py).  `spec` holds e0 (projected perpendicular to the direction) and the direction (normalised)."""
+    name: str
+    spec: _planewave.PlaneWave = None
+    boxes: List[Box] = field(default_factory=list)
+
+    def add_box(self, start, stop, priority=0):
+        if self.boxes:
+            raise ValueError(f"plane wave '{self.name}': one box per plane wave, and one plane wave per scene (several boxes are not supported)")
+        self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
+        return self
+
+
 def _density(name, density) -> float:
     if np.ndim(density) != 0 or not (np.isfinite(float(density)) and float(density) >= 0):
         raise ValueError(f"material '{name}': density = {density!r} must be one finite value >= 0 [kg/m^3]")
@@ -162,6 +178,7 @@ class Scene:
     metals: List[Metal] = field(default_factory=list)
     ports: List[LumpedPort] = field(default_factory=list)
     elements: List[LumpedElement] = field(default_factory=list)
+    plane_waves: List[PlaneWaveSource] = field(default_factory=list)
 
     def add_material(self, name, eps_r=1.0, kappa=0.0, mu_r=1.0, sigma_m=0.0, density=0.0) -> Material:
         """mu_r >= 1 and sigma_m >= 0 (magnetic loss sigma* [ohm/m]) make the material magnetic (magnetic.py); anisotropic
@@ -219,6 +236,17 @@ class Scene:
         return el
 
 
+    def add_plane_wave(self, name, e0, direction) -> PlaneWaveSource:
+        """A plane wave E0 s(t - k.(r - r0)/c0) travelling along `direction`, injected on the surface of the box given with
+        .add_box(start, stop): total field inside, scattered field outside (planewave.py).  e0 [V/m] is projected perpendicular to
+        the direction; one plane wave per scene."""
+        if self.plane_waves:
+            raise ValueError(f"plane wave '{name}': the scene already has the plane wave '{self.plane_waves[0].name}' (one plane-wave box per scene)")
+        pw = PlaneWaveSource(str(name), _planewave.PlaneWave(str(name), e0, direction))
+        self.plane_waves.append(pw)
+        return pw
+
+
 @dataclass
 class PortOnGrid:
     port: LumpedPort
@@ -257,6 +285,8 @@ class VoxelScene:
     fractions: Optional["_conformal.Fractions"] = None
     # mass density per cell [kg/m^3] of the material that owns it (None: no material of the scene has one): sar.py
     density: Optional[np.ndarray] = None
+    # plane-wave excitation (None: the scene has none): direction, e0 and the box snapped to whole nodes (planewave.PlaneWave)
+    plane_wave: Optional["_planewave.PlaneWave"] = None
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -328,6 +358,13 @@ def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = Fa
         vs.density = np.array([m.density for m in scene.materials] + [0.0])[vs.cell_material]
     if conformal:
         vs.fractions = _conformal.fractions(scene, grid, device_fractions)
+    for src in getattr(scene, "plane_waves", []):
+        if not src.boxes:
+            raise ValueError(f"plane wave '{src.name}' has no box: add_box(start, stop) gives the total-field region")
+        bx, u = src.boxes[0], scene.unit
+        lo = tuple(grid.snap(a, min(bx.start[a], bx.stop[a]) * u) for a in range(3))
+        hi = tuple(grid.snap(a, max(bx.start[a], bx.stop[a]) * u) for a in range(3))
+        vs.plane_wave = _planewave.PlaneWave(src.name, src.spec.e0, src.spec.direction, lo, hi)
     return vs
 
 

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 import numpy as np
 
-from .constants import C0, EPS0, MU0
+from .constants import C0, EPS0, MU0, ETA0
 from .grid import RectGrid
 from .scene import VoxelScene
 from .ecoperator import build_operator, ECOperator, metric_lists, pack_metric_tables, lumped_overrides, LumpedEdge
@@ -23,9 +23,10 @@ from . import lorentz as _lorentz
 from . import magnetic as _magnetic
 from . import conformal as _conformal
 from . import sar as _sar
+from . import planewave as _planewave
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
-from .nf2ff import NF2FFBox
+from .nf2ff import NF2FFBox, calc_nf2ff
 from . import _capi
 from ._capi import Engine, KIND_V, KIND_I
 
@@ -152,6 +153,7 @@ class RunStats:
     lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
     magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
     conformal: Optional[dict] = None          # conformal PEC boundaries (conformal.py): faces per component, R, dt factor, faces clamped
+    planewave: Optional[dict] = None          # plane-wave excitation (planewave.py): direction, e0, the box in nodes, entries per list
     sar: Optional[dict] = None                # SAR boxes (sar.py): per name the voxels, tissue voxels, mass, method and, once Simulation.sar has run, status counts and averaging time
 
 
@@ -315,11 +317,33 @@ class Simulation:
             self.element_lumped = [LumpedEdge(int(c), int(a), int(b), int(q), float(fold[m][0] + fold[m][1]), float(fold[m][2]))
                                    for c, a, b, q, m in zip(el.comp, i, j, k, el.elem)]
             self.element_stepped = el.stepped()
+        # plane-wave excitation: the box checked against everything else in the scene; the two entry lists are built in build(), from the
+        # operator the engine holds (fdtd_get_operator), and stepped by the engine (fdtd_planewave_set)
+        self.plane_wave = getattr(vox, "plane_wave", None)
+        self.signal2, self.planewave_tables = None, None
+        if self.plane_wave is not None:
+            self._check_plane_wave()
+            self.signal2 = _planewave.signal2(self.f0, self.fc, self.dt, len(self.signal))
+            reach = int(np.ceil(self.plane_wave.far_delay(grid) / self.dt)) + len(self.signal)
+            if reach > self.nr_ts and self.excitation_warning is None:
+                self.excitation_warning = (f"the excitation pulse is {len(self.signal)} timesteps long and the plane wave '{self.plane_wave.name}' needs "
+                                           f"{reach - len(self.signal)} more to cross its box, but NrTS = {self.nr_ts}: the run ends before the pulse has left the box")
+                import warnings
+                warnings.warn(self.excitation_warning, RuntimeWarning, stacklevel=2)
         self.engine: Optional[Engine] = None
         self.lib = None
         self.external_transport = None     # distributed.SlabComm when halos travel through the host
         self._port_probe_ids = []
         self._nf_ids = []
+
+    def _check_plane_wave(self):
+        """planewave.check_placement against the scene as this simulation holds it (again when a SAR box is added)."""
+        v = self.vox
+        reqs = [] if self.nf2ff_box is None else [(r.kind, r.comp, r.lo, r.hi) for r in self.nf2ff_box.requests]
+        _planewave.check_placement(self.grid, self.plane_wave, cpml_cells=self.bc.face_cells(), kinds=self.bc.kinds, eps_r=v.eps_r, kappa=v.kappa,
+                                   mu_r=getattr(v, "mu_r", None), sigma_m=getattr(v, "sigma_m", None), pec=v.pec, sheets=self.sheets,
+                                   elements=self.elements, debye=self.debye, lorentz=self.lorentz, conformal=self.conformal, ports=v.ports,
+                                   dft_boxes=reqs, sar_boxes=self.sar_boxes)
 
     @property
     def op(self) -> ECOperator:
@@ -361,6 +385,8 @@ class Simulation:
             raise _capi.FdtdError("magnetic materials need a single slab (world = 1): a decomposed run with magnetic media is not supported")
         if self.conformal is not None and world > 1:
             raise _capi.FdtdError("conformal boundaries need a single slab (world = 1): a decomposed run with cut faces is not supported")
+        if self.plane_wave is not None and world > 1:
+            raise _capi.FdtdError("plane-wave excitation needs a single slab (world = 1): a decomposed run with a plane wave is not supported")
         if self.sar_boxes and world > 1:
             raise _capi.FdtdError("SAR boxes need a single slab (world = 1): a decomposed run with SAR boxes is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
@@ -393,6 +419,10 @@ class Simulation:
             e.set_magnetic(*self.magnetic.tables())
         if self.conformal is not None:
             e.set_conformal(*self.conformal_tables())
+        if self.plane_wave is not None:
+            op = e.get_operator()
+            self.planewave_tables = _planewave.tables(g, self.plane_wave, self.dt, op[1], op[3], self.signal2)
+            e.set_planewave(*self.planewave_tables.args())
         if self.cpml is not None:
             e.set_cpml(*self.cpml.for_slab(k0, nk))
         if self.mur_enable.any():
@@ -493,6 +523,12 @@ class Simulation:
             if miss:
                 raise ValueError(f"SAR box '{name}': frequency {miss[0]:g} Hz is not among nf2ff_freqs ({rec.tolist()}): the running DFT "
                                  f"accumulates those only — add it to nf2ff_freqs or use nf2ff_mode='record'")
+        if self.plane_wave is not None:
+            self.sar_boxes[name] = {"lo": tuple(lo), "hi": tuple(hi)}
+            try:
+                self._check_plane_wave()
+            finally:
+                del self.sar_boxes[name]
         self.rec_bytes += nbytes
         self.sar_boxes[name] = {"lo": tuple(lo), "hi": tuple(hi), "freqs": f, "mass": mass, "method": method}
         self._sar_report[name] = {"voxels": int(np.prod([hi[a] - lo[a] for a in range(3)])), "tissue_voxels": int(np.count_nonzero(rho[sl] > 0)),
@@ -630,6 +666,47 @@ class Simulation:
         c = self.conformal
         return {"faces": c.faces(), "cut_edges": int(c.frac.idx.size), "ratio": c.ratio, "dt_factor": c.dt_factor, "clamped": c.clamped}
 
+    def planewave_info(self) -> Optional[dict]:
+        """What RunStats.planewave reports: direction, e0, the box in nodes and the entries of the two lists."""
+        if self.plane_wave is None:
+            return None
+        pw, t = self.plane_wave, self.planewave_tables
+        return {"name": pw.name, "direction": pw.direction.tolist(), "e0": pw.e0.tolist(), "lo": list(pw.lo), "hi": list(pw.hi),
+                "edges": None if t is None else int(t.E[0].size), "faces": None if t is None else int(t.H[0].size)}
+
+    def incident_spectrum(self, freqs) -> np.ndarray:
+        """s^(f) of the incident pulse, single-sided and scaled by 2 dt like the port spectra of CalcPort and nf2ff_boxes: the
+        incident field at r is E0 s^(f) exp(-j 2 pi f k.(r - r0)/c0)."""
+        if self.plane_wave is None:
+            raise RuntimeError("incident_spectrum: the scene has no plane wave (Scene.add_plane_wave / AddExcitation)")
+        return _planewave.incident_spectrum(freqs, self.signal2, self.dt)
+
+    def rcs(self, freq, theta, phi) -> np.ndarray:
+        """Bistatic radar cross-section [m^2] over theta x phi [rad] at `freq`, after the run: 4 pi U(theta, phi) / S_inc with U the
+        radiation intensity of the SCATTERED field (an NF2FF box strictly outside the plane-wave box) and
+        S_inc = 1/2 |E0|^2 |s^(f)|^2 / Z0 the incident power density."""
+        if self.plane_wave is None:
+            raise RuntimeError("rcs: the scene has no plane wave (Scene.add_plane_wave / AddExcitation)")
+        if self.nf2ff_box is None or self.engine is None:
+            raise RuntimeError("rcs: needs an NF2FF box (nf2ff_freqs=) outside the plane-wave box, and a finished run")
+        pw, nb = self.plane_wave, self.nf2ff_box
+        if not all(nb.lo[a] < pw.lo[a] and nb.hi[a] > pw.hi[a] for a in range(3)):
+            raise ValueError(f"rcs: the NF2FF box (nodes {nb.lo}..{nb.hi}) does not enclose the box of plane wave '{pw.name}' (nodes {pw.lo}..{pw.hi}): "
+                             f"it records the total field, not the scattered one")
+        f = float(freq)
+        if self.nf2ff_mode == "record":
+            boxes = self.nf2ff_boxes(freqs=[f])
+        else:
+            rec = np.asarray(self.nf2ff_freqs, float)
+            row = int(np.argmin(np.abs(rec - f)))
+            if abs(rec[row] - f) > 1e-6 * max(f, 1.0):
+                raise ValueError(f"rcs: frequency {f:g} Hz was not recorded (recorded: {rec.tolist()})")
+            boxes = [b[row:row + 1] for b in self.nf2ff_boxes()]
+        centre = [0.5 * (self.grid.lines[a][pw.lo[a]] + self.grid.lines[a][pw.hi[a]]) for a in range(3)]
+        res = calc_nf2ff(self.lib, nb, boxes, [f], np.atleast_1d(theta), np.atleast_1d(phi), centre, device=getattr(self, "device", 0))
+        s_inc = 0.5 * float(pw.e0 @ pw.e0) * abs(self.incident_spectrum([f])[0]) ** 2 / ETA0
+        return 4.0 * np.pi * res.P_rad[0] / s_inc
+
     def magnetic_info(self) -> Optional[dict]:
         """What RunStats.magnetic reports: the magnetic media, the (a, b) classes, the faces per component and their boxes."""
         if self.magnetic is None:
@@ -747,6 +824,7 @@ class Simulation:
         stats.lumped = self.lumped_info()
         stats.magnetic = self.magnetic_info()
         stats.conformal = self.conformal_info()
+        stats.planewave = self.planewave_info()
         stats.sar = self._sar_report if self.sar_boxes else None      # Simulation.sar fills in the status counts and the averaging time
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
