@@ -852,11 +852,14 @@ static bool mur_post_fusable(const fdtd_ctx* c, bool multi, bool fused) {
 // k_sheet runs between the two launches and reads and writes V: a sheet edge on the node plane of an enabled face takes the apply pass
 // too (the header's order: Mur passes, then the correction).  k_debye needs no such rule: the operator holds vi = 0 on every edge of a
 // grid face, and fdtd_debye_set leaves those edges out (their V is never the correction's to change, their states never act).
-// k_lumped is a sparse correction as k_sheet is: the two questions the planner has are asked of "a sheet or lumped edge".
-static bool correction_on_face(const fdtd_ctx* c, int f) { return ((c->sheet.faces | c->lumped.faces) >> f) & 1u; }   // (0 without edges)
+// k_lumped is a sparse correction as k_sheet is, and so is k_planewave's edge list (fdtd_planewave_set takes any existing edge; the
+// operator holds vi = 0 on a face's node plane, but the list's coefficients are the caller's): the two questions the planner has are
+// asked of "a sheet, lumped or plane-wave edge".  The plane wave's FACE list is not asked: fused I-probes are sampled by the next
+// update_E's probe blocks or by the flush at the end of the call, both behind it, and the Mur passes never touch I.
+static bool correction_on_face(const fdtd_ctx* c, int f) { return ((c->sheet.faces | c->lumped.faces | c->pw_faces) >> f) & 1u; }   // (0 without edges)
 static bool correction_at(const fdtd_ctx* c, int off) {   // an edge of a sparse correction on the node at local offset `off`
-  for (const EdgeList* l : {&c->sheet, &c->lumped})
-    if (std::binary_search(l->h_off.begin(), l->h_off.end(), off)) return true;
+  for (const std::vector<int>* h : {&c->sheet.h_off, &c->lumped.h_off, &c->pw_h_off})
+    if (std::binary_search(h->begin(), h->end(), off)) return true;
   return false;
 }
 
@@ -1033,7 +1036,8 @@ struct StepPlan {
 // of a timestep are otherwise sampled by the probe blocks of update_H, i.e. after the corrections: wrong as soon as a correction changes
 // a voltage a probe reads.  Debye media are volumes (ports sit inside substrates): always.  Sheet edges are few and the scene layer keeps
 // them off the probe lines: only when a V-probe cell sits on the node of a sheet edge (whatever the components: cheap and on the safe side).
-// Lumped-element edges: as the sheets'.
+// Lumped-element edges: as the sheets'.  The plane wave's edge list: as the sheets' (the scene layer keeps probes off the box surface, the
+// C ABI does not).
 static bool probes_first(const fdtd_ctx* c) {
   if (c->nprobe == 0) return false;
   if (correction(c, CORR_DEBYE).active || correction(c, CORR_LORENTZ).active) return true;   // (Lorentz / Drude media are volumes as well)
@@ -1156,7 +1160,7 @@ static int phase_E(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   if (!post_in_E) launch_mur(c, 1, s);          // post pass (a no-op without Mur faces)
   if (pl.mur != MUR_DIRECT) launch_mur(c, 2, s);   // apply pass, unless update_H takes the candidates itself
   if (!pl.fused) launch_post(c, FDTD_KIND_V, step, true, s);
-  // Debye media, a sheet edge under a V-probe: the correction follows the V-probes, so these cannot wait for the probe blocks of update_H
+  // Debye media, a sheet, lumped or plane-wave edge under a V-probe: the correction follows the V-probes, so these cannot wait for the probe blocks of update_H
   // (phase_H leaves them out)
   else if (pl.probes_first) launch_post(c, FDTD_KIND_V, step, false, s);
   launch_dft(c, FDTD_KIND_V, step, s);

@@ -319,6 +319,11 @@ struct fdtd_ctx {
   // offset and component and two terms (coefficient, whole half-steps of delay, fraction) — and the pulse at half-step resolution
   struct PlaneWaveList { int n = 0; int* off = nullptr; int8_t* comp = nullptr; float2* coef = nullptr; int2* m0 = nullptr; float2* w = nullptr; };
   PlaneWaveList pw[2];
+  // ... and for the planner what an EdgeList keeps of its edges, of the EDGE list alone: the grid faces whose node plane holds one (bit f:
+  // x-, x+, y-, y+, z-, z+) and the offsets once more, sorted, on the host.  (The face list needs neither: fused I-probes are sampled by
+  // the next update_E's probe blocks or by the flush at the end of the call, both behind it, and the Mur passes never touch I.)
+  unsigned pw_faces = 0;
+  std::vector<int> pw_h_off;
   float* pw_sig2 = nullptr; int pw_nsig2 = 0;
   std::string err;
 };

@@ -57,7 +57,7 @@ void list_free(fdtd_ctx::PlaneWaveList* l) {
 }
 
 // one list checked and turned into the arrays the kernel reads (nothing on the device yet)
-struct HostList { std::vector<int> off; std::vector<int8_t> comp; std::vector<float2> coef, w; std::vector<int2> m0; };
+struct HostList { std::vector<int> off; std::vector<int8_t> comp; std::vector<float2> coef, w; std::vector<int2> m0; unsigned planes = 0; };
 int list_check(fdtd_ctx* c, const char* what, bool faces, int n, const int64_t* idx, const int8_t* comp, const float* coef,
                const int32_t* m0, const float* w, HostList* out) {
   const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
@@ -77,6 +77,7 @@ int list_check(fdtd_ctx* c, const char* what, bool faces, int n, const int64_t* 
       if (!(wq >= 0.f && wq < 1.f)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_planewave_set: %s %d: the fraction of the delay must be in [0, 1)", what, e);
     }
     keys[e] = idx[e] * 3 + m;
+    for (int a = 0; a < 3; ++a) out->planes |= (pos[a] == 0 ? 1u : 0u) << (2 * a) | (pos[a] == nn[a] - 1 ? 1u : 0u) << (2 * a + 1);   // (as edge_list_set)
     out->off[e] = off; out->comp[e] = (int8_t)m;
     out->coef[e] = make_float2(coef[2 * (size_t)e], coef[2 * (size_t)e + 1]);
     out->m0[e] = make_int2(m0[2 * (size_t)e], m0[2 * (size_t)e + 1]);
@@ -100,6 +101,7 @@ hipError_t list_upload(fdtd_ctx::PlaneWaveList* l, const HostList& h) {
 void planewave_free(fdtd_ctx* c) {
   list_free(&c->pw[0]); list_free(&c->pw[1]);
   hipFree(c->pw_sig2); c->pw_sig2 = nullptr; c->pw_nsig2 = 0;
+  c->pw_faces = 0; c->pw_h_off.clear();
 }
 
 void launch_planewave(fdtd_ctx* c, int kind, long long step, hipStream_t s) {
@@ -139,6 +141,11 @@ int fdtd_planewave_set(fdtd_ctx* c,
     return fdtd_fail_hip(c, "fdtd_planewave_set", e);
   }
   c->pw_nsig2 = nsig2;
+  // what the planner asks of the edge list (api.hip correction_on_face, correction_at): a V-probe cell on a listed edge is sampled in
+  // front of the corrections, a listed edge on the node plane of a Mur face takes the apply pass as a launch of its own
+  c->pw_faces = hE.planes;
+  c->pw_h_off.swap(hE.off);
+  std::sort(c->pw_h_off.begin(), c->pw_h_off.end());
   return FDTD_OK;
 }
 

@@ -27,7 +27,9 @@
  *           wave), before the I-probes and the I-DFT / recorder are sampled.
  * The placement rules of planewave.check_placement keep every other correction, probe and recording box off the corrected
  * elements, so the order is immaterial for a scene the host layers accept; it is fixed all the same.  fdtd_half_step(ctx,
- * FDTD_PHASE_E / FDTD_PHASE_H) applies the matching list.
+ * FDTD_PHASE_E / FDTD_PHASE_H) applies the matching list.  Keeping it has a price only for lists the host layers would refuse: an
+ * edge of the E list under a V-probe cell costs the V-probe launch in front of the corrections, an edge on the node plane of a Mur
+ * face costs the Mur apply pass as a launch of its own.
  *
  * A context with a plane wave steps under the two-launch schedule (three with Mur faces) plus the two k_planewave launches per
  * timestep; forcing FDTD_FLAG_KERNEL_WAVEFRONT or FDTD_FLAG_KERNEL_RESIDENT returns FDTD_E_UNSUPPORTED, and so do world > 1,

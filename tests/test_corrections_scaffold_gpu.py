@@ -98,7 +98,8 @@ def test_magnetic_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
         assert np.array_equal(ip[cls[c] == 0], before[cls[c] == 0]) and np.any(ip[cls[c] != 0] != before[cls[c] != 0])
 
 
-# ---- the refusals: one context of 8 x 8 x 8 nodes per correction, one edge, one face or a box of one cell ---------------------------
+# ---- the refusals: one context of 8 x 8 x 8 nodes per correction (all seven of the planner's table, correction() in csrc/api.hip), one
+# edge, one face or a box of one cell ------------------------------------------------------------------------------------------------
 E_PHASE = "their correction runs between the E phase and the H update"
 H_PHASE = "their correction runs between the H update and the next E phase"
 ONE = [(3, 3, 3)] * 3, [(4, 4, 4)] * 3
@@ -129,12 +130,18 @@ def _set_conformal(e):
     e.set_conformal(EDGE[1], EDGE[0], np.full((1, 4), 0.1, np.float32))
 
 
+def _set_planewave(e):
+    one = (np.array([[1e-3, 0.0]], np.float32), np.zeros((1, 2), np.int32), np.array([[0.5, 0.0]], np.float32))
+    e.set_planewave(*EDGE, *one, *EDGE, *one, np.ones(4, np.float32))                # one edge, and the face at the same node
+
+
 REFUSALS = [("fdtd_sheet_set", _set_sheet, f"conducting sheets: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_debye_set", _set_debye, f"Debye media: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_lorentz_set", _set_lorentz, f"Lorentz media: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_lumped_set", _set_lumped, f"lumped elements: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_magnetic_set", _set_magnetic, f"magnetic materials: the two-launch schedule only ({H_PHASE})"),
-            ("fdtd_conformal_set", _set_conformal, f"conformal boundaries: the two-launch schedule only ({H_PHASE})")]
+            ("fdtd_conformal_set", _set_conformal, f"conformal boundaries: the two-launch schedule only ({H_PHASE})"),
+            ("fdtd_planewave_set", _set_planewave, f"plane-wave excitation: the two-launch schedule only ({H_PHASE})")]
 
 
 @pytest.mark.gpu

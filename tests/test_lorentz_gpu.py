@@ -1,13 +1,14 @@
 """Lorentz and Drude media on the GPU (csrc/lorentz.hip): the HIP step loop against the oracle's half-steps plus the numpy restatement
 of every correction (Debye media, Lorentz media, sheets, elements after the E phase, magnetic faces after the H update), bit for bit;
-block and vector boundaries through the raw ABI; the order of the V-probes, the V-DFT boxes and the correction; the schedules a context
-with Lorentz media may take and what the library refuses; S11 through the openEMS API mirror."""
+block and vector boundaries through the raw ABI; the order of the V-probes, the V-DFT boxes and the correction; media on the node
+planes of grid faces under both Mur schedules; the schedules a context with Lorentz media may take and what the library refuses; S11
+through the openEMS API mirror."""
 import numpy as np
 import pytest
 
 from conftest import pkg
 from helpers import seeded_fields
-from test_dispersion_model_cpu import _fr4
+from test_dispersion_model_cpu import _fr4, _graded
 from test_sheet_model_cpu import _grid
 from test_lorentz_model_cpu import TWO_PI, RestatedLorentz, lorentz_cavity, lorentz_patch, restating_build
 
@@ -232,6 +233,61 @@ def test_v_probe_and_v_dft_box_read_the_voltage_before_the_correction(hip_lib, o
         box = e.get_dft_box(bid)[0]
         assert box.shape == acc.shape
         assert np.abs(box - acc).max() <= 1e-12 * scale, np.abs(box - acc).max() / scale
+
+
+def _face_sim(name, nr_ts):
+    """The four scenes of test_dispersion_gpu.test_media_on_grid_faces_under_both_mur_schedules with the Debye medium replaced by the
+    two-pole Lorentz medium of _order_sim: a substrate slab that runs into the four side faces / a medium that fills the grid up to all
+    six, on the graded 23 x 21 x 19 mesh, a port inside the medium."""
+    sc, sim = pkg("scene"), pkg("simulation")
+    g = _graded((23, 21, 19), seed=14)
+    x, y, z = (l * 1e3 for l in g.lines)
+    at = lambda p: [x[p[0]], y[p[1]], z[p[2]]]
+    lo, hi = ((0, 0, 6), (22, 20, 10)) if name.startswith("slab") else ((0, 0, 0), (22, 20, 18))
+    s = sc.Scene(unit=1e-3)
+    s.add_lorentz_material("m", 2.0, 0.0, TWO_PI * np.array([8e9, 6e9]), TWO_PI * np.array([0.0, 12e9]), [4e9, 1e9]).add_box(at(lo), at(hi))
+    s.add_lumped_port(1, 50.0, at((11, 10, 6)), at((11, 10, 10)), "z", 1.0)
+    return sim.Simulation(g, sc.voxelize(s, g), f0=9e9, fc=5e9, boundary="MUR" if name.endswith("mur") else "PEC", nr_ts=nr_ts, end_criteria=0.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["slab-to-four-mur", "filled-mur", "slab-to-four-pec", "filled-pec"])
+def test_lorentz_media_on_grid_faces_under_both_mur_schedules(hip_lib, oracle_lib, monkeypatch, name):
+    """Lorentz cells on the node planes of Mur (and PEC) faces, as test_dispersion_gpu has them for Debye media (the two share
+    media_set and the dense box).  Without an apply pass the face voltages in memory between update_E and update_H are not the
+    timestep's final ones, and k_lorentz runs exactly there; with FDTD_MUR_APPLY_PASS=1 they are.  The operator holds every edge of a
+    face node plane (vi = 0) and such edges are no dispersive edges (fdtd_hip_lorentz.h): fields, port series and fdtd_lorentz_get's
+    v_prev, states and vi of EVERY edge agree among both schedules and the restatement, bit for bit."""
+    nsteps = 120
+    ref_sim = _face_sim(name, nsteps)
+    ref = RestatedLorentz(ref_sim, oracle_lib, seed=8)
+    ref.run(nsteps)
+    d = ref_sim.lorentz
+    held = sum(int(np.count_nonzero((np.asarray(d.w[c]).reshape(ref.lor["vi"][c].shape) != 0) & (ref.lor["vi"][c] == 0))) for c in range(3))
+    assert held > 300, held                      # the edges in question exist, in numbers
+    fo = ref.e.fields()
+    assert np.all(np.isfinite(fo)) and np.abs(fo).max() > 0 and min(np.abs(x).max() for x in ref.lor["x"]) > 0
+    mur = name.endswith("mur")
+    for apply_pass, want in ((None, 2), ("1", 3 if mur else 2)):
+        if apply_pass is None:
+            monkeypatch.delenv("FDTD_MUR_APPLY_PASS", raising=False)
+        else:
+            monkeypatch.setenv("FDTD_MUR_APPLY_PASS", apply_pass)
+        s = _face_sim(name, nsteps)
+        e = s.build(hip_lib)
+        assert e.schedule_info()["launches_per_timestep"] == want, e.schedule_info()
+        seeded_fields(e, 8)
+        e.run(nsteps)
+        fh = e.fields()
+        assert np.array_equal(fh, fo), f"fields differ at {np.count_nonzero(fh != fo)} entries, first {tuple(np.argwhere(fh != fo)[0])}"
+        _same_state(e, ref)
+        for c in range(3):
+            vp, x, vi = e.lorentz_state(c)
+            rest = vi == 0
+            assert rest.any() and np.all(vp[rest] == 0) and np.all(x[:, :, rest] == 0)
+        for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
+            assert np.abs(qu).max() > 0 and np.abs(qi).max() > 0 and np.array_equal(pu[:nsteps], qu[:nsteps]) and np.array_equal(pi[:nsteps], qi[:nsteps])
+        e.close()
 
 
 @pytest.mark.gpu
