@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <mutex>
 #include <chrono>
+#include <unordered_map>
 #include <vector>
 
 #include "host_tables.hpp"
@@ -238,6 +239,7 @@ int fdtd_create(const fdtd_desc* d, fdtd_ctx** out) {
   if (chip_cus(d->device) != 256 && !getenv("FDTD_XCD_BALANCE")) { c->xcd_balance = false; c->xcd_adapt = false; }
   p.src_dense_ok = 1;
   p.src_rng = nullptr; p.src_ids = nullptr; p.nsrc = 0; p.src_off = nullptr; p.src_comp = nullptr; p.src_amp = nullptr; p.src_delay = nullptr;
+  p.src_chain = nullptr;
   p.sig = c->sig; p.nsig = 0;
   p.probes = c->d_probe; p.nprobe = 0; p.max_steps = d->max_steps;
   *out = c;
@@ -260,7 +262,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   for (int n = 0; n < 12; ++n) hipFree(c->psi[n]);
   hipFree(c->d_mur);
   hipFree(c->rt_tw[0]); hipFree(c->rt_tw[1]); hipFree(c->rt_out);
-  hipFree(c->sig); hipFree(c->src_off); hipFree(c->src_comp); hipFree(c->src_amp); hipFree(c->src_delay);
+  hipFree(c->sig); hipFree(c->src_off); hipFree(c->src_comp); hipFree(c->src_amp); hipFree(c->src_delay); hipFree(c->src_chain);
   for (int q = 0; q < c->nprobe; ++q) {
     hipFree((void*)c->probe[q].off); hipFree((void*)c->probe[q].comp); hipFree((void*)c->probe[q].w); hipFree(c->probe[q].series);
   }
@@ -566,6 +568,17 @@ int fdtd_add_source(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, 
   {   // two sources on one edge?  (then the dense form of body_E, which gives every edge one slot, is not taken)
     std::vector<long long> key(c->h_src_off.size());
     for (size_t e = 0; e < key.size(); ++e) key[e] = (long long)c->h_src_off[e] * 4 + c->h_src_comp[e];
+    // ... and k_post, one thread per entry, must still add the entries of one edge in list order (float32 adds do not commute with the rounding):
+    // the first entry of an edge walks the chain of the later ones, which their own threads skip
+    std::vector<unsigned> chain(key.size(), 0u);
+    std::unordered_map<long long, size_t> last;
+    for (size_t e = 0; e < key.size(); ++e) {
+      auto it = last.find(key[e]);
+      if (it == last.end()) last.emplace(key[e], e);
+      else { chain[it->second] |= (unsigned)e + 1u; chain[e] = 0x80000000u; it->second = e; }
+    }
+    HIPCK(c, to_device(&c->src_chain, chain));
+    c->p.src_chain = c->src_chain;
     std::sort(key.begin(), key.end());
     c->p.src_dense_ok = std::adjacent_find(key.begin(), key.end()) == key.end() ? 1 : 0;
   }
@@ -1150,7 +1163,10 @@ static int phase_E(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   };
   if (!split) { int r = wait_halo(); if (r) return r; }
   const bool post_in_E = pl.mur == MUR_DIRECT || pl.mur == MUR_POST_IN_E;
-  launch_update_E(c, split ? 1 : 0, nk, step, pl.fused, true, s, post_in_E);
+  // the I-probes of step - 1 ride in this launch — unless the call before this one has flushed them: a probe added between two calls has no
+  // entry for a timestep before it existed, and fields set between two calls are not sampled as that timestep's
+  launch_update_E(c, split ? 1 : 0, nk, step, pl.fused, c->iprb_pending, s, post_in_E);
+  c->iprb_pending = false;
   c->kev0 = c->kev1 = nullptr;
   if (split) {
     int r = wait_halo();
@@ -1185,6 +1201,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   if (!split) { int r = wait_halo(); if (r) return r; }
   // Mur scenes: the pre pass of step + 1 rides in this launch (it reads V only, which is final and not written here)
   launch_update_H(c, 0, split ? nk - 1 : nk, step, pl.fused, s, pl.fused ? pl.mur : MUR_NONE, !pl.probes_first);
+  if (pl.fused) c->iprb_pending = true;   // sampled by the next update_E's probe blocks or by the flush at the end of the call
   if (pl.fused && c->any_mur && (c->p.mur_nb > 0 || c->p.mur_direct)) c->mur_pre_step = step + 1;   // (mur_direct: the main blocks ran the pre pass)
   c->kev0 = c->kev1 = nullptr;
   if (split) {
@@ -1313,7 +1330,8 @@ static int p2p_enqueue_E(fdtd_ctx* c, ProfEvents* pe, int n) {
   HIPCK(c, hipSetDevice(c->d.device));
   p2p_prime_if_needed(c);
   if (pe) { c->kev0 = pe->e0[n]; c->kev1 = pe->e1[n]; }
-  launch_update_E(c, 0, c->d.nk, c->step, true, true, c->stream);
+  launch_update_E(c, 0, c->d.nk, c->step, true, c->iprb_pending, c->stream);   // (the I-probes of step - 1, unless already flushed: phase_E)
+  c->iprb_pending = false;
   c->kev0 = c->kev1 = nullptr;
   launch_dft(c, FDTD_KIND_V, c->step, c->stream);
   return FDTD_OK;
@@ -1322,6 +1340,7 @@ static int p2p_enqueue_H(fdtd_ctx* c, ProfEvents* pe, int n) {
   HIPCK(c, hipSetDevice(c->d.device));
   if (pe) { c->kev0 = pe->h0[n]; c->kev1 = pe->h1[n]; }
   launch_update_H(c, 0, c->d.nk, c->step, true, c->stream);
+  c->iprb_pending = true;
   c->kev0 = c->kev1 = nullptr;
   launch_dft(c, FDTD_KIND_I, c->step, c->stream);
   return FDTD_OK;
@@ -1332,7 +1351,7 @@ static int step_loop_p2p(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     if ((r = p2p_enqueue_E(c, pe, n)) || (r = p2p_enqueue_H(c, pe, n))) return r;
     c->step++;
   }
-  if (nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);   // flush the last step's I-probes
+  if (nsteps > 0) { launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream); c->iprb_pending = false; }   // flush the last step's I-probes
   HIPCK(c, hipGetLastError());
   return launch_status(c);
 }
@@ -1361,7 +1380,7 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
     if (multi && (r = exchange(c, FDTD_HALO_H_UP, pl.rccl_inline))) return r;
     c->step++;
   }
-  if (pl.fused && nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);   // flush the last step's I-probes
+  if (pl.fused && nsteps > 0) { launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream); c->iprb_pending = false; }   // flush the last step's I-probes
   HIPCK(c, hipGetLastError());
   return launch_status(c);
 }
@@ -1930,7 +1949,7 @@ int fdtd_run_linked(fdtd_ctx** ctxs, int n, int nsteps) {
       fdtd_ctx* c = ctxs[r];
       if (one(r)) continue;
       HIPCK(c, hipSetDevice(c->d.device));
-      if (nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);
+      if (nsteps > 0) { launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream); c->iprb_pending = false; }
     }
     for (int r = 0; r < n; ++r) {
       fdtd_ctx* c = ctxs[r];
@@ -1963,7 +1982,7 @@ int fdtd_run_linked(fdtd_ctx** ctxs, int n, int nsteps) {
   for (int r = 0; r < n; ++r) {
     fdtd_ctx* c = ctxs[r];
     HIPCK(c, hipSetDevice(c->d.device));
-    if (plan[r].fused && nsteps > 0) launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream);
+    if (plan[r].fused && nsteps > 0) { launch_post(c, FDTD_KIND_I, c->step - 1, false, c->stream); c->iprb_pending = false; }
     HIPCK(c, hipGetLastError());
   }
   for (int r = 0; r < n; ++r) {

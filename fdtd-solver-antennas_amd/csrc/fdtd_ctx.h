@@ -135,6 +135,7 @@ struct DevParams {
   const int* src_ids;
   int nsrc; const int* src_off; const int8_t* src_comp; const float* src_amp; const int* src_delay;
   int src_dense_ok;          // 1: no two sources on one edge — strip-planes with more than SRC_SCAN_MAX sources take the dense form (body_E)
+  const unsigned* src_chain; // [nsrc], read when src_dense_ok == 0 (k_post): (next entry on the same edge + 1, or 0) | bit 31: not the first entry of its edge
   const float* sig; int nsig;
   const struct DevProbe* probes; int nprobe; int max_steps;
   // Mur "pre" pass of the NEXT step as extra blocks of the update_H launch (it only reads V, which update_H does not write)
@@ -262,10 +263,12 @@ struct fdtd_ctx {
   // excitation
   float* sig = nullptr; int nsig = 0;
   int nsrc = 0; int* src_off = nullptr; int8_t* src_comp = nullptr; float* src_amp = nullptr; int* src_delay = nullptr;
+  unsigned* src_chain = nullptr;     // the entries of one edge linked in list order (DevParams::src_chain)
   int src_max_per_strip_plane = 0;   // most source edges in one strip-plane of the current tiling (scanning path: at most FDTD_BLOCK)
   std::vector<int> h_src_off; std::vector<int8_t> h_src_comp; std::vector<float> h_src_amp; std::vector<int> h_src_delay;
   // probes
   int nprobe = 0; DevProbe probe[FDTD_MAX_PROBES] = {}; DevProbe* d_probe = nullptr;
+  bool iprb_pending = false;     // fused probes: the I-probes of timestep step - 1 are still to be sampled (by the probe blocks of the next update_E, or by the flush that ends a call)
   // dft
   int nfreq = 0, every = 0, nsamples = 0; double *tw_v = nullptr, *tw_i = nullptr;
   bool recorder = false;         // boxes keep time-domain samples (fdtd_set_recorder) instead of running-DFT sums

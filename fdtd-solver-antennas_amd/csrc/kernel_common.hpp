@@ -223,30 +223,38 @@ __device__ __forceinline__ void wf_poll(const DevParams& p, const unsigned* f, c
 // that overwrite probe cells in the NEXT timestep of the launch wait for that.
 template <bool MULTI = false>
 __device__ __forceinline__ void wf_probe_tail(const DevParams& p, const int q, const long long step, const unsigned target, double* red) {
-  if (step < 0 || step >= p.max_steps) {
-    if (MULTI && threadIdx.x == 0) __hip_atomic_store(p.wf_prb_done + q, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
+  // A timestep beyond the series (step >= max_steps) records nothing.  MULTI: its block still waits for the owner blocks before it says "cells read".
+  // The words of one probe must grow in timestep order — a block that said so at once could overtake the block of the timestep before it, which is
+  // still polling; that block's store then took the word BACK by one, and the E blocks of the next timestep waited for a value that never came
+  // (a run of two or more timesteps past max_steps in one launch timed out) — and a word that runs ahead would let a block overwrite cells the
+  // earlier probe block has yet to read.  Behind its owner blocks a probe block is behind the probe block of the timestep before: those owner
+  // blocks waited for that one's word.
+  const bool rec = step >= 0 && step < p.max_steps;
+  if (!rec && !MULTI) return;
   const DevProbe pr = p.probes[q];
   const int2 rng = p.wf_prb_rng[q];
   const unsigned* flags = pr.kind == FDTD_KIND_V ? p.wf_flags : p.wf_flagsH;
   for (int e = rng.x + (int)threadIdx.x; e < rng.y; e += FDTD_BLOCK) wf_poll(p, flags + p.wf_prb_blk[e], target);
   __syncthreads();
-  double s = 0.0;
-  for (int e = threadIdx.x; e < pr.n; e += FDTD_BLOCK) {
-    const float* F = (pr.kind == FDTD_KIND_V ? p.V[pr.comp[e]] : p.I[pr.comp[e]]);
-    const unsigned bits = __hip_atomic_load(reinterpret_cast<const unsigned*>(F + pr.off[e]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s = fma((double)pr.w[e], (double)__uint_as_float(bits), s);
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = FDTD_BLOCK / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+  if (rec) {   // (block-uniform)
+    double s = 0.0;
+    for (int e = threadIdx.x; e < pr.n; e += FDTD_BLOCK) {
+      const float* F = (pr.kind == FDTD_KIND_V ? p.V[pr.comp[e]] : p.I[pr.comp[e]]);
+      const unsigned bits = __hip_atomic_load(reinterpret_cast<const unsigned*>(F + pr.off[e]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s = fma((double)pr.w[e], (double)__uint_as_float(bits), s);
+    }
+    red[threadIdx.x] = s;
     __syncthreads();
+    for (int w = FDTD_BLOCK / 2; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+      __syncthreads();
+    }
   }
   if (threadIdx.x == 0) {
-    pr.series[step] = red[0];
-    if (MULTI) __hip_atomic_store(p.wf_prb_done + q, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (every thread's loads were consumed before the first barrier above)
+    if (rec) pr.series[step] = red[0];
+    // (every thread's loads were consumed before the first barrier above; max, not a plain store: a probe WITHOUT cells has no owner blocks to order
+    //  its blocks, and the word must not go back when an earlier timestep's block comes last)
+    if (MULTI) __hip_atomic_fetch_max(p.wf_prb_done + q, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 // A block that is about to overwrite cells a probe of `kind` samples: wait until the probe blocks of the previous timestep

@@ -857,11 +857,21 @@ __global__ __launch_bounds__(FDTD_BLOCK) void k_post(const DevParams p, const in
                                                      const long long step) {
   __shared__ double red[FDTD_BLOCK];
   if (sources) {
+    // one thread per entry; with two entries on one edge (src_dense_ok == 0) the thread of the edge's FIRST entry adds them all, in list order
+    // (two threads on one edge would lose an add, or add in another order than the list's), and the threads of the later entries skip theirs
     for (int e = threadIdx.x; e < p.nsrc; e += FDTD_BLOCK) {
-      const long long t = step - p.src_delay[e];
-      if (t >= 0 && t < p.nsig) {
-        float* v = p.V[p.src_comp[e]] + p.src_off[e];
-        *v = *v + p.src_amp[e] * p.sig[t];
+      unsigned link = p.src_dense_ok ? 0u : p.src_chain[e];
+      if (link >> 31) continue;
+      for (int q = e;;) {
+        const long long t = step - p.src_delay[q];
+        if (t >= 0 && t < p.nsig) {
+          float* v = p.V[p.src_comp[q]] + p.src_off[q];
+          *v = *v + p.src_amp[q] * p.sig[t];
+        }
+        link &= 0x7fffffffu;
+        if (link == 0u) break;
+        q = (int)link - 1;
+        link = p.src_chain[q];
       }
     }
     __threadfence_block();

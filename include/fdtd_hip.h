@@ -206,10 +206,13 @@ int fdtd_set_mur(fdtd_ctx* ctx, const int32_t enable[6], const float coeff[6]);
 
 /* ---- excitation, probes, frequency-domain recording ------------------------------------- */
 int fdtd_set_signal(fdtd_ctx* ctx, const float* sig, int n);
-/* V[comp[e]][idx[e]] += amp[e] * sig[step - delay[e]];  idx = (k*ny + j)*nx + i, GLOBAL k. */
+/* V[comp[e]][idx[e]] += amp[e] * sig[step - delay[e]];  idx = (k*ny + j)*nx + i, GLOBAL k.  Nothing is added where step - delay[e]
+ * lies outside the signal table.  Entries on ONE edge are added in list order (float32), under every schedule.  Sources and probes
+ * may be added between two fdtd_run calls: a source acts from the next timestep, a probe's entries before it was added are 0. */
 int fdtd_add_source(fdtd_ctx* ctx, int n, const int64_t* idx, const int8_t* comp,
                     const float* amp, const int32_t* delay);
-/* value[step] = sum_e w[e] * field[comp[e]][idx[e]] over the edges this slab owns. */
+/* value[step] = sum_e w[e] * field[comp[e]][idx[e]] over the edges this slab owns (V after the E half-step with Mur passes and sources
+ * applied, I after the H half-step); max_steps entries per probe, later timesteps are not recorded; at most 64 probes ("too many probes"). */
 int fdtd_add_probe(fdtd_ctx* ctx, int kind, int n, const int64_t* idx, const int8_t* comp,
                    const float* w, int* id_out);
 int fdtd_get_probe(fdtd_ctx* ctx, int id, double* out, int cap, int* n_out);

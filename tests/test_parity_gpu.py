@@ -476,24 +476,14 @@ def test_mur_with_sources_next_to_and_away_from_a_face(hip_lib, oracle_lib, src_
     """Mur scene driven through the C ABI directly: a source edge ON the plane next to the x- Mur face (src_i = 1: the
     order 'Mur post, then source' matters, so the library must take the unfused launch sequence) and in the interior
     (src_i = 9: sources/probes stay fused in the main kernels) — both identical to the oracle, fields and probe series."""
-    capi, const = pkg("_capi"), pkg("constants")
-    from opbuild_cases import random_scene
-    grid, eps, kap, pec, _ = random_scene(21, (22, 20, 18), False, 3, n_lumped=0, pec_frac=0.0)
-    dt = grid.courant_dt()
-    nx, ny, nz = grid.shape
+    capi = pkg("_capi")
+    from source_probe_cases import raw_engine
+    nx, ny, nz = 22, 20, 18
     n = 160
     out = []
     for lib in (hip_lib, oracle_lib):
-        e = capi.Engine(lib, nx, ny, nz, dt, max_steps=n + 8)
-        eco = pkg("ecoperator")
-        emet, hmet = eco.pack_metric_tables(*eco.metric_lists(grid, dt), grid)
-        e.build_operator(grid.d, eps, kap, pec, const.EPS0, eco.lumped_overrides(grid, eps, kap, pec, dt, []), emet, hmet)
-        coeff = []
-        for f in range(6):
-            l = grid.lines[f // 2]
-            d = (l[-1] - l[-2]) if f % 2 else (l[1] - l[0])
-            coeff.append((const.C0 * dt - d) / (const.C0 * dt + d))
-        e.set_mur([1] * 6, coeff)
+        e = raw_engine(lib, (21, (nx, ny, nz)), "MUR", max_steps=n + 8)
+        dt = e.dt
         t = np.arange(n) * dt
         e.set_signal(np.sin(2 * np.pi * 8e9 * t) * np.exp(-((t - 40 * dt) / (15 * dt)) ** 2))
         j, k = ny // 2, nz // 2

@@ -116,24 +116,13 @@ def test_energy_sum_is_reproducible(hip_lib, oracle_lib):
 def test_mur_on_five_node_wide_grids(hip_lib, oracle_lib, shape):
     """Mur faces on a grid 5 nodes wide: along x both inner nodes (1 and 3) lie in ONE thread's four cells, so the post
     pass fused into update_E (one x pair of S values per thread) must not be taken there; 6 wide it is."""
-    capi, const = pkg("_capi"), pkg("constants")
-    from opbuild_cases import random_scene
-    grid, eps, kap, pec, _ = random_scene(5, shape, False, 3, n_lumped=0, pec_frac=0.0)
-    dt = grid.courant_dt()
-    nx, ny, nz = grid.shape
+    from source_probe_cases import raw_engine
+    nx, ny, nz = shape
     n = 90
     out = []
     for lib in (hip_lib, oracle_lib):
-        e = capi.Engine(lib, nx, ny, nz, dt, max_steps=n + 8)
-        eco = pkg("ecoperator")
-        emet, hmet = eco.pack_metric_tables(*eco.metric_lists(grid, dt), grid)
-        e.build_operator(grid.d, eps, kap, pec, const.EPS0, eco.lumped_overrides(grid, eps, kap, pec, dt, []), emet, hmet)
-        coeff = []
-        for f in range(6):
-            l = grid.lines[f // 2]
-            d = (l[-1] - l[-2]) if f % 2 else (l[1] - l[0])
-            coeff.append((const.C0 * dt - d) / (const.C0 * dt + d))
-        e.set_mur([1] * 6, coeff)
+        e = raw_engine(lib, (5, shape), "MUR", max_steps=n + 8)
+        dt = e.dt
         t = np.arange(n) * dt
         e.set_signal(np.sin(2 * np.pi * 8e9 * t) * np.exp(-((t - 30 * dt) / (12 * dt)) ** 2))
         i, j, k = nx // 2, ny // 2, nz // 2
