@@ -20,3 +20,4 @@ class CSPrimitives:
     CSPrimBox = _api.CSPrimBox
     CSPrimCylinder = CSPrimCylindricalShell = CSPrimSphere = CSPrimSphericalShell = _api.CSPrimCurved
     CSPrimPolygon = CSPrimLinPoly = CSPrimCurve = CSPrimWire = _api.CSPrimCurved
+    CSPrimPolyhedronReader = _api.CSPrimPolyhedronReader

@@ -1,7 +1,9 @@
 // voxel.hip — rasterise the primitive table of include/fdtd_hip_voxel.h onto the Yee grid (what scene.voxelize did in numpy over
 // whole-grid temporaries).  One kernel, templated on the pass: the cell pass tests cell centres against the material records and
 // keeps the winner; the edge pass tests every node and its +x, +y, +z neighbours against the metal records and keeps the winner
-// per component.  float64 throughout, in the operation order the header spells (primitives._inside is the same text in numpy;
+// per component.  Triangle meshes (POLYHEDRON records) run in a second launch of the same kernel (POLY = true: the same tile, point map
+// and single writer, starting from the owners the first launch stored), so the registers of the first stay sized by the analytic
+// types; a table without a mesh launches what it always did.  float64 throughout, in the operation order the header spells (primitives._inside is the same text in numpy;
 // -ffp-contract=off keeps the compiler from fusing), so the owners are those of primitives.rasterise_spec bit for bit.
 //
 // A block of 256 threads owns a tile of one z-plane: VX_TY rows of VX_TX threads, four consecutive x points per thread.  The table
@@ -23,6 +25,7 @@ namespace {
 constexpr int VX_BLOCK = 256, VX_TX = 32, VX_TY = 8, VX_PTS = 4;
 constexpr int VX_CHUNK = 48;                                  // records per LDS chunk: 48 * 248 B = 11.6 KiB
 constexpr int VX_WORDS = (int)(sizeof(fdtd_voxel_prim) / 8);  // 31
+constexpr int VX_TRI_CHUNK = VX_BLOCK;                        // triangles per chunk, one per thread: 256 * 72 B = 18 KiB of LDS
 enum { PASS_CELL = 0, PASS_EDGE = 1 };
 
 struct VoxArgs {
@@ -53,8 +56,116 @@ __device__ __forceinline__ bool seg_near(double wx, double wy, double wz, double
   return s <= 0.0 ? ww <= lim2 : (s >= L ? gg <= lim2 : ww * L - s * s <= lim2 * L);
 }
 
-// Bit q of the result: point q is inside record r (in LDS) under its role's rule.  `gate` masks the points outside the index box.
+// ---- POLYHEDRON (include/fdtd_hip_voxel.h): a closed triangle mesh, parity of the crossings of the ray towards +x ---------------
+// ((b - a) x (p - a)) . n >= 0: p is on the inner side of the triangle's edge a -> b
+__device__ __forceinline__ bool tri_side(double ax, double ay, double az, double bx, double by, double bz, double px, double py,
+                                         double pz, double nx, double ny, double nz) {
+  const double dx = bx - ax, dy = by - ay, dz = bz - az;
+  const double vx = px - ax, vy = py - ay, vz = pz - az;
+  const double cx = dy * vz - dz * vy, cy = dz * vx - dx * vz, cz = dx * vy - dy * vx;
+  return (cx * nx + cy * ny) + cz * nz >= 0.0;
+}
+// one crossing of the projected edge P -> Q, its end points taken in canonical order (the smaller z first, then the smaller y)
+__device__ __forceinline__ bool tri_cross(double Py, double Pz, double Qy, double Qz, double y, double z) {
+  const bool sw = Qz < Pz || (Qz == Pz && Qy < Py);
+  const double ay = sw ? Qy : Py, az = sw ? Qz : Pz, by = sw ? Py : Qy, bz = sw ? Pz : Qz;
+  const double du = by - ay, dv = bz - az, wu = y - ay, wv = z - az;
+  return ((az > z) != (bz > z)) && (wu * dv < wv * du);
+}
+// Records are in drawing order, so within one launch >= lets the later one win a tie; the polyhedron launch meets owners of either side.
+template <bool POLY> __device__ __forceinline__ bool vx_wins(int prio, int idx, int best, int own) {
+  return POLY ? (prio > best || (prio == best && idx > own)) : prio >= best;
+}
+// The points of a caller that share (y, z) with an earlier one (PtMap: the cell pass's four, the edge pass's 5 + 4 + 4) take its
+// gate and its projected hit when the record has no transform: the earlier point's index.
+template <int N> constexpr __host__ __device__ int vx_yz_rep(int q) { return N == 4 ? 0 : (N == 13 ? (q < 5 ? 0 : (q < 9 ? 5 : 9)) : q); }
+
+// the gate of a triangle T[9]: its (y, z) bounding box grown by g
+__device__ __forceinline__ void tri_gate(const double* T, const double g, double& y0, double& y1, double& z0, double& z1) {
+  const double ay = T[1], az = T[2], by = T[4], bz = T[5], cy = T[7], cz = T[8];
+  const double ymn = ay < by ? ay : by, ymx = ay > by ? ay : by, zmn = az < bz ? az : bz, zmx = az > bz ? az : bz;
+  y0 = (ymn < cy ? ymn : cy) - g; y1 = (ymx > cy ? ymx : cy) + g;
+  z0 = (zmn < cz ? zmn : cz) - g; z1 = (zmx > cz ? zmx : cz) + g;
+}
+
+// ntri triangles at V (global memory or LDS; every lane reads the same one) on the N local points: par ^= crossings, near |= within tol
 template <int N>
+__device__ __forceinline__ void vx_tris(const double* V, const int ntri, const bool has_matrix, const double tol, const double (&x)[N],
+                                        const double (&y)[N], const double (&z)[N], const unsigned gate, unsigned& par, unsigned& near) {
+  const double tol2 = tol * tol, g = 2.0 * tol;
+  for (int tr = 0; tr < ntri; ++tr) {
+    const double* T = V + 9 * (size_t)tr;
+    const double ax = T[0], ay = T[1], az = T[2], bx = T[3], by = T[4], bz = T[5], cx = T[6], cy = T[7], cz = T[8];
+    double y0, y1, z0, z1;
+    tri_gate(T, g, y0, y1, z0, z1);
+    unsigned inyz = 0u;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      const int rq = vx_yz_rep<N>(q);
+      bool b;
+      if (rq != q && !has_matrix) b = (inyz >> rq) & 1u;
+      else b = ((y[q] >= y0) && (y[q] <= y1)) && ((z[q] >= z0) && (z[q] <= z1));
+      inyz |= (b ? 1u : 0u) << q;
+    }
+    if ((inyz & gate) == 0u) continue;                           // the triangle's (y, z) box misses every point of this lane
+    const double e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    if (nx != 0.0) {
+      unsigned proj = 0u;
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const int rq = vx_yz_rep<N>(q);
+        bool b;
+        if (rq != q && !has_matrix) b = (proj >> rq) & 1u;
+        else b = (tri_cross(ay, az, by, bz, y[q], z[q]) != tri_cross(by, bz, cy, cz, y[q], z[q])) != tri_cross(cy, cz, ay, az, y[q], z[q]);
+        proj |= (b ? 1u : 0u) << q;
+      }
+      proj &= inyz;
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const double wx = x[q] - ax, wy = y[q] - ay, wz = z[q] - az;
+        const double s = (nx * wx + ny * wy) + nz * wz;
+        const bool c = ((proj >> q) & 1u) && (nx > 0.0 ? s < 0.0 : s > 0.0);
+        par ^= (c ? 1u : 0u) << q;
+      }
+    }
+    const double xmn = ax < bx ? ax : bx, xmx = ax > bx ? ax : bx;
+    const double x0 = (xmn < cx ? xmn : cx) - g, x1 = (xmx > cx ? xmx : cx) + g;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      if (!((inyz & gate & ~near) >> q & 1u) || !((x[q] >= x0) && (x[q] <= x1))) continue;   // near is an OR: a held bit needs no test
+      const double wx = x[q] - ax, wy = y[q] - ay, wz = z[q] - az;
+      const double s = (nx * wx + ny * wy) + nz * wz;
+      const bool c0 = tri_side(ax, ay, az, bx, by, bz, x[q], y[q], z[q], nx, ny, nz);
+      const bool c1 = tri_side(bx, by, bz, cx, cy, cz, x[q], y[q], z[q], nx, ny, nz);
+      const bool c2 = tri_side(cx, cy, cz, ax, ay, az, x[q], y[q], z[q], nx, ny, nz);
+      bool nr;
+      if (c0 && c1 && c2) {
+        nr = s * s <= tol2 * nn;
+      } else {
+        const double ux = x[q] - bx, uy = y[q] - by, uz = z[q] - bz, tx = x[q] - cx, ty = y[q] - cy, tz = z[q] - cz;
+        nr = seg_near(wx, wy, wz, ux, uy, uz, bx - ax, by - ay, bz - az, tol2) ||
+             seg_near(ux, uy, uz, tx, ty, tz, cx - bx, cy - by, cz - bz, tol2) ||
+             seg_near(tx, ty, tz, wx, wy, wz, ax - cx, ay - cy, az - cz, tol2);
+      }
+      near |= (nr ? 1u : 0u) << q;
+    }
+  }
+}
+
+template <int N>
+__device__ __forceinline__ unsigned vx_poly(const bool metal, const int vert0, const int nvert, const bool has_matrix,
+                                            const double* __restrict__ verts, const double tol, const double (&x)[N],
+                                            const double (&y)[N], const double (&z)[N], const unsigned gate) {
+  unsigned par = 0u, near = 0u;
+  vx_tris<N>(verts + vert0, nvert / 3, has_matrix, tol, x, y, z, gate, par, near);
+  return metal ? (par | near) : (par & ~near);
+}
+
+// Bit q of the result: point q is inside record r (in LDS) under its role's rule.  `gate` masks the points outside the index box.
+// POLY = false leaves the POLYHEDRON case out (k_voxel<pass, false>; k_voxel<pass, true> takes those records, through vx_tris).
+template <int N, bool POLY = true>
 __device__ __forceinline__ unsigned vx_test(const fdtd_voxel_prim* r, const int type, const bool metal, const int norm_dir,
                                             const int vert0, const int nvert, const bool has_matrix,
                                             const double* __restrict__ verts, const double tol, const double (&wx)[N],
@@ -76,6 +187,9 @@ __device__ __forceinline__ unsigned vx_test(const fdtd_voxel_prim* r, const int 
   }
   const double p0 = r->par[0], p1 = r->par[1], p2 = r->par[2], p3 = r->par[3], p4 = r->par[4], p5 = r->par[5], p6 = r->par[6],
                p7 = r->par[7];
+  if constexpr (POLY) {
+    if (type == FDTD_VOXEL_POLYHEDRON) return vx_poly<N>(metal, vert0, nvert, has_matrix, verts, tol, x, y, z, gate) & gate;
+  }
   unsigned in = 0u;
   switch (type) {
     case FDTD_VOXEL_BOX: {
@@ -199,12 +313,16 @@ __device__ __forceinline__ unsigned vx_test(const fdtd_voxel_prim* r, const int 
   return in & gate;
 }
 
-template <int PASS>
+// POLY = false: every record but the polyhedra, from no owner.  POLY = true: the polyhedron records alone, from the owners the first
+// launch left in a.out (priority of an owner: its record's); the same tile, point map and single writer.
+template <int PASS, bool POLY = false>
 __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
   using M = PtMap<PASS>;
   constexpr int N = M::N;
   constexpr int NOUT = PASS == PASS_CELL ? VX_PTS : 3 * VX_PTS;
   __shared__ unsigned long long s_tab[VX_CHUNK * VX_WORDS];
+  __shared__ double s_tri[POLY ? VX_TRI_CHUNK * 9 : 1];           // the triangles of a chunk whose gate meets this tile
+  __shared__ int s_cnt[VX_BLOCK / 64];
 
   // point counts of this pass and the block's tile
   const int px = PASS == PASS_CELL ? a.nx - 1 : a.nx, py = PASS == PASS_CELL ? a.ny - 1 : a.ny;
@@ -238,6 +356,25 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
   int best[NOUT], own[NOUT];
 #pragma unroll
   for (int q = 0; q < NOUT; ++q) { best[q] = INT32_MIN; own[q] = -1; }
+  double cx[2] = {0.0, 0.0}, cy[2] = {0.0, 0.0}, cz[2] = {0.0, 0.0};   // POLY: the tile's first and last coordinate per axis (block-uniform);
+  if constexpr (POLY) {                                              // the lines increase, so every point of the tile lies between them
+    const int ix[2] = {bx0, tx1}, iy[2] = {by0, ty1}, iz[2] = {k, tz1};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      cx[q] = PASS == PASS_CELL ? 0.5 * (lx[ix[q]] + lx[ix[q] + 1]) : lx[ix[q]];
+      cy[q] = PASS == PASS_CELL ? 0.5 * (ly[iy[q]] + ly[iy[q] + 1]) : ly[iy[q]];
+      cz[q] = PASS == PASS_CELL ? 0.5 * (lz[iz[q]] + lz[iz[q] + 1]) : lz[iz[q]];
+    }
+    if (j < py) {
+#pragma unroll
+      for (int q = 0; q < NOUT; ++q) {
+        if (i0 + q % VX_PTS >= px) continue;
+        const size_t at = (size_t)(q / VX_PTS) * ((size_t)px * (size_t)py * (size_t)pz) + ((size_t)k * (size_t)py + (size_t)j) * (size_t)px + (size_t)(i0 + q % VX_PTS);
+        own[q] = a.out[at];
+        best[q] = own[q] >= 0 ? a.table[own[q]].priority : INT32_MIN;
+      }
+    }
+  }
 
   for (int c0 = 0; c0 < a.nprim; c0 += VX_CHUNK) {
     const int cn = min(VX_CHUNK, a.nprim - c0);
@@ -255,6 +392,9 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
       const int b4 = __builtin_amdgcn_readfirstlane(box[4]), b5 = __builtin_amdgcn_readfirstlane(box[5]);
       if (b3 < bx0 || b0 > tx1 || b4 < by0 || b1 > ty1 || b5 < k || b2 > tz1) continue;   // misses the tile: block-uniform
       const int type = __builtin_amdgcn_readfirstlane(r->type);
+      if constexpr (POLY) {
+        if (type != FDTD_VOXEL_POLYHEDRON) continue;              // the other launch holds no polyhedron: vx_test<N, false> gives it no point
+      }
       const int prio = __builtin_amdgcn_readfirstlane(r->priority);
       const int norm_dir = __builtin_amdgcn_readfirstlane(r->norm_dir);
       const int vert0 = __builtin_amdgcn_readfirstlane(r->vert0), nvert = __builtin_amdgcn_readfirstlane(r->nvert);
@@ -266,12 +406,73 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
         const bool g = i >= b0 && i <= b3 && jj >= b1 && jj <= b4 && kk >= b2 && kk <= b5;
         gate |= (g ? 1u : 0u) << q;
       }
-      const unsigned in = vx_test<N>(r, type, PASS == PASS_EDGE, norm_dir, vert0, nvert, has_matrix, a.verts, a.tol, wx, wy, wz, gate);
+      unsigned in;
+      if constexpr (POLY) {
+        // The record's triangles in chunks of one per thread: a thread tests its triangle's gate against the tile's (y, z) range in the
+        // record's frame (each local coordinate is monotone in every world coordinate, so the tile's eight corners bound it); the
+        // triangles that meet the tile are packed into LDS (ballot + prefix count, no atomics), and every thread runs those alone.
+        // The order of the triangles does not matter: parity is an XOR, near an OR.
+        double x[N], y[N], z[N];
+        double Ylo = cy[0], Yhi = cy[1], Zlo = cz[0], Zhi = cz[1];
+        if (has_matrix) {
+          const double m0 = r->m[0], m1 = r->m[1], m2 = r->m[2], m3 = r->m[3], m4 = r->m[4], m5 = r->m[5], m6 = r->m[6], m7 = r->m[7],
+                       m8 = r->m[8], m9 = r->m[9], m10 = r->m[10], m11 = r->m[11];
+#pragma unroll
+          for (int q = 0; q < N; ++q) {
+            x[q] = ((m0 * wx[q] + m1 * wy[q]) + m2 * wz[q]) + m3;
+            y[q] = ((m4 * wx[q] + m5 * wy[q]) + m6 * wz[q]) + m7;
+            z[q] = ((m8 * wx[q] + m9 * wy[q]) + m10 * wz[q]) + m11;
+          }
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const double X = cx[q & 1], Y = cy[(q >> 1) & 1], Z = cz[q >> 2];
+            const double yy = ((m4 * X + m5 * Y) + m6 * Z) + m7, zz = ((m8 * X + m9 * Y) + m10 * Z) + m11;
+            Ylo = (q == 0 || yy < Ylo) ? yy : Ylo; Yhi = (q == 0 || yy > Yhi) ? yy : Yhi;
+            Zlo = (q == 0 || zz < Zlo) ? zz : Zlo; Zhi = (q == 0 || zz > Zhi) ? zz : Zhi;
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < N; ++q) { x[q] = wx[q]; y[q] = wy[q]; z[q] = wz[q]; }
+        }
+        unsigned par = 0u, near = 0u;
+        const int ntri = nvert / 3;
+        const double* V = a.verts + vert0;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int t0 = 0; t0 < ntri; t0 += VX_TRI_CHUNK) {
+          __syncthreads();                                          // the previous chunk's triangles are no longer read
+          const int t = t0 + (int)threadIdx.x;
+          double T[9];
+          bool keep = false;
+          if (t < ntri) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) T[q] = V[9 * (size_t)t + q];
+            double y0, y1, z0, z1;
+            tri_gate(T, 2.0 * a.tol, y0, y1, z0, z1);
+            keep = !(Yhi < y0 || Ylo > y1 || Zhi < z0 || Zlo > z1);
+          }
+          const unsigned long long m = __ballot(keep);
+          if (lane == 0) s_cnt[wave] = __popcll(m);
+          __syncthreads();
+          int base = 0, total = 0;
+#pragma unroll
+          for (int w = 0; w < VX_BLOCK / 64; ++w) { const int c = s_cnt[w]; base += w < wave ? c : 0; total += c; }
+          if (keep) {
+            const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+            for (int q = 0; q < 9; ++q) s_tri[9 * pos + q] = T[q];
+          }
+          __syncthreads();
+          vx_tris<N>(s_tri, total, has_matrix, a.tol, x, y, z, gate, par, near);
+        }
+        in = (PASS == PASS_EDGE ? (par | near) : (par & ~near)) & gate;
+      } else {
+        in = vx_test<N, false>(r, type, PASS == PASS_EDGE, norm_dir, vert0, nvert, has_matrix, a.verts, a.tol, wx, wy, wz, gate);
+      }
       const int idx = c0 + p;
       if (PASS == PASS_CELL) {
 #pragma unroll
         for (int q = 0; q < VX_PTS; ++q) {
-          const bool w = ((in >> q) & 1u) && prio >= best[q];     // records are in drawing order: >= lets the later one win a tie
+          const bool w = ((in >> q) & 1u) && vx_wins<POLY>(prio, idx, best[q], own[q]);
           best[q] = w ? prio : best[q];
           own[q] = w ? idx : own[q];
         }
@@ -280,7 +481,8 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
         for (int q = 0; q < VX_PTS; ++q) {
           const bool n0 = (in >> q) & 1u;
           const bool ex = n0 && ((in >> (q + 1)) & 1u), ey = n0 && ((in >> (q + 5)) & 1u), ez = n0 && ((in >> (q + 9)) & 1u);
-          const bool w0 = ex && prio >= best[q], w1 = ey && prio >= best[VX_PTS + q], w2 = ez && prio >= best[2 * VX_PTS + q];
+          const bool w0 = ex && vx_wins<POLY>(prio, idx, best[q], own[q]), w1 = ey && vx_wins<POLY>(prio, idx, best[VX_PTS + q], own[VX_PTS + q]),
+                     w2 = ez && vx_wins<POLY>(prio, idx, best[2 * VX_PTS + q], own[2 * VX_PTS + q]);
           best[q] = w0 ? prio : best[q];                       own[q] = w0 ? idx : own[q];
           best[VX_PTS + q] = w1 ? prio : best[VX_PTS + q];         own[VX_PTS + q] = w1 ? idx : own[VX_PTS + q];
           best[2 * VX_PTS + q] = w2 ? prio : best[2 * VX_PTS + q]; own[2 * VX_PTS + q] = w2 ? idx : own[2 * VX_PTS + q];
@@ -392,9 +594,10 @@ int vx_check_table(int nx, int ny, int nz, int nprim, const void* table, int nve
     if (r.type < 0 || r.type >= FDTD_VOXEL_NTYPES || (r.role != FDTD_VOXEL_MATERIAL && r.role != FDTD_VOXEL_METAL))
       return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d has type %d, role %d", p, r.type, r.role);
     const bool poly = r.type == FDTD_VOXEL_POLYGON || r.type == FDTD_VOXEL_LINPOLY, wire = r.type == FDTD_VOXEL_WIRE;
-    if (poly || wire) {
+    const bool mesh = r.type == FDTD_VOXEL_POLYHEDRON;                 // nvert = 3 * ntri points of three doubles
+    if (poly || wire || mesh) {
       const long long need = (long long)r.vert0 + (long long)(poly ? 2 : 3) * (long long)r.nvert;
-      if (r.vert0 < 0 || r.nvert < 1 || need > (long long)nvert)
+      if (r.vert0 < 0 || r.nvert < 1 || need > (long long)nvert || (mesh && r.nvert % 3 != 0))
         return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d reads vertices %d + %d of %d", p, r.vert0, r.nvert, nvert);
       if (poly && (r.norm_dir < 0 || r.norm_dir > 2))
         return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d has norm_dir %d", p, r.norm_dir);
@@ -448,14 +651,21 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
   if (rc == FDTD_OK) {
     VoxArgs a{nx, ny, nz, d_lines, nprim, d_tab, d_verts, tol, nullptr};
     const int per_x = VX_TX * VX_PTS;
+    bool mesh[2] = {false, false};                               // a polyhedron among the materials / the metals: its own launch
+    for (int p = 0; p < nprim; ++p)
+      if (tab[p].type == FDTD_VOXEL_POLYHEDRON) mesh[tab[p].role == FDTD_VOXEL_METAL ? 1 : 0] = true;
     if (cell_owner) {
       a.out = d_cell;
       hipLaunchKernelGGL(k_voxel<PASS_CELL>, dim3((nx - 1 + per_x - 1) / per_x, (ny - 1 + VX_TY - 1) / VX_TY, nz - 1), dim3(VX_BLOCK), 0, 0, a);
+      if (mesh[0])
+        hipLaunchKernelGGL((k_voxel<PASS_CELL, true>), dim3((nx - 1 + per_x - 1) / per_x, (ny - 1 + VX_TY - 1) / VX_TY, nz - 1), dim3(VX_BLOCK), 0, 0, a);
       VX(hipGetLastError());
     }
     if (edge_owner) {
       a.out = d_edge;
       hipLaunchKernelGGL(k_voxel<PASS_EDGE>, dim3((nx + per_x - 1) / per_x, (ny + VX_TY - 1) / VX_TY, nz), dim3(VX_BLOCK), 0, 0, a);
+      if (mesh[1])
+        hipLaunchKernelGGL((k_voxel<PASS_EDGE, true>), dim3((nx + per_x - 1) / per_x, (ny + VX_TY - 1) / VX_TY, nz), dim3(VX_BLOCK), 0, 0, a);
       VX(hipGetLastError());
     }
     VX(hipDeviceSynchronize());

@@ -187,6 +187,50 @@ class CSPrimCurved(_CSPrimitive):
         return lo, hi
 
 
+class CSPrimPolyhedronReader(CSPrimCurved):
+    """AddPolyhedronReader: a closed triangle mesh read from an STL file (stl.py), coordinates in the grid's drawing unit."""
+
+    def __init__(self, entry: dict, filename, priority):
+        _CSPrimitive.__init__(self, entry, priority)
+        self.kind = "Polyhedron"
+        self.prim = None
+        self._filename = os.fspath(filename)
+        self._error = None
+
+    def GetFileName(self):
+        return self._filename
+
+    def SetFileName(self, filename):
+        self._filename = os.fspath(filename)
+        self._entry["filename"] = self._filename
+        self.prim = None
+
+    def ReadFile(self) -> bool:
+        """Read the file now; False (as CSXCAD does) when it cannot be read — drawing the scene then raises with the reason."""
+        from . import stl as _stl
+        try:
+            self.prim = _prims.make("Polyhedron", self.priority, triangles=_stl.read_stl(self._filename))
+            self._error = None
+        except ValueError as e:
+            self.prim, self._error = None, str(e)
+        return self.prim is not None
+
+    def _need(self):
+        if self.prim is None and not self.ReadFile():
+            raise ValueError(f"AddPolyhedronReader: {self._error}")
+
+    def to_scene(self):
+        self._need()
+        return super().to_scene()
+
+    def bounding_box(self):
+        self._need()
+        pts = self.prim.triangles.reshape(-1, 3)
+        if not np.allclose(self.matrix, np.eye(4)):
+            pts = pts @ self.matrix[:3, :3].T + self.matrix[:3, 3]
+        return pts.min(axis=0), pts.max(axis=0)
+
+
 class CSProperty:
     def __init__(self, log: _CallLog, kind: str, name: str, **kw):
         self._log, self.kind, self.name = log, kind, name
@@ -237,6 +281,24 @@ class CSProperty:
 
     def AddWire(self, points, radius, priority=0, **kw):
         return self._add("Wire", priority, points=np.asarray(points, float), radius=radius)
+
+    def AddPolyhedronReader(self, filename, priority=0, **kw):
+        """A solid from an STL file (binary or ASCII); call ReadFile() on the result, as with CSXCAD (drawing the scene reads a file
+        that was not read yet)."""
+        if self.kind == "ConductingSheet":
+            raise ValueError(f"AddPolyhedronReader on {self.kind} '{self.name}': polyhedra are for materials and metals (AddMetal) only")
+        if self.kind == "LumpedElement":
+            raise ValueError(f"AddPolyhedronReader on lumped element '{self.name}': lumped elements take boxes only")
+        ft = kw.get("file_type")
+        if ft is not None and not (isinstance(ft, str) and ft.lower() in ("stl", "stl_file")) and ft != 1:
+            raise ValueError(f"AddPolyhedronReader '{filename}': file_type {ft!r} is not supported by the HIP backend: STL only (no PLY)")
+        if ft is None and os.path.splitext(os.fspath(filename))[1].lower() != ".stl":
+            raise ValueError(f"AddPolyhedronReader '{filename}': the file type is taken from the extension, and only .stl is supported "
+                             f"(pass file_type='STL' for an STL file of another name)")
+        self._log.add("AddPolyhedronReader", prop=self.name, priority=priority, filename=os.fspath(filename))
+        b = CSPrimPolyhedronReader(self._log.calls[-1], filename, priority)
+        self.boxes.append(b)
+        return b
 
     def _out_of_scope(self, what):
         raise ValueError(f"{what} is not supported by the HIP backend: out of scope (boxes, cylinders, spheres, shells, polygons, "

@@ -9,6 +9,9 @@ by tol, a polygon point within tol of an edge is outside); a *metal* holds a nod
 (radii grow by tol, a polygon point within tol of an edge is inside).  Ownership: the highest priority wins, the later primitive
 on a tie (materials in scene order, then drawing order inside a material); an edge is metal when ONE primitive holds both its end
 nodes.  Curves (and the centre line of a wire) are snapped to grid edges on the host (``snap_curve``).
+
+A ``Polyhedron`` is a closed triangle mesh (stl.read_stl gives one): inside is the parity of the crossings of the ray towards +x, with
+the polygon's tol rule for points within tol of a triangle (``_tri_into``; DESIGN 6.1 says why the edges are taken in canonical order).
 """
 from __future__ import annotations
 
@@ -17,7 +20,10 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 T_BOX, T_SPHERE, T_SPHERICAL_SHELL, T_CYLINDER, T_CYLINDRICAL_SHELL, T_DISC, T_POLYGON, T_LINPOLY, T_WIRE = range(9)
-N_TYPES = 9
+N_TYPES = 9                # the analytic types above; the triangle mesh is appended after them
+T_POLYHEDRON = 9
+N_TYPES_ALL = 10           # == FDTD_VOXEL_NTYPES
+MAX_TRIANGLES = 1 << 20    # per record
 ROLE_MATERIAL, ROLE_METAL = 0, 1
 N_PAR = 8
 
@@ -88,7 +94,14 @@ class Wire(Curve):
     radius: float = 0.0
 
 
-NEW_TYPES = (Cylinder, CylindricalShell, Sphere, SphericalShell, Polygon, LinPoly, Curve, Wire)
+@dataclass
+class Polyhedron(_Prim):
+    """A closed triangle mesh: triangles [ntri][3][3] (triangle, corner A B C, x y z) in drawing units.  Facet normals and the winding
+    of a triangle do not matter; every edge must be used by an even number of triangles (pack_table refuses an open mesh)."""
+    triangles: np.ndarray = None
+
+
+NEW_TYPES = (Cylinder, CylindricalShell, Sphere, SphericalShell, Polygon, LinPoly, Curve, Wire, Polyhedron)
 
 
 def _f3(v, what):
@@ -130,6 +143,11 @@ def make(kind: str, priority=0, **kw) -> _Prim:
         if pts.ndim != 2 or pts.shape[0] != 3 or pts.shape[1] < 2 or not np.all(np.isfinite(pts)):
             raise ValueError(f"{kind}: points must be 3 x N with N >= 2")
         return Curve(p, None, pts) if kind == "Curve" else Wire(p, None, pts, pos("radius"))
+    if kind.lower() == "polyhedron":
+        tri = np.array(kw["triangles"], float)
+        if tri.ndim != 3 or tri.shape[0] < 1 or tri.shape[1:] != (3, 3) or not np.all(np.isfinite(tri)):
+            raise ValueError("Polyhedron: triangles must be ntri x 3 x 3 finite coordinates with ntri >= 1")
+        return Polyhedron(p, None, tri)
     raise ValueError(f"unknown primitive '{kind}'")
 
 
@@ -144,7 +162,7 @@ def has_new(scene) -> bool:
 @dataclass
 class Table:
     rec: np.ndarray                    # RECORD [nprim], in ownership order
-    verts: np.ndarray                  # float64: polygon vertices (u, v pairs) and wire points (x, y, z triples), metres
+    verts: np.ndarray                  # float64: polygon vertices (u, v pairs), wire points and triangle corners (x, y, z triples), metres
     tol: float
     curves: List[tuple] = field(default_factory=list)     # (metal index, points [N][3] in world metres) of curves and wires
     names: List[str] = field(default_factory=list)        # per record: "<property>: <type>" for messages
@@ -171,6 +189,29 @@ def _index_box(coords, lo, hi, pad):
     return out
 
 
+def _closed_triangles(tri, what):
+    """The triangles [ntri][3][3] (metres) without the zero-area ones; ValueError for an open mesh or one beyond MAX_TRIANGLES."""
+    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    tri = tri[((nx * nx + ny * ny) + nz * nz) != 0.0]
+    if tri.shape[0] > MAX_TRIANGLES:
+        raise ValueError(f"{what}: {tri.shape[0]} triangles in one polyhedron, at most {MAX_TRIANGLES} are supported")
+    if tri.shape[0] == 0:
+        raise ValueError(f"{what}: the polyhedron has no triangle of non-zero area")
+    _, vid = np.unique(tri.reshape(-1, 3) + 0.0, axis=0, return_inverse=True)      # weld by exact coordinates (+ 0.0: -0.0 == 0.0)
+    vid = vid.reshape(-1, 3)
+    ends = np.stack([vid, np.roll(vid, -1, axis=1)], axis=2).reshape(-1, 2)
+    ends = ends[ends[:, 0] != ends[:, 1]]
+    _, uses = np.unique(np.sort(ends, axis=1), axis=0, return_counts=True)
+    nopen = int(np.count_nonzero(uses % 2))
+    if nopen:
+        raise ValueError(f"{what}: the polyhedron is not closed: {nopen} open edges (edges used by an odd number of triangles); the "
+                         f"inside of an open mesh is undefined")
+    return tri
+
+
 def pack_table(scene, grid) -> Table:
     """One flat table for both rasterisers: materials in scene order, then metals, each in drawing order.  Parameters in metres."""
     from .scene import Box, ConductingSheet, _tol
@@ -183,6 +224,8 @@ def pack_table(scene, grid) -> Table:
         for qi, prop in enumerate(props):
             for pr in prop.boxes:
                 Minv, M = _world_inverse(pr.matrix, u)
+                if isinstance(pr, Polyhedron) and isinstance(prop, ConductingSheet):
+                    raise ValueError(f"'{prop.name}': Polyhedron is for materials and plain metals (AddMetal) only")
                 if isinstance(pr, Curve):
                     if role != ROLE_METAL or isinstance(prop, ConductingSheet):
                         raise ValueError(f"'{prop.name}': {type(pr).__name__} is for metals (AddMetal) only")
@@ -244,6 +287,13 @@ def pack_table(scene, grid) -> Table:
                     verts.append(pts.T.reshape(-1))
                     nvert += 3 * pts.shape[1]
                     lo, hi = pts.min(axis=1) - par[0], pts.max(axis=1) + par[0]
+                elif isinstance(pr, Polyhedron):
+                    tri = _closed_triangles(np.asarray(pr.triangles, float) * u, f"'{prop.name}'")
+                    r["type"] = T_POLYHEDRON
+                    r["vert0"], r["nvert"] = nvert, 3 * tri.shape[0]
+                    verts.append(tri.reshape(-1))
+                    nvert += tri.size
+                    lo, hi = tri.reshape(-1, 3).min(axis=0), tri.reshape(-1, 3).max(axis=0)
                 else:
                     raise ValueError(f"'{prop.name}': unknown primitive {type(pr).__name__}")
                 r["par"] = par
@@ -273,6 +323,50 @@ def _seg_near(wx, wy, wz, ex, ey, ez, dx, dy, dz, lim2):
     ww = (wx * wx + wy * wy) + wz * wz
     ee = (ex * ex + ey * ey) + ez * ez
     return np.where(s <= 0.0, ww <= lim2, np.where(s >= L, ee <= lim2, ww * L - s * s <= lim2 * L))
+
+
+def _tri_side(ax, ay, az, bx, by, bz, px, py, pz, nx, ny, nz):
+    """((b - a) x (p - a)) . n >= 0: p is on the inner side of the triangle's edge a -> b."""
+    dx, dy, dz = bx - ax, by - ay, bz - az
+    vx, vy, vz = px - ax, py - ay, pz - az
+    cx, cy, cz = dy * vz - dz * vy, dz * vx - dx * vz, dx * vy - dy * vx
+    return (cx * nx + cy * ny) + cz * nz >= 0.0
+
+
+def _tri_cross(Py, Pz, Qy, Qz, y, z):
+    """One crossing of the projected edge P -> Q, its end points in canonical order (the smaller z first, then the smaller y)."""
+    if Qz < Pz or (Qz == Pz and Qy < Py):
+        Py, Pz, Qy, Qz = Qy, Qz, Py, Pz
+    du, dv, wu, wv = Qy - Py, Qz - Pz, y - Py, z - Pz
+    return ((Pz > z) != (Qz > z)) & (wu * dv < wv * du)
+
+
+def _tri_into(par, near, x, y, z, t9, tol, g):
+    """One triangle of a POLYHEDRON on the points (x, y, z), broadcastable to the bool arrays par and near, which are updated in place:
+    par ^= the ray towards +x crosses it, near |= the point is within tol of it; both only inside the triangle's box grown by g."""
+    ax, ay, az, bx, by, bz, cx, cy, cz = t9
+    tol2 = tol * tol
+    inyz = (((y >= min(ay, by, cy) - g) & (y <= max(ay, by, cy) + g)) & ((z >= min(az, bz, cz) - g) & (z <= max(az, bz, cz) + g)))
+    if not inyz.any():
+        return
+    e1x, e1y, e1z, e2x, e2y, e2z = bx - ax, by - ay, bz - az, cx - ax, cy - ay, cz - az
+    nx, ny, nz = e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x
+    nn = (nx * nx + ny * ny) + nz * nz
+    wx, wy, wz = x - ax, y - ay, z - az
+    s = (nx * wx + ny * wy) + nz * wz
+    if nx != 0.0:
+        proj = (_tri_cross(ay, az, by, bz, y, z) != _tri_cross(by, bz, cy, cz, y, z)) != _tri_cross(cy, cz, ay, az, y, z)
+        par ^= (proj & inyz) & ((s < 0.0) if nx > 0.0 else (s > 0.0))
+    inbox = inyz & ((x >= min(ax, bx, cx) - g) & (x <= max(ax, bx, cx) + g))
+    if not inbox.any():
+        return
+    c = (_tri_side(ax, ay, az, bx, by, bz, x, y, z, nx, ny, nz) & _tri_side(bx, by, bz, cx, cy, cz, x, y, z, nx, ny, nz) &
+         _tri_side(cx, cy, cz, ax, ay, az, x, y, z, nx, ny, nz))
+    ux, uy, uz, tx, ty, tz = x - bx, y - by, z - bz, x - cx, y - cy, z - cz
+    edge = (_seg_near(wx, wy, wz, ux, uy, uz, bx - ax, by - ay, bz - az, tol2) |
+            _seg_near(ux, uy, uz, tx, ty, tz, cx - bx, cy - by, cz - bz, tol2) |
+            _seg_near(tx, ty, tz, wx, wy, wz, ax - cx, ay - cy, az - cz, tol2))
+    near |= inbox & np.where(c, s * s <= tol2 * nn, edge)
 
 
 def _inside(r, verts, x, y, z, tol):
@@ -372,6 +466,25 @@ def _inside(r, verts, x, y, z, tol):
             b = [float(v) for v in V[min(e + 1, nv - 1)]]
             out = out | _seg_near(x - a[0], y - a[1], z - a[2], x - b[0], y - b[1], z - b[2],
                                   b[0] - a[0], b[1] - a[1], b[2] - a[2], re2)
+    elif ty == T_POLYHEDRON:
+        v0, nv = int(r["vert0"]), int(r["nvert"])
+        T = verts[v0:v0 + 3 * nv].reshape(nv // 3, 9)
+        g = 2.0 * tol
+        par = np.zeros(shape, bool)
+        near = np.zeros(shape, bool)
+        # a block of mesh lines (x, y, z each along its own axis): a triangle is evaluated on the rows and planes its gate holds only
+        rows = len(shape) == 3 and x.shape == (1, 1, shape[2]) and y.shape == (1, shape[1], 1) and z.shape == (shape[0], 1, 1)
+        for tr in range(T.shape[0]):
+            t9 = [float(v) for v in T[tr]]
+            if not rows:
+                _tri_into(par, near, x, y, z, t9, tol, g)
+                continue
+            js = np.flatnonzero((y.reshape(-1) >= min(t9[1], t9[4], t9[7]) - g) & (y.reshape(-1) <= max(t9[1], t9[4], t9[7]) + g))
+            ks = np.flatnonzero((z.reshape(-1) >= min(t9[2], t9[5], t9[8]) - g) & (z.reshape(-1) <= max(t9[2], t9[5], t9[8]) + g))
+            if js.size and ks.size:
+                sj, sk = slice(js[0], js[-1] + 1), slice(ks[0], ks[-1] + 1)
+                _tri_into(par[sk, sj], near[sk, sj], x, y[:, sj], z[sk], t9, tol, g)
+        out = (par | near) if metal else (par & ~near)
     else:
         raise ValueError(f"primitive type {ty}")
     return np.broadcast_to(out, shape)

@@ -66,6 +66,12 @@ class _Drawable:
     def add_lin_poly(self, points, norm_dir, elevation, length, priority=0):
         return self._add("LinPoly", priority, points=points, norm_dir=norm_dir, elevation=elevation, length=length)
 
+    def add_polyhedron(self, triangles, priority=0):
+        """A closed triangle mesh, triangles [ntri][3][3] in drawing units (stl.read_stl gives them)."""
+        if isinstance(self, ConductingSheet):
+            raise ValueError(f"conducting sheet '{self.name}': a polyhedron is for materials and plain metals (add_metal) only")
+        return self._add("Polyhedron", priority, triangles=triangles)
+
 
 @dataclass
 class Material(_Drawable):

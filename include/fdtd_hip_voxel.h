@@ -1,4 +1,4 @@
-/* fdtd_hip_voxel.h — rasterise CSXCAD primitives (boxes, spheres, cylinders, shells, polygons, wires) onto the Yee grid on the
+/* fdtd_hip_voxel.h — rasterise CSXCAD primitives (boxes, spheres, cylinders, shells, polygons, wires, triangle meshes) onto the Yee grid on the
  * device.  Exported by libfdtd_hip.so only; not part of fdtd_hip.h nor of FDTD_ABI_VERSION (as the other feature headers).
  *
  * The numpy rasteriser primitives.rasterise_spec is the specification; fdtd_voxelize gives the same owners bit for bit, because
@@ -36,7 +36,27 @@
  *   LINPOLY    p = lo, hi along n: pn >= p0 - t && pn <= p1 + t, and the polygon's test in the plane.
  *   WIRE       p = r; points (x, y, z) = verts[vert0 + 3 e ...], metals only: re = r + t; re2 = re re; any segment e from A to B
  *              (one point: A = B):  d = B - A; w = p - A; g = p - B; L, s, ww as for the cylinder; gg = (gx gx + gy gy) + gz gz;
- *                                 s <= 0 ? ww <= re2 : s >= L ? gg <= re2 : ww L - s s <= re2 L.
+ *                                 s <= 0 ? ww <= re2 : s >= L ? gg <= re2 : ww L - s s <= re2 L.   (this is seg_near(w, g, d, re2))
+ *   POLYHEDRON a CLOSED triangle mesh (every undirected edge used by an even number of triangles; facet normals and the order of a
+ *              triangle's corners do not matter); nvert = 3 ntri points, the triangle's corners A, B, C = verts[vert0 + 9 tr ...]
+ *              (x, y, z each); par unused.  A point is inside when the ray from it towards +x crosses an odd number of triangles.
+ *              With g = 2 tol, per triangle:
+ *                gate:  inyz = y >= min(Ay, By, Cy) - g && y <= max(...) + g && z >= min(Az, Bz, Cz) - g && z <= max(...) + g;
+ *                       a triangle whose gate a point fails neither crosses its ray nor is near it.
+ *                e1 = B - A; e2 = C - A; n = e1 x e2, each component a b - c d: nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z,
+ *                nz = e1x e2y - e1y e2x; nn = (nx nx + ny ny) + nz nz; w = p - A; s = (nx wx + ny wy) + nz wz.
+ *                projected hit: for each edge (A B, B C, C A) take its end points in CANONICAL order, a = the end with the smaller
+ *                       z, the smaller y on a tie (so both triangles of a shared edge evaluate the identical expression, and a ray
+ *                       through a shared edge or vertex is counted once):  du = by - ay; dv = bz - az; wu = y - ay; wv = z - az;
+ *                       crossing: (az > z) != (bz > z) && wu dv < wv du;  in_proj = the parity of the three crossings.
+ *                ray:   nx != 0 && inyz && in_proj && (nx > 0 ? s < 0 : s > 0)  -> parity ^= 1.
+ *                near (only inside the box: inyz && x >= min(Ax, Bx, Cx) - g && x <= max(...) + g):
+ *                       c_k = ((b - a) x (p - a)) . n >= 0 for the edges A->B, B->C, C->A in the triangle's own order, the cross
+ *                       product as above (d = b - a, v = p - a: dy vz - dz vy, dz vx - dx vz, dx vy - dy vx), the dot product
+ *                       (cx nx + cy ny) + cz nz;  all three: s s <= (tol tol) nn;  otherwise: seg_near(p - a, p - b, b - a, tol tol)
+ *                       of any of the three edges.
+ *              metal: parity || near (any triangle);  material: parity && !near.  A face exactly on a mesh plane is therefore
+ *              decided by `near` for a metal (its nodes are held) and by the half-open crossing rule for a material's cell centres.
  */
 #ifndef FDTD_HIP_VOXEL_H
 #define FDTD_HIP_VOXEL_H
@@ -48,12 +68,13 @@ extern "C" {
 #endif
 
 enum { FDTD_VOXEL_BOX = 0, FDTD_VOXEL_SPHERE, FDTD_VOXEL_SPHERICAL_SHELL, FDTD_VOXEL_CYLINDER, FDTD_VOXEL_CYLINDRICAL_SHELL,
-       FDTD_VOXEL_DISC, FDTD_VOXEL_POLYGON, FDTD_VOXEL_LINPOLY, FDTD_VOXEL_WIRE, FDTD_VOXEL_NTYPES };
+       FDTD_VOXEL_DISC, FDTD_VOXEL_POLYGON, FDTD_VOXEL_LINPOLY, FDTD_VOXEL_WIRE, FDTD_VOXEL_POLYHEDRON,
+       FDTD_VOXEL_NTYPES };
 enum { FDTD_VOXEL_MATERIAL = 0, FDTD_VOXEL_METAL = 1 };
 
 typedef struct fdtd_voxel_prim {
   int32_t type, role, prop, priority, order;   /* prop: index of the material / metal; order: drawing order (== record index) */
-  int32_t vert0, nvert;                        /* offset into verts (in doubles) and number of vertices / points */
+  int32_t vert0, nvert;                        /* offset into verts (in doubles) and number of vertices / points (3 per triangle) */
   int32_t norm_dir, has_matrix, pad;
   int32_t cbox[6], nbox[6];                    /* inclusive index boxes x0 y0 z0 x1 y1 z1 on the cell / node grid; x0 > x1: empty */
   double par[8];
@@ -62,8 +83,8 @@ typedef struct fdtd_voxel_prim {
 
 /* lines: the nx + ny + nz mesh lines in metres; table: nprim records; verts: nvert doubles.  cell_owner: int32 [nz-1][ny-1][nx-1],
  * edge_owner: int32 [3][nz][ny][nx], host pointers, either may be NULL (that pass is not run).  Returns FDTD_OK or a negative
- * FDTD_E_* code (message: fdtd_last_error(NULL)); index boxes are clipped to the grid, a record with an unknown type or vertices
- * outside verts is FDTD_E_ARG.  nprim == 0 and primitives outside the grid give owners of -1. */
+ * FDTD_E_* code (message: fdtd_last_error(NULL)); index boxes are clipped to the grid, a record with an unknown type, vertices
+ * outside verts or a polyhedron whose nvert is no multiple of 3 is FDTD_E_ARG.  nprim == 0 and primitives outside the grid give owners of -1. */
 int fdtd_voxelize(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
                   const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner);
 
