@@ -45,6 +45,9 @@ MAGNETIC_MAX_CLASSES = 255
 TRAFFIC_SYMBOLS = ["fdtd_traffic_info"]
 # include/fdtd_hip_voxel.h: primitives rasterised on the device, likewise
 VOXEL_SYMBOLS = ["fdtd_voxelize"]
+# include/fdtd_hip_voxel.h: voxel body models (disc materials) looked up on the device, likewise
+DISCMATERIAL_SYMBOLS = ["fdtd_voxelize_maps"]
+VOXEL_MAX_MAPS = 4
 # include/fdtd_hip_conformal.h: conformal PEC boundaries and the cut edges' fractions on the device, likewise
 CONFORMAL_SYMBOLS = ["fdtd_conformal_set", "fdtd_conformal_get", "fdtd_voxel_fractions"]
 # include/fdtd_hip_sar.h: local and mass-averaged SAR on the device, likewise
@@ -61,6 +64,12 @@ class FdtdDesc(C.Structure):
                 ("rank", C.c_int32), ("world", C.c_int32),
                 ("device", C.c_int32), ("max_steps", C.c_int32),
                 ("flags", C.c_uint32), ("dt", C.c_double)]
+
+
+class FdtdVoxelMap(C.Structure):
+    """struct fdtd_voxel_map (include/fdtd_hip_voxel.h), 152 bytes."""
+    _fields_ = [("m", C.c_double * 12), ("lines", C.c_void_p * 3), ("data", C.c_void_p), ("ndata", C.c_int64),
+                ("n", C.c_int32 * 3), ("use_db_background", C.c_int32)]
 
 
 class FdtdProfile(C.Structure):
@@ -197,6 +206,15 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    disc_sig = {
+        "fdtd_voxelize_maps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, C.c_int, p, C.c_int, p, C.c_double, p, p, p, C.c_int, p, p]),
+    }
+    assert sorted(disc_sig) == sorted(DISCMATERIAL_SYMBOLS)
+    for name, (res, args) in disc_sig.items():      # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     conformal_sig = {
         "fdtd_conformal_set": (C.c_int, [p, C.c_int, p, p, p]),
         "fdtd_conformal_get": (C.c_int, [p, p, p]),
@@ -247,6 +265,11 @@ def has_conformal(lib: C.CDLL) -> bool:
 def has_voxelize(lib: C.CDLL) -> bool:
     """Whether `lib` exports the device rasteriser (include/fdtd_hip_voxel.h)."""
     return all(hasattr(lib, n) for n in VOXEL_SYMBOLS)
+
+
+def has_discmaterial(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the device rasteriser with voxel maps (include/fdtd_hip_voxel.h: fdtd_voxelize_maps)."""
+    return all(hasattr(lib, n) for n in DISCMATERIAL_SYMBOLS)
 
 
 def has_traffic_info(lib: C.CDLL) -> bool:
@@ -873,6 +896,8 @@ def voxelize_raw(lib: C.CDLL, grid, table, device: int = 0, cells: bool = True, 
         raise ValueError("the table's records must be primitives.RECORD")
     cown = np.empty((nz - 1, ny - 1, nx - 1), np.int32) if cells else None
     eown = np.empty((3, nz, ny, nx), np.int32) if edges else None
+    if getattr(table, "maps", None):
+        return voxelize_maps_raw(lib, grid, table, device, cown, eown)
     rc = lib.fdtd_voxelize(int(device), nx, ny, nz, _ptr(lines), int(rec.size), _ptr(rec) if rec.size else None, int(verts.size),
                            _ptr(verts) if verts.size else None, float(table.tol), _ptr(cown), _ptr(eown))
     if rc != 0:
@@ -881,9 +906,56 @@ def voxelize_raw(lib: C.CDLL, grid, table, device: int = 0, cells: bool = True, 
     return cown, eown
 
 
+def voxelize_maps_raw(lib: C.CDLL, grid, table, device: int = 0, cown=None, eown=None, force: bool = False):
+    """fdtd_voxelize_maps on a primitives.Table: (cell_owner, edge_owner, cell_voxel) into the given arrays (None: that pass is not
+    run; cell_voxel is None without cell_owner).  `force`: call the entry point for a table without maps too (nmaps = 0)."""
+    if not has_discmaterial(lib):
+        raise FdtdError("this library has no device lookup of voxel maps (fdtd_voxelize_maps)")
+    nx, ny, nz = grid.shape
+    maps = list(getattr(table, "maps", None) or [])
+    if not maps and not force:
+        raise ValueError("the table has no voxel maps (fdtd_voxelize takes it)")
+    if len(maps) > VOXEL_MAX_MAPS:
+        raise ValueError(f"{len(maps)} voxel maps: at most {VOXEL_MAX_MAPS}")
+    lines = _arr(np.concatenate(grid.lines), np.float64)
+    rec = np.ascontiguousarray(table.rec)
+    verts = _arr(table.verts, np.float64)
+    if rec.dtype.itemsize != 248:
+        raise ValueError("the table's records must be primitives.RECORD")
+    rec_map = _arr(table.rec_map if maps else np.zeros(rec.size, np.int32), np.int32)
+    if rec_map.shape != (rec.size,):
+        raise ValueError("the table's rec_map must hold one int32 per record")
+    keep = []                                        # the arrays the structs point into
+    cmaps = (FdtdVoxelMap * max(len(maps), 1))()
+    for q, mp in enumerate(maps):
+        M, data = _arr(mp.M, np.float64).reshape(-1), _arr(mp.data, np.uint8).reshape(-1)
+        ml = [_arr(l, np.float64).reshape(-1) for l in mp.lines]
+        if M.size != 12 or len(ml) != 3:
+            raise ValueError("a voxel map needs M[12] and three line arrays")
+        keep += [M, data] + ml
+        cmaps[q].m[:] = M.tolist()
+        for a in range(3):
+            cmaps[q].lines[a] = ml[a].ctypes.data
+            cmaps[q].n[a] = ml[a].size
+        cmaps[q].data, cmaps[q].ndata, cmaps[q].use_db_background = data.ctypes.data, data.size, int(bool(mp.use_db_background))
+    cvox = np.empty((nz - 1, ny - 1, nx - 1), np.int32) if cown is not None else None
+    rc = lib.fdtd_voxelize_maps(int(device), nx, ny, nz, _ptr(lines), int(rec.size), _ptr(rec) if rec.size else None, int(verts.size),
+                                _ptr(verts) if verts.size else None, float(table.tol), _ptr(cown), _ptr(eown),
+                                _ptr(rec_map) if rec.size else None, len(maps), C.cast(cmaps, C.c_void_p) if maps else None, _ptr(cvox))
+    del keep
+    if rc != 0:
+        msg = lib.fdtd_last_error(None)
+        raise FdtdError(f"fdtd_voxelize_maps failed ({rc}): {msg.decode() if msg else ''}")
+    return cown, eown, cvox
+
+
 def voxelize_device(lib: C.CDLL, device: int = 0):
-    """A `rasteriser` for scene.voxelize(scene, grid, rasteriser): primitives.rasterise_spec's result, computed by csrc/voxel.hip."""
+    """A `rasteriser` for scene.voxelize(scene, grid, rasteriser): primitives.rasterise_spec's result, computed by csrc/voxel.hip.  A
+    table with voxel maps takes fdtd_voxelize_maps where `lib` exports it, else the specification."""
     def rasteriser(grid, table):
+        if getattr(table, "maps", None) and not has_discmaterial(lib):
+            from . import primitives as _prims
+            return _prims.rasterise_spec(grid, table)
         return voxelize_raw(lib, grid, table, device)
     return rasteriser
 

@@ -5,6 +5,7 @@
 // and single writer, starting from the owners the first launch stored), so the registers of the first stay sized by the analytic
 // types; a table without a mesh launches what it always did.  float64 throughout, in the operation order the header spells (primitives._inside is the same text in numpy;
 // -ffp-contract=off keeps the compiler from fusing), so the owners are those of primitives.rasterise_spec bit for bit.
+// Records that delimit a voxel map (fdtd_voxelize_maps) take a third launch, k_voxel_map below, which merges them into those owners.
 //
 // A block of 256 threads owns a tile of one z-plane: VX_TY rows of VX_TX threads, four consecutive x points per thread.  The table
 // is staged through LDS in chunks of VX_CHUNK records; a record whose index box misses the block's tile is skipped before any
@@ -509,6 +510,141 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel(const VoxArgs a) {
     }
   }
 }
+// ---- voxel maps (include/fdtd_hip_voxel.h: fdtd_voxelize_maps; discmaterial.lookup_spec is the same text in numpy) ---------------------
+// One further launch over the records that delimit a voxel map, on k_voxel's tile and point map: it starts from the owners the earlier
+// launches stored (as the polyhedron launch does, vx_wins<true>), tests the record's own predicate through vx_test, and for a cell the
+// record would win looks its centre up in the map: three binary searches, every result range-checked, the linear index in 64 bits,
+// one byte load.  Nothing is indexed by the byte.  Owner and voxel index have one writer each and are always written.
+struct VxMapDev {
+  double m[12];
+  const double* lines[3];
+  const uint8_t* data;
+  int n[3];
+  int use_bg;
+};
+struct MapArgs {
+  VoxArgs v;                  // table: every record with its own index box; out: the owners of the earlier launches
+  const int32_t* rec_map;     // per record: 0 none, m + 1
+  const VxMapDev* maps;
+  int32_t* vox;               // [nz-1][ny-1][nx-1]
+};
+
+// (the number of t with L[t] <= q) - 1 over the n increasing lines L: -1 .. n - 1; a NaN compares false everywhere: -1
+__device__ __forceinline__ int vx_line_index(const double* __restrict__ L, const int n, const double q) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;                                  // 0 <= mid <= n - 1
+    if (L[mid] <= q) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+__global__ __launch_bounds__(VX_BLOCK) void k_voxel_map(const MapArgs ma) {
+  using M = PtMap<PASS_CELL>;
+  constexpr int N = M::N;
+  const VoxArgs& a = ma.v;
+  __shared__ unsigned long long s_tab[VX_CHUNK * VX_WORDS];
+  __shared__ int s_map[VX_CHUNK];
+
+  const int px = a.nx - 1, py = a.ny - 1;
+  const int tx = threadIdx.x % VX_TX, ty = threadIdx.x / VX_TX;
+  const int bx0 = blockIdx.x * (VX_TX * VX_PTS), by0 = blockIdx.y * VX_TY, k = blockIdx.z;   // k < nz - 1: the grid's z extent
+  const int i0 = bx0 + tx * VX_PTS, j = by0 + ty;
+  const int tx1 = min(bx0 + VX_TX * VX_PTS - 1, px - 1), ty1 = min(by0 + VX_TY - 1, py - 1);
+
+  // cell centres (indices clamped to the grid: a clamped point is never inside an index box at its own index)
+  const double* lx = a.lines;
+  const double* ly = a.lines + a.nx;
+  const double* lz = a.lines + a.nx + a.ny;
+  double wx[N], wy[N], wz[N];
+  {
+    const int jj = min(j, py - 1);
+    const double yc = 0.5 * (ly[jj] + ly[jj + 1]), zc = 0.5 * (lz[k] + lz[k + 1]);
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      const int i = min(i0 + q, px - 1);
+      wx[q] = 0.5 * (lx[i] + lx[i + 1]); wy[q] = yc; wz[q] = zc;
+    }
+  }
+  const bool live = j < py && i0 < px;
+  const size_t row = ((size_t)k * (size_t)py + (size_t)min(j, py - 1)) * (size_t)px + (size_t)min(i0, px - 1);
+  int best[VX_PTS], own[VX_PTS], vox[VX_PTS];
+#pragma unroll
+  for (int q = 0; q < VX_PTS; ++q) {
+    best[q] = INT32_MIN; own[q] = -1; vox[q] = -1;
+    if (live && i0 + q < px) {
+      own[q] = a.out[row + q];
+      best[q] = own[q] >= 0 ? a.table[own[q]].priority : INT32_MIN;
+    }
+  }
+
+  for (int c0 = 0; c0 < a.nprim; c0 += VX_CHUNK) {
+    const int cn = min(VX_CHUNK, a.nprim - c0);
+    __syncthreads();                                              // the previous chunk is no longer read
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(a.table + c0);
+    for (int w = threadIdx.x; w < cn * VX_WORDS; w += VX_BLOCK) s_tab[w] = src[w];
+    if ((int)threadIdx.x < cn) s_map[threadIdx.x] = ma.rec_map[c0 + threadIdx.x];
+    __syncthreads();
+    for (int p = 0; p < cn; ++p) {
+      const int mi = __builtin_amdgcn_readfirstlane(s_map[p]);
+      if (mi == 0) continue;                                      // the earlier launches took this record
+      const fdtd_voxel_prim* r = reinterpret_cast<const fdtd_voxel_prim*>(s_tab + p * VX_WORDS);
+      const int b0 = __builtin_amdgcn_readfirstlane(r->cbox[0]), b1 = __builtin_amdgcn_readfirstlane(r->cbox[1]);
+      const int b2 = __builtin_amdgcn_readfirstlane(r->cbox[2]), b3 = __builtin_amdgcn_readfirstlane(r->cbox[3]);
+      const int b4 = __builtin_amdgcn_readfirstlane(r->cbox[4]), b5 = __builtin_amdgcn_readfirstlane(r->cbox[5]);
+      if (b3 < bx0 || b0 > tx1 || b4 < by0 || b1 > ty1 || b5 < k || b2 > k) continue;     // misses the tile: block-uniform
+      const int type = __builtin_amdgcn_readfirstlane(r->type);
+      const int prio = __builtin_amdgcn_readfirstlane(r->priority);
+      const int norm_dir = __builtin_amdgcn_readfirstlane(r->norm_dir);
+      const int vert0 = __builtin_amdgcn_readfirstlane(r->vert0), nvert = __builtin_amdgcn_readfirstlane(r->nvert);
+      const bool has_matrix = __builtin_amdgcn_readfirstlane(r->has_matrix) != 0;
+      const int idx = c0 + p;
+      unsigned gate = 0u;
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const int i = i0 + q;
+        const bool g = i >= b0 && i <= b3 && j >= b1 && j <= b4 && k >= b2 && k <= b5 && vx_wins<true>(prio, idx, best[q], own[q]);
+        gate |= (g ? 1u : 0u) << q;                               // a cell the record cannot win needs neither test
+      }
+      const unsigned in = vx_test<N, false>(r, type, false, norm_dir, vert0, nvert, has_matrix, a.verts, a.tol, wx, wy, wz, gate);
+      if (in == 0u) continue;
+      const VxMapDev* mp = ma.maps + (mi - 1);                    // host: 1 <= mi <= nmaps
+      const double m0 = mp->m[0], m1 = mp->m[1], m2 = mp->m[2], m3 = mp->m[3], m4 = mp->m[4], m5 = mp->m[5], m6 = mp->m[6], m7 = mp->m[7],
+                   m8 = mp->m[8], m9 = mp->m[9], m10 = mp->m[10], m11 = mp->m[11];
+      const int n0 = mp->n[0], n1 = mp->n[1], n2 = mp->n[2];
+      const bool bg = mp->use_bg != 0;
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        if (!((in >> q) & 1u)) continue;
+        const double qx = ((m0 * wx[q] + m1 * wy[q]) + m2 * wz[q]) + m3;
+        const double qy = ((m4 * wx[q] + m5 * wy[q]) + m6 * wz[q]) + m7;
+        const double qz = ((m8 * wx[q] + m9 * wy[q]) + m10 * wz[q]) + m11;
+        const int ix = vx_line_index(mp->lines[0], n0, qx);
+        if (ix < 0 || ix > n0 - 2) continue;
+        const int iy = vx_line_index(mp->lines[1], n1, qy);
+        if (iy < 0 || iy > n1 - 2) continue;
+        const int iz = vx_line_index(mp->lines[2], n2, qz);
+        if (iz < 0 || iz > n2 - 2) continue;
+        const long long lin = ((long long)iz * (long long)(n1 - 1) + (long long)iy) * (long long)(n0 - 1) + (long long)ix;
+        const uint8_t v = mp->data[lin];                          // 0 <= lin < (n0-1)(n1-1)(n2-1) == the data's length (host) <= 2^31 - 1
+        if (v == 0 && !bg) continue;                              // the background voxel is transparent
+        best[q] = prio; own[q] = idx; vox[q] = (int)lin;
+      }
+    }
+  }
+
+  if (!live) return;
+  const bool wide = px % 4 == 0;                                  // block-uniform; i0 and then row are multiples of 4 (hipMalloc aligns the base)
+  if (wide) {
+    *reinterpret_cast<int4*>(a.out + row) = make_int4(own[0], own[1], own[2], own[3]);
+    *reinterpret_cast<int4*>(ma.vox + row) = make_int4(vox[0], vox[1], vox[2], vox[3]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < VX_PTS; ++q)
+      if (i0 + q < px) { a.out[row + q] = own[q]; ma.vox[row + q] = vox[q]; }
+  }
+}
+
 // ---- conformal fractions (include/fdtd_hip_conformal.h, conformal.fractions_spec) -----------------------------------------------
 // Both kernels call vx_test<1> on the records in global memory: the inside predicates are the rasteriser's own text, so a node's
 // or a bisection point's verdict has the bits of primitives._inside.  A cut edge costs nbisect * (records whose node box holds one
@@ -612,11 +748,37 @@ int vx_check_table(int nx, int ny, int nz, int nprim, const void* table, int nve
   }
   return FDTD_OK;
 }
+
+// The host part of fdtd_voxelize_maps: rec_map and the maps themselves.  After it no lookup can leave a map's lines or data.
+int vx_check_maps(int nprim, const fdtd_voxel_prim* tab, const int32_t* rec_map, int nmaps, const fdtd_voxel_map* maps) {
+  if (nmaps < 0 || nmaps > FDTD_VOXEL_MAX_MAPS || (nmaps > 0 && (!maps || (nprim > 0 && !rec_map))))
+    return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: %d voxel maps (0..%d, with rec_map and maps)", nmaps, (int)FDTD_VOXEL_MAX_MAPS);
+  for (int m = 0; m < nmaps; ++m) {
+    const fdtd_voxel_map& v = maps[m];
+    long long nvox = 1;
+    for (int ax = 0; ax < 3; ++ax) {
+      if (v.n[ax] < 2 || !v.lines[ax]) return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: map %d has %d lines on axis %d (>= 2)", m, v.n[ax], ax);
+      for (int t = 1; t < v.n[ax]; ++t)
+        if (!(v.lines[ax][t] > v.lines[ax][t - 1])) return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: map %d: the lines of axis %d do not increase at %d", m, ax, t);
+      nvox *= (long long)(v.n[ax] - 1);                           // each factor < 2^31: checked after every product
+      if (nvox > (long long)INT32_MAX) return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: map %d has more than 2^31 - 1 voxels", m);
+    }
+    if (!v.data || (long long)v.ndata != nvox)
+      return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: map %d: data of %lld bytes for %lld voxels", m, (long long)v.ndata, nvox);
+  }
+  for (int p = 0; p < nprim && nmaps > 0; ++p) {
+    if (rec_map[p] < 0 || rec_map[p] > nmaps) return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d refers to map %d of %d", p, rec_map[p], nmaps);
+    if (rec_map[p] != 0 && (tab[p].role != FDTD_VOXEL_MATERIAL || tab[p].type == FDTD_VOXEL_POLYHEDRON))
+      return fdtd_fail(nullptr, FDTD_E_ARG, "voxelize: record %d delimits a voxel map: a material that is no polyhedron expected", p);
+  }
+  return FDTD_OK;
+}
 }  // namespace
 
-extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
-                             const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner) {
-  if (!lines || (nvert > 0 && !verts) || !(tol >= 0.0)) return fdtd_fail(nullptr, FDTD_E_ARG, "bad voxelize argument");
+static int vx_run(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert, const double* verts,
+                  double tol, int32_t* cell_owner, int32_t* edge_owner, const int32_t* rec_map, int nmaps, const fdtd_voxel_map* maps,
+                  int32_t* cell_voxel) {
+  if (!lines || (nvert > 0 && !verts) || !(tol >= 0.0) || (cell_voxel && !cell_owner)) return fdtd_fail(nullptr, FDTD_E_ARG, "bad voxelize argument");
   std::vector<fdtd_voxel_prim> tab;
   try {
     tab.resize((size_t)(nprim > 0 ? nprim : 0));
@@ -625,7 +787,25 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
   }
   int rc = vx_check_table(nx, ny, nz, nprim, table, nvert, tab.data());
   if (rc != FDTD_OK) return rc;
+  rc = vx_check_maps(nprim, tab.data(), rec_map, nmaps, maps);
+  if (rc != FDTD_OK) return rc;
   const size_t ncell = (size_t)(nx - 1) * (size_t)(ny - 1) * (size_t)(nz - 1), nedge = 3 * (size_t)nx * (size_t)ny * (size_t)nz;
+  // The records that delimit a voxel map leave the launches below (an empty index box misses every tile) and take k_voxel_map, which
+  // reads them from `full`.
+  std::vector<fdtd_voxel_prim> full;
+  bool mapped = false;
+  for (int p = 0; p < nprim && nmaps > 0; ++p) mapped = mapped || rec_map[p] != 0;
+  if (mapped) {
+    try {
+      full = tab;
+    } catch (...) {
+      return fdtd_fail(nullptr, FDTD_E_NOMEM, "voxelize: no host memory for %d records", nprim);
+    }
+    const int32_t none[6] = {0, 0, 0, -1, -1, -1};
+    for (int p = 0; p < nprim; ++p)
+      if (rec_map[p] != 0) memcpy(tab[p].cbox, none, sizeof(none));
+  }
+  if (cell_voxel && !mapped) for (size_t q = 0; q < ncell; ++q) cell_voxel[q] = -1;
   if (nprim == 0) {                                               // nothing drawn: no device work
     if (cell_owner) for (size_t q = 0; q < ncell; ++q) cell_owner[q] = -1;
     if (edge_owner) for (size_t q = 0; q < nedge; ++q) edge_owner[q] = -1;
@@ -636,6 +816,13 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
   double *d_lines = nullptr, *d_verts = nullptr;
   fdtd_voxel_prim* d_tab = nullptr;
   int32_t *d_cell = nullptr, *d_edge = nullptr;
+  // voxel maps (cell pass with mapped records only): the full table, rec_map, the maps' descriptors, per map its lines and voxels
+  const bool run_maps = mapped && cell_owner;
+  fdtd_voxel_prim* d_full = nullptr;
+  int32_t *d_recmap = nullptr, *d_vox = nullptr;
+  VxMapDev* d_maps = nullptr;
+  double* d_mlines[FDTD_VOXEL_MAX_MAPS] = {nullptr, nullptr, nullptr, nullptr};
+  uint8_t* d_mdata[FDTD_VOXEL_MAX_MAPS] = {nullptr, nullptr, nullptr, nullptr};
   const size_t nl = (size_t)nx + (size_t)ny + (size_t)nz;
 #define VX(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess && rc == FDTD_OK) rc = fdtd_fail(nullptr, e_ == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
   VX(hipMalloc(&d_lines, nl * sizeof(double)));
@@ -643,10 +830,40 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
   VX(hipMalloc(&d_tab, (size_t)nprim * sizeof(fdtd_voxel_prim)));
   if (cell_owner) VX(hipMalloc(&d_cell, ncell * sizeof(int32_t)));
   if (edge_owner) VX(hipMalloc(&d_edge, nedge * sizeof(int32_t)));
+  if (run_maps) {
+    VX(hipMalloc(&d_full, (size_t)nprim * sizeof(fdtd_voxel_prim)));
+    VX(hipMalloc(&d_recmap, (size_t)nprim * sizeof(int32_t)));
+    VX(hipMalloc(&d_maps, (size_t)nmaps * sizeof(VxMapDev)));
+    VX(hipMalloc(&d_vox, ncell * sizeof(int32_t)));
+    for (int m = 0; m < nmaps; ++m) {
+      VX(hipMalloc(&d_mlines[m], ((size_t)maps[m].n[0] + (size_t)maps[m].n[1] + (size_t)maps[m].n[2]) * sizeof(double)));
+      VX(hipMalloc(&d_mdata[m], (size_t)maps[m].ndata));
+    }
+  }
   if (rc == FDTD_OK) {
     VX(hipMemcpy(d_lines, lines, nl * sizeof(double), hipMemcpyHostToDevice));
     if (nvert > 0) VX(hipMemcpy(d_verts, verts, (size_t)nvert * sizeof(double), hipMemcpyHostToDevice));
     VX(hipMemcpy(d_tab, tab.data(), (size_t)nprim * sizeof(fdtd_voxel_prim), hipMemcpyHostToDevice));
+  }
+  if (rc == FDTD_OK && run_maps) {
+    VxMapDev dev[FDTD_VOXEL_MAX_MAPS];
+    for (int m = 0; m < nmaps; ++m) {
+      const fdtd_voxel_map& v = maps[m];
+      memcpy(dev[m].m, v.m, sizeof(v.m));
+      size_t off = 0;
+      for (int ax = 0; ax < 3; ++ax) {
+        VX(hipMemcpy(d_mlines[m] + off, v.lines[ax], (size_t)v.n[ax] * sizeof(double), hipMemcpyHostToDevice));
+        dev[m].lines[ax] = d_mlines[m] + off;
+        dev[m].n[ax] = v.n[ax];
+        off += (size_t)v.n[ax];
+      }
+      VX(hipMemcpy(d_mdata[m], v.data, (size_t)v.ndata, hipMemcpyHostToDevice));
+      dev[m].data = d_mdata[m];
+      dev[m].use_bg = v.use_db_background != 0 ? 1 : 0;
+    }
+    VX(hipMemcpy(d_maps, dev, (size_t)nmaps * sizeof(VxMapDev), hipMemcpyHostToDevice));
+    VX(hipMemcpy(d_full, full.data(), (size_t)nprim * sizeof(fdtd_voxel_prim), hipMemcpyHostToDevice));
+    VX(hipMemcpy(d_recmap, rec_map, (size_t)nprim * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if (rc == FDTD_OK) {
     VoxArgs a{nx, ny, nz, d_lines, nprim, d_tab, d_verts, tol, nullptr};
@@ -659,6 +876,11 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
       hipLaunchKernelGGL(k_voxel<PASS_CELL>, dim3((nx - 1 + per_x - 1) / per_x, (ny - 1 + VX_TY - 1) / VX_TY, nz - 1), dim3(VX_BLOCK), 0, 0, a);
       if (mesh[0])
         hipLaunchKernelGGL((k_voxel<PASS_CELL, true>), dim3((nx - 1 + per_x - 1) / per_x, (ny - 1 + VX_TY - 1) / VX_TY, nz - 1), dim3(VX_BLOCK), 0, 0, a);
+      if (run_maps) {                                             // same stream: after the owners of the launches above are stored
+        MapArgs ma{a, d_recmap, d_maps, d_vox};
+        ma.v.table = d_full;
+        hipLaunchKernelGGL(k_voxel_map, dim3((nx - 1 + per_x - 1) / per_x, (ny - 1 + VX_TY - 1) / VX_TY, nz - 1), dim3(VX_BLOCK), 0, 0, ma);
+      }
       VX(hipGetLastError());
     }
     if (edge_owner) {
@@ -671,10 +893,22 @@ extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* l
     VX(hipDeviceSynchronize());
     if (rc == FDTD_OK && cell_owner) VX(hipMemcpy(cell_owner, d_cell, ncell * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (rc == FDTD_OK && edge_owner) VX(hipMemcpy(edge_owner, d_edge, nedge * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (rc == FDTD_OK && run_maps && cell_voxel) VX(hipMemcpy(cell_voxel, d_vox, ncell * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
 #undef VX
   hipFree(d_lines); hipFree(d_verts); hipFree(d_tab); hipFree(d_cell); hipFree(d_edge);
+  hipFree(d_full); hipFree(d_recmap); hipFree(d_maps); hipFree(d_vox);
+  for (int m = 0; m < FDTD_VOXEL_MAX_MAPS; ++m) { hipFree(d_mlines[m]); hipFree(d_mdata[m]); }
   return rc;
+}
+extern "C" int fdtd_voxelize(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
+                             const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner) {
+  return vx_run(device, nx, ny, nz, lines, nprim, table, nvert, verts, tol, cell_owner, edge_owner, nullptr, 0, nullptr, nullptr);
+}
+extern "C" int fdtd_voxelize_maps(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
+                                  const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner, const int32_t* rec_map, int nmaps,
+                                  const fdtd_voxel_map* maps, int32_t* cell_voxel) {
+  return vx_run(device, nx, ny, nz, lines, nprim, table, nvert, verts, tol, cell_owner, edge_owner, rec_map, nmaps, maps, cell_voxel);
 }
 extern "C" int fdtd_voxel_fractions(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
                                     const double* verts, double tol, double snap, int nbisect, uint8_t* node_in, int64_t ncut,

@@ -314,6 +314,26 @@ class CSProperty:
         self._out_of_scope("AddMultiBox")
 
 
+class CSPropDiscMaterial(CSProperty):
+    """What ContinuousStructure.AddDiscMaterial returns: a voxel body model (discmaterial.py); AddBox (with or without AddTransform)
+    and the analytic solids delimit it, a polyhedron does not."""
+
+    def __init__(self, log: _CallLog, name: str, vmap, filename):
+        super().__init__(log, "DiscMaterial", name, filename=filename, scale=vmap.scale,
+                         transform=None if vmap.matrix is None else vmap.matrix, use_db_background=vmap.use_db_background,
+                         voxels=list(vmap.shape), db_size=vmap.db_size)
+        self.vmap = vmap
+
+    def _add(self, kind, priority, **kw):
+        if kind in ("Polygon",):
+            raise ValueError(f"Add{kind} on disc material '{self.name}': a flat polygon holds no cell")
+        return super()._add(kind, priority, **kw)
+
+    def AddPolyhedronReader(self, filename, priority=0, **kw):
+        raise ValueError(f"AddPolyhedronReader on disc material '{self.name}': a polyhedron cannot delimit a voxel map (boxes and the "
+                         f"analytic solids can)")
+
+
 class CSExcitation(CSProperty):
     """What ContinuousStructure.AddExcitation returns: a plane wave (excitation type 10) on the box given with AddBox."""
 
@@ -447,6 +467,42 @@ class ContinuousStructure:
         self.properties.append(p)
         return p
 
+    def AddDiscMaterial(self, name, filename=None, scale=1.0, transform=None, use_db_background=False, **kw):
+        """CSXCAD's discrete material (CSPropDiscMaterial): a segmented voxel phantom.  ``filename``: an .npz holding upstream's dataset
+        names mesh_x, mesh_y, mesh_z, DiscData ([nz-1][ny-1][nx-1] uint8), epsR, kappa, density (optionally mueR and sigma, which must
+        be 1 / 0) — an .h5 / .hdf5 file is refused (no HDF5 reader here; discmaterial.save_npz writes the .npz).  Without a file the
+        same names are taken as keywords.  ``scale`` multiplies the map's mesh lines; ``transform``: a 4x4 matrix (map -> drawing
+        coordinates) or a list of ["Translate", [..]] / ["RotateAxis", axis, degrees] steps; ``use_db_background``: voxels of index 0
+        take table entry 0 instead of being transparent.  AddBox on the returned property delimits the phantom."""
+        from . import discmaterial as _disc
+        M = None
+        if transform is not None:
+            steps = not isinstance(transform, np.ndarray) and len(transform) > 0 and isinstance(transform[0][0], str)
+            if not steps:
+                M = np.asarray(transform, float)
+            else:
+                t = _CSPrimitive({}, 0)
+                for step in transform:
+                    t.AddTransform(step[0], *step[1:])
+                M = t.matrix
+        if filename is not None:
+            if kw:
+                raise TypeError(f"AddDiscMaterial '{name}': unknown keyword(s) {sorted(kw)} (a file was given)")
+            vmap = _disc.load_npz(filename, name, scale, M, use_db_background)
+        else:
+            missing = [k for k in _disc.NPZ_KEYS if k not in kw]
+            extra = sorted(set(kw) - set(_disc.NPZ_KEYS) - {"mueR", "sigma"})
+            if missing or extra:
+                raise TypeError(f"AddDiscMaterial '{name}': without a file the keywords {', '.join(_disc.NPZ_KEYS)} are needed"
+                                + (f"; missing {missing}" if missing else "") + (f"; unknown {extra}" if extra else ""))
+            vmap = _disc.make_map(name, (kw["mesh_x"], kw["mesh_y"], kw["mesh_z"]), kw["DiscData"], kw["epsR"], kw["kappa"], kw["density"],
+                                  scale, M, use_db_background, mue_r=kw.get("mueR"), sigma=kw.get("sigma"))
+        if sum(q.kind == "DiscMaterial" for q in self.properties) >= _disc.MAX_MAPS:
+            raise ValueError(f"AddDiscMaterial '{name}': a structure takes at most {_disc.MAX_MAPS} voxel maps")
+        p = CSPropDiscMaterial(self._log, name, vmap, None if filename is None else os.fspath(filename))
+        self.properties.append(p)
+        return p
+
     def AddExcitation(self, name, exc_type, exc_val, delay=0):
         """CSXCAD's excitation property, for the plane wave only: ``exc_type`` 10 with ``exc_val`` = E0 [V/m]; ``SetPropagationDir``
         and one ``AddBox`` on the returned property give the direction and the total-field box (planewave.py).  The field
@@ -491,6 +547,25 @@ class ContinuousStructure:
 # ---------------------------------------------------------------------------------------------------
 # openEMS side
 # ---------------------------------------------------------------------------------------------------
+def _disc_summary(scene, grid, vox) -> dict:
+    """Per voxel map of the scene, for the run dump: the cells it owns, and per tissue index how many of them and their mass
+    [kg] (the sum of density x cell volume)."""
+    out = {}
+    dx, dy, dz = (np.diff(l) for l in grid.lines)
+    vol = dz[:, None, None] * dy[None, :, None] * dx[None, None, :]
+    for qi, m in enumerate(scene.materials):
+        vmap = getattr(m, "vmap", None)
+        if vmap is None:
+            continue
+        sel = (vox.cell_material == qi) & (vox.cell_voxel >= 0)
+        tissue = vmap.data.reshape(-1)[vox.cell_voxel[sel]]
+        cells = np.bincount(tissue, minlength=vmap.db_size)
+        mass = np.bincount(tissue, weights=vmap.density[tissue] * vol[sel], minlength=vmap.db_size)
+        out[m.name] = {"voxels": list(vmap.shape), "db_size": vmap.db_size, "use_db_background": bool(vmap.use_db_background),
+                       "cells_owned": int(sel.sum()), "cells_per_index": cells.tolist(), "mass_kg_per_index": mass.tolist()}
+    return out
+
+
 class UIData:
     def __init__(self, t, val):
         self.ui_time = [np.asarray(t)]
@@ -729,6 +804,10 @@ class openEMS:
                     m.medium.fit_info = getattr(p, "fit_info", None)
                 for b in p.boxes:
                     self._draw(m, b)
+            elif p.kind == "DiscMaterial":
+                m = sc.add_voxel_map(p.vmap)
+                for b in p.boxes:
+                    self._draw(m, b)
             elif p.kind == "Excitation":
                 if p.params["prop_dir"] is None:
                     raise ValueError(f"excitation '{p.name}': a plane wave needs its direction (SetPropagationDir)")
@@ -836,7 +915,8 @@ class openEMS:
                                "halo_transport": getattr(self._comm, "transport_used", None),
                                "halo_transports_failed": list(self.stats.transports_failed),
                                "schedule_fallback": self.stats.schedule_fallback,
-                               **({"sar": self.stats.sar} if self.stats.sar else {})}, fh)
+                               **({"sar": self.stats.sar} if self.stats.sar else {}),
+                               **({"disc_materials": _disc_summary(sc, grid, vox)} if vox.cell_voxel is not None else {})}, fh)
                 # a plane wave: the excitation signal as upstream's two-column `et` file (time, value), which its RCS post-processing
                 # reads for the incident spectrum (P_rad of CalcNF2FF over the spectrum of et)
                 if self.sim.plane_wave is not None:

@@ -19,6 +19,8 @@ from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 import numpy as np
 
+from . import discmaterial as _disc
+
 T_BOX, T_SPHERE, T_SPHERICAL_SHELL, T_CYLINDER, T_CYLINDRICAL_SHELL, T_DISC, T_POLYGON, T_LINPOLY, T_WIRE = range(9)
 N_TYPES = 9                # the analytic types above; the triangle mesh is appended after them
 T_POLYHEDRON = 9
@@ -152,8 +154,10 @@ def make(kind: str, priority=0, **kw) -> _Prim:
 
 
 def has_new(scene) -> bool:
-    """Whether the scene draws anything but boxes (then every primitive, boxes included, goes through the owner arrays)."""
-    return any(isinstance(p, NEW_TYPES) for prop in list(scene.materials) + list(scene.metals) for p in prop.boxes)
+    """Whether the scene draws anything but boxes, or has a disc material (then every primitive, boxes included, goes through the
+    owner arrays)."""
+    return (any(isinstance(p, NEW_TYPES) for prop in list(scene.materials) + list(scene.metals) for p in prop.boxes) or
+            any(getattr(m, "vmap", None) is not None for m in scene.materials))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -166,6 +170,19 @@ class Table:
     tol: float
     curves: List[tuple] = field(default_factory=list)     # (metal index, points [N][3] in world metres) of curves and wires
     names: List[str] = field(default_factory=list)        # per record: "<property>: <type>" for messages
+    # voxel maps (discmaterial.py): rec_map int32 per record (0: none, m + 1: the record is a delimiter of maps[m]); None: no maps
+    rec_map: Optional[np.ndarray] = None
+    maps: List["PackedMap"] = field(default_factory=list)
+
+
+@dataclass
+class PackedMap:
+    """One voxel map as both rasterisers read it: M the 3 x 4 world (metres) -> map coordinates, the map's lines, its voxels (flat,
+    x fastest) and its background flag."""
+    M: np.ndarray
+    lines: Tuple[np.ndarray, np.ndarray, np.ndarray]
+    data: np.ndarray
+    use_db_background: bool
 
 
 def _world_inverse(matrix, u):
@@ -219,11 +236,20 @@ def pack_table(scene, grid) -> Table:
     tol = _tol(grid)
     centers = [grid.centers(a) for a in range(3)]
     recs, verts, curves, names = [], [], [], []
+    rec_map, maps = [], []
     nvert = 0
     for role, props in ((ROLE_MATERIAL, scene.materials), (ROLE_METAL, scene.metals)):
         for qi, prop in enumerate(props):
+            vmap = getattr(prop, "vmap", None) if role == ROLE_MATERIAL else None
+            if vmap is not None:
+                if len(maps) == _disc.MAX_MAPS:
+                    raise ValueError(f"disc material '{prop.name}': a scene takes at most {_disc.MAX_MAPS} voxel maps")
+                maps.append(PackedMap(vmap.world_to_map(u), vmap.lines, np.ascontiguousarray(vmap.data.reshape(-1)),
+                                      bool(vmap.use_db_background)))
             for pr in prop.boxes:
                 Minv, M = _world_inverse(pr.matrix, u)
+                if vmap is not None and isinstance(pr, Polyhedron):
+                    raise ValueError(f"disc material '{prop.name}': a polyhedron cannot delimit a voxel map (boxes and the analytic solids can)")
                 if isinstance(pr, Polyhedron) and isinstance(prop, ConductingSheet):
                     raise ValueError(f"'{prop.name}': Polyhedron is for materials and plain metals (AddMetal) only")
                 if isinstance(pr, Curve):
@@ -307,10 +333,12 @@ def pack_table(scene, grid) -> Table:
                 r["cbox"] = _index_box(centers, lo, hi, pad)
                 r["nbox"] = _index_box(grid.lines, lo, hi, pad)
                 recs.append(r)
+                rec_map.append(len(maps) if vmap is not None else 0)
                 names.append(f"{prop.name}: {type(pr).__name__}")
     rec = np.array(recs, RECORD) if recs else np.zeros(0, RECORD)
     v = np.concatenate(verts) if verts else np.zeros(0)
-    return Table(np.ascontiguousarray(rec), np.ascontiguousarray(v, np.float64), float(tol), curves, names)
+    return Table(np.ascontiguousarray(rec), np.ascontiguousarray(v, np.float64), float(tol), curves, names,
+                 np.array(rec_map, np.int32) if maps else None, maps)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -525,12 +553,19 @@ def _edges_of(node, c):
 
 def rasterise_spec(grid, table: Table, cells: bool = True, edges: bool = True):
     """(cell_owner int32 [nz-1][ny-1][nx-1], edge_owner int32 [3][nz][ny][nx]): the index of the owning record, -1 for none
-    (None for a pass that was not asked for).  THE specification."""
+    (None for a pass that was not asked for).  THE specification.
+    A table with voxel maps (table.maps) gives a third result, cell_voxel int32 [nz-1][ny-1][nx-1]: a record that refers to a map
+    holds a cell centre iff its primitive holds it AND the map holds it (discmaterial.lookup_spec); cell_voxel is the linear index of
+    the centre's voxel where the owning record has a map, -1 elsewhere."""
     nx, ny, nz = grid.shape
-    cown = eown = None
+    cown = eown = cvox = None
+    has_maps = bool(table.maps)
     if cells:
         cown = np.full((nz - 1, ny - 1, nx - 1), -1, np.int32)
         cprio = np.full(cown.shape, np.iinfo(np.int32).min, np.int64)
+        if has_maps:
+            cvox = np.full(cown.shape, -1, np.int32)
+            centers = [grid.centers(a) for a in range(3)]
     if edges:
         eown = np.full((3, nz, ny, nx), -1, np.int32)
         eprio = np.full(eown.shape, np.iinfo(np.int32).min, np.int64)
@@ -543,9 +578,17 @@ def rasterise_spec(grid, table: Table, cells: bool = True, edges: bool = True):
             if res is None:
                 continue
             mask, sl = res
+            lin = None
+            if has_maps and int(table.rec_map[q]):
+                mp = table.maps[int(table.rec_map[q]) - 1]
+                x, y, z, _ = _block(centers, r["cbox"])
+                held, lin = _disc.lookup_spec(mp.M, mp.lines, mp.data, mp.use_db_background, x, y, z)
+                mask = mask & held
             win = mask & (cprio[sl] <= pr)
             cprio[sl][win] = pr
             cown[sl][win] = q
+            if has_maps:
+                cvox[sl][win] = -1 if lin is None else lin[win]
         elif edges:
             res = node_mask(grid, table, q)
             if res is None:
@@ -559,7 +602,7 @@ def rasterise_spec(grid, table: Table, cells: bool = True, edges: bool = True):
                 win = e & (eprio[c][esl] <= pr)
                 eprio[c][esl][win] = pr
                 eown[c][esl][win] = q
-    return cown, eown
+    return (cown, eown, cvox) if has_maps else (cown, eown)
 
 
 def marks_any_edge(grid, table: Table, q: int) -> bool:

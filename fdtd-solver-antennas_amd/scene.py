@@ -31,6 +31,7 @@ from . import magnetic as _magnetic
 from . import conformal as _conformal
 from . import primitives as _prims
 from . import planewave as _planewave
+from . import discmaterial as _discmaterial
 
 
 @dataclass
@@ -98,6 +99,17 @@ class DebyeMaterial(Material):
 class LorentzMaterial(Material):
     """add_lorentz_material(name, eps_inf, kappa, wp, w0, gamma): Lorentz / Drude poles (lorentz.py).  eps_r holds eps_inf."""
     medium: Optional[_lorentz.LorentzMedium] = None
+
+
+@dataclass
+class DiscMaterial(Material):
+    """add_disc_material(name, lines, data, eps_r, kappa, density, ...): a voxel body model (discmaterial.py).  Its boxes and analytic
+    solids delimit the map: such a primitive owns a cell whose centre it holds AND whose voxel is not the background (index 0), unless
+    use_db_background.  eps_r / kappa / density of the material itself are those of table entry 0; a cell takes its voxel's."""
+    vmap: Optional[_discmaterial.VoxelMap] = None
+
+    def add_polyhedron(self, triangles, priority=0):
+        raise ValueError(f"disc material '{self.name}': a polyhedron cannot delimit a voxel map (boxes and the analytic solids can)")
 
 
 @dataclass
@@ -211,6 +223,22 @@ class Scene:
         self.materials.append(m)
         return m
 
+    def add_disc_material(self, name, lines, data, eps_r, kappa, density, scale=1.0, matrix=None, use_db_background=False) -> DiscMaterial:
+        """A voxel body model: lines = (X, Y, Z) the map's mesh lines (its own drawing unit, times `scale` the scene's), data uint8
+        [nZ-1][nY-1][nX-1] one tissue index per voxel, eps_r / kappa / density one value per tissue (entry 0: the background), matrix
+        an optional 4x4 placement (map -> scene drawing coordinates).  add_box (or an analytic solid) on the result delimits it;
+        voxels of index 0 are transparent unless use_db_background.  At most discmaterial.MAX_MAPS per scene."""
+        vmap = _discmaterial.make_map(name, lines, data, eps_r, kappa, density, scale, matrix, use_db_background)
+        return self.add_voxel_map(vmap)
+
+    def add_voxel_map(self, vmap: "_discmaterial.VoxelMap") -> DiscMaterial:
+        """add_disc_material for a map that is already validated (discmaterial.make_map / load_npz)."""
+        if sum(isinstance(m, DiscMaterial) for m in self.materials) >= _discmaterial.MAX_MAPS:
+            raise ValueError(f"disc material '{vmap.name}': a scene takes at most {_discmaterial.MAX_MAPS} voxel maps")
+        m = DiscMaterial(vmap.name, float(vmap.eps_r[0]), float(vmap.kappa[0]), density=float(vmap.density[0]), vmap=vmap)
+        self.materials.append(m)
+        return m
+
     def add_metal(self, name) -> Metal:
         m = Metal(name)
         self.metals.append(m)
@@ -293,6 +321,9 @@ class VoxelScene:
     density: Optional[np.ndarray] = None
     # plane-wave excitation (None: the scene has none): direction, e0 and the box snapped to whole nodes (planewave.PlaneWave)
     plane_wave: Optional["_planewave.PlaneWave"] = None
+    # voxel body models (None: the scene has no disc material): per cell the linear index of its voxel in the map of the disc
+    # material that owns it (cell_material says which), -1 where another material or the background does
+    cell_voxel: Optional[np.ndarray] = None
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -360,8 +391,9 @@ def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = Fa
     also the fractions of the edges the plain metals cut (conformal.fractions; `device_fractions`: _capi.default_fractions' callable,
     None: numpy) — the staircase itself, every other field of the result, stays what it is."""
     vs = _voxelize(scene, grid, rasteriser)
-    if any(m.density > 0 for m in scene.materials):
+    if any(m.density > 0 or (isinstance(m, DiscMaterial) and np.any(m.vmap.density > 0)) for m in scene.materials):
         vs.density = np.array([m.density for m in scene.materials] + [0.0])[vs.cell_material]
+        _from_voxels(scene, vs.cell_material, vs.cell_voxel, "density", vs.density)
     if conformal:
         vs.fractions = _conformal.fractions(scene, grid, device_fractions)
     for src in getattr(scene, "plane_waves", []):
@@ -372,6 +404,16 @@ def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = Fa
         hi = tuple(grid.snap(a, max(bx.start[a], bx.stop[a]) * u) for a in range(3))
         vs.plane_wave = _planewave.PlaneWave(src.name, src.spec.e0, src.spec.direction, lo, hi)
     return vs
+
+
+def _from_voxels(scene: Scene, cell_material, cell_voxel, what: str, out: np.ndarray) -> None:
+    """out[cell] = the table value `what` (eps_r, kappa, density) of the cell's voxel, for the cells a disc material owns."""
+    if cell_voxel is None:
+        return
+    for qi, m in enumerate(scene.materials):
+        if isinstance(m, DiscMaterial):
+            sel = (cell_material == qi) & (cell_voxel >= 0)
+            out[sel] = getattr(m.vmap, what)[m.vmap.data.reshape(-1)[cell_voxel[sel]]]
 
 
 def _voxelize(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
@@ -697,10 +739,15 @@ def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene
     nx, ny, nz = grid.shape
     u = scene.unit
     table = _prims.pack_table(scene, grid)
-    cown, eown = (rasteriser or _prims.rasterise_spec)(grid, table)
+    res = (rasteriser or _prims.rasterise_spec)(grid, table)
+    if len(res) != (3 if table.maps else 2):
+        raise ValueError("the rasteriser returned no cell_voxel for a table with voxel maps" if table.maps else
+                         "the rasteriser returned three results for a table without voxel maps")
+    cown, eown = res[0], res[1]
+    cvox = res[2] if table.maps else None         # per cell: the voxel of the owning disc record, -1 elsewhere (None: no maps)
     rec = table.rec
     shape = (nz - 1, ny - 1, nx - 1)
-    if cown.shape != shape or eown.shape != (3, nz, ny, nx):
+    if cown.shape != shape or eown.shape != (3, nz, ny, nx) or (cvox is not None and cvox.shape != shape):
         raise ValueError("the rasteriser returned owner arrays of the wrong shape")
     media, media_names, medium_of = _merged_media(scene.materials, DebyeMaterial)
     if len(media) > _disp.MAX_MEDIA:
@@ -716,6 +763,8 @@ def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene
         return np.array(list(values) + [background], dtype)[cmat]
     eps = per_cell((m.eps_r for m in mats), 1.0)
     kap = per_cell((m.kappa for m in mats), 0.0)
+    _from_voxels(scene, cmat, cvox, "eps_r", eps)
+    _from_voxels(scene, cmat, cvox, "kappa", kap)
     mur = per_cell((m.mu_r for m in mats), 1.0)
     sgm = per_cell((m.sigma_m for m in mats), 0.0)
     cmed = per_cell((medium_of[m.medium.key()] if isinstance(m, DebyeMaterial) else -1 for m in mats), -1, np.int8) if media else None
@@ -760,10 +809,10 @@ def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene
             return filled
         vs = _sheets_from_owners(scene, grid, eps, kap, emet, node_masks, filled_of)
         vs.debye, vs.lorentz = debye, lorentz
-        vs.mu_r, vs.sigma_m, vs.cell_material, vs.material_names = mur, sgm, cmat, names
+        vs.mu_r, vs.sigma_m, vs.cell_material, vs.material_names, vs.cell_voxel = mur, sgm, cmat, names, cvox
         vs.elements = _elements_on_grid(scene, grid, vs.pec, vs.ports, vs.sheets)
         return vs
     pec = emet >= 0
     ports = [_port_on_grid(p, grid, u) for p in scene.ports]
     return VoxelScene(eps, kap, pec, ports, debye=debye, lorentz=lorentz, elements=_elements_on_grid(scene, grid, pec, ports, None),
-                      mu_r=mur, sigma_m=sgm, cell_material=cmat, material_names=names)
+                      mu_r=mur, sigma_m=sgm, cell_material=cmat, material_names=names, cell_voxel=cvox)

@@ -57,6 +57,18 @@
  *                       of any of the three edges.
  *              metal: parity || near (any triangle);  material: parity && !near.  A face exactly on a mesh plane is therefore
  *              decided by `near` for a metal (its nodes are held) and by the half-open crossing rule for a material's cell centres.
+ *
+ * Voxel maps (fdtd_voxelize_maps; discmaterial.lookup_spec is the same text in numpy): a material record p with rec_map[p] = m + 1 is a
+ * delimiter of map m and holds a cell centre iff its own predicate above holds it AND the map holds it.  With M = maps[m].m and
+ * (x, y, z) the centre in world metres (NOT the record's local frame):
+ *   q_x = ((M[0] x + M[1] y) + M[2] z) + M[3], q_y with M[4..7], q_z with M[8..11];
+ *   per axis a with the n_a lines L_a: i_a = (the number of t with L_a[t] <= q_a) - 1; the point has a voxel iff
+ *   0 <= i_a <= n_a - 2 on all three axes (half-open: L[0] <= q < L[n - 1]; a NaN has none);
+ *   voxel = (i_z (n_y - 1) + i_y) (n_x - 1) + i_x (in 64 bits), v = data[voxel];
+ *   the map holds the point iff it has a voxel && (v != 0 || use_db_background).
+ * Only comparisons follow the three q.  cell_voxel is `voxel` where the owning record has a map, -1 elsewhere.  Ownership is
+ * unchanged: the highest priority, the later record on a tie — so index 0 is transparent (unless use_db_background) and shows
+ * whatever lower priority lies under it.
  */
 #ifndef FDTD_HIP_VOXEL_H
 #define FDTD_HIP_VOXEL_H
@@ -87,6 +99,28 @@ typedef struct fdtd_voxel_prim {
  * outside verts or a polyhedron whose nvert is no multiple of 3 is FDTD_E_ARG.  nprim == 0 and primitives outside the grid give owners of -1. */
 int fdtd_voxelize(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
                   const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner);
+
+/* One voxel map: m the 3 x 4 world (metres) -> map coordinates; lines[a] the n[a] >= 2 strictly increasing lines of axis a; data
+ * uint8 [n[2]-1][n[1]-1][n[0]-1], x fastest, ndata = its length (checked against n); host pointers. */
+typedef struct fdtd_voxel_map {
+  double m[12];
+  const double* lines[3];
+  const uint8_t* data;
+  int64_t ndata;
+  int32_t n[3];
+  int32_t use_db_background;
+} fdtd_voxel_map;                              /* 152 bytes */
+
+enum { FDTD_VOXEL_MAX_MAPS = 4 };
+
+/* fdtd_voxelize with voxel maps: rec_map int32 [nprim] (0: none, m + 1: the record delimits maps[m]; NULL with nmaps == 0), maps
+ * [nmaps <= FDTD_VOXEL_MAX_MAPS], cell_voxel int32 [nz-1][ny-1][nx-1] (needs cell_owner; NULL: not wanted).  The records without a map
+ * are rasterised as fdtd_voxelize does; one further launch merges the mapped records into those owners by (priority, record index).
+ * FDTD_E_ARG: a mapped record that is a metal or a polyhedron, rec_map out of range, a map with n < 2, lines that do not increase,
+ * more than 2^31 - 1 voxels or ndata != (n[0]-1)(n[1]-1)(n[2]-1).  With nmaps == 0 the owners are fdtd_voxelize's and cell_voxel is -1. */
+int fdtd_voxelize_maps(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
+                       const double* verts, double tol, int32_t* cell_owner, int32_t* edge_owner, const int32_t* rec_map, int nmaps,
+                       const fdtd_voxel_map* maps, int32_t* cell_voxel);
 
 #ifdef __cplusplus
 }
