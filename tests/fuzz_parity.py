@@ -15,6 +15,9 @@ the energy to 1e-12, the NF2FF face spectra to 1e-6 of their largest entry (floa
     python tests/fuzz_parity.py --media ...     # scenes with Debye media and / or conducting sheets (k_debye, k_sheet and their place in the step
                                                 # loop) against the oracle's half-steps plus the numpy restatement of the two corrections
                                                 # (draw_media_case / run_media_case below); tests/test_media_fuzz_cpu.py guards what the draw covers
+    python tests/fuzz_parity.py --corrections ...   # scenes with at least three of the seven corrections of the step loop, often all of them (Debye and
+                                                # Lorentz media, sheets, elements, magnetic faces, conformal faces, a plane wave), against the composed
+                                                # restatement (draw_corrections_case / run_corrections_case); tests/test_corrections_fuzz_cpu.py guards the draw
 
 Lives under tests/ because it loads the oracle (test infrastructure); tests/test_round3_gpu.py::test_randomised_cases_equal_the_oracle
 runs a fixed-seed batch of it in the -m gpu suite.
@@ -506,6 +509,568 @@ def run_media_case(case, hip, oracle):
     return problems, info
 
 
+# ---- all seven corrections in one context ---------------------------------------------------------------------------------------------
+CORRECTIONS_BATCH = (24, 2)   # (cases, seed) of the batch in the -m gpu suite (tests/test_corrections_fuzz_gpu.py); test_corrections_fuzz_cpu.py guards its coverage
+CORRECTION_NAMES = ("debye", "lorentz", "sheets", "elements", "magnetic", "conformal", "planewave")
+TWO_PI = 2 * np.pi
+
+
+def _line_edges(lo, hi):
+    """The edges (comp, i, j, k) with both end nodes in the node box lo..hi (a line: an element or a port; a plane: a sheet)."""
+    out = set()
+    for c in range(3):
+        if hi[c] > lo[c]:
+            r = [range(lo[a], hi[a] + (0 if a == c else 1)) for a in range(3)]
+            out |= {(c, i, j, k) for i in r[0] for j in r[1] for k in r[2]}
+    return out
+
+
+def _lorentz_poles(rng, K):
+    """K poles (wp, w0, gamma) in rad/s, Drude (w0 = 0) and Lorentz ones, loss-free and lossy, rounded so that repr() holds them."""
+    wp = [round(float(rng.uniform(2.0, 8.0)), 2) * 1e9 * TWO_PI for _ in range(K)]
+    w0 = [0.0 if rng.random() < 0.4 else round(float(rng.uniform(6.0, 20.0)), 2) * 1e9 * TWO_PI for _ in range(K)]
+    gamma = [0.0 if rng.random() < 0.3 else round(float(rng.uniform(0.5, 20.0)), 2) * 1e9 for _ in range(K)]
+    return wp, w0, gamma
+
+
+def draw_corrections_case(rng):
+    """One scene with at least three of the seven corrections of the step loop (often all of them) as a plain dict: Debye media, Lorentz
+    / Drude media, conducting sheets, lumped elements, magnetic materials, a curved metal with conformal faces, a plane wave.  All
+    positions are node indices; a box owns the cells [lo, hi).  The media stand behind each other along y or z (the longer of the two
+    inside the layers), the curved metal beside them along x, the plane wave's box one cell outside everything and the NF2FF box outside
+    that.  What each item is there for: the table in docs/HISTORY.md (randomised corrections)."""
+    touchy = False
+    if rng.random() < 0.3:
+        want = dict.fromkeys(CORRECTION_NAMES, True)
+    else:
+        touchy = bool(rng.random() < 0.4)      # media up to the grid faces along x: no plane wave, no NF2FF box, no CPML there
+        while True:
+            want = {k: bool(rng.random() < 0.55) for k in CORRECTION_NAMES}
+            if touchy:
+                want["planewave"] = False
+            if sum(want.values()) >= 3:
+                break
+    roomy = want["planewave"] or want["conformal"] or sum(want.values()) >= 6
+    n = [int(rng.integers(30, 71)), int(rng.integers(24, 37)), int(rng.integers(20, 29))] if roomy else \
+        [int(rng.integers(14, 71)), int(rng.integers(12, 37)), int(rng.integers(12, 29))]
+    if rng.random() < 0.3:
+        kinds = [str(rng.choice(["PEC", "MUR", "CPML"]))] * 6
+    else:
+        kinds = [str(rng.choice(["PEC", "MUR", "CPML"])) for _ in range(6)]
+    if touchy:
+        kinds[0], kinds[1] = str(rng.choice(["PEC", "MUR", "MUR"])), str(rng.choice(["PEC", "MUR", "MUR"]))
+    cells = int(rng.integers(2, max(2, min(3 if roomy else 6, (min(n) - 8) // 2)) + 1))
+    layer = [cells if k == "CPML" else 0 for k in kinds]
+    nf = "none" if touchy else str(rng.choice(["none", "dft", "record"]))
+    pw = want["planewave"]
+
+    def margins(nf, pw):      # nodes between a grid face and the region the scene may fill
+        out = []
+        for f in range(6):
+            o, nfp = max(2, layer[f] + 1), max(layer[f] + 2, 3)
+            if nf != "none":
+                o = max(o, nfp + 1)                     # strictly inside the NF2FF box
+            if pw:
+                o = max(o, max(layer[f] + 2, nfp + 2 if nf != "none" else 0) + 1)      # a vacuum cell inside the plane wave's box
+            out.append(o)
+        return out
+
+    need = [12 if want["conformal"] else 6, 5, 5]
+    fits = lambda m: all(n[a] - 1 - m[2 * a] - m[2 * a + 1] >= need[a] for a in range(3))
+    if not fits(margins(nf, pw)) and fits(margins("none", pw)):
+        nf = "none"
+    if not fits(margins(nf, pw)):
+        pw, need[0] = False, 6
+        want["planewave"] = want["conformal"] = False
+        if not fits(margins(nf, pw)):
+            nf = "none"
+    m = margins(nf, pw)
+    R0, R1 = [m[2 * a] for a in range(3)], [n[a] - 1 - m[2 * a + 1] for a in range(3)]        # the region, in nodes
+    while any(R1[a] - R0[a] < 4 for a in range(3)):      # (a 12-plane grid under six cells of CPML)
+        cells -= 1
+        layer = [cells if k == "CPML" else 0 for k in kinds]
+        m = margins(nf, pw)
+        R0, R1 = [m[2 * a] for a in range(3)], [n[a] - 1 - m[2 * a + 1] for a in range(3)]
+    # the curved metal: a box of 4 ... 6 cells at one end of the region along x, the media a cell away from it or touching its plane
+    metal = None
+    M0, M1 = list(R0), list(R1)                          # the media's share of the region
+    if want["conformal"] and R1[0] - R0[0] >= 11:
+        bw, side, gap = int(rng.integers(4, 7)), int(rng.integers(0, 2)), int(rng.integers(0, 2))
+        metal = {"shape": str(rng.choice(["sphere", "sphere", "cylinder"])), "side": side, "gap": gap, "bw": bw}
+        if side == 0:
+            M0[0] = R0[0] + bw + gap
+        else:
+            M1[0] = R1[0] - bw - gap
+    want["conformal"] = metal is not None
+    # media up to a grid face along x (never into a CPML layer, never with a plane wave or an NF2FF box around)
+    T0, T1 = list(M0), list(M1)
+    if touchy:
+        if not (metal and metal["side"] == 0) and rng.random() < 0.7:
+            T0[0] = 0
+        if not (metal and metal["side"] == 1) and rng.random() < 0.7:
+            T1[0] = n[0] - 1
+    s = 1 if M1[1] - M0[1] >= M1[2] - M0[2] else 2       # the media stand behind each other along this axis
+    t = 3 - s
+    nD = int(rng.integers(1, 4)) if want["debye"] else 0
+    nL = int(rng.integers(1, 3)) if want["lorentz"] else 0
+    nM = int(rng.integers(1, 3)) if want["magnetic"] else 0
+    span = M1[s] - M0[s]
+
+    def segments():
+        seg = []
+        for kind, cnt in (("D", nD), ("L", nL), ("M", nM)):
+            for q in range(cnt):
+                if kind == "M":      # on the face plane of the dispersive medium in front of it, or a cell away
+                    gap_ = 0 if (seg and (seg[-1][0] == "M" or rng.random() < 0.6)) else (1 if seg else 0)
+                else:                # two dispersive media never share an edge
+                    gap_ = 1 if seg else 0
+                seg.append([kind, gap_, 1])
+        return seg
+    seg = segments()
+    while sum(g_ + l_ for _, g_, l_ in seg) > span:
+        if nD > 1:
+            nD -= 1
+        elif nL > 1:
+            nL -= 1
+        elif nM > 1:
+            nM -= 1
+        elif nD:
+            nD = 0
+        else:
+            nL = 0
+        seg = segments()
+    for _ in range(int(rng.integers(0, span - sum(g_ + l_ for _, g_, l_ in seg) + 1)) if seg else 0):
+        seg[int(rng.integers(0, len(seg)))][2] += 1
+    if rng.random() < 0.5:
+        seg = seg[::-1]
+        for q in range(len(seg) - 1, 0, -1):
+            seg[q][1] = seg[q - 1][1]
+        if seg:
+            seg[0][1] = 0
+    room = max(3, (M1[0] - M0[0]) // 4)
+    boxes = []
+    pos = M0[s] + (int(rng.integers(0, span - sum(g_ + l_ for _, g_, l_ in seg) + 1)) if seg else 0)
+    for q, (kind, gap_, len_) in enumerate(seg):
+        pos += gap_
+        lo, hi = list(T0), list(T1)
+        lo[s], hi[s] = pos, pos + len_
+        pos += len_
+        first = not any(b["kind"] == kind for b in boxes)
+        if kind != "D":       # x0 and x1 with uniform residues mod 4
+            if not (T0[0] == 0 and rng.random() < 0.6):
+                lo[0] = _pick_mod4(rng, M0[0], M0[0] + room)
+            if not (T1[0] == n[0] - 1 and rng.random() < 0.6):
+                hi[0] = _pick_mod4(rng, M1[0] - room, M1[0])
+            if hi[0] - lo[0] < 2:
+                lo[0], hi[0] = M0[0], M1[0]
+        if kind == "M" and metal is not None and metal["gap"] == 0:      # magnetic cells stay a cell clear of the curved metal
+            if metal["side"] == 0:
+                lo[0] = max(lo[0], M0[0] + 1)
+            else:
+                hi[0] = min(hi[0], M1[0] - 1)
+        if not first and rng.random() < 0.5:
+            lo[t] = int(rng.integers(M0[t], M1[t] - 1))
+            hi[t] = int(rng.integers(lo[t] + 2, M1[t] + 1))
+        boxes.append({"kind": kind, "lo": [int(v) for v in lo], "hi": [int(v) for v in hi]})
+    debye, lorentz, magnetic = [], [], []
+    kmax = int(rng.choice([1, 2, 3, 4]))                 # the poles of the Lorentz media: every k_lorentz<multi, 1 / 2 / 4>
+    for b in boxes:
+        if b["kind"] == "D":
+            K = int(rng.choice([1, 3, 4, 5, 8], p=[0.2, 0.3, 0.15, 0.1, 0.25]))
+            kappa = float(rng.choice([0.0, 0.0, round(float(rng.uniform(0.005, 0.05)), 4)]))
+            if K == 1:
+                par = ("poles", round(float(rng.uniform(1.5, 4.0)), 3), kappa, [round(float(rng.uniform(0.2, 1.5)), 3)],
+                       [round(float(rng.uniform(5.0, 40.0)), 2) * 1e-12])
+            else:
+                par = ("fit", round(float(rng.uniform(2.0, 6.0)), 3), round(float(rng.uniform(0.005, 0.05)), 4), K, kappa)
+            debye.append({"medium": par, "lo": b["lo"], "hi": b["hi"]})
+        elif b["kind"] == "L":
+            K = kmax if not lorentz else int(rng.integers(1, kmax + 1))
+            lorentz.append({"medium": (round(float(rng.uniform(1.0, 2.5)), 3), float(rng.choice([0.0, 0.0, 0.01])), *_lorentz_poles(rng, K)),
+                            "lo": b["lo"], "hi": b["hi"]})
+        else:
+            how = str(rng.choice(["mu", "sigma", "both"]))
+            magnetic.append({"eps_r": round(float(rng.uniform(1.0, 2.0)), 2), "mu_r": round(float(rng.uniform(1.5, 4.0)), 2) if how != "sigma" else 1.0,
+                             "sigma_m": round(float(rng.uniform(50.0, 2000.0)), 1) if how != "mu" else 0.0, "lo": b["lo"], "hi": b["hi"]})
+    # what sheets, elements and the port may use: the media's share of the region without the planes on grid faces, a node off the
+    # curved metal's plane
+    S0, S1 = list(M0), list(M1)
+    if metal is not None and metal["gap"] == 0:
+        S0[0] += metal["side"] == 0
+        S1[0] -= metal["side"] == 1
+    clip = lambda b: ([max(b["lo"][a], S0[a]) for a in range(3)], [min(b["hi"][a], S1[a]) for a in range(3)])
+    # one lumped port along z: inside a medium (a magnetic one: its current loop runs through magnetic faces) or in the open
+    port = None
+    if boxes and rng.random() < 0.75:
+        lo, hi = clip(boxes[int(rng.integers(0, len(boxes)))])
+        inner = [(lo[a] + 1, hi[a] - 1) if hi[a] - lo[a] >= 2 else (lo[a], hi[a]) for a in range(2)]
+        if hi[2] > lo[2]:
+            z0 = int(rng.integers(lo[2], hi[2]))
+            port = (int(rng.integers(inner[0][0], inner[0][1] + 1)), int(rng.integers(inner[1][0], inner[1][1] + 1)), z0,
+                    int(min(hi[2], z0 + rng.integers(1, 5))))
+    if port is None:
+        z0 = int(rng.integers(S0[2], S1[2]))
+        port = (int(rng.integers(S0[0] + 1, S1[0])), int(rng.integers(S0[1], S1[1] + 1)), z0, int(min(S1[2], z0 + rng.integers(1, 5))))
+    taken = _line_edges([port[0], port[1], port[2]], [port[0], port[1], port[3]])
+    # conducting sheets of zero thickness: on a face of a dispersive medium (its edges are dispersive edges too), else anywhere
+    sheets = []
+    disp = [b for b in boxes if b["kind"] != "M"]
+    for q in range(int(rng.integers(1, 4)) if want["sheets"] else 0):
+        for _ in range(8):
+            if disp and (q == 0 or rng.random() < 0.7):
+                b = disp[(q + int(rng.integers(0, 2))) % len(disp)]
+                lo, hi = clip(b)
+                a = s if rng.random() < 0.7 else int(rng.integers(0, 3))
+                lo[a] = hi[a] = lo[a] if rng.random() < 0.5 else hi[a]
+            else:
+                a = int(rng.integers(0, 3))
+                lo, hi = list(S0), list(S1)
+                lo[a] = hi[a] = int(rng.integers(S0[a], S1[a] + 1))
+            for c in range(3):
+                if c != a and hi[c] - lo[c] > 2 and rng.random() < 0.7:
+                    lo[c] = int(rng.integers(lo[c], hi[c] - 1))
+                    hi[c] = int(rng.integers(lo[c] + 2, min(hi[c], lo[c] + 9) + 1))
+            if any(hi[c] <= lo[c] for c in range(3) if c != a):
+                continue
+            edges = _line_edges(lo, hi)
+            if edges & taken:      # (the scene refuses a sheet edge that is a port edge, an element edge or another metal's)
+                continue
+            taken |= edges
+            sheets.append((float(rng.choice([5.8e7, 9.1e6, 3e5, 1e5])), float(rng.choice([5e-6, 35e-6, 1e-3])), [int(v) for v in lo], [int(v) for v in hi]))
+            break
+    # lumped elements: lines of one to five edges inside a medium of each kind, or next to the curved metal
+    elements = []
+    for q in range(int(rng.integers(1, 5)) if want["elements"] else 0):
+        for _ in range(8):
+            d = int(rng.integers(0, 3))
+            if metal is not None and metal["gap"] == 1 and rng.random() < 0.3:      # a tangential edge on the plane between metal and media
+                d = int(rng.integers(1, 3))
+                lo = [M0[0] - 1 if metal["side"] == 0 else M1[0] + 1, int(rng.integers(S0[1], S1[1])), int(rng.integers(S0[2], S1[2]))]
+                length = 1
+            elif boxes:
+                blo, bhi = clip(boxes[(q + int(rng.integers(0, 2))) % len(boxes)])
+                if bhi[d] <= blo[d]:
+                    continue
+                length = int(rng.integers(1, min(5, bhi[d] - blo[d]) + 1))
+                lo = [int(rng.integers(blo[a], bhi[a] - length + 1)) if a == d else
+                      int(rng.integers(blo[a] + 1, bhi[a])) if bhi[a] - blo[a] >= 2 else int(rng.integers(blo[a], bhi[a] + 1)) for a in range(3)]
+            else:
+                length = int(rng.integers(1, min(5, S1[d] - S0[d]) + 1))
+                lo = [int(rng.integers(S0[a], S1[a] - (length if a == d else 0) + 1)) for a in range(3)]
+            hi = list(lo)
+            hi[d] += length
+            edges = _line_edges(lo, hi)
+            if edges & taken:
+                continue
+            taken |= edges
+            kind = str(rng.choice(["parallel", "series"]))
+            R = float(rng.choice([1.0, 50.0, 100.0, 1000.0]))
+            L = float(rng.choice([1e-9, 3e-9]))
+            C = float(rng.choice([0.2e-12, 1e-12]))
+            if kind == "parallel":      # the inductor carries the state; R and C fold into the operator
+                parts = [(None, L, None), (R, L, None), (None, L, C), (R, L, C)][int(rng.integers(0, 4))]
+            else:
+                parts = [(R, L, None), (None, L, C), (R, L, C), (R, None, C), (None, L, None)][int(rng.integers(0, 5))]
+            elements.append({"dir": d, "kind": kind, "R": parts[0], "L": parts[1], "C": parts[2], "lo": [int(v) for v in lo], "hi": [int(v) for v in hi]})
+            break
+    if metal is not None:      # the metal's box: bw cells along x at its end of the region, beside a dispersive medium where there is one
+        lo, hi = [0, 0, 0], [0, 0, 0]
+        lo[0], hi[0] = (R0[0], R0[0] + metal["bw"]) if metal["side"] == 0 else (R1[0] - metal["bw"], R1[0])
+        ref_box = disp[0] if disp else boxes[0] if boxes else None
+        for a in (1, 2):
+            w_ = int(min(metal["bw"], R1[a] - R0[a]))
+            mid = (ref_box["lo"][a] + ref_box["hi"][a]) // 2 if ref_box else (R0[a] + R1[a]) // 2
+            lo[a] = int(min(max(mid - w_ // 2 + int(rng.integers(-1, 2)), R0[a]), R1[a] - w_))
+            hi[a] = lo[a] + w_
+        metal = {"shape": metal["shape"], "side": metal["side"], "gap": metal["gap"], "lo": lo, "hi": hi,
+                 "shift": [round(float(rng.uniform(-0.3, 0.3)), 2) for _ in range(3)], "tilt": [round(float(rng.uniform(10, 40)), 1), round(float(rng.uniform(10, 40)), 1)]}
+    wave = None
+    if pw:
+        if rng.random() < 0.4:
+            k = [0.0, 0.0, 0.0]
+            k[int(rng.integers(0, 3))] = float(rng.choice([-1.0, 1.0]))
+        else:
+            k = [round(float(v), 2) for v in rng.uniform(-1, 1, 3)]
+            if max(abs(v) for v in k) < 0.2:
+                k[2] = 1.0
+        e0 = [round(float(v), 2) for v in np.cross(k, rng.uniform(-1, 1, 3) + [0.1, 0.2, 0.3])]
+        if max(abs(v) for v in e0) < 0.05:
+            e0 = [round(float(v), 2) for v in np.cross(k, [1.0, 0.0, 0.0] if abs(k[0]) < 0.9 else [0.0, 1.0, 0.0])]
+        wave = {"e0": e0, "dir": k, "lo": [R0[a] - 1 for a in range(3)], "hi": [R1[a] + 1 for a in range(3)]}
+    env = {}
+    if "MUR" in kinds and rng.random() < 0.4:
+        env["FDTD_MUR_APPLY_PASS"] = "1"
+    if rng.random() < 0.25:
+        env["FDTD_TYS"] = str(int(rng.choice([1, 2, 3, 5, 7, 16])))
+    calls = [int(rng.integers(1, 61)) for _ in range(int(rng.integers(1, 6)))]
+    while sum(calls) > 150:
+        q = int(np.argmax(calls))
+        calls[q] = max(1, calls[q] - (sum(calls) - 150))
+    if wave is not None and sum(calls) < 40:      # (the pulse's first timesteps lie below float32 rounding of the seeded fields)
+        calls[-1] += 40 - sum(calls)
+    sets = [(int(rng.integers(0, 2)), int(rng.integers(0, 3)), int(rng.integers(1, 1 << 30))) if rng.random() < 0.4 else None for _ in calls[1:]]
+    return {"shape": tuple(n), "graded": int(rng.integers(1, 1 << 20)) if rng.random() < 0.6 else 0, "kinds": kinds, "cells": cells,
+            "classes": bool(rng.random() < 0.7), "debye": debye, "lorentz": lorentz, "sheets": sheets, "elements": elements, "magnetic": magnetic,
+            "metal": metal, "planewave": wave, "port": port, "nf2ff": nf, "drive": str(rng.choice(["auto", "direct", "half"])), "env": env,
+            "calls": calls, "sets": sets, "seed": int(rng.integers(1, 1 << 30))}
+
+
+def corrections_case_sim(case):
+    """The Simulation of a drawn case (ValueError: a set-up the host layer refuses)."""
+    sc, simm, gr, lor = _mod("scene"), _mod("simulation"), _mod("grid"), _mod("lorentz")
+    n = case["shape"]
+    if case["graded"]:
+        g = np.random.default_rng(case["graded"])
+        lines = [np.concatenate([[0.0], np.cumsum(MEDIA_H * g.uniform(0.7, 1.4, k - 1))]) for k in n]
+    else:
+        lines = [np.arange(k) * MEDIA_H for k in n]
+    grid = gr.RectGrid(*lines)
+    at = lambda p: [float(lines[a][p[a]]) * 1e3 for a in range(3)]
+    s = sc.Scene(unit=1e-3)
+    for q, m in enumerate(case["debye"]):
+        med = media_case_medium(m["medium"])
+        s.add_debye_material(f"d{q}", med.eps_inf, med.kappa, med.delta_eps, med.tau).add_box(at(m["lo"]), at(m["hi"]), priority=1)
+    for q, m in enumerate(case["lorentz"]):
+        eps_inf, kappa, wp, w0, gamma = m["medium"]
+        s.add_lorentz_material(f"l{q}", eps_inf, kappa, wp, w0, gamma).add_box(at(m["lo"]), at(m["hi"]), priority=1)
+    for q, m in enumerate(case["magnetic"]):
+        s.add_material(f"f{q}", eps_r=m["eps_r"], mu_r=m["mu_r"], sigma_m=m["sigma_m"]).add_box(at(m["lo"]), at(m["hi"]), priority=1)
+    for q, (sigma, t, lo, hi) in enumerate(case["sheets"]):
+        s.add_conducting_sheet(f"s{q}", sigma, t).add_box(at(lo), at(hi))
+    for q, el in enumerate(case["elements"]):
+        s.add_lumped_element(f"e{q}", "xyz"[el["dir"]], R=el["R"], L=el["L"], C=el["C"], kind=el["kind"]).add_box(at(el["lo"]), at(el["hi"]))
+    px, py, z0, z1 = case["port"]
+    s.add_lumped_port(1, 50.0, at((px, py, z0)), at((px, py, z1)), "z", 1.0)
+    mt = case["metal"]
+    if mt is not None:      # a ball (or a tilted disc inside that ball) that touches the plane towards the media
+        lo, hi = at(mt["lo"]), at(mt["hi"])
+        r = 0.47 * min(hi[a] - lo[a] for a in range(3))      # (clear of the far plane of its box: that one may lie next to a Mur face)
+        c = [0.5 * (lo[a] + hi[a]) + mt["shift"][a] * (0.5 * (hi[a] - lo[a]) - r) for a in range(3)]
+        c[0] = hi[0] - r if mt["side"] == 0 else lo[0] + r
+        if mt["shape"] == "sphere":
+            s.add_metal("ball").add_sphere(c, r)
+        else:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            from primitives_cases import rot
+            h = 0.8
+            d = s.add_metal("dish")
+            d.add_cylinder((0.0, 0.0, -h), (0.0, 0.0, h), float(np.sqrt(r * r - h * h)))
+            d.boxes[-1].matrix = rot(0, mt["tilt"][0]) @ rot(1, mt["tilt"][1])
+            d.boxes[-1].matrix[:3, 3] = c
+    pw = case["planewave"]
+    if pw is not None:
+        s.add_plane_wave("pw", pw["e0"], pw["dir"]).add_box(at(pw["lo"]), at(pw["hi"]))
+    vox = sc.voxelize(s, grid, conformal=mt is not None)
+    total = sum(case["calls"])
+    return simm.Simulation(grid, vox, f0=MEDIA_F0, fc=MEDIA_FC, boundary=case["kinds"], cpml_cells=case["cells"], nr_ts=total + 8,
+                           end_criteria=0.0, nf2ff_freqs=None if case["nf2ff"] == "none" else [MEDIA_F0, 1.3 * MEDIA_F0],
+                           use_classes=case["classes"], nf2ff_mode="dft" if case["nf2ff"] == "none" else case["nf2ff"], conformal=mt is not None)
+
+
+def corrections_present(sim):
+    """Which of the seven corrections the engine steps for this simulation."""
+    have = (sim.debye is not None, sim.lorentz is not None, sim.sheets is not None, sim.element_stepped.size > 0, sim.magnetic is not None,
+            sim.conformal is not None, sim.plane_wave is not None)
+    return {name for name, h in zip(CORRECTION_NAMES, have) if h}
+
+
+class Composed:
+    """The restatement of everything `sim` holds on the oracle's half-steps: RestatedLorentz (Debye and Lorentz media, sheets, elements,
+    magnetic faces) inside RestatedConformal (if the simulation lists conformal faces) inside RestatedPlaneWave (if it has a plane
+    wave).  .top steps; .lor, .conf, .pw are the three layers (None where absent); .e the oracle's engine."""
+
+    def __init__(self, sim, oracle, seed=None):
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_conformal_model_cpu import RestatedConformal
+        from test_lorentz_model_cpu import RestatedLorentz
+        from test_planewave_model_cpu import RestatedPlaneWave
+        self.sim, self.lor, self.conf, self.pw = sim, None, None, None
+
+        def make_lor(s, lib):
+            self.lor = RestatedLorentz(s, lib, seed=seed)
+            return self.lor
+
+        def make_conf(s, lib):
+            if s.conformal is None:
+                return make_lor(s, lib)
+            self.conf = RestatedConformal(s, lib, make=make_lor)
+            return self.conf
+        if sim.plane_wave is not None:
+            self.top = self.pw = RestatedPlaneWave(sim, oracle, make=make_conf)
+        else:
+            self.top = make_conf(sim, oracle)
+        self.e = self.top.e
+        self.pw_changed = [False, False]      # the plane wave's lists changed V / I on their elements
+
+    def set_field(self, kind, comp, a):
+        (self.conf or self.lor).set_field(kind, comp, a)
+
+    def step(self):
+        if self.pw is None or all(self.pw_changed):
+            return self.top.step()
+        pw, seen = self.pw, {}
+        real = pw._correct
+
+        def correct(kind, n):
+            tab = pw.tables.E if kind == 0 else pw.tables.H
+            comps = [int(c) for c in np.unique(tab[1])]
+            before = {c: self.e.get_field(kind, c) for c in comps}
+            real(kind, n)
+            seen[kind] = any(np.any(self.e.get_field(kind, c) != before[c]) for c in comps)
+        pw._correct = correct
+        try:
+            self.top.step()
+        finally:
+            del pw._correct
+        for kind in (0, 1):
+            self.pw_changed[kind] |= bool(seen.get(kind))
+
+    def run(self, n):
+        for _ in range(int(n)):
+            self.step()
+        self.lor.note_moved()
+
+
+def corrections_reference_problems(ref):
+    """media_reference_problems for a Composed restatement: what the reference side must show by itself for every correction present."""
+    r = ref.lor
+    problems = media_reference_problems(r)
+    if r.lor is not None:
+        L = r.lor
+        for c in range(3):
+            if not L["w"][c].size:
+                continue
+            live = (L["w"][c] != 0) & (L["vi"][c] != 0)
+            need = live[None] & (L["tab"][c][1][:, 0] != 0)      # (gam == 0: the padding poles of a shorter medium, which stay at rest)
+            if not np.isfinite(L["x"][c]).all():
+                problems.append(f"reference Lorentz states of component {c} not finite")
+            if live.any() and (not np.all(r.x_moved[c][:, 0][need]) or not np.all(L["vprev"][c][live] != 0)):
+                problems.append(f"component {c}: {np.count_nonzero(~r.x_moved[c][:, 0][need])} Lorentz branch currents of {np.count_nonzero(need)} never left zero")
+            if np.any(L["x"][c][:, :, ~live] != 0) or np.any(L["vprev"][c][~live] != 0):
+                problems.append(f"component {c}: Lorentz states of edges that are not dispersive edges moved")
+        if not any(((L["w"][c] != 0) & (L["vi"][c] != 0)).any() for c in range(3) if L["w"][c].size):
+            problems.append("reference: Lorentz media without a live edge")
+    if r.lumped is not None and not (np.isfinite(r.lumped["x"]).all() and np.all(np.any(r.lumped["x"] != 0, axis=0))):
+        problems.append("reference: an element edge without branch current")
+    if r.mag is not None:
+        for c in range(3):
+            on = r.mag["cls"][c] != 0
+            if on.any() and not (np.isfinite(r.mag["iprev"][c]).all() and np.all(r.mag["iprev"][c][on] != 0)):
+                problems.append(f"reference: i_prev of {np.count_nonzero(r.mag['iprev'][c][on] == 0)} magnetic faces of component {c} is zero")
+    if ref.conf is not None and not (ref.conf.iprev.size and np.isfinite(ref.conf.iprev).all() and np.all(ref.conf.iprev != 0)):
+        problems.append("reference: i_prev of a listed conformal face is zero")
+    if ref.pw is not None and not all(ref.pw_changed):
+        problems.append(f"reference: the plane wave's lists changed nothing (V: {ref.pw_changed[0]}, I: {ref.pw_changed[1]})")
+    return problems
+
+
+def _differs(name, a, b):
+    if a.shape != b.shape:
+        return [f"{name}: shape {a.shape} vs {b.shape}"]
+    if np.array_equal(a, b):
+        return []
+    bad = np.argwhere(a != b)
+    return [f"{name} differs at {len(bad)} of {b.size} entries, first {tuple(int(v) for v in bad[0])}: {a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}"]
+
+
+def corrections_state_problems(eh, ref):
+    """Fields and every state array of the HIP engine against the composed restatement, bit for bit."""
+    problems = []
+    r = ref.lor
+    fh, fo = eh.fields(), ref.e.fields()
+    problems += _differs("fields", fh, fo)
+    if not problems:
+        nzm = fo != 0
+        if not np.array_equal(fh[nzm].view(np.uint32), fo[nzm].view(np.uint32)):
+            problems.append("fields equal as values but not as bits where the reference is non-zero")
+    for c in range(len(r.w)):
+        hv, hu, hvi = eh.debye_state(c)
+        for name, a, b in (("v_prev", hv, r.vprev[c]), ("u", hu, r.u[c]), ("vi", hvi, r.vi[c])):
+            problems += _differs(f"Debye {name} of component {c}", a, b)
+    if r.lor is not None:
+        for c in range(3):
+            for name, a, b in zip(("v_prev", "x", "vi"), eh.lorentz_state(c), (r.lor["vprev"][c], r.lor["x"][c], r.lor["vi"][c])):
+                problems += _differs(f"Lorentz {name} of component {c}", a, b)
+    if r.sheet is not None:
+        hv, hib = eh.sheet_state()
+        problems += _differs("sheet v_prev", hv, r.sheet["vprev"]) + _differs("sheet branch currents", hib, r.sheet["ib"])
+    if r.lumped is not None:
+        hv, hx = eh.lumped_state()
+        problems += _differs("element v_prev", hv, r.lumped["vprev"]) + _differs("element states", hx, r.lumped["x"])
+    if r.mag is not None:
+        for c in range(3):
+            problems += _differs(f"magnetic i_prev of component {c}", eh.magnetic_state(c)[0], r.mag["iprev"][c])
+    if ref.conf is not None:
+        problems += _differs("conformal i_prev", eh.conformal_state(), ref.conf.iprev)
+    return problems
+
+
+def run_corrections_case(case, hip, oracle):
+    """hip = None: the reference side alone (what tests/test_corrections_fuzz_cpu.py steps without a GPU).  Compared after every call."""
+    capi = _mod("_capi")
+    flags = {"auto": 0, "direct": capi.FLAG_KERNEL_DIRECT, "half": 0}[case["drive"]]
+    saved = {k: os.environ.pop(k, None) for k in ENV_KNOBS}
+    os.environ.update(case["env"])
+    problems = []
+    try:
+        so = corrections_case_sim(case)
+        ref = Composed(so, oracle, seed=case["seed"])
+        sh = eh = None
+        if hip is not None:
+            sh = corrections_case_sim(case)
+            eh = sh.build(hip, flags=flags)
+            rng = np.random.default_rng(case["seed"])
+            for kind in (0, 1):
+                for c in range(3):
+                    eh.set_field(kind, c, (1e-3 * rng.standard_normal(eh.local_shape)).astype(np.float32))
+        done = 0
+        for q, nsteps in enumerate(case["calls"]):
+            if q and case["sets"][q - 1] is not None:      # fdtd_set_field between two calls: re-primes i_prev, leaves the E-side states alone
+                kind, comp, seed = case["sets"][q - 1]
+                a = (1e-3 * np.random.default_rng(seed).standard_normal(ref.e.local_shape)).astype(np.float32)
+                ref.set_field(kind, comp, a)
+                if eh is not None:
+                    eh.set_field(kind, comp, a)
+            ref.run(nsteps)
+            done += nsteps
+            if eh is None:
+                continue
+            if case["drive"] == "half":
+                for _ in range(nsteps):
+                    eh.half_step(0)
+                    eh.half_step(1)
+            else:
+                eh.run(nsteps)
+            if not problems:      # the first call where something differs names itself; later ones only repeat it
+                found = corrections_state_problems(eh, ref)
+                for (uid, iid), (ru, ri) in zip(sh._port_probe_ids, so._port_probe_ids):
+                    for name, a, b in (("port voltage", eh.get_probe(uid), ref.e.get_probe(ru)), ("port current", eh.get_probe(iid), ref.e.get_probe(ri))):
+                        if not np.array_equal(np.asarray(a)[:done], np.asarray(b)[:done]):
+                            found.append(f"{name} series differs")
+                problems += [f"after call {q} ({done} timesteps): {p}" for p in found]
+    finally:
+        for k in ENV_KNOBS:
+            os.environ.pop(k, None)
+            if saved[k] is not None:
+                os.environ[k] = saved[k]
+    problems = corrections_reference_problems(ref) + problems
+    if eh is None:
+        return problems, {"launches_per_timestep": 0, "lag_planes": 0, "timesteps_per_launch_max": 0}
+    for (ru, ri) in so._port_probe_ids:
+        if not (np.abs(ref.e.get_probe(ru)).max() > 0 and np.abs(ref.e.get_probe(ri)).max() > 0):
+            problems.append("reference: a port series is all zero")
+    if case["nf2ff"] != "none":
+        bh, bo = sh.nf2ff_boxes(), so.nf2ff_boxes()
+        worst = max(float(np.abs(np.asarray(a) - np.asarray(b)).max()) / max(float(np.abs(b).max()), 1e-300) for a, b in zip(bh, bo))
+        if len(bh) != len(bo) or not worst <= 1e-6:
+            problems.append(f"NF2FF face spectra differ ({worst:.2e} of the largest entry)")
+    info = eh.schedule_info()
+    if info["resident"] or info["launches_per_timestep"] not in (2, 3):
+        problems.append(f"schedule {info}: a context with corrections steps under two or three launches per timestep")
+    eh.close()
+    return problems, info
+
+
 def load_libs():
     capi = _mod("_capi")
     so = os.path.join(ROOT, "oracle", "libfdtd_oracle.so")
@@ -516,26 +1081,26 @@ def load_libs():
     return capi.load_hip_library(), capi.bind(ctypes.CDLL(so))
 
 
-def run_batch(ncases, seed, hip, oracle, only=None, log=print, slabs=False, mur=False, media=False):
+def run_batch(ncases, seed, hip, oracle, only=None, log=print, slabs=False, mur=False, media=False, corrections=False):
     rng = np.random.default_rng(seed)
     failed = []
     for n in range(ncases):
-        case = draw_media_case(rng) if media else draw_slab_case(rng) if slabs else draw_case(rng, mur)
+        case = draw_corrections_case(rng) if corrections else draw_media_case(rng) if media else draw_slab_case(rng) if slabs else draw_case(rng, mur)
         if only is not None and n != only:
             continue
         t0 = time.perf_counter()
         try:
-            problems, info = (run_media_case if media else run_slab_case if slabs else run_case)(case, hip, oracle)
+            problems, info = (run_corrections_case if corrections else run_media_case if media else run_slab_case if slabs else run_case)(case, hip, oracle)
         except ValueError as exc:      # a drawn set-up the host layer refuses (e.g. layers that leave no room for the NF2FF box)
             log(f"case {n}: skipped ({exc}) {case}")
             continue
         except _mod("_capi").FdtdError as exc:      # an error from the library (a bounded wait that ran out, ...) is a failing case
-            if media:      # ... always with --media: no schedule is forced there that the library may refuse
+            if media or corrections:      # ... always with --media / --corrections: no schedule is forced there that the library may refuse
                 pass
             elif "(-5): resident schedule" in str(exc) or "(-5): wavefront schedule" in str(exc):    # ... or a grid the schedule asked for by name cannot hold
                 log(f"case {n}: refused ({str(exc)[:120]}) {case}")
                 continue
-            if not media and "not starvation-free" in str(exc):    # ... except a drawn decomposition the library REFUSES: slabs sharing the test GPU that could pin every workgroup slot
+            if not (media or corrections) and "not starvation-free" in str(exc):    # ... except a drawn decomposition the library REFUSES: slabs sharing the test GPU that could pin every workgroup slot
                 log(f"case {n}: refused ({str(exc)[:150]}...) {case}")
                 continue
             log(f"case {n}: FAIL (library error) {case}  -> {exc}")
@@ -557,9 +1122,11 @@ def main():
     ap.add_argument("--slabs", action="store_true", help="decomposed runs: 2 ... 6 P2P slabs in one process against one slab on the oracle")
     ap.add_argument("--mur", action="store_true", help="every case with Mur faces, mostly on the two / three launches per timestep")
     ap.add_argument("--media", action="store_true", help="scenes with Debye media and / or conducting sheets against the numpy restatement of their corrections")
+    ap.add_argument("--corrections", action="store_true", help="scenes with at least three of the seven corrections of the step loop (often all) in one context against their composed restatement")
     args = ap.parse_args()
     hip, oracle = load_libs()
-    failed = run_batch(args.cases, args.seed, hip, oracle, args.only, log=lambda s: print(s, flush=True), slabs=args.slabs, mur=args.mur, media=args.media)
+    failed = run_batch(args.cases, args.seed, hip, oracle, args.only, log=lambda s: print(s, flush=True), slabs=args.slabs, mur=args.mur, media=args.media,
+                       corrections=args.corrections)
     print(f"{len(failed)} failing case(s) of {args.cases} (seed {args.seed})", flush=True)
     sys.exit(1 if failed else 0)
 

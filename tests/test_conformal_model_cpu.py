@@ -76,13 +76,19 @@ class RestatedConformal:
     loaded from the I arrays when the set is made (after `seed`) and by set_field(1, ...), as fdtd_conformal_set / fdtd_set_field do.
     The oracle samples its I-probes inside the H half-step, BEFORE the correction, so the I-probe series are kept here (get_probe of
     the engine returns them): sum_e w_e I_e in double in the probe's edge order.  `tables`: (comp, idx, coef), default the
-    simulation's own."""
+    simulation's own.
+    `make(sim, lib)`: an inner restatement (test_lorentz_model_cpu.RestatedLorentz and its bases: Debye and Lorentz media, sheets,
+    elements, magnetic faces) built while the simulation's conformal faces are hidden; it seeds the fields itself.  Its step runs first,
+    its magnetic correction included, and the listed faces follow on the currents it leaves, as include/fdtd_hip_conformal.h orders;
+    the voltages the correction reads are the ones in memory right in front of the H half-step, behind every E-side correction.  Without
+    `make` nothing changes: the bare oracle, stepped here."""
 
-    def __init__(self, sim, lib, flags=0, seed=None, tables=None):
+    def __init__(self, sim, lib, flags=0, seed=None, tables=None, make=None):
         saved = sim.conformal
         sim.conformal = None                          # the base operator at the simulation's (reduced) dt
         try:
-            self.e = sim.build(lib, flags=flags)
+            self.inner = None if make is None else make(sim, lib)
+            self.e = sim.build(lib, flags=flags) if make is None else self.inner.e
         finally:
             sim.conformal = saved
         self.sim = sim
@@ -118,16 +124,37 @@ class RestatedConformal:
             self.iprev[q] = self.e.get_field(1, c).reshape(-1)[self.idx[q]]
 
     def set_field(self, kind, comp, a):
-        self.e.set_field(kind, comp, a)
+        if self.inner is not None and hasattr(self.inner, "set_field"):
+            self.inner.set_field(kind, comp, a)      # (re-primes the magnetic faces' i_prev)
+        else:
+            self.e.set_field(kind, comp, a)
         if kind == 1:
             q = self.comp == comp
             self.iprev[q] = np.asarray(a, np.float32).reshape(-1)[self.idx[q]]
 
+    def _inner_step(self):
+        """The inner restatement's whole step; self.V: the voltages in memory when its (last) H half-step begins."""
+        e = self.e
+        real = e.half_step
+
+        def half_step(phase):
+            if phase == 1:
+                self.V = np.stack([e.get_field(0, c) for c in range(3)])
+            return real(phase)
+        e.half_step = half_step
+        try:
+            self.inner.step()
+        finally:
+            e.__dict__.pop("half_step", None)
+
     def step(self):
         e = self.e
-        e.half_step(0)
-        self.V = np.stack([e.get_field(0, c) for c in range(3)])
-        e.half_step(1)
+        if self.inner is not None:
+            self._inner_step()
+        else:
+            e.half_step(0)
+            self.V = np.stack([e.get_field(0, c) for c in range(3)])
+            e.half_step(1)
         self.I_uncorrected = [e.get_field(1, c) for c in range(3)]
         Is = [a.copy() for a in self.I_uncorrected]
         r = _cf().correction(self.V, self.iprev, self.comp, self.idx, self.coef)

@@ -1,0 +1,278 @@
+"""Guards of the randomised parity run of all seven corrections in one context (tests/fuzz_parity.py --corrections) that need no GPU: the
+fixed-seed batch of the -m gpu suite is accepted by the host layer and covers, together, what it was written to reach; the same seed
+gives the same cases; the reference side of the first cases moves every state of every correction present; the composed restatement
+with one correction present gives the bits of that correction's own restatement."""
+import collections
+
+import numpy as np
+import pytest
+
+import corrections_overlap_cases as oc
+import fuzz_parity
+from conftest import pkg
+from test_conformal_model_cpu import RestatedConformal, sphere_sim
+from test_lorentz_model_cpu import TWO_PI, RestatedLorentz, lorentz_cavity
+from test_planewave_model_cpu import RestatedPlaneWave, _placed
+
+NAMES = fuzz_parity.CORRECTION_NAMES
+WANTED = ({f"k_debye<{m},{k}>" for m in ("false", "true") for k in (4, 8)} | {f"k_lorentz<{m},{k}>" for m in ("false", "true") for k in (1, 2, 4)}
+          | {f"{what} {x} mod 4 = {r}" for what in ("lorentz", "magnetic") for x in ("x0", "x1") for r in range(4)}
+          | {f"nx mod 4 = {r}" for r in range(4)} | {f"{kind} element along {a}" for kind in ("series", "parallel") for a in "xyz"}
+          | {f"drive {d}" for d in ("auto", "direct", "half")} | {f"face {k}" for k in ("PEC", "MUR", "CPML")}
+          | {"sheet on a Debye face", "sheet on a Lorentz face", "element inside a Debye medium", "element inside a Lorentz medium",
+             "element inside a magnetic material", "magnetic faces on a dispersive medium's face plane", "cut face next to a dispersive edge",
+             "port loop through a magnetic material", "mu_r only", "sigma_m only", "mu_r and sigma_m", "box at x = 0", "box on the last column",
+             "medium on a Mur face node, no apply pass", "medium on a Mur face node, apply pass", "set_field of a V component", "set_field of an I component",
+             ">= 3 calls", "nf2ff none", "nf2ff dft", "nf2ff record", "raw operator", "graded", "uniform", "plane wave", "no plane wave",
+             "oblique plane wave", "axis-aligned plane wave", "sphere", "tilted cylinder", "R, L and C in one element"})
+
+
+def _edge_mask(d, shape):
+    """bool [3][nz][ny][nx]: the dispersive edges (w != 0) of a DebyeEdges / LorentzEdges, None -> all False."""
+    out = np.zeros((3,) + shape, bool)
+    if d is not None:
+        for c in range(3):
+            if d.w[c].size:
+                (i0, j0, k0), (i1, j1, k1) = d.lo[c], d.hi[c]
+                out[c, k0:k1, j0:j1, i0:i1] = np.asarray(d.w[c]).reshape(k1 - k0, j1 - j0, i1 - i0) != 0
+    return out
+
+
+def _list_mask(comp, idx, shape):
+    out = np.zeros((3,) + shape, bool)
+    out.reshape(3, -1)[np.asarray(comp, np.int64), np.asarray(idx, np.int64)] = True
+    return out
+
+
+def _faces_next_to(faces, edges):
+    """Is one of the faces (bool [3][nz][ny][nx]) spanned by one of the edges (same layout)?"""
+    for n in range(3):
+        for ce, off in pkg("conformal").face_edges(n):
+            em = edges[ce]
+            if off is not None:      # the edge at p + e_off, seen from p
+                sh = np.zeros_like(em)
+                src = [slice(None)] * 3
+                dst = [slice(None)] * 3
+                src[2 - off], dst[2 - off] = slice(1, None), slice(0, -1)
+                sh[tuple(dst)] = em[tuple(src)]
+                em = sh
+            if np.any(faces[n] & em):
+                return True
+    return False
+
+
+def features(case, sim):
+    """What a drawn, accepted case reaches (the table of the randomised corrections run in docs/HISTORY.md)."""
+    n = case["shape"]
+    shape = (n[2], n[1], n[0])
+    out = {f"nx mod 4 = {n[0] % 4}", f"nf2ff {case['nf2ff']}", "graded" if case["graded"] else "uniform", f"drive {case['drive']}"}
+    out |= {f"face {k}" for k in case["kinds"]}
+    if len(case["calls"]) >= 3:
+        out.add(">= 3 calls")
+    if not case["classes"]:
+        out.add("raw operator")
+    for st in case["sets"]:
+        if st is not None:
+            out.add("set_field of a V component" if st[0] == 0 else "set_field of an I component")
+    deb, lor = _edge_mask(sim.debye, shape), _edge_mask(sim.lorentz, shape)
+    if sim.debye is not None:
+        out.add(f"k_debye<{'true' if len(sim.debye.media) > 1 else 'false'},{4 if sim.debye.K <= 4 else 8}>")
+    if sim.lorentz is not None:
+        K = sim.lorentz.K
+        out.add(f"k_lorentz<{'true' if len(sim.lorentz.media) > 1 else 'false'},{1 if K <= 1 else 2 if K <= 2 else 4}>")
+    for d in (sim.debye, sim.lorentz):
+        for c in range(3 if d is not None else 0):
+            if not d.w[c].size:
+                continue
+            for f in range(6):
+                a = f // 2
+                if case["kinds"][f] == "MUR" and c != a and (d.hi[c][a] == n[a] if f % 2 else d.lo[c][a] == 0):
+                    out.add("medium on a Mur face node, " + ("apply pass" if case["env"].get("FDTD_MUR_APPLY_PASS") == "1" else "no apply pass"))
+    mag = np.zeros((3,) + shape, bool)
+    if sim.magnetic is not None:
+        mag = sim.magnetic.full_classes(shape) != 0
+        if _faces_next_to(mag, deb | lor):
+            out.add("magnetic faces on a dispersive medium's face plane")
+        p = sim.vox.ports[0]
+        if np.any(mag.reshape(3, -1)[np.asarray(p.i_comp, np.int64), np.asarray(p.i_idx, np.int64)]):
+            out.add("port loop through a magnetic material")
+    for what, d in (("lorentz", sim.lorentz), ("magnetic", sim.magnetic)):
+        for c in range(3 if d is not None else 0):
+            if d.hi[c][0] <= d.lo[c][0]:
+                continue
+            out |= {f"{what} x0 mod 4 = {d.lo[c][0] % 4}", f"{what} x1 mod 4 = {d.hi[c][0] % 4}"}
+            if d.lo[c][0] == 0:
+                out.add("box at x = 0")
+            last = (n[0] - 1 if c == 0 else n[0]) if what == "lorentz" else (n[0] if c == 0 else n[0] - 1)      # edges / faces along x
+            if d.hi[c][0] == last:
+                out.add("box on the last column")
+    if sim.sheets is not None:
+        sh = _list_mask(sim.sheets.comp, sim.sheets.idx, shape)
+        if np.any(sh & deb):
+            out.add("sheet on a Debye face")
+        if np.any(sh & lor):
+            out.add("sheet on a Lorentz face")
+    if sim.element_stepped.size:
+        st = sim.element_stepped
+        el = _list_mask(sim.elements.comp[st], sim.elements.idx[st], shape)
+        if np.any(el & deb):
+            out.add("element inside a Debye medium")
+        if np.any(el & lor):
+            out.add("element inside a Lorentz medium")
+        if _faces_next_to(mag, el):
+            out.add("element inside a magnetic material")
+        for e in case["elements"]:
+            out.add(f"{e['kind']} element along {'xyz'[e['dir']]}")
+            if None not in (e["R"], e["L"], e["C"]):
+                out.add("R, L and C in one element")
+    for m in case["magnetic"]:
+        out.add("mu_r only" if m["sigma_m"] == 0 else "sigma_m only" if m["mu_r"] == 1 else "mu_r and sigma_m")
+    if sim.conformal is not None:
+        out.add("sphere" if case["metal"]["shape"] == "sphere" else "tilted cylinder")
+        cut = _list_mask(sim.conformal.comp, sim.conformal.idx, shape)
+        if _faces_next_to(cut, deb | lor):
+            out.add("cut face next to a dispersive edge")
+        assert not np.any(cut & mag)
+    if sim.plane_wave is not None:
+        out |= {"plane wave", "axis-aligned plane wave" if sorted(map(abs, case["planewave"]["dir"]))[1] == 0 else "oblique plane wave"}
+    else:
+        out.add("no plane wave")
+    return out
+
+
+def test_fixed_seed_batch_is_accepted_and_covers_what_it_is_for():
+    ncases, seed = fuzz_parity.CORRECTIONS_BATCH
+    rng = np.random.default_rng(seed)
+    seen, accepted, refused, count, how_many = set(), 0, [], collections.Counter(), []
+    for q in range(ncases):
+        case = fuzz_parity.draw_corrections_case(rng)
+        nx, ny, nz = case["shape"]
+        assert 14 <= nx <= 70 and 12 <= ny <= 36 and 12 <= nz <= 28 and 2 <= case["cells"] <= 6
+        assert 1 <= len(case["calls"]) <= 5 and all(1 <= k <= 60 for k in case["calls"]) and sum(case["calls"]) <= 150
+        assert len(case["sets"]) == len(case["calls"]) - 1
+        assert len(case["debye"]) <= 3 and len(case["lorentz"]) <= 2 and len(case["sheets"]) <= 3 and len(case["elements"]) <= 4 and len(case["magnetic"]) <= 2
+        assert all(1 <= e["hi"][e["dir"]] - e["lo"][e["dir"]] <= 5 for e in case["elements"])
+        assert eval(repr(case)) == case                      # printable, and reproducible from what the log prints
+        try:
+            sim = fuzz_parity.corrections_case_sim(case)
+        except ValueError as exc:
+            refused.append((q, str(exc)))
+            continue
+        accepted += 1
+        have = fuzz_parity.corrections_present(sim)
+        assert len(have) >= 3, (q, have, case)
+        count.update(have)
+        how_many.append(len(have))
+        seen |= features(case, sim)
+    print(f"{accepted} of {ncases} accepted; refused: {refused}; cases per correction: {dict(count)}; corrections per case: {sorted(how_many)}")
+    assert 6 * accepted >= 5 * ncases, refused
+    assert all(count[name] >= 4 for name in NAMES), count
+    assert how_many.count(7) >= 2 and 3 * sum(h >= 5 for h in how_many) >= accepted, how_many
+    assert not WANTED - seen, sorted(WANTED - seen)
+
+
+def test_same_seed_same_cases():
+    first = fuzz_parity.draw_corrections_case(np.random.default_rng(5))
+    rng = np.random.default_rng(5)
+    assert fuzz_parity.draw_corrections_case(rng) == first and fuzz_parity.draw_corrections_case(rng) != first
+
+
+def test_reference_side_of_the_first_cases_moves_everywhere(oracle_lib):
+    """The first cases of the batch stepped on the composed restatement alone: finite, non-zero, every state of every correction present
+    off zero, the plane wave's lists changing V and I on their elements."""
+    rng = np.random.default_rng(fuzz_parity.CORRECTIONS_BATCH[1])
+    ran, have = 0, set()
+    for q in range(8):
+        case = fuzz_parity.draw_corrections_case(rng)
+        try:
+            problems, _ = fuzz_parity.run_corrections_case(case, None, oracle_lib)
+        except ValueError:
+            continue
+        assert problems == [], (q, case, problems)
+        have |= fuzz_parity.corrections_present(fuzz_parity.corrections_case_sim(case))
+        ran += 1
+    assert ran >= 7 and have == set(NAMES), (ran, have)
+
+
+def test_composed_with_conformal_faces_alone_is_restated_conformal(oracle_lib):
+    nsteps = 40
+    a = RestatedConformal(sphere_sim(nr_ts=nsteps, tilted_disc=True), oracle_lib, seed=5)
+    b = fuzz_parity.Composed(sphere_sim(nr_ts=nsteps, tilted_disc=True), oracle_lib, seed=5)
+    assert b.conf is not None and b.pw is None and b.lor.lor is None and b.lor.mag is None and not b.lor.w
+    g = a.sim.grid
+    probe = (np.array([g.flat(7, 10, 5), g.flat(12, 5, 4)], np.int64), np.array([2, 0], np.int8), np.array([1.0, -2.0], np.float32))
+    pa, pb = a.e.add_probe(1, *probe), b.e.add_probe(1, *probe)
+    for r in (a, b):
+        r.run(nsteps // 2)
+        r.set_field(1, 2, np.full(r.e.local_shape, 1e-4, np.float32))
+        r.run(nsteps // 2)
+    assert a.iprev.size > 100 and np.all(a.iprev != 0)
+    assert np.array_equal(a.e.fields(), b.e.fields()) and np.array_equal(a.iprev, b.conf.iprev)
+    sa, sb = a.e.get_probe(pa), b.e.get_probe(pb)
+    assert sa.size == nsteps and np.abs(sa).max() > 0 and np.array_equal(sa, sb)
+
+
+def test_composed_with_lorentz_media_alone_is_restated_lorentz(oracle_lib):
+    nsteps = 40
+    mk = lambda: lorentz_cavity(lambda s: s.add_lorentz_material("block", 2.0, 0.0, TWO_PI * np.array([8e9, 6e9]), TWO_PI * np.array([0.0, 12e9]),
+                                                                 [4e9, 1e9]).add_box([4, 4, 3], [9, 8, 8]), nr_ts=nsteps)
+    a = RestatedLorentz(mk(), oracle_lib, seed=4)
+    b = fuzz_parity.Composed(mk(), oracle_lib, seed=4)
+    assert b.top is b.lor and b.conf is None and b.pw is None
+    a.run(nsteps)
+    b.run(nsteps)
+    assert np.abs(a.lor["x"][0]).max() > 0 and np.array_equal(a.e.fields(), b.e.fields())
+    for c in range(3):
+        assert np.array_equal(a.lor["x"][c], b.lor.lor["x"][c]) and np.array_equal(a.lor["vprev"][c], b.lor.lor["vprev"][c])
+    assert fuzz_parity.corrections_reference_problems(b) == []
+
+
+def test_composed_with_a_plane_wave_and_conformal_faces_is_the_pair_it_was(oracle_lib):
+    """RestatedPlaneWave around RestatedConformal, as test_planewave_model_cpu.restating_build nests them, against the composed one whose
+    conformal layer steps an (empty) inner restatement."""
+    nsteps = 60
+    mk = lambda: _placed(lambda s: s.add_metal("ball").add_sphere((12.3, 11.8, 12.1), 2.4), conformal=True, nr_ts=nsteps)
+    a = RestatedPlaneWave(mk(), oracle_lib, make=lambda s, l: RestatedConformal(s, l))
+    b = fuzz_parity.Composed(mk(), oracle_lib)
+    assert b.pw is not None and b.conf is not None
+    a.run(nsteps)
+    b.run(nsteps)
+    assert all(b.pw_changed) and np.abs(a.e.fields()).max() > 0 and np.all(a.inner.iprev != 0)
+    assert np.array_equal(a.e.fields(), b.e.fields()) and np.array_equal(a.inner.iprev, b.conf.iprev)
+
+
+@pytest.mark.parametrize("mur", [False, True], ids=["pec", "one-mur-face"])
+def test_overlap_reference_tells_every_correction_apart(oracle_lib, mur):
+    """The hand tables of corrections_overlap_cases.py on the reference alone: the lists do overlap where the case says, the run is
+    finite and every state moves, the V-probes kept here are the oracle's own (sampled in front of every E-side correction), the
+    I-probes are not (sampled behind every H-side one), and dropping any one correction changes the values the GPU test compares on the
+    shared edge or face itself."""
+    ref = oc.reference(oracle_lib, mur)
+    T = ref.T
+    key = lambda el: (int(el[0]), oc.flat(*el[1:]))
+    listed = lambda idx, comp: set(zip(map(int, comp), map(int, idx)))
+    for edge, box in ((oc.A, "debye"), (oc.B, "lorentz")):
+        assert key(edge) in listed(*T["sheets"][:2]) & listed(*T["elements"][:2]) & listed(*T["pw"].E[:2])
+        c, i, j, k = edge
+        lo, w = T[box][3][c], T[box][5][c]
+        assert w[k - lo[2], j - lo[1], i - lo[0]] != 0 and ref.e.get_operator()[1][c][k, j, i] != 0
+    c, i, j, k = oc.F
+    lo = T["magnetic"][2][c]
+    assert T["magnetic"][4][c][k - lo[2], j - lo[1], i - lo[0]] != 0
+    assert key(oc.F) in listed(T["conformal"][1], T["conformal"][0]) & listed(*T["pw"].H[:2])
+    assert np.isfinite(ref.fields).all() and all(np.abs(a).max() > 0 for name in ref.state for a in ref.state[name])
+    for pid, s in zip(ref.own_v, ref.v_series):
+        assert np.array_equal(ref.e.get_probe(pid)[:oc.STEPS], np.array(s)) and np.abs(s).max() > 0
+    at = lambda r, kind, el: r.fields[kind][el[0]][el[3], el[2], el[1]]
+    for name in oc.NAMES:
+        d = oc.reference(oracle_lib, mur, name)
+        assert not np.array_equal(d.fields, ref.fields), name
+        if name in ("magnetic", "conformal", "pw_h"):
+            assert at(d, 1, oc.F) != at(ref, 1, oc.F) and not np.array_equal(d.i_series[0], ref.i_series[0]), name
+            assert np.abs(d.i_acc[0] - ref.i_acc[0]).max() > 1e-6 * np.abs(ref.i_acc[0]).max(), name
+        else:
+            shared = [oc.A, oc.B] if name in ("sheets", "elements", "pw_e") else [oc.A] if name == "debye" else [oc.B]
+            for q, el in enumerate([oc.A, oc.B]):
+                if el in shared:
+                    assert at(d, 0, el) != at(ref, 0, el), (name, el)
+                    assert not np.array_equal(d.v_series[q], ref.v_series[q]), (name, el)
