@@ -54,6 +54,8 @@ CONFORMAL_SYMBOLS = ["fdtd_conformal_set", "fdtd_conformal_get", "fdtd_voxel_fra
 SAR_SYMBOLS = ["fdtd_sar_local", "fdtd_sar_average"]
 # include/fdtd_hip_planewave.h: plane-wave excitation on a total-field / scattered-field box, likewise
 PLANEWAVE_SYMBOLS = ["fdtd_planewave_set"]
+# include/fdtd_hip_fields.h: field dumps (E, H, J, rot-H on a point lattice) on the device, likewise
+FIELDS_SYMBOLS = ["fdtd_field_interp"]
 # FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
 MAX_BOXES = 64
 
@@ -244,7 +246,19 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    fields_sig = {"fdtd_field_interp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p, p, p, p, p])}
+    assert sorted(fields_sig) == sorted(FIELDS_SYMBOLS)
+    for name, (res, args) in fields_sig.items():     # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_fields(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the field-dump entry point (include/fdtd_hip_fields.h)."""
+    return all(hasattr(lib, n) for n in FIELDS_SYMBOLS)
 
 
 def has_sar(lib: C.CDLL) -> bool:
@@ -1007,6 +1021,50 @@ def sar_device(lib: C.CDLL, device: int = 0):
     if os.environ.get("FDTD_SAR", "").lower() == "host" or not has_sar(lib):
         return None
     return (lambda *a: sar_local_raw(lib, *a, device=device)), (lambda *a: sar_average_raw(lib, *a, device=device))
+
+
+def field_interp_raw(lib: C.CDLL, kind, mode, lines, lo, hi, V=None, I=None, kappa=None, sub=(1, 1, 1), device: int = 0):
+    """fdtd_field_interp: field [3][nz][ny][nx], complex128 or float64 — fields.interp_spec's result, bit for bit (same arguments)."""
+    from . import fields as _fields
+    if not has_fields(lib):
+        raise FdtdError("this library has no device field dumps (fdtd_field_interp)")
+    lines, lo, hi, sub = _fields.check_args(kind, mode, lines, lo, hi, sub)
+    rlo, _ = _fields.region(lo, hi)
+    rshape = tuple(hi[a] - rlo[a] + 1 for a in (2, 1, 0))
+    src = I if _fields.NEEDS_I[kind] else V
+    if src is None or len(src) != 3:
+        raise ValueError(f"field dump: kind {kind} needs the three recorded {'face currents I' if _fields.NEEDS_I[kind] else 'edge voltages V'}")
+    src = [np.ascontiguousarray(a) for a in src]
+    cplx = [np.iscomplexobj(a) for a in src]
+    if any(cplx) != all(cplx):
+        raise ValueError("field dump: the three recorded arrays must be all real or all complex")
+    src = [_arr(a, np.complex128 if cplx[0] else np.float64) for a in src]
+    kap = [None] * 3
+    if kind == "J":
+        if kappa is None or len(kappa) != 3:
+            raise ValueError("field dump: kind J needs the three edge conductivities")
+        kap = [_arr(k, np.float64) for k in kappa]
+    if any(a.shape != rshape for a in src) or any(k is not None and k.shape != rshape for k in kap):
+        raise ValueError(f"field dump: the recorded arrays and conductivities must cover the region [nz][ny][nx] = {rshape}")
+    nx, ny, nz = _fields.out_counts(mode, lo, hi, sub)
+    out = np.empty((3, nz, ny, nx), np.complex128 if cplx[0] else np.float64)
+    i32 = lambda v: _arr(v, np.int32)
+    n_a, lo_a, hi_a, sub_a = i32([l.size for l in lines]), i32(lo), i32(hi), i32(sub)
+    rc = lib.fdtd_field_interp(int(device), int(_fields.KINDS[kind]), int(mode), 2 if cplx[0] else 1, _ptr(n_a), _ptr(lo_a), _ptr(hi_a),
+                               _ptr(sub_a), _ptr(lines[0]), _ptr(lines[1]), _ptr(lines[2]), _ptr(src[0]), _ptr(src[1]), _ptr(src[2]),
+                               _ptr(kap[0]), _ptr(kap[1]), _ptr(kap[2]), _ptr(out))
+    if rc != 0:
+        msg = lib.fdtd_last_error(None)
+        raise FdtdError(f"fdtd_field_interp failed ({rc}): {msg.decode() if msg else ''}")
+    return out
+
+
+def fields_device(lib: C.CDLL, device: int = 0):
+    """What Simulation.field hands to fields.evaluate: fdtd_field_interp of csrc/fields.hip when `lib` exports it and FDTD_FIELDS is
+    not "host", else None (the numpy specification, fields.interp_spec)."""
+    if os.environ.get("FDTD_FIELDS", "").lower() == "host" or not has_fields(lib):
+        return None
+    return lambda *a: field_interp_raw(lib, *a, device=device)
 
 
 def default_rasteriser(lib: C.CDLL, device: int = 0):

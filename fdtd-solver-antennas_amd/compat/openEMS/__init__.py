@@ -12,3 +12,6 @@ _api = _il.import_module("fdtd-solver-antennas_amd.openems_api")
 openEMS = _api.openEMS
 from . import physical_constants  # noqa: E402,F401
 import CSXCAD  # noqa: E402,F401  (the reference also does `from openEMS import CSXCAD`, fixed.py:100)
+# the field dumps' result type and writers (openEMS.AddFieldDump / GetFieldDump are methods of the class above)
+fields = _il.import_module("fdtd-solver-antennas_amd.fields")
+FieldDump = fields.FieldDump

@@ -528,10 +528,12 @@ class ContinuousStructure:
         """CSXCAD's dump box, for the SAR dump types only: ``dump_type`` 20 = local SAR, 21 = 1 g, 22 = 10 g averaged, at the
         frequencies ``frequency`` [Hz]; ``AddBox`` on the returned property places it (one box), ``openEMS.GetSAR(name)`` returns the
         result after ``Run`` (sar.SARResult; no HDF5 file is written).  ``sar_method``: "ieee" (default) or "simple".  Field dumps
-        (every other dump_type) are refused; other keywords (dump_mode, file_type ...) are logged and have no effect."""
+        (every other dump_type) are refused here — they have their own entry point, ``openEMS.AddFieldDump``; other keywords
+        (dump_mode, file_type ...) are logged and have no effect."""
         if dump_type not in self.SAR_DUMP_MASS:
             raise ValueError(f"AddDump '{name}': dump_type {dump_type!r} is not supported by the HIP backend: out of scope — field dumps are "
-                             f"not supported (the SAR dump types 20, 21 and 22 are)")
+                             f"not supported (the SAR dump types 20, 21 and 22 are) by AddDump; the field dump types 0..3 and 10..13 have "
+                             f"their own entry point, openEMS.AddFieldDump(name, dump_type, start, stop, ...)")
         f = [] if frequency is None else [float(v) for v in np.atleast_1d(frequency)]
         if not f or not all(np.isfinite(v) and v > 0 for v in f):
             raise ValueError(f"AddDump '{name}': a SAR dump needs frequency=[...] with values > 0")
@@ -706,6 +708,8 @@ class openEMS:
         self.sim: Optional[Simulation] = None
         self.stats = None
         self._sar = {}                 # (dump name, frequency) -> sar.SARResult of the last Run
+        self._field_dumps = {}         # name -> the arguments of AddFieldDump
+        self._fields = {}              # (dump name, frequency or timestep taken) -> fields.FieldDump of the last Run
 
     @property
     def calls(self):
@@ -774,6 +778,43 @@ class openEMS:
         self.calls_log.add("CreateNF2FFBox")
         self._nf2ff = nf2ff(self, name, start, stop)
         return self._nf2ff
+
+    def AddFieldDump(self, name, dump_type, start, stop, *, dump_mode=1, frequency=None, timesteps=None, sub_sampling=(1, 1, 1),
+                     file_type=0):
+        """A field dump box, start / stop in drawing units.  ``dump_type`` as upstream: 0 / 1 / 2 / 3 = E / H / J / rot-H in the time
+        domain (``timesteps=[...]``: snapshots at the recorder's samples nearest to them), 10 / 11 / 12 / 13 the same in the
+        frequency domain (``frequency=[...]`` in Hz).  ``dump_mode`` 0 raw, 1 node-interpolated, 2 cell-interpolated;
+        ``sub_sampling`` keeps every s-th point per axis; ``file_type`` 0 writes one ASCII VTK rectilinear grid per frequency or
+        snapshot into sim_path, 1 one .npz (no HDF5).  ``GetFieldDump(name)`` returns the result after ``Run`` (fields.FieldDump).
+        CSX.AddDump keeps refusing these types: its boxes come by AddBox, after the call, and a scene is built from them."""
+        from . import fields as _fields
+        self.calls_log.add("AddFieldDump", name=name, dump_type=dump_type, start=list(start), stop=list(stop), dump_mode=dump_mode,
+                           frequency=None if frequency is None else [float(v) for v in np.atleast_1d(frequency)],
+                           timesteps=None if timesteps is None else [int(v) for v in np.atleast_1d(timesteps)],
+                           sub_sampling=list(sub_sampling), file_type=file_type)
+        if dump_type not in _fields.DUMP_TYPES:
+            raise ValueError(f"AddFieldDump '{name}': dump_type {dump_type!r} is not a field dump type — "
+                             + ", ".join(f"{t} ({n})" for t, n in sorted(_fields.DUMP_TYPE_NAMES.items()))
+                             + "; the SAR dump types 20, 21 and 22 go through CSX.AddDump")
+        if name in self._field_dumps:
+            raise ValueError(f"AddFieldDump '{name}' is defined twice")
+        kind, in_freq = _fields.DUMP_TYPES[dump_type]
+        if frequency is not None and timesteps is not None:
+            raise ValueError(f"AddFieldDump '{name}': takes frequency=[...] or timesteps=[...], not both")
+        if in_freq and frequency is None:
+            raise ValueError(f"AddFieldDump '{name}': dump_type {dump_type} ({_fields.DUMP_TYPE_NAMES[dump_type]}) is a frequency-domain dump and needs "
+                             f"frequency=[...]" + (" (timesteps= belongs to the time-domain types 0..3)" if timesteps is not None else ""))
+        if not in_freq and timesteps is None:
+            raise ValueError(f"AddFieldDump '{name}': dump_type {dump_type} ({_fields.DUMP_TYPE_NAMES[dump_type]}) is a time-domain dump and needs "
+                             f"timesteps=[...]" + (" (frequency= belongs to the frequency-domain types 10..13)" if frequency is not None else ""))
+        if dump_mode not in (0, 1, 2):
+            raise ValueError(f"AddFieldDump '{name}': dump_mode must be 0 (raw), 1 (node-interpolated) or 2 (cell-interpolated), got {dump_mode!r}")
+        if file_type not in (0, 1):
+            raise ValueError(f"AddFieldDump '{name}': file_type must be 0 (vtk) or 1 (npz; HDF5 is not written), got {file_type!r}")
+        self._field_dumps[name] = dict(kind=kind, mode=int(dump_mode), start=np.asarray(start, float), stop=np.asarray(stop, float),
+                                       freqs=None if frequency is None else [float(v) for v in np.atleast_1d(frequency)],
+                                       timesteps=None if timesteps is None else [int(v) for v in np.atleast_1d(timesteps)],
+                                       sub_sampling=tuple(sub_sampling), file_type=int(file_type), dump_type=int(dump_type))
 
     # -- run ------------------------------------------------------------------------------------------
     @staticmethod
@@ -863,10 +904,10 @@ class openEMS:
             freqs = [self._f0] if self._nf2ff_freqs is None else list(self._nf2ff_freqs)
 
         dumps = [p for p in self._csx.properties if p.kind == "Dump"]
-        dump_freqs = sorted({f for p in dumps for f in p.params["frequency"]})
+        dump_freqs = sorted({f for p in dumps for f in p.params["frequency"]} | {f for d in self._field_dumps.values() for f in d["freqs"] or []})
 
         def make(fr):
-            if fr is not None and dump_freqs:          # a running DFT accumulates the SAR frequencies too
+            if fr is not None and dump_freqs:          # a running DFT accumulates the SAR and field-dump frequencies too
                 fr = np.unique(np.concatenate([np.atleast_1d(np.asarray(fr, float)), dump_freqs]))
             sim = Simulation(grid, vox, f0=self._f0, fc=self._fc, boundary=bc, nr_ts=int(min(self.NrTS, 2**31 - 2)),
                              end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode,
@@ -877,10 +918,13 @@ class openEMS:
                 b = p.boxes[0]
                 sim.add_sar_box(p.name, b.start * grid_unit, b.stop * grid_unit, p.params["frequency"],
                                 ContinuousStructure.SAR_DUMP_MASS[p.params["dump_type"]], p.params["sar_method"])
+            for name, d in self._field_dumps.items():
+                sim.add_field_box(name, d["start"] * grid_unit, d["stop"] * grid_unit, d["kind"], mode=d["mode"], freqs=d["freqs"],
+                                  timesteps=d["timesteps"], sub_sampling=d["sub_sampling"])
             return sim
         grid_unit = self._csx.GetGrid().GetDeltaUnit()
         self.sim = make(freqs)
-        self._nf2ff_snap, self._box_cache, self._sar = False, {}, {}
+        self._nf2ff_snap, self._box_cache, self._sar, self._fields = False, {}, {}, {}
         if self._nf2ff is not None and self.sim.nf2ff_mode == "dft" and self._nf2ff_freqs is None:
             self.sim = make(nf2ff_comb(self._f0))     # no time-domain record: a comb, CalcNF2FF snaps to it
             self._nf2ff_snap = True
@@ -903,9 +947,25 @@ class openEMS:
             self._box_cache = {tuple(float(x) for x in f): self.sim.nf2ff_boxes(allreduce, freqs=f)}
         # the SAR dumps, as upstream writes them during the run: every dump at each of its frequencies (stats.sar: counts and time)
         self._sar = {(p.name, f): self.sim.sar(p.name, f) for p in dumps for f in p.params["frequency"]}
+        # the field dumps, likewise: every dump at each of its frequencies or snapshots; the files go into sim_path below
+        field_report = {}
+        for name, d in self._field_dumps.items():
+            b = self.sim.field_boxes[name]
+            if b["freqs"] is not None:
+                got = [self.sim.field(name, freq=float(f)) for f in b["freqs"]]
+                self._fields.update({(name, float(f)): r for f, r in zip(b["freqs"], got)})
+            else:
+                got = [self.sim.field(name, timestep=int(t)) for t in dict.fromkeys(int(t) for t in b["timesteps"])]
+                self._fields.update({(name, int(r.timestep)): r for r in got})
+            field_report[name] = {**self.stats.fields[name], "dump_type": d["dump_type"], "file_type": d["file_type"],
+                                  "seconds": float(sum(r.seconds for r in got)), "device": all(r.device for r in got), "files": []}
         if sim_path and self._rank == 0:
             try:
                 os.makedirs(sim_path, exist_ok=True)
+                from . import fields as _fields
+                for name, d in self._field_dumps.items():
+                    got = [r for (n, _), r in self._fields.items() if n == name]
+                    field_report[name]["files"] = [os.path.basename(f) for f in _fields.write(sim_path, got, d["file_type"])]
                 nx, ny, nz = grid.shape
                 with open(os.path.join(sim_path, "fdtd_hip_run.json"), "w") as fh:
                     json.dump({"grid": [nx, ny, nz], "cells": grid.ncells, "dt": self.sim.dt,
@@ -916,6 +976,7 @@ class openEMS:
                                "halo_transports_failed": list(self.stats.transports_failed),
                                "schedule_fallback": self.stats.schedule_fallback,
                                **({"sar": self.stats.sar} if self.stats.sar else {}),
+                               **({"fields": field_report} if field_report else {}),
                                **({"disc_materials": _disc_summary(sc, grid, vox)} if vox.cell_voxel is not None else {})}, fh)
                 # a plane wave: the excitation signal as upstream's two-column `et` file (time, value), which its RCS post-processing
                 # reads for the incident spectrum (P_rad of CalcNF2FF over the spectrum of et)
@@ -952,6 +1013,25 @@ class openEMS:
         if normalise_to is None and (name, f) in self._sar:
             return self._sar[(name, f)]
         return self.sim.sar(name, f, normalise_to=normalise_to)
+
+    def GetFieldDump(self, name, freq=None, timestep=None):
+        """The result of the field dump `name` (AddFieldDump): a fields.FieldDump at `freq` (default: the dump's first frequency) or
+        at the recorder sample nearest to `timestep` (default: its first)."""
+        if self.sim is None or self.stats is None:
+            raise RuntimeError("Run() first")
+        if name not in self._field_dumps:
+            raise KeyError(f"no field dump '{name}'")
+        b = self.sim.field_boxes[name]
+        if b["freqs"] is not None and timestep is None:
+            key = (name, float(b["freqs"][0] if freq is None else freq))
+        elif b["freqs"] is None and freq is None:
+            t = int(b["timesteps_asked"][0] if timestep is None else timestep)
+            key = (name, int(np.clip((t + self.sim.dft_every // 2) // self.sim.dft_every, 0, self.sim.dft_nsamples - 1)) * self.sim.dft_every)
+        else:
+            key = None
+        if key in self._fields:
+            return self._fields[key]
+        return self.sim.field(name, freq=freq, timestep=timestep)
 
     def _calc_nf2ff(self, freq, theta_deg, phi_deg, radius, center):
         if self.sim is None or self._nf2ff is None or self.sim.nf2ff_box is None:

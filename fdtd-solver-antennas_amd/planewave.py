@@ -302,11 +302,11 @@ def check_box(grid: RectGrid, pw: PlaneWave, cpml_cells: Sequence[int] = (0,) * 
 
 def check_placement(grid: RectGrid, pw: PlaneWave, *, cpml_cells: Sequence[int] = (0,) * 6, kinds: Sequence[str] = ("PEC",) * 6,
                     eps_r=None, kappa=None, mu_r=None, sigma_m=None, pec=None, sheets=None, elements=None, debye=None, lorentz=None,
-                    conformal=None, ports=(), dft_boxes=(), sar_boxes=None) -> None:
+                    conformal=None, ports=(), dft_boxes=(), sar_boxes=None, field_boxes=None) -> None:
     """Refuse (ValueError) a box the corrections cannot serve: see the rules in DESIGN.  eps_r ... sigma_m: per cell
     [nz-1][ny-1][nx-1]; pec: bool [3][nz][ny][nx]; sheets / elements: objects with idx, comp; debye / lorentz: with cell_medium and
     names; conformal: conformal.ConformalFaces; ports: scene.PortOnGrid; dft_boxes: (kind, comp, lo, hi) of the recording requests;
-    sar_boxes: {name: {"lo", "hi"}}."""
+    sar_boxes: {name: {"lo", "hi"}}; field_boxes: {name: {"rlo", "hi", "kind"}} (the recorded region; kinds H and rotH record faces)."""
     check_box(grid, pw, cpml_cells, kinds)
     nx, ny, nz = grid.shape
     lo, hi = pw.lo, pw.hi
@@ -384,3 +384,11 @@ def check_placement(grid: RectGrid, pw: PlaneWave, *, cpml_cells: Sequence[int] 
             if all(b["lo"][a] <= v <= b["hi"][a] for a, v in enumerate((i, j, k))):
                 raise ValueError(f"{who}: SAR box '{name}' records the surface edge {at((c, g))}: it would hold a mixed field — keep it strictly "
                                  f"inside the plane-wave box or strictly outside")
+    for name, b in (field_boxes or {}).items():
+        on_faces = b["kind"] in ("H", "rotH")
+        for c, g in sorted(faces if on_faces else edges):
+            k, r = divmod(g, nx * ny)
+            j, i = divmod(r, nx)
+            if all(b["rlo"][a] <= v <= b["hi"][a] for a, v in enumerate((i, j, k))):
+                raise ValueError(f"{who}: field box '{name}' records the {'outer face' if on_faces else 'surface edge'} {at((c, g))}: it would hold "
+                                 f"a mixed field — keep it (and the node below its low corner) strictly inside the plane-wave box or strictly outside")

@@ -24,6 +24,7 @@ from . import magnetic as _magnetic
 from . import conformal as _conformal
 from . import sar as _sar
 from . import planewave as _planewave
+from . import fields as _fields
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox, calc_nf2ff
@@ -154,6 +155,7 @@ class RunStats:
     magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
     conformal: Optional[dict] = None          # conformal PEC boundaries (conformal.py): faces per component, R, dt factor, faces clamped
     planewave: Optional[dict] = None          # plane-wave excitation (planewave.py): direction, e0, the box in nodes, entries per list
+    fields: Optional[dict] = None             # field boxes (fields.py): per name the kind, mode, box and points and, once Simulation.field has run, the interpolation time and device yes/no
     sar: Optional[dict] = None                # SAR boxes (sar.py): per name the voxels, tissue voxels, mass, method and, once Simulation.sar has run, status counts and averaging time
 
 
@@ -215,6 +217,7 @@ class Simulation:
         # what add_sar_box needs to set the recorder / DFT up itself when there is no NF2FF box
         self._mode_asked, self._dft_oversample, self._rec_budget = nf2ff_mode, float(dft_oversample), rec_budget_bytes
         self.sar_boxes, self._sar_ids, self._sar_report = {}, {}, {}
+        self.field_boxes, self._field_ids, self._field_report, self._kap_e = {}, {}, {}, None
         if nf2ff_freqs is not None:
             self.nf2ff_freqs = np.atleast_1d(np.asarray(nf2ff_freqs, float))
             n = grid.shape
@@ -343,7 +346,7 @@ class Simulation:
         _planewave.check_placement(self.grid, self.plane_wave, cpml_cells=self.bc.face_cells(), kinds=self.bc.kinds, eps_r=v.eps_r, kappa=v.kappa,
                                    mu_r=getattr(v, "mu_r", None), sigma_m=getattr(v, "sigma_m", None), pec=v.pec, sheets=self.sheets,
                                    elements=self.elements, debye=self.debye, lorentz=self.lorentz, conformal=self.conformal, ports=v.ports,
-                                   dft_boxes=reqs, sar_boxes=self.sar_boxes)
+                                   dft_boxes=reqs, sar_boxes=self.sar_boxes, field_boxes=self.field_boxes)
 
     @property
     def op(self) -> ECOperator:
@@ -389,6 +392,8 @@ class Simulation:
             raise _capi.FdtdError("plane-wave excitation needs a single slab (world = 1): a decomposed run with a plane wave is not supported")
         if self.sar_boxes and world > 1:
             raise _capi.FdtdError("SAR boxes need a single slab (world = 1): a decomposed run with SAR boxes is not supported")
+        if self.field_boxes and world > 1:
+            raise _capi.FdtdError("field boxes need a single slab (world = 1): a decomposed run with field boxes is not supported")
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
@@ -436,7 +441,7 @@ class Simulation:
             uid = e.add_probe(KIND_V, p.v_idx, p.v_comp, p.v_w)
             iid = e.add_probe(KIND_I, p.i_idx, p.i_comp, p.i_w)
             self._port_probe_ids.append((uid, iid))
-        if self.nf2ff_box is not None or self.sar_boxes:
+        if self.nf2ff_box is not None or self.sar_boxes or self.field_boxes:
             if self.nf2ff_mode == "record":
                 try:
                     e.set_recorder(self.dft_every, self.dft_nsamples)
@@ -455,10 +460,13 @@ class Simulation:
         return e
 
     def _register_boxes(self, e: Engine):
-        """The NF2FF faces, then per SAR box its three voltage boxes (kind V, components 0..2) on the node box."""
+        """The NF2FF faces, then per SAR box its three voltage boxes (kind V, components 0..2) on the node box, then per field box
+        its three voltage or current boxes on the recorded region (fields.region)."""
         if self.nf2ff_box is not None:
             self._nf_ids = self.nf2ff_box.register(e)
         self._sar_ids = {name: [e.add_dft_box(KIND_V, c, b["lo"], b["hi"]) for c in range(3)] for name, b in self.sar_boxes.items()}
+        self._field_ids = {name: [e.add_dft_box(KIND_I if _fields.NEEDS_I[b["kind"]] else KIND_V, c, b["rlo"], b["hi"]) for c in range(3)]
+                           for name, b in self.field_boxes.items()}
 
     # ---------------------------------------------------------------------------------------------
     def add_sar_box(self, name, start, stop, freqs, mass, method: str = "ieee"):
@@ -498,7 +506,7 @@ class Simulation:
         if rho is None or not np.any(rho[sl] > 0):
             raise ValueError(f"SAR box '{name}' holds no cell of a material with density > 0: there is no tissue to average over "
                              f"(AddMaterial(..., density=) / Scene.add_material(..., density=))")
-        used = (0 if self.nf2ff_box is None else len(self.nf2ff_box.requests)) + 3 * len(self.sar_boxes)
+        used = (0 if self.nf2ff_box is None else len(self.nf2ff_box.requests)) + 3 * len(self.sar_boxes) + 3 * len(self.field_boxes)
         if used + 3 > _capi.MAX_BOXES:
             raise ValueError(f"SAR box '{name}': its three voltage boxes would make {used + 3} recording boxes, a context takes "
                              f"{_capi.MAX_BOXES} (FDTD_MAX_BOXES)")
@@ -583,6 +591,162 @@ class Simulation:
         return _sar.SARResult(name=name, freq=f, averaging_mass=b["mass"], method=b["method"], sar_local=s_loc, sar_avg=s_avg, status=status,
                               half_side=half, peak=peak, peak_cell=cell, peak_position=pos, P_abs=p_abs, mass=box_mass, counts=cnt,
                               x=ctr[0], y=ctr[1], z=ctr[2], device=calls is not None, seconds=secs, normalised_to=normalise_to)
+
+    # ---------------------------------------------------------------------------------------------
+    def add_field_box(self, name, start, stop, kind, *, mode: int = 1, freqs=None, timesteps=None, sub_sampling=(1, 1, 1)):
+        """A field box (before build): start / stop in metres, snapped to nodes; `kind` "E", "H", "J" or "rotH"; `mode` 0 raw, 1
+        node-interpolated, 2 cell-interpolated (fields.py); exactly one of `freqs` (spectra) and `timesteps` (snapshots, which need
+        nf2ff_mode='record' and snap to the recorder's samples).  Only the boxes the kind needs are recorded — three voltage boxes
+        (E, J) or three current boxes (H, rotH) on the box grown by one node on each low side — like the SAR boxes, in the mode the
+        run uses; without an NF2FF or SAR box the recorder / DFT is set up here, by the same rules."""
+        who = f"field box '{name}'"
+        if self.engine is not None:
+            raise ValueError(f"{who}: add_field_box comes before build")
+        if name in self.field_boxes:
+            raise ValueError(f"{who} is defined twice")
+        if kind not in _fields.KINDS:
+            raise ValueError(f"{who}: kind must be one of {sorted(_fields.KINDS)}, got {kind!r}")
+        if mode not in (_fields.MODE_RAW, _fields.MODE_NODE, _fields.MODE_CELL):
+            raise ValueError(f"{who}: mode must be 0 (raw), 1 (node-interpolated) or 2 (cell-interpolated), got {mode!r}")
+        if (freqs is None) == (timesteps is None):
+            raise ValueError(f"{who}: needs exactly one of freqs=[...] (spectra) and timesteps=[...] (snapshots)")
+        sub = tuple(int(v) for v in sub_sampling)
+        if len(sub) != 3 or min(sub) < 1 or any(int(v) != v for v in sub_sampling):
+            raise ValueError(f"{who}: sub_sampling must be three whole numbers >= 1")
+        f = ts = None
+        if freqs is not None:
+            f = np.atleast_1d(np.asarray(freqs, float))
+            if f.size == 0 or not np.all(np.isfinite(f)) or np.any(f <= 0):
+                raise ValueError(f"{who}: needs at least one frequency > 0")
+        else:
+            ts = np.atleast_1d(np.asarray(timesteps))
+            if ts.size == 0 or not np.all(np.isfinite(ts.astype(float))) or np.any(ts < 0) or np.any(ts != np.round(ts)):
+                raise ValueError(f"{who}: timesteps must be whole numbers >= 0")
+            ts = ts.astype(np.int64)
+        g = self.grid
+        lo = [g.snap(a, min(start[a], stop[a])) for a in range(3)]
+        hi = [g.snap(a, max(start[a], stop[a])) for a in range(3)]
+        for a in range(3):
+            if mode == _fields.MODE_CELL and hi[a] <= lo[a]:
+                raise ValueError(f"{who}: holds no whole cell along {'xyz'[a]} on this mesh (nodes {lo[a]}..{hi[a]}): cell interpolation needs one")
+        rlo, _ = _fields.region(lo, hi)
+        what = "current" if _fields.NEEDS_I[kind] else "voltage"
+        used = (0 if self.nf2ff_box is None else len(self.nf2ff_box.requests)) + 3 * len(self.sar_boxes) + 3 * len(self.field_boxes)
+        if used + 3 > _capi.MAX_BOXES:
+            raise ValueError(f"{who}: its three {what} boxes would make {used + 3} recording boxes, a context takes "
+                             f"{_capi.MAX_BOXES} (FDTD_MAX_BOXES)")
+        fresh = self.nf2ff_freqs is None      # no NF2FF box, no SAR or field box yet: the rules of __init__'s NF2FF block
+        keep = (self.nf2ff_freqs, self.nf2ff_fmax, self.nf2ff_mode, getattr(self, "dft_every", None), getattr(self, "dft_nsamples", None))
+        if fresh:
+            if self._mode_asked not in ("dft", "record", "auto"):
+                raise ValueError("nf2ff_mode must be 'dft', 'record' or 'auto'")
+            fmax = self.f0 + self.fc if f is None else max(self.f0 + self.fc, float(np.max(f)))
+            self.dft_every = max(1, int(np.floor(1.0 / (2.0 * fmax * self._dft_oversample * self.dt))))
+            self.dft_nsamples = self.nr_ts // self.dft_every + 1
+            self.nf2ff_freqs, self.nf2ff_fmax = (np.array([self.f0]) if f is None else f.copy()), fmax
+            self.nf2ff_mode = self._mode_asked
+        try:
+            nbytes = 4 * self.dft_nsamples * 3 * int(np.prod([hi[a] - rlo[a] + 1 for a in range(3)]))
+            mode_run = self.nf2ff_mode
+            if mode_run == "auto":
+                budget = int(os.environ.get("FDTD_REC_BUDGET_BYTES", 32 << 30)) if self._rec_budget is None else int(self._rec_budget)
+                mode_run = "record" if nbytes <= budget else "dft"
+            taken = None
+            if ts is not None:
+                if mode_run != "record":
+                    need = self.rec_bytes + nbytes
+                    raise ValueError(f"{who}: snapshots (timesteps=) are samples of the time-domain record, and this run keeps running DFT "
+                                     f"sums — nf2ff_mode='record' would take {need} bytes ({need / 2**30:.2f} GiB) of device memory")
+                taken = np.clip((ts + self.dft_every // 2) // self.dft_every, 0, self.dft_nsamples - 1) * self.dft_every
+            elif mode_run == "record":
+                if float(np.max(f)) > self.nf2ff_fmax * (1 + 1e-9):
+                    raise ValueError(f"{who}: frequency {float(np.max(f)):g} Hz is above the recorder's band ({self.nf2ff_fmax:g} Hz)")
+            else:
+                rec = np.asarray(self.nf2ff_freqs, float)
+                miss = [x for x in f if np.min(np.abs(rec - x)) > 1e-6 * max(x, 1.0)]
+                if miss:
+                    raise ValueError(f"{who}: frequency {miss[0]:g} Hz is not among nf2ff_freqs ({rec.tolist()}): the running DFT "
+                                     f"accumulates those only — add it to nf2ff_freqs or use nf2ff_mode='record'")
+            box = {"lo": tuple(lo), "hi": tuple(hi), "rlo": tuple(rlo), "kind": kind, "mode": int(mode), "freqs": f, "timesteps": taken,
+                   "timesteps_asked": ts, "sub": sub}
+            if self.plane_wave is not None:
+                self.field_boxes[name] = box
+                try:
+                    self._check_plane_wave()
+                finally:
+                    del self.field_boxes[name]
+        except ValueError:
+            if fresh:
+                self.nf2ff_freqs, self.nf2ff_fmax, self.nf2ff_mode = keep[:3]
+                if keep[3] is None:
+                    del self.dft_every, self.dft_nsamples
+            raise
+        self.nf2ff_mode = mode_run
+        self.rec_bytes += nbytes
+        self.field_boxes[name] = box
+        self._field_report[name] = {"kind": kind, "mode": int(mode), "lo": list(lo), "hi": list(hi), "sub_sampling": list(sub),
+                                    "points": list(_fields.out_counts(mode, lo, hi, sub)), "seconds": None, "device": None}
+
+    def edge_conductivity(self):
+        """The three kap_e arrays [nz][ny][nx] of the operator (ecoperator._edge_average of the cells' kappa as this run folds it)."""
+        if self._kap_e is None:
+            from .ecoperator import _edge_average
+            self._kap_e = [_edge_average(np.asarray(self.kappa_cells, np.float64), self.grid, c) for c in range(3)]
+        return self._kap_e
+
+    def field(self, name, freq=None, timestep=None) -> "_fields.FieldDump":
+        """The dump of field box `name`, after the run: at `freq` (default: the box's first frequency) the single-sided spectrum, scaled
+        like the port spectra; at `timestep` (default: the box's first) the recorder sample nearest to it — the result names the
+        timestep taken and its time.  Recorded spectra or samples -> csrc/fields.hip, or fields.py where the library has no
+        fdtd_field_interp or FDTD_FIELDS=host.  H and rotH are taken at the time of H, half a step after E."""
+        if name not in self.field_boxes:
+            raise KeyError(f"no field box '{name}' (defined: {sorted(self.field_boxes)})")
+        if self.engine is None or name not in self._field_ids:
+            raise RuntimeError("field dump: build and run first")
+        b = self.field_boxes[name]
+        kind, ids = b["kind"], self._field_ids[name]
+        half = 0.5 if _fields.H_TIME[kind] else 0.0
+        f = step = when = None
+        if b["timesteps"] is not None:
+            if freq is not None:
+                raise ValueError(f"field box '{name}' holds snapshots: ask with timestep=, not freq=")
+            t = int(b["timesteps"][0] if timestep is None else timestep)
+            s = int(np.clip((t + self.dft_every // 2) // self.dft_every, 0, self.dft_nsamples - 1))
+            if s * self.dft_every > int(self.engine.step):
+                raise ValueError(f"field box '{name}': timestep {s * self.dft_every} was not reached (the run made {int(self.engine.step)} timesteps)")
+            tw = np.zeros((self.dft_nsamples, 1, 2))
+            tw[s, 0, 0] = 1.0                          # one-hot: the transform returns the sample itself
+            A = [np.ascontiguousarray(self.engine.rec_transform(q, tw)[0][0].real) for q in ids]
+            step, when = s * self.dft_every, (s * self.dft_every + half) * self.dt
+        else:
+            if timestep is not None:
+                raise ValueError(f"field box '{name}' holds spectra: ask with freq=, not timestep=")
+            f = float(b["freqs"][0] if freq is None else freq)
+            if self.nf2ff_mode == "record":
+                if f > self.nf2ff_fmax * (1 + 1e-9):
+                    raise ValueError(f"field dump frequency {f:g} Hz is above the recorder's band ({self.nf2ff_fmax:g} Hz)")
+                tw = dft_twiddles(np.array([f]), self.dt, self.dft_every, self.dft_nsamples, half)
+                A = [self.engine.rec_transform(q, tw)[0][0] for q in ids]
+            else:
+                rec = np.asarray(self.nf2ff_freqs, float)
+                row = int(np.argmin(np.abs(rec - f)))
+                if abs(rec[row] - f) > 1e-6 * max(f, 1.0):
+                    raise ValueError(f"field dump frequency {f:g} Hz was not recorded (recorded: {rec.tolist()})")
+                A = [self.engine.get_dft_box(q)[0][row] for q in ids]
+            scale = 2.0 * self.dt * self.dft_every
+            A = [a * scale for a in A]
+        lo, hi, rlo, mode, sub = b["lo"], b["hi"], b["rlo"], b["mode"], b["sub"]
+        kap = None
+        if kind == "J":
+            sl = tuple(slice(rlo[a], hi[a] + 1) for a in (2, 1, 0))
+            kap = [np.ascontiguousarray(k[sl]) for k in self.edge_conductivity()]
+        call = _capi.fields_device(self.lib, self.device)
+        V, I = (None, A) if _fields.NEEDS_I[kind] else (A, None)
+        fld, secs = _fields.evaluate(kind, mode, self.grid.lines, lo, hi, V, I, kap, sub, call)
+        x, y, z = _fields.points(mode, self.grid.lines, lo, hi, sub)
+        self._field_report[name].update(seconds=secs, device=call is not None)
+        return _fields.FieldDump(name=name, type=kind, mode=mode, x=x, y=y, z=z, field=fld, freq=f, timestep=step, time=when,
+                                 offsets=_fields.offsets(kind, mode), device=call is not None, seconds=secs)
 
     def sheet_vi(self) -> np.ndarray:
         """float32 vi of the sheet edges, as the engine expands it: m (the edge's lumped-edge override, float32) times the separable
@@ -825,6 +989,7 @@ class Simulation:
         stats.magnetic = self.magnetic_info()
         stats.conformal = self.conformal_info()
         stats.planewave = self.planewave_info()
+        stats.fields = self._field_report if self.field_boxes else None  # Simulation.field fills in the seconds and device yes/no
         stats.sar = self._sar_report if self.sar_boxes else None      # Simulation.sar fills in the status counts and the averaging time
         stats.schedule = e.schedule_info()
         stats.mcells_per_s = self.grid.ncells * done / max(stats.seconds, 1e-9) / 1e6
