@@ -116,13 +116,13 @@ def receive(case, out):
     r, tv, pv = unit_vectors(th, ph)
     if where != "MI355X":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
-        from test_planewave_model_cpu import restating_build
+        from restatement import install
 
-        class _MP:          # the one call restating_build makes
+        class _MP:          # the one call install makes
             @staticmethod
             def setattr(obj, name, value):
                 setattr(obj, name, value)
-        restating_build(_MP)
+        install(_MP)
     fdtd, port, _ = scene(lib, 0.0, wave=(tv if pol == "theta" else pv, -r))
     fdtd.Run(os.path.join(out, f"rx{case}"), verbose=0, cleanup=True)
     f_res = json.load(open(os.path.join(out, "transmit.json")))["f_res"]

@@ -10,19 +10,19 @@ of 12 x 10 x 9 nodes with PEC faces (and again with a Mur face at x+, far from t
           H list, under an I-probe and inside an I-DFT box;
   and a few more elements per list that overlap in pairs or not at all.
 
-The reference applies the headers' statement lists in the headers' order, by the numpy functions the restatements use, on the oracle's
+The reference is restatement.Restatement with these raw tables: the headers' statement lists in the headers' order on the oracle's
 half-steps: Debye, Lorentz, sheets, elements, plane wave (E list) between the E phase and the H update, magnetic, conformal, plane wave
 (H list) behind the H update.  V-probes and V-DFT boxes read in front of every E-side correction (the oracle's own E phase samples
 them there), I-probes and I-DFT boxes behind every H-side one (kept here: the oracle samples I inside its H half-step)."""
 import numpy as np
 
 from conftest import pkg
-from helpers import seeded_fields
+from restatement import E_SIDE, ORDER, Restatement
 
 N = (12, 10, 9)
 STEPS, CALLS, SEED = 60, (25, 35), 11
 EVERY, FREQS = 5, np.array([8e9, 11e9])
-NAMES = ("debye", "lorentz", "sheets", "elements", "pw_e", "magnetic", "conformal", "pw_h")
+NAMES = ORDER
 A, B, F = (2, 6, 5, 4), (0, 6, 6, 3), (1, 6, 5, 4)
 V_PROBES = [([A], [1.0]), ([B], [-0.5])]
 I_PROBES = [([F], [1.0]), ([F, (2, 6, 5, 4)], [2.0, -1.0])]
@@ -156,48 +156,19 @@ def _slices(lo, hi, inclusive=False):
 
 
 class Ordered:
-    """The oracle's half-steps with the headers' statement lists applied in the headers' order.  After run(): .fields, .state (the
-    arrays the getters of the C ABI return, keyed as `hip_state`), .v_series / .i_series [probe][step] (double), .v_acc / .i_acc the
-    DFT sums of the boxes (complex128 [2 frequencies] + box shape)."""
+    """The hand tables stepped by restatement.Restatement (the headers' statement lists in the headers' order on the oracle's
+    half-steps), with the probes and DFT sums kept here.  After run(): .fields, .state (the arrays the getters of the C ABI return,
+    keyed as `hip_state`), .v_series / .i_series [probe][step] (double), .v_acc / .i_acc the DFT sums of the boxes (complex128
+    [2 frequencies] + box shape)."""
 
     def __init__(self, lib, T, mur=False):
         sim = overlap_sim(mur)
         self.sim, self.T = sim, T
-        e = self.e = sim.build(lib)
+        r = self.r = Restatement(sim, lib, seed=SEED, tables=T, before=self._before)
+        e = self.e = r.e
         self.own_v = [e.add_probe(0, *_list(el), np.array(w, np.float32)) for el, w in V_PROBES]
-        seeded_fields(e, SEED)
-        vi = e.get_operator()[1]
+        self.first = next(name for name in E_SIDE if name in r.parts)
         self.tw = twiddles(sim.dt)
-        self.n = 0
-        if "debye" in T:
-            al, om, be, lo, hi, w, _ = T["debye"]
-            sl = _slices(lo[2], hi[2])
-            self.deb = dict(sl=sl, vi=vi[2][sl].copy(), w=np.where(vi[2][sl] == 0, np.float32(0), w[2]), tab=(al[0], om[0], be[0]),
-                            vprev=np.zeros(w[2].shape, np.float32), u=np.zeros((al.shape[1],) + w[2].shape, np.float32))
-        if "lorentz" in T:
-            phi, gam, h, lo, hi, w, med = T["lorentz"]
-            sl = _slices(lo[0], hi[0])
-            m = med[0].astype(np.int64)
-            self.lor = dict(sl=sl, vi=vi[0][sl].copy(), w=np.where(vi[0][sl] == 0, np.float32(0), w[0]),
-                            tab=(np.moveaxis(phi[m], (-3, -2, -1), (0, 1, 2)).copy(), np.moveaxis(gam[m], (-2, -1), (0, 1)).copy(),
-                                 np.moveaxis(h[m], (-2, -1), (0, 1)).copy()),
-                            vprev=np.zeros(w[0].shape, np.float32), x=np.zeros((phi.shape[1], 2) + w[0].shape, np.float32))
-        if "sheets" in T:
-            idx, comp, svi, cls, al, b = T["sheets"]
-            self.sheet = dict(idx=idx, comp=comp, vi=svi, al=al[cls].T.copy(), b=b[cls].T.copy(), vprev=np.zeros(idx.size, np.float32),
-                              ib=np.zeros((al.shape[1], idx.size), np.float32))
-        if "elements" in T:
-            idx, comp, lvi, cls, phi, gam, h = T["elements"]
-            self.lum = dict(idx=idx, comp=comp, vi=lvi, phi=np.moveaxis(phi[cls], 0, -1).copy(), gam=gam[cls].T.copy(), h=h[cls].T.copy(),
-                            vprev=np.zeros(idx.size, np.float32), x=np.zeros((2, idx.size), np.float32))
-        if "magnetic" in T:
-            ta, tb, lo, hi, cls = T["magnetic"]
-            sl = [_slices(lo[c], hi[c]) for c in range(3)]
-            self.mag = dict(ta=ta, tb=tb, sl=sl, cls=cls, iprev=[e.get_field(1, c)[sl[c]].copy() for c in range(3)])
-        if "conformal" in T:
-            comp, idx, coef = T["conformal"]
-            self.conf = dict(comp=comp.astype(np.int64), idx=idx, coef=coef,
-                             iprev=np.array([e.get_field(1, int(c)).reshape(-1)[g] for c, g in zip(comp, idx)], np.float32))
         self.v_series = [[] for _ in V_PROBES]
         self.i_series = [[] for _ in I_PROBES]
         self.v_acc = [np.zeros((2,) + tuple(h - l + 1 for l, h in zip(lo[::-1], hi[::-1])), np.complex128) for _, lo, hi in V_BOXES]
@@ -205,62 +176,24 @@ class Ordered:
 
     def _sample(self, kind, Fs):
         series, acc, probes, boxes = ((self.v_series, self.v_acc, V_PROBES, V_BOXES) if kind == 0 else (self.i_series, self.i_acc, I_PROBES, I_BOXES))
+        n = self.r.n
         for q, (el, w) in enumerate(probes):
             s = 0.0
             for (c, i, j, k), wq in zip(el, w):
                 s = float(np.float32(wq)) * float(Fs[c][k, j, i]) + s
             series[q].append(s)
-        if self.n % EVERY == 0:
-            t = self.tw[kind][self.n // EVERY, :, 0] + 1j * self.tw[kind][self.n // EVERY, :, 1]
+        if n % EVERY == 0:
+            t = self.tw[kind][n // EVERY, :, 0] + 1j * self.tw[kind][n // EVERY, :, 1]
             for q, (c, lo, hi) in enumerate(boxes):
                 acc[q] += t[:, None, None, None] * Fs[c][_slices(lo, hi, True)].astype(np.float64)[None]
 
-    def _listed(self, s, Vs, fn):
-        V = np.array([Vs[c].reshape(-1)[g] for c, g in zip(s["comp"], s["idx"])], np.float32)
-        v = fn(V)
-        s["vprev"] = v
-        for q, (c, g) in enumerate(zip(s["comp"], s["idx"])):
-            Vs[c].reshape(-1)[g] = v[q]
+    def _before(self, name, kind, Fs):
+        if name == self.first:
+            self._sample(0, Fs)                               # V-probes and V-DFT boxes: in front of every E-side correction
 
     def step(self):
-        e, T = self.e, self.T
-        e.half_step(0)
-        Vs = [e.get_field(0, c) for c in range(3)]
-        self._sample(0, Vs)                                   # V-probes and V-DFT boxes: in front of every E-side correction
-        if "debye" in T:
-            d = self.deb
-            Vs[2][d["sl"]] = pkg("dispersion").correction(Vs[2][d["sl"]], d["vi"], d["w"], d["vprev"], d["u"], *d["tab"])
-        if "lorentz" in T:
-            d = self.lor
-            Vs[0][d["sl"]] = pkg("lorentz").correction(Vs[0][d["sl"]], d["vi"], d["w"], d["vprev"], d["x"], *d["tab"])
-        if "sheets" in T:
-            s = self.sheet
-            self._listed(s, Vs, lambda V: pkg("sheet").correction(V, s["vi"], s["vprev"], s["ib"], s["al"], s["b"]))
-        if "elements" in T:
-            s = self.lum
-            self._listed(s, Vs, lambda V: pkg("lumped").correction(V, s["vi"], s["vprev"], s["x"], s["phi"], s["gam"], s["h"]))
-        if "pw" in T:
-            pkg("planewave").apply(Vs, T["pw"], self.n, 0)
-        for c in range(3):
-            e.set_field(0, c, Vs[c])
-        e.half_step(1)
-        Is = [e.get_field(1, c) for c in range(3)]
-        if "magnetic" in T:
-            m = self.mag
-            for c in range(3):
-                if m["cls"][c].size:
-                    Is[c][m["sl"][c]] = pkg("magnetic").correction(Is[c][m["sl"][c]], m["iprev"][c], m["cls"][c], m["ta"], m["tb"])
-        if "conformal" in T:
-            f = self.conf
-            r = pkg("conformal").correction(np.stack(Vs), f["iprev"], f["comp"], f["idx"], f["coef"])
-            for q, (c, g) in enumerate(zip(f["comp"], f["idx"])):
-                Is[c].reshape(-1)[g] = r[q]
-        if "pw" in T:
-            pkg("planewave").apply(Is, T["pw"], self.n, 1)
-        for c in range(3):
-            e.set_field(1, c, Is[c])
-        self._sample(1, Is)                                   # I-probes and I-DFT boxes: behind every H-side correction
-        self.n += 1
+        self.r.step()
+        self._sample(1, self.r.I)                             # I-probes and I-DFT boxes: behind every H-side one
 
     def run(self, n=STEPS):
         for _ in range(n):
@@ -270,19 +203,19 @@ class Ordered:
 
     @property
     def state(self):
-        out = {}
+        r, out = self.r, {}
         if "debye" in self.T:
-            out["debye"] = (self.deb["vprev"], self.deb["u"])
+            out["debye"] = (r.debye.vprev[2], r.debye.u[2])
         if "lorentz" in self.T:
-            out["lorentz"] = (self.lor["vprev"], self.lor["x"])
+            out["lorentz"] = (r.lorentz.vprev[0], r.lorentz.x[0])
         if "sheets" in self.T:
-            out["sheets"] = (self.sheet["vprev"], self.sheet["ib"])
+            out["sheets"] = (r.sheets.vprev, r.sheets.ib)
         if "elements" in self.T:
-            out["elements"] = (self.lum["vprev"], self.lum["x"])
+            out["elements"] = (r.elements.vprev, r.elements.x)
         if "magnetic" in self.T:
-            out["magnetic"] = (self.mag["iprev"][0], self.mag["iprev"][1])
+            out["magnetic"] = (r.magnetic.iprev[0], r.magnetic.iprev[1])
         if "conformal" in self.T:
-            out["conformal"] = (self.conf["iprev"],)
+            out["conformal"] = (r.conformal.iprev,)
         return out
 
 

@@ -16,8 +16,8 @@ the energy to 1e-12, the NF2FF face spectra to 1e-6 of their largest entry (floa
                                                 # loop) against the oracle's half-steps plus the numpy restatement of the two corrections
                                                 # (draw_media_case / run_media_case below); tests/test_media_fuzz_cpu.py guards what the draw covers
     python tests/fuzz_parity.py --corrections ...   # scenes with at least three of the seven corrections of the step loop, often all of them (Debye and
-                                                # Lorentz media, sheets, elements, magnetic faces, conformal faces, a plane wave), against the composed
-                                                # restatement (draw_corrections_case / run_corrections_case); tests/test_corrections_fuzz_cpu.py guards the draw
+                                                # Lorentz media, sheets, elements, magnetic faces, conformal faces, a plane wave), against
+                                                # tests/restatement.py (draw_corrections_case / run_corrections_case); tests/test_corrections_fuzz_cpu.py guards the draw
 
 Lives under tests/ because it loads the oracle (test infrastructure); tests/test_round3_gpu.py::test_randomised_cases_equal_the_oracle
 runs a fixed-seed batch of it in the -m gpu suite.
@@ -410,34 +410,36 @@ def media_case_sim(case):
                            use_classes=case["classes"], nf2ff_mode="dft" if case["nf2ff"] == "none" else case["nf2ff"])
 
 
-def _restated(sim, oracle, seed):
+def _restatement():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_dispersion_model_cpu import Restated
-    return Restated(sim, oracle, seed=seed)
+    mod = importlib.import_module("restatement")
+    assert {"planewave" if name in ("pw_e", "pw_h") else name for name in mod.ORDER} == set(CORRECTION_NAMES)
+    return mod
 
 
 def media_reference_problems(r):
     """What the reference side must show by itself, so that a medium or a sheet the wave never reached cannot pass silently: finite and
     non-zero fields and states, every branch state of every dispersive edge the operator does not hold (w != 0, vi != 0) and the
-    branch currents of every sheet edge off zero — at one of Restated's checkpoints (the first step, every eighth, the end of a run():
-    a single state update cancels to exactly 0.0f about once in 2^24, which a few of 1e8 final values do)."""
+    branch currents of every sheet edge off zero — at one of the Restatement's checkpoints (the first step, every eighth, the end of a
+    run(): a single state update cancels to exactly 0.0f about once in 2^24, which a few of 1e8 final values do)."""
     r.note_moved()
     problems = []
     fo = r.e.fields()
     if not np.isfinite(fo).all() or not np.abs(fo).max() > 0:
         problems.append("reference fields not finite / all zero")
-    for c in range(len(r.w)):
-        if not r.w[c].size:
+    d = r.debye
+    for c in range(3 if d else 0):
+        if not d.w[c].size:
             continue
-        if not (np.isfinite(r.u[c]).all() and np.isfinite(r.vprev[c]).all()):
+        if not (np.isfinite(d.u[c]).all() and np.isfinite(d.vprev[c]).all()):
             problems.append(f"reference states of component {c} not finite")
-        live = (r.w[c] != 0) & (r.vi[c] != 0)
-        need = live[None] & (r.tab[c][1] != 0)           # (oma == 0: the padding poles of a shorter medium, which stay at rest)
-        if not live.any() or not np.all(r.u_moved[c][need]) or not np.all(r.vprev_moved[c][live]):
-            problems.append(f"component {c}: {np.count_nonzero(~r.u_moved[c][need])} branch states of {np.count_nonzero(need)} on dispersive edges never left zero")
-        if np.any(r.u[c][:, ~live] != 0) or np.any(r.vprev[c][~live] != 0):
+        live = (d.w[c] != 0) & (d.vi[c] != 0)
+        need = live[None] & (d.tab[c][1] != 0)           # (oma == 0: the padding poles of a shorter medium, which stay at rest)
+        if not live.any() or not np.all(d.u_moved[c][need]) or not np.all(d.vprev_moved[c][live]):
+            problems.append(f"component {c}: {np.count_nonzero(~d.u_moved[c][need])} branch states of {np.count_nonzero(need)} on dispersive edges never left zero")
+        if np.any(d.u[c][:, ~live] != 0) or np.any(d.vprev[c][~live] != 0):
             problems.append(f"component {c}: states of edges that are not dispersive edges moved")
-    if r.sheet is not None and not (np.isfinite(r.sheet["ib"]).all() and np.all(r.ib_moved.any(axis=0))):
+    if r.sheets is not None and not (np.isfinite(r.sheets.ib).all() and np.all(r.sheets.ib_moved.any(axis=0))):
         problems.append("reference: a sheet edge without branch current")
     return problems
 
@@ -450,7 +452,7 @@ def run_media_case(case, hip, oracle):
     os.environ.update(case["env"])
     try:
         so = media_case_sim(case)
-        ref = _restated(so, oracle, case["seed"])
+        ref = _restatement().Restatement(so, oracle, seed=case["seed"])
         sh = eh = None
         if hip is not None:
             sh = media_case_sim(case)
@@ -479,17 +481,17 @@ def run_media_case(case, hip, oracle):
         nzm = fo != 0
         if not np.array_equal(fh[nzm].view(np.uint32), fo[nzm].view(np.uint32)):
             problems.append("fields equal as values but not as bits where the reference is non-zero")
-    for c in range(len(ref.w)):
+    for c in range(3 if ref.debye else 0):
         hv, hu, hvi = eh.debye_state(c)
-        for name, a, b in (("v_prev", hv, ref.vprev[c]), ("u", hu, ref.u[c]), ("vi", hvi, ref.vi[c])):
+        for name, a, b in (("v_prev", hv, ref.debye.vprev[c]), ("u", hu, ref.debye.u[c]), ("vi", hvi, ref.debye.vi[c])):
             if not np.array_equal(a, b):
                 bad = np.argwhere(a != b)
                 problems.append(f"Debye {name} of component {c} differs at {len(bad)} of {b.size} entries, first {tuple(bad[0])}: "
                                 f"{a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}")
-    if ref.sheet is not None:
+    if ref.sheets is not None:
         hv, hib = eh.sheet_state()
-        if not np.array_equal(hv, ref.sheet["vprev"]) or not np.array_equal(hib, ref.sheet["ib"]):
-            problems.append(f"sheet states differ ({np.count_nonzero(hv != ref.sheet['vprev'])} v_prev, {np.count_nonzero(hib != ref.sheet['ib'])} branch currents)")
+        if not np.array_equal(hv, ref.sheets.vprev) or not np.array_equal(hib, ref.sheets.ib):
+            problems.append(f"sheet states differ ({np.count_nonzero(hv != ref.sheets.vprev)} v_prev, {np.count_nonzero(hib != ref.sheets.ib)} branch currents)")
     uh, uo = sh.port_series()[0], so.port_series()[0]
     for q, name in ((0, "port voltage"), (1, "port current")):
         a, b = np.asarray(uh[q], float), np.asarray(uo[q], float)
@@ -511,7 +513,7 @@ def run_media_case(case, hip, oracle):
 
 # ---- all seven corrections in one context ---------------------------------------------------------------------------------------------
 CORRECTIONS_BATCH = (24, 2)   # (cases, seed) of the batch in the -m gpu suite (tests/test_corrections_fuzz_gpu.py); test_corrections_fuzz_cpu.py guards its coverage
-CORRECTION_NAMES = ("debye", "lorentz", "sheets", "elements", "magnetic", "conformal", "planewave")
+CORRECTION_NAMES = ("debye", "lorentz", "sheets", "elements", "magnetic", "conformal", "planewave")      # (the order the cases are drawn in)
 TWO_PI = 2 * np.pi
 
 
@@ -874,93 +876,51 @@ def corrections_present(sim):
     return {name for name, h in zip(CORRECTION_NAMES, have) if h}
 
 
-class Composed:
-    """The restatement of everything `sim` holds on the oracle's half-steps: RestatedLorentz (Debye and Lorentz media, sheets, elements,
-    magnetic faces) inside RestatedConformal (if the simulation lists conformal faces) inside RestatedPlaneWave (if it has a plane
-    wave).  .top steps; .lor, .conf, .pw are the three layers (None where absent); .e the oracle's engine."""
+def watch_plane_wave(ref):
+    """Hooks on a Restatement: did the plane wave's two lists change V / I on their elements?  The returned dict answers per list."""
+    changed, held = {name: False for name in ("pw_e", "pw_h") if name in ref.parts}, {}
 
-    def __init__(self, sim, oracle, seed=None):
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        from test_conformal_model_cpu import RestatedConformal
-        from test_lorentz_model_cpu import RestatedLorentz
-        from test_planewave_model_cpu import RestatedPlaneWave
-        self.sim, self.lor, self.conf, self.pw = sim, None, None, None
+    def before(name, kind, F):
+        if name in changed and not changed[name]:
+            held[name] = [a.copy() for a in F]
 
-        def make_lor(s, lib):
-            self.lor = RestatedLorentz(s, lib, seed=seed)
-            return self.lor
-
-        def make_conf(s, lib):
-            if s.conformal is None:
-                return make_lor(s, lib)
-            self.conf = RestatedConformal(s, lib, make=make_lor)
-            return self.conf
-        if sim.plane_wave is not None:
-            self.top = self.pw = RestatedPlaneWave(sim, oracle, make=make_conf)
-        else:
-            self.top = make_conf(sim, oracle)
-        self.e = self.top.e
-        self.pw_changed = [False, False]      # the plane wave's lists changed V / I on their elements
-
-    def set_field(self, kind, comp, a):
-        (self.conf or self.lor).set_field(kind, comp, a)
-
-    def step(self):
-        if self.pw is None or all(self.pw_changed):
-            return self.top.step()
-        pw, seen = self.pw, {}
-        real = pw._correct
-
-        def correct(kind, n):
-            tab = pw.tables.E if kind == 0 else pw.tables.H
-            comps = [int(c) for c in np.unique(tab[1])]
-            before = {c: self.e.get_field(kind, c) for c in comps}
-            real(kind, n)
-            seen[kind] = any(np.any(self.e.get_field(kind, c) != before[c]) for c in comps)
-        pw._correct = correct
-        try:
-            self.top.step()
-        finally:
-            del pw._correct
-        for kind in (0, 1):
-            self.pw_changed[kind] |= bool(seen.get(kind))
-
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
-        self.lor.note_moved()
+    def after(name, kind, F):
+        if name in held:
+            changed[name] = any(np.any(a != b) for a, b in zip(F, held.pop(name)))
+    ref.before, ref.after = before, after
+    return changed
 
 
-def corrections_reference_problems(ref):
-    """media_reference_problems for a Composed restatement: what the reference side must show by itself for every correction present."""
-    r = ref.lor
+def corrections_reference_problems(r):
+    """media_reference_problems for every correction present: what the reference side must show by itself.  `r.pw_changed`: what
+    watch_plane_wave returned for it."""
     problems = media_reference_problems(r)
-    if r.lor is not None:
-        L = r.lor
+    if r.lorentz is not None:
+        L = r.lorentz
         for c in range(3):
-            if not L["w"][c].size:
+            if not L.w[c].size:
                 continue
-            live = (L["w"][c] != 0) & (L["vi"][c] != 0)
-            need = live[None] & (L["tab"][c][1][:, 0] != 0)      # (gam == 0: the padding poles of a shorter medium, which stay at rest)
-            if not np.isfinite(L["x"][c]).all():
+            live = (L.w[c] != 0) & (L.vi[c] != 0)
+            need = live[None] & (L.tab[c][1][:, 0] != 0)      # (gam == 0: the padding poles of a shorter medium, which stay at rest)
+            if not np.isfinite(L.x[c]).all():
                 problems.append(f"reference Lorentz states of component {c} not finite")
-            if live.any() and (not np.all(r.x_moved[c][:, 0][need]) or not np.all(L["vprev"][c][live] != 0)):
-                problems.append(f"component {c}: {np.count_nonzero(~r.x_moved[c][:, 0][need])} Lorentz branch currents of {np.count_nonzero(need)} never left zero")
-            if np.any(L["x"][c][:, :, ~live] != 0) or np.any(L["vprev"][c][~live] != 0):
+            if live.any() and (not np.all(L.x_moved[c][:, 0][need]) or not np.all(L.vprev[c][live] != 0)):
+                problems.append(f"component {c}: {np.count_nonzero(~L.x_moved[c][:, 0][need])} Lorentz branch currents of {np.count_nonzero(need)} never left zero")
+            if np.any(L.x[c][:, :, ~live] != 0) or np.any(L.vprev[c][~live] != 0):
                 problems.append(f"component {c}: Lorentz states of edges that are not dispersive edges moved")
-        if not any(((L["w"][c] != 0) & (L["vi"][c] != 0)).any() for c in range(3) if L["w"][c].size):
+        if not any(((L.w[c] != 0) & (L.vi[c] != 0)).any() for c in range(3) if L.w[c].size):
             problems.append("reference: Lorentz media without a live edge")
-    if r.lumped is not None and not (np.isfinite(r.lumped["x"]).all() and np.all(np.any(r.lumped["x"] != 0, axis=0))):
+    if r.elements is not None and not (np.isfinite(r.elements.x).all() and np.all(np.any(r.elements.x != 0, axis=0))):
         problems.append("reference: an element edge without branch current")
-    if r.mag is not None:
+    if r.magnetic is not None:
         for c in range(3):
-            on = r.mag["cls"][c] != 0
-            if on.any() and not (np.isfinite(r.mag["iprev"][c]).all() and np.all(r.mag["iprev"][c][on] != 0)):
-                problems.append(f"reference: i_prev of {np.count_nonzero(r.mag['iprev'][c][on] == 0)} magnetic faces of component {c} is zero")
-    if ref.conf is not None and not (ref.conf.iprev.size and np.isfinite(ref.conf.iprev).all() and np.all(ref.conf.iprev != 0)):
+            on = r.magnetic.cls[c] != 0
+            if on.any() and not (np.isfinite(r.magnetic.iprev[c]).all() and np.all(r.magnetic.iprev[c][on] != 0)):
+                problems.append(f"reference: i_prev of {np.count_nonzero(r.magnetic.iprev[c][on] == 0)} magnetic faces of component {c} is zero")
+    if r.conformal is not None and not (r.conformal.iprev.size and np.isfinite(r.conformal.iprev).all() and np.all(r.conformal.iprev != 0)):
         problems.append("reference: i_prev of a listed conformal face is zero")
-    if ref.pw is not None and not all(ref.pw_changed):
-        problems.append(f"reference: the plane wave's lists changed nothing (V: {ref.pw_changed[0]}, I: {ref.pw_changed[1]})")
+    if r.pw_e is not None and not all(r.pw_changed.values()):
+        problems.append(f"reference: the plane wave's lists changed nothing (V: {r.pw_changed['pw_e']}, I: {r.pw_changed['pw_h']})")
     return problems
 
 
@@ -973,36 +933,42 @@ def _differs(name, a, b):
     return [f"{name} differs at {len(bad)} of {b.size} entries, first {tuple(int(v) for v in bad[0])}: {a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}"]
 
 
-def corrections_state_problems(eh, ref):
-    """Fields and every state array of the HIP engine against the composed restatement, bit for bit."""
+def corrections_state_problems(eh, r):
+    """Fields and every state array of the HIP engine against the restatement, bit for bit."""
     problems = []
-    r = ref.lor
-    fh, fo = eh.fields(), ref.e.fields()
+    fh, fo = eh.fields(), r.e.fields()
     problems += _differs("fields", fh, fo)
     if not problems:
         nzm = fo != 0
         if not np.array_equal(fh[nzm].view(np.uint32), fo[nzm].view(np.uint32)):
             problems.append("fields equal as values but not as bits where the reference is non-zero")
-    for c in range(len(r.w)):
+    for c in range(3 if r.debye else 0):
         hv, hu, hvi = eh.debye_state(c)
-        for name, a, b in (("v_prev", hv, r.vprev[c]), ("u", hu, r.u[c]), ("vi", hvi, r.vi[c])):
+        for name, a, b in (("v_prev", hv, r.debye.vprev[c]), ("u", hu, r.debye.u[c]), ("vi", hvi, r.debye.vi[c])):
             problems += _differs(f"Debye {name} of component {c}", a, b)
-    if r.lor is not None:
+    if r.lorentz is not None:
         for c in range(3):
-            for name, a, b in zip(("v_prev", "x", "vi"), eh.lorentz_state(c), (r.lor["vprev"][c], r.lor["x"][c], r.lor["vi"][c])):
+            for name, a, b in zip(("v_prev", "x", "vi"), eh.lorentz_state(c), (r.lorentz.vprev[c], r.lorentz.x[c], r.lorentz.vi[c])):
                 problems += _differs(f"Lorentz {name} of component {c}", a, b)
-    if r.sheet is not None:
+    if r.sheets is not None:
         hv, hib = eh.sheet_state()
-        problems += _differs("sheet v_prev", hv, r.sheet["vprev"]) + _differs("sheet branch currents", hib, r.sheet["ib"])
-    if r.lumped is not None:
+        problems += _differs("sheet v_prev", hv, r.sheets.vprev) + _differs("sheet branch currents", hib, r.sheets.ib)
+    if r.elements is not None:
         hv, hx = eh.lumped_state()
-        problems += _differs("element v_prev", hv, r.lumped["vprev"]) + _differs("element states", hx, r.lumped["x"])
-    if r.mag is not None:
+        problems += _differs("element v_prev", hv, r.elements.vprev) + _differs("element states", hx, r.elements.x)
+    if r.magnetic is not None:
         for c in range(3):
-            problems += _differs(f"magnetic i_prev of component {c}", eh.magnetic_state(c)[0], r.mag["iprev"][c])
-    if ref.conf is not None:
-        problems += _differs("conformal i_prev", eh.conformal_state(), ref.conf.iprev)
+            problems += _differs(f"magnetic i_prev of component {c}", eh.magnetic_state(c)[0], r.magnetic.iprev[c])
+    if r.conformal is not None:
+        problems += _differs("conformal i_prev", eh.conformal_state(), r.conformal.iprev)
     return problems
+
+
+def corrections_reference(sim, oracle, seed=None):
+    """The Restatement of everything `sim` holds, with the plane wave's lists watched (.pw_changed)."""
+    ref = _restatement().Restatement(sim, oracle, seed=seed)
+    ref.pw_changed = watch_plane_wave(ref)
+    return ref
 
 
 def run_corrections_case(case, hip, oracle):
@@ -1014,7 +980,7 @@ def run_corrections_case(case, hip, oracle):
     problems = []
     try:
         so = corrections_case_sim(case)
-        ref = Composed(so, oracle, seed=case["seed"])
+        ref = corrections_reference(so, oracle, case["seed"])
         sh = eh = None
         if hip is not None:
             sh = corrections_case_sim(case)
@@ -1044,7 +1010,7 @@ def run_corrections_case(case, hip, oracle):
             if not problems:      # the first call where something differs names itself; later ones only repeat it
                 found = corrections_state_problems(eh, ref)
                 for (uid, iid), (ru, ri) in zip(sh._port_probe_ids, so._port_probe_ids):
-                    for name, a, b in (("port voltage", eh.get_probe(uid), ref.e.get_probe(ru)), ("port current", eh.get_probe(iid), ref.e.get_probe(ri))):
+                    for name, a, b in (("port voltage", eh.get_probe(uid), ref.get_probe(ru)), ("port current", eh.get_probe(iid), ref.get_probe(ri))):
                         if not np.array_equal(np.asarray(a)[:done], np.asarray(b)[:done]):
                             found.append(f"{name} series differs")
                 problems += [f"after call {q} ({done} timesteps): {p}" for p in found]
@@ -1057,7 +1023,7 @@ def run_corrections_case(case, hip, oracle):
     if eh is None:
         return problems, {"launches_per_timestep": 0, "lag_planes": 0, "timesteps_per_launch_max": 0}
     for (ru, ri) in so._port_probe_ids:
-        if not (np.abs(ref.e.get_probe(ru)).max() > 0 and np.abs(ref.e.get_probe(ri)).max() > 0):
+        if not (np.abs(ref.get_probe(ru)).max() > 0 and np.abs(ref.get_probe(ri)).max() > 0):
             problems.append("reference: a port series is all zero")
     if case["nf2ff"] != "none":
         bh, bo = sh.nf2ff_boxes(), so.nf2ff_boxes()
@@ -1122,7 +1088,7 @@ def main():
     ap.add_argument("--slabs", action="store_true", help="decomposed runs: 2 ... 6 P2P slabs in one process against one slab on the oracle")
     ap.add_argument("--mur", action="store_true", help="every case with Mur faces, mostly on the two / three launches per timestep")
     ap.add_argument("--media", action="store_true", help="scenes with Debye media and / or conducting sheets against the numpy restatement of their corrections")
-    ap.add_argument("--corrections", action="store_true", help="scenes with at least three of the seven corrections of the step loop (often all) in one context against their composed restatement")
+    ap.add_argument("--corrections", action="store_true", help="scenes with at least three of the seven corrections of the step loop (often all) in one context against tests/restatement.py")
     args = ap.parse_args()
     hip, oracle = load_libs()
     failed = run_batch(args.cases, args.seed, hip, oracle, args.only, log=lambda s: print(s, flush=True), slabs=args.slabs, mur=args.mur, media=args.media,

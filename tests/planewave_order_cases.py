@@ -7,13 +7,13 @@ box and grid face, so the cases are hand tables in the style of test_planewave_g
   Mur scene    test_sheet_model_cpu.cavity_sim(..., sheet=False, boundary="MUR"): tangential edges on the node plane of each of the six
                faces and on the plane next to it, faces touching those planes, and a handful of both in the middle.
 
-The reference is RestatedPlaneWave on the oracle from seeded fields, run once per session and left unchanged."""
+The reference is restatement.Restatement on the oracle from seeded fields, run once per session and left unchanged."""
 import numpy as np
 
 from conftest import pkg
 from helpers import seeded_fields
+from restatement import Restatement
 from test_lumped_model_cpu import pec_cavity
-from test_planewave_model_cpu import RestatedPlaneWave
 from test_sheet_model_cpu import cavity_sim
 
 N = (14, 13, 12)
@@ -127,15 +127,6 @@ class Order:
         return [(np.array([flat(i, j, k)], np.int64), np.array([c], np.int8), np.array([1.0], np.float32)) for c, i, j, k in self.cells[kind]]
 
 
-class _Recording(RestatedPlaneWave):
-    """RestatedPlaneWave that keeps the fields in front of and behind each list of the last timestep: seen[kind] = (before, after)."""
-
-    def _correct(self, kind, n):
-        before = [self.e.get_field(kind, c) for c in range(3)]
-        super()._correct(kind, n)
-        self.seen[kind] = (before, [self.e.get_field(kind, c) for c in range(3)])
-
-
 _ORDER_RUN = {}
 
 
@@ -146,8 +137,8 @@ def order_reference(oracle_lib):
     list; I: in front of the H list); `fields` the final fields."""
     if "run" not in _ORDER_RUN:
         o = Order()
-        ref = _Recording(order_sim(), oracle_lib, tables=o.tables)
-        ref.seen = [None, None]
+        ref = Restatement(order_sim(), oracle_lib, tables={"pw": o.tables})
+        seen = ref.record("pw_e", "pw_h")      # the fields in front of and behind each list of the last timestep
         pids = [[ref.e.add_probe(kind, *a) for a in o.probe_args(kind)] for kind in (0, 1)]
         seeded_fields(ref.e, ORDER_SEED)
         series = [[np.zeros((ORDER_STEPS, 3), np.float32) for _ in range(2)] for _ in range(2)]
@@ -156,7 +147,7 @@ def order_reference(oracle_lib):
             ref.step()
             for kind in (0, 1):
                 for q in range(2):
-                    F = ref.seen[kind][q]
+                    F = seen[("pw_e", "pw_h")[kind]][q]
                     series[kind][q][n] = [F[c][k, j, i] for c, i, j, k in o.cells[kind]]
                     if n % EVERY == 0:
                         t = o.tw[kind][n // EVERY, :, 0] + 1j * o.tw[kind][n // EVERY, :, 1]
@@ -228,7 +219,7 @@ _MUR_RUNS = {}
 def mur_reference(oracle_lib, which="full"):
     """The Mur scene restated on the oracle from seeded fields, MUR_STEPS timesteps, once per session per table set: the final fields."""
     if which not in _MUR_RUNS:
-        ref = RestatedPlaneWave(mur_sim(), oracle_lib, tables=mur_tables(which))
+        ref = Restatement(mur_sim(), oracle_lib, tables={"pw": mur_tables(which)})
         seeded_fields(ref.e, MUR_SEED)
         ref.run(MUR_STEPS)
         f = ref.e.fields()

@@ -1,6 +1,6 @@
 """Conformal PEC boundaries on the GPU (csrc/conformal.hip, fdtd_voxel_fractions in csrc/voxel.hip): the device fractions against
 conformal.fractions_spec, bit for bit; the HIP step loop against the oracle's half-steps plus the numpy restatement of the correction
-(test_conformal_model_cpu.RestatedConformal), bit for bit, i_prev included; the order of the H update, the correction and whatever
+(restatement.Restatement), bit for bit, i_prev included; the order of the H update, the correction and whatever
 samples I; the schedules a context with listed faces may take; S11 of a circular patch through the openEMS API mirror."""
 import numpy as np
 import pytest
@@ -8,7 +8,8 @@ import pytest
 import primitives_cases as pc
 from conftest import pkg
 from helpers import seeded_fields
-from test_conformal_model_cpu import RestatedConformal, circular_patch_script, restating_build, sphere_scene, sphere_sim
+from restatement import Restatement, install
+from test_conformal_model_cpu import circular_patch_script, sphere_scene, sphere_sim
 
 N = (26, 23, 11)
 NSTEPS = 200
@@ -71,15 +72,15 @@ CASES = {"sphere-pec": lambda n: sphere_sim(N, nr_ts=n),
 
 
 def _same(e, ref):
-    assert np.abs(ref.e.fields()).max() > 0 and np.abs(ref.iprev).max() > 0
+    assert np.abs(ref.e.fields()).max() > 0 and np.abs(ref.conformal.iprev).max() > 0
     assert np.array_equal(e.fields(), ref.e.fields())
-    assert np.array_equal(e.conformal_state(), ref.iprev)
+    assert np.array_equal(e.conformal_state(), ref.conformal.iprev)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name):
-    ref = RestatedConformal(CASES[name](NSTEPS), oracle_lib, seed=7)
+    ref = Restatement(CASES[name](NSTEPS), oracle_lib, seed=7)
     ref.run(NSTEPS)
     s = CASES[name](NSTEPS)
     e = s.build(hip_lib)
@@ -101,8 +102,8 @@ def test_list_lengths_through_the_raw_abi(hip_lib, oracle_lib, nfaces):
     comp, idx, coef = sphere_sim(N, nr_ts=60).conformal_tables()
     pick = np.random.default_rng(nfaces).permutation(idx.size)[:nfaces]
     tables = (comp[pick], idx[pick], coef[pick])
-    ref = RestatedConformal(mk(), oracle_lib, seed=9, tables=tables)
-    before = ref.iprev.copy()
+    ref = Restatement(mk(), oracle_lib, seed=9, tables={"conformal": tables})
+    before = ref.conformal.iprev.copy()
     ref.run(60)
     e = mk().build(hip_lib)
     seeded_fields(e, 9)
@@ -117,7 +118,7 @@ def test_list_lengths_through_the_raw_abi(hip_lib, oracle_lib, nfaces):
 @pytest.mark.gpu
 def test_chunked_runs_and_set_field_mid_run(hip_lib, oracle_lib):
     """fdtd_run in chunks of 1, 7 and 61 steps; then fdtd_set_field(I) (and V) mid-run, which loads i_prev again; then the rest."""
-    ref = RestatedConformal(sphere_sim(N, nr_ts=NSTEPS), oracle_lib, seed=2)
+    ref = Restatement(sphere_sim(N, nr_ts=NSTEPS), oracle_lib, seed=2)
     e = sphere_sim(N, nr_ts=NSTEPS).build(hip_lib)
     seeded_fields(e, 2)
     for n in (1, 7, 61):
@@ -131,8 +132,8 @@ def test_chunked_runs_and_set_field_mid_run(hip_lib, oracle_lib):
             e.set_field(kind, c, a)
             ref.set_field(kind, c, a)
             if kind == 1:
-                q = ref.comp == c
-                assert np.array_equal(e.conformal_state()[q], a.reshape(-1)[ref.idx[q]])
+                q = ref.conformal.comp == c
+                assert np.array_equal(e.conformal_state()[q], a.reshape(-1)[ref.conformal.idx[q]])
     e.run(NSTEPS - 69)
     ref.run(NSTEPS - 69)
     _same(e, ref)
@@ -164,9 +165,9 @@ def test_i_probe_and_i_dft_box_read_the_corrected_current(hip_lib, oracle_lib):
     nsamp = nsteps // every + 1
     tw_v = exc.dft_twiddles(freqs, sims[0].dt, every, nsamp, 0.0)
     tw_i = exc.dft_twiddles(freqs, sims[0].dt, every, nsamp, 0.5)
-    ref = RestatedConformal(sims[0], oracle_lib, seed=4)
+    ref = Restatement(sims[0], oracle_lib, seed=4)
     e_run, e_half = sims[1].build(hip_lib), sims[2].build(hip_lib)
-    pids, bids = [ref.e.add_probe(capi.KIND_I, idx, comp, w)], []
+    pids, bids = [ref.add_probe(capi.KIND_I, idx, comp, w)], []
     for e in (e_run, e_half):
         pids.append(e.add_probe(capi.KIND_I, idx, comp, w))
         e.set_dft(every, tw_v, tw_i)
@@ -176,20 +177,21 @@ def test_i_probe_and_i_dft_box_read_the_corrected_current(hip_lib, oracle_lib):
     assert listed[1][sl].sum() >= 1
     acc = np.zeros((2,) + tuple(s.stop - s.start for s in sl), np.complex128)
     acc_raw = np.zeros_like(acc)
-    raw_series = []
+    raw_series, seen = [], ref.record("conformal")
     for n in range(nsteps):
         ref.step()
-        raw_series.append(sum(float(wq) * float(ref.I_uncorrected[c].reshape(-1)[q]) for wq, c, q in zip(w, comp, idx)))
+        uncorrected = seen["conformal"][0]
+        raw_series.append(sum(float(wq) * float(uncorrected[c].reshape(-1)[q]) for wq, c, q in zip(w, comp, idx)))
         if n % every == 0:
             t = tw_i[n // every, :, 0] + 1j * tw_i[n // every, :, 1]
             acc += t[:, None, None, None] * ref.I[1][sl].astype(np.float64)[None]
-            acc_raw += t[:, None, None, None] * ref.I_uncorrected[1][sl].astype(np.float64)[None]
+            acc_raw += t[:, None, None, None] * uncorrected[1][sl].astype(np.float64)[None]
     e_run.run(70)
     e_run.run(80)
     for _ in range(nsteps):
         e_half.half_step(0)
         e_half.half_step(1)
-    want = ref.e.get_probe(pids[0])
+    want = ref.get_probe(pids[0])
     assert want.size == nsteps and np.abs(want).max() > 0
     assert np.max(np.abs(want - np.array(raw_series))) > 1e-3 * np.abs(want).max()      # the correction does change what the probe reads
     assert np.array_equal(e_half.get_probe(pids[2])[:nsteps], want)
@@ -259,7 +261,7 @@ def test_schedules_with_listed_faces(hip_lib, oracle_lib):
 # ---- 4. through the API ------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_s11_of_a_circular_patch_through_openems_api(hip_lib, oracle_lib, tmp_path, monkeypatch):
-    restating_build(monkeypatch)
+    install(monkeypatch)
     oe = pkg("openems_api")
     freq = np.linspace(3e9, 9e9, 13)
     s11 = []

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, pkg
-from helpers import rel_l2, seeded_fields
+from helpers import rel_l2
+from restatement import Restatement, install
 
 C0 = 299792458.0
 KAT = os.path.join(ROOT, "profiles", "conformal", "kat.txt")
@@ -68,128 +69,6 @@ def sphere_sim(n=(26, 23, 11), nr_ts=200, boundary="PEC", cpml_cells=None, ratio
     vox = sc.voxelize(s, g, conformal=True)
     return sim.Simulation(g, vox, f0=12e9, fc=6e9, boundary=boundary, cpml_cells=cpml_cells, nr_ts=nr_ts, end_criteria=0.0,
                           conformal=conformal, conformal_ratio=ratio)
-
-
-class RestatedConformal:
-    """An engine of `lib` (no conformal entry points needed: the oracle) stepped by half-steps, with the listed faces' correction
-    (conformal.correction, the six fp32 statements of include/fdtd_hip_conformal.h) applied in numpy after the H half-step.  i_prev is
-    loaded from the I arrays when the set is made (after `seed`) and by set_field(1, ...), as fdtd_conformal_set / fdtd_set_field do.
-    The oracle samples its I-probes inside the H half-step, BEFORE the correction, so the I-probe series are kept here (get_probe of
-    the engine returns them): sum_e w_e I_e in double in the probe's edge order.  `tables`: (comp, idx, coef), default the
-    simulation's own.
-    `make(sim, lib)`: an inner restatement (test_lorentz_model_cpu.RestatedLorentz and its bases: Debye and Lorentz media, sheets,
-    elements, magnetic faces) built while the simulation's conformal faces are hidden; it seeds the fields itself.  Its step runs first,
-    its magnetic correction included, and the listed faces follow on the currents it leaves, as include/fdtd_hip_conformal.h orders;
-    the voltages the correction reads are the ones in memory right in front of the H half-step, behind every E-side correction.  Without
-    `make` nothing changes: the bare oracle, stepped here."""
-
-    def __init__(self, sim, lib, flags=0, seed=None, tables=None, make=None):
-        saved = sim.conformal
-        sim.conformal = None                          # the base operator at the simulation's (reduced) dt
-        try:
-            self.inner = None if make is None else make(sim, lib)
-            self.e = sim.build(lib, flags=flags) if make is None else self.inner.e
-        finally:
-            sim.conformal = saved
-        self.sim = sim
-        e = self.e
-        self.i_probes, self.i_series = {}, {}
-        for p, (_, iid) in zip(sim.vox.ports, sim._port_probe_ids):
-            self.i_probes[iid] = (np.asarray(p.i_idx, np.int64), np.asarray(p.i_comp, np.int64), np.asarray(p.i_w, np.float32))
-        real_add, real_get = e.add_probe, e.get_probe
-
-        def add_probe(kind, idx, comp, w):
-            pid = real_add(kind, idx, comp, w)
-            if kind == 1:
-                self.i_probes[pid] = (np.asarray(idx, np.int64), np.asarray(comp, np.int64), np.asarray(w, np.float32))
-            return pid
-
-        def get_probe(pid):
-            return np.array(self.i_series.get(pid, []), np.float64) if pid in self.i_probes else real_get(pid)
-        e.add_probe, e.get_probe = add_probe, get_probe
-        if seed is not None:
-            seeded_fields(e, seed)
-        if tables is None:
-            sim.conformal = saved
-            tables = sim.conformal_tables()
-        self.set_conformal(tables)
-
-    def set_conformal(self, tables):
-        comp, idx, coef = tables
-        self.comp, self.idx = np.asarray(comp, np.int64), np.asarray(idx, np.int64)
-        self.coef = np.asarray(coef, np.float32).reshape(-1, 4)
-        self.iprev = np.zeros(self.idx.size, np.float32)
-        for c in range(3):
-            q = self.comp == c
-            self.iprev[q] = self.e.get_field(1, c).reshape(-1)[self.idx[q]]
-
-    def set_field(self, kind, comp, a):
-        if self.inner is not None and hasattr(self.inner, "set_field"):
-            self.inner.set_field(kind, comp, a)      # (re-primes the magnetic faces' i_prev)
-        else:
-            self.e.set_field(kind, comp, a)
-        if kind == 1:
-            q = self.comp == comp
-            self.iprev[q] = np.asarray(a, np.float32).reshape(-1)[self.idx[q]]
-
-    def _inner_step(self):
-        """The inner restatement's whole step; self.V: the voltages in memory when its (last) H half-step begins."""
-        e = self.e
-        real = e.half_step
-
-        def half_step(phase):
-            if phase == 1:
-                self.V = np.stack([e.get_field(0, c) for c in range(3)])
-            return real(phase)
-        e.half_step = half_step
-        try:
-            self.inner.step()
-        finally:
-            e.__dict__.pop("half_step", None)
-
-    def step(self):
-        e = self.e
-        if self.inner is not None:
-            self._inner_step()
-        else:
-            e.half_step(0)
-            self.V = np.stack([e.get_field(0, c) for c in range(3)])
-            e.half_step(1)
-        self.I_uncorrected = [e.get_field(1, c) for c in range(3)]
-        Is = [a.copy() for a in self.I_uncorrected]
-        r = _cf().correction(self.V, self.iprev, self.comp, self.idx, self.coef)
-        for c in range(3):
-            q = self.comp == c
-            if q.any():
-                Is[c].reshape(-1)[self.idx[q]] = r[q]
-                e.set_field(1, c, Is[c])
-        self.I = Is
-        for pid, (idx, comp, w) in self.i_probes.items():
-            s = 0.0
-            for g, c, wq in zip(idx, comp, w):
-                s = float(wq) * float(Is[c].reshape(-1)[g]) + s
-            self.i_series.setdefault(pid, []).append(s)
-
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
-
-
-def restating_build(monkeypatch):
-    """Simulation.build -> for a library without conformal entry points (the oracle) an engine whose run() is the restatement."""
-    Sim = pkg("simulation").Simulation
-    orig = Sim.build
-
-    def build(self, lib, **kw):
-        if self.conformal is None or pkg("_capi").has_conformal(lib):
-            return orig(self, lib, **kw)
-        r = RestatedConformal(self, lib, flags=kw.get("flags", 0))
-        r.e.run = r.run
-        self.engine, self.lib = r.e, lib
-        self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
-        self.restated = r
-        return r.e
-    monkeypatch.setattr(Sim, "build", build)
 
 
 def build_raw(sim, lib, conformal="own"):
@@ -407,7 +286,7 @@ def test_correction_form_agrees_with_the_raw_operator(oracle_lib):
     nsteps, seed = 300, 3
     g = _graded16()
     mk = lambda: sphere_sim(nr_ts=nsteps, grid=g, centre=(7.1, 6.8, 6.3), radius=5.3)
-    a = RestatedConformal(mk(), oracle_lib, seed=seed)
+    a = Restatement(mk(), oracle_lib, seed=seed)
     f = a.sim.conformal.frac.dense()
     start = a.e.fields()
     a.run(nsteps)
@@ -596,7 +475,7 @@ def test_the_off_switch_changes_nothing():
 
 
 def test_conformal_reaches_the_simulation_through_the_api(oracle_lib, tmp_path, monkeypatch):
-    restating_build(monkeypatch)
+    install(monkeypatch)
     oe = pkg("openems_api")
     f, port = circular_patch_script(oe, oracle_lib, nr_ts=60)
     f.Run(str(tmp_path / "c"), verbose=0)

@@ -1,7 +1,7 @@
 """Guards of the randomised parity run of all seven corrections in one context (tests/fuzz_parity.py --corrections) that need no GPU: the
 fixed-seed batch of the -m gpu suite is accepted by the host layer and covers, together, what it was written to reach; the same seed
-gives the same cases; the reference side of the first cases moves every state of every correction present; the composed restatement
-with one correction present gives the bits of that correction's own restatement."""
+gives the same cases; the reference side of the first cases moves every state of every correction present; raw tables handed
+to the restatement give the bits of the simulation's own."""
 import collections
 
 import numpy as np
@@ -10,9 +10,10 @@ import pytest
 import corrections_overlap_cases as oc
 import fuzz_parity
 from conftest import pkg
-from test_conformal_model_cpu import RestatedConformal, sphere_sim
-from test_lorentz_model_cpu import TWO_PI, RestatedLorentz, lorentz_cavity
-from test_planewave_model_cpu import RestatedPlaneWave, _placed
+from restatement import Restatement
+from test_conformal_model_cpu import sphere_sim
+from test_lorentz_model_cpu import TWO_PI, lorentz_cavity
+from test_planewave_model_cpu import _placed
 
 NAMES = fuzz_parity.CORRECTION_NAMES
 WANTED = ({f"k_debye<{m},{k}>" for m in ("false", "true") for k in (4, 8)} | {f"k_lorentz<{m},{k}>" for m in ("false", "true") for k in (1, 2, 4)}
@@ -178,7 +179,7 @@ def test_same_seed_same_cases():
 
 
 def test_reference_side_of_the_first_cases_moves_everywhere(oracle_lib):
-    """The first cases of the batch stepped on the composed restatement alone: finite, non-zero, every state of every correction present
+    """The first cases of the batch stepped on the restatement alone: finite, non-zero, every state of every correction present
     off zero, the plane wave's lists changing V and I on their elements."""
     rng = np.random.default_rng(fuzz_parity.CORRECTIONS_BATCH[1])
     ran, have = 0, set()
@@ -195,50 +196,54 @@ def test_reference_side_of_the_first_cases_moves_everywhere(oracle_lib):
 
 
 def test_composed_with_conformal_faces_alone_is_restated_conformal(oracle_lib):
+    """The conformal faces handed over as the raw tables of fdtd_conformal_set against the simulation's own, the fuzz harness's way."""
     nsteps = 40
-    a = RestatedConformal(sphere_sim(nr_ts=nsteps, tilted_disc=True), oracle_lib, seed=5)
-    b = fuzz_parity.Composed(sphere_sim(nr_ts=nsteps, tilted_disc=True), oracle_lib, seed=5)
-    assert b.conf is not None and b.pw is None and b.lor.lor is None and b.lor.mag is None and not b.lor.w
+    sim = sphere_sim(nr_ts=nsteps, tilted_disc=True)
+    a = Restatement(sim, oracle_lib, seed=5, tables={"conformal": sim.conformal_tables()})
+    b = fuzz_parity.corrections_reference(sphere_sim(nr_ts=nsteps, tilted_disc=True), oracle_lib, seed=5)
+    assert b.conformal is not None and b.pw_e is None and b.lorentz is None and b.magnetic is None and b.debye is None
     g = a.sim.grid
     probe = (np.array([g.flat(7, 10, 5), g.flat(12, 5, 4)], np.int64), np.array([2, 0], np.int8), np.array([1.0, -2.0], np.float32))
-    pa, pb = a.e.add_probe(1, *probe), b.e.add_probe(1, *probe)
+    pa, pb = a.add_probe(1, *probe), b.add_probe(1, *probe)
     for r in (a, b):
         r.run(nsteps // 2)
         r.set_field(1, 2, np.full(r.e.local_shape, 1e-4, np.float32))
         r.run(nsteps // 2)
-    assert a.iprev.size > 100 and np.all(a.iprev != 0)
-    assert np.array_equal(a.e.fields(), b.e.fields()) and np.array_equal(a.iprev, b.conf.iprev)
-    sa, sb = a.e.get_probe(pa), b.e.get_probe(pb)
+    assert a.conformal.iprev.size > 100 and np.all(a.conformal.iprev != 0)
+    assert np.array_equal(a.e.fields(), b.e.fields()) and np.array_equal(a.conformal.iprev, b.conformal.iprev)
+    sa, sb = a.get_probe(pa), b.get_probe(pb)
     assert sa.size == nsteps and np.abs(sa).max() > 0 and np.array_equal(sa, sb)
 
 
 def test_composed_with_lorentz_media_alone_is_restated_lorentz(oracle_lib):
+    """The Lorentz media handed over as the raw tables of fdtd_lorentz_set against the simulation's own, the fuzz harness's way."""
     nsteps = 40
     mk = lambda: lorentz_cavity(lambda s: s.add_lorentz_material("block", 2.0, 0.0, TWO_PI * np.array([8e9, 6e9]), TWO_PI * np.array([0.0, 12e9]),
                                                                  [4e9, 1e9]).add_box([4, 4, 3], [9, 8, 8]), nr_ts=nsteps)
-    a = RestatedLorentz(mk(), oracle_lib, seed=4)
-    b = fuzz_parity.Composed(mk(), oracle_lib, seed=4)
-    assert b.top is b.lor and b.conf is None and b.pw is None
+    sim = mk()
+    a = Restatement(sim, oracle_lib, seed=4, tables={"lorentz": sim.lorentz_tables()})
+    b = fuzz_parity.corrections_reference(mk(), oracle_lib, seed=4)
+    assert list(b.parts) == ["lorentz"]
     a.run(nsteps)
     b.run(nsteps)
-    assert np.abs(a.lor["x"][0]).max() > 0 and np.array_equal(a.e.fields(), b.e.fields())
+    assert np.abs(a.lorentz.x[0]).max() > 0 and np.array_equal(a.e.fields(), b.e.fields())
     for c in range(3):
-        assert np.array_equal(a.lor["x"][c], b.lor.lor["x"][c]) and np.array_equal(a.lor["vprev"][c], b.lor.lor["vprev"][c])
+        assert np.array_equal(a.lorentz.x[c], b.lorentz.x[c]) and np.array_equal(a.lorentz.vprev[c], b.lorentz.vprev[c])
     assert fuzz_parity.corrections_reference_problems(b) == []
 
 
 def test_composed_with_a_plane_wave_and_conformal_faces_is_the_pair_it_was(oracle_lib):
-    """RestatedPlaneWave around RestatedConformal, as test_planewave_model_cpu.restating_build nests them, against the composed one whose
-    conformal layer steps an (empty) inner restatement."""
+    """A plane wave and conformal faces: the restatement test_planewave_model_cpu's plugin tests install against the fuzz harness's, whose
+    hooks watch the plane wave's lists."""
     nsteps = 60
     mk = lambda: _placed(lambda s: s.add_metal("ball").add_sphere((12.3, 11.8, 12.1), 2.4), conformal=True, nr_ts=nsteps)
-    a = RestatedPlaneWave(mk(), oracle_lib, make=lambda s, l: RestatedConformal(s, l))
-    b = fuzz_parity.Composed(mk(), oracle_lib)
-    assert b.pw is not None and b.conf is not None
+    a = Restatement(mk(), oracle_lib)
+    b = fuzz_parity.corrections_reference(mk(), oracle_lib)
+    assert b.pw_e is not None and b.pw_h is not None and b.conformal is not None
     a.run(nsteps)
     b.run(nsteps)
-    assert all(b.pw_changed) and np.abs(a.e.fields()).max() > 0 and np.all(a.inner.iprev != 0)
-    assert np.array_equal(a.e.fields(), b.e.fields()) and np.array_equal(a.inner.iprev, b.conf.iprev)
+    assert all(b.pw_changed.values()) and np.abs(a.e.fields()).max() > 0 and np.all(a.conformal.iprev != 0)
+    assert np.array_equal(a.e.fields(), b.e.fields()) and np.array_equal(a.conformal.iprev, b.conformal.iprev)
 
 
 @pytest.mark.parametrize("mur", [False, True], ids=["pec", "one-mur-face"])

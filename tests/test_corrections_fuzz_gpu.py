@@ -1,6 +1,6 @@
 """All seven corrections of the step loop in one context on the GPU (Debye and Lorentz media, sheets, elements and the plane wave's edge
 list behind the E phase; magnetic faces, conformal faces and the plane wave's face list behind the H update): a fixed-seed batch of
-tests/fuzz_parity.py --corrections against the composed restatement; lists that overlap, through the raw C ABI, against the headers'
+tests/fuzz_parity.py --corrections against restatement.Restatement; lists that overlap, through the raw C ABI, against the headers'
 statement lists applied in the headers' order; fdtd_set_field of every component between two calls with everything present."""
 import numpy as np
 import pytest
@@ -101,7 +101,7 @@ def test_set_field_of_every_component_with_all_seven_present(hip_lib, oracle_lib
     case = next(c for c in _batch() if fuzz_parity.corrections_present(fuzz_parity.corrections_case_sim(c)) == set(fuzz_parity.CORRECTION_NAMES))
     case = dict(case, calls=[30, 30], sets=[None], env={}, drive="auto")
     so, sh = fuzz_parity.corrections_case_sim(case), fuzz_parity.corrections_case_sim(case)
-    ref = fuzz_parity.Composed(so, oracle_lib, seed=case["seed"])
+    ref = fuzz_parity.corrections_reference(so, oracle_lib, seed=case["seed"])
     e = sh.build(hip_lib)
     seeded_fields(e, case["seed"])
     ref.run(30)
@@ -133,5 +133,5 @@ def test_set_field_of_every_component_with_all_seven_present(hip_lib, oracle_lib
     assert fuzz_parity.corrections_reference_problems(ref) == []
     assert fuzz_parity.corrections_state_problems(e, ref) == []
     for (uid, iid), (ru, ri) in zip(sh._port_probe_ids, so._port_probe_ids):
-        assert np.array_equal(e.get_probe(uid)[:60], ref.e.get_probe(ru)[:60]) and np.array_equal(e.get_probe(iid)[:60], ref.e.get_probe(ri)[:60])
+        assert np.array_equal(e.get_probe(uid)[:60], ref.get_probe(ru)[:60]) and np.array_equal(e.get_probe(iid)[:60], ref.get_probe(ri)[:60])
     e.close()

@@ -9,9 +9,9 @@ import pytest
 
 from conftest import pkg
 from helpers import seeded_fields
+from restatement import Restatement
 from test_dispersion_gpu import X_ALIGN
-from test_lorentz_model_cpu import TWO_PI, RestatedLorentz
-from test_magnetic_model_cpu import RestatedMagnetic
+from test_lorentz_model_cpu import TWO_PI
 from test_sheet_model_cpu import _grid
 import test_lorentz_gpu
 import test_magnetic_gpu
@@ -60,14 +60,14 @@ def test_lorentz_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
              lor.LorentzMedium(1.0, 0.0, TWO_PI * np.array([4e9, 6e9]), TWO_PI * np.array([11e9, 0.0]), np.array([0.0, 8e9]))]
     sim0 = _plain_sim(nx)
     tables = lor.tables(media, sim0.dt, K=2) + (lo, hi, w, med)
-    ref = RestatedLorentz(sim0, oracle_lib, seed=x0 + 100 * x1, lorentz=tables)
+    ref = Restatement(sim0, oracle_lib, seed=x0 + 100 * x1, tables={"lorentz": tables})
     ref.run(NSTEPS)
     e = _plain_sim(nx).build(hip_lib)
     seeded_fields(e, x0 + 100 * x1)
     e.set_lorentz(*tables)
     e.run(NSTEPS)
-    assert all(np.any(ref.lor["w"][c] != 0) and np.any(w[c] == 0) for c in range(3))
-    assert min(np.abs(x).max() for x in ref.lor["x"]) > 0
+    assert all(np.any(ref.lorentz.w[c] != 0) and np.any(w[c] == 0) for c in range(3))
+    assert min(np.abs(x).max() for x in ref.lorentz.x) > 0
     assert np.array_equal(e.fields(), ref.e.fields())
     test_lorentz_gpu._same_state(e, ref)
 
@@ -84,7 +84,7 @@ def test_magnetic_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
     for q in cls:
         q.reshape(-1)[:3] = (1, 0, 2)
     tables = (np.array([0.97, 1.0], np.float32), np.array([0.5, 0.25], np.float32), lo, hi, cls)
-    ref = RestatedMagnetic(_plain_sim(nx), oracle_lib, seed=x0 + 100 * x1, magnetic=tables)
+    ref = Restatement(_plain_sim(nx), oracle_lib, seed=x0 + 100 * x1, tables={"magnetic": tables})
     seed_I = [ref.e.get_field(1, c) for c in range(3)]
     ref.run(NSTEPS)
     e = _plain_sim(nx).build(hip_lib)
@@ -94,7 +94,7 @@ def test_magnetic_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
     assert np.array_equal(e.fields(), ref.e.fields())
     test_magnetic_gpu._same_state(e, ref)
     for c in range(3):
-        ip, before = e.magnetic_state(c)[0], seed_I[c][ref.mag["sl"][c]]
+        ip, before = e.magnetic_state(c)[0], seed_I[c][ref.magnetic.sl[c]]
         assert np.array_equal(ip[cls[c] == 0], before[cls[c] == 0]) and np.any(ip[cls[c] != 0] != before[cls[c] != 0])
 
 

@@ -6,7 +6,8 @@ import pytest
 
 from conftest import pkg
 from helpers import patch_sim, seeded_fields
-from test_dispersion_model_cpu import Restated, _fr4, _graded, _grid, restating_build
+from restatement import Restatement, install
+from test_dispersion_model_cpu import _fr4, _graded, _grid
 
 
 def _media_scene(g, boxes, port=None, sheets=(), plain=()):
@@ -116,17 +117,17 @@ def _same_as_restatement(s, e, ref_sim, ref):
     fh = e.fields()
     assert np.array_equal(fh, fo), f"fields differ at {np.count_nonzero(fh != fo)} entries, first {tuple(np.argwhere(fh != fo)[0])}"
     assert np.array_equal(fh[fo != 0].view(np.uint32), fo[fo != 0].view(np.uint32))
-    for c in range(len(ref.w)):
+    for c in range(3 if ref.debye else 0):
         hv, hu, hvi = e.debye_state(c)
-        assert np.array_equal(hvi, ref.vi[c])
-        assert np.array_equal(hv, ref.vprev[c]), (c, np.count_nonzero(hv != ref.vprev[c]))
-        assert np.array_equal(hu, ref.u[c]), (c, np.count_nonzero(hu != ref.u[c]))
-        off = ref.w[c] == 0
+        assert np.array_equal(hvi, ref.debye.vi[c])
+        assert np.array_equal(hv, ref.debye.vprev[c]), (c, np.count_nonzero(hv != ref.debye.vprev[c]))
+        assert np.array_equal(hu, ref.debye.u[c]), (c, np.count_nonzero(hu != ref.debye.u[c]))
+        off = ref.debye.w[c] == 0
         assert np.all(hv[off] == 0) and np.all(hu[:, off] == 0)
-    if ref.sheet is not None:
+    if ref.sheets is not None:
         hv, hib = e.sheet_state()
-        assert np.array_equal(hv, ref.sheet["vprev"]) and np.array_equal(hib, ref.sheet["ib"])
-    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
+        assert np.array_equal(hv, ref.sheets.vprev) and np.array_equal(hib, ref.sheets.ib)
+    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
         assert np.abs(qu).max() > 0 and np.abs(qi).max() > 0 and np.array_equal(pu, qu) and np.array_equal(pi, qi)
 
 
@@ -138,7 +139,7 @@ CASES = ["pec-uniform", "pec-uniform-raw", "pec-graded-k8", "mur-graded", "cpml8
 def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name):
     nsteps = 300
     ref_sim = _sim(name, nsteps)
-    ref = Restated(ref_sim, oracle_lib)
+    ref = Restatement(ref_sim, oracle_lib)
     ref.run(nsteps)
     s = _sim(name, nsteps)
     e = s.build(hip_lib)
@@ -152,18 +153,18 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name):
     nonzero = 0
     for c in range(3):
         hv, hu, hvi = e.debye_state(c)
-        assert np.array_equal(hvi, ref.vi[c])                      # the vi the library took from its own operator
-        assert np.array_equal(hv, ref.vprev[c]) and np.array_equal(hu, ref.u[c])
-        off = ref.w[c] == 0
+        assert np.array_equal(hvi, ref.debye.vi[c])                      # the vi the library took from its own operator
+        assert np.array_equal(hv, ref.debye.vprev[c]) and np.array_equal(hu, ref.debye.u[c])
+        off = ref.debye.w[c] == 0
         assert np.all(hv[off] == 0) and np.all(hu[:, off] == 0)    # edges of the box outside the medium are left alone
         nonzero += np.count_nonzero(hu)
     assert nonzero > 0
-    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
+    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
         assert np.abs(qu).max() > 0 and np.array_equal(pu, qu) and np.array_equal(pi, qi)
     if name == "media-and-sheets-mur":
         hv, hib = e.sheet_state()
-        assert np.abs(hib).max() > 0 and np.array_equal(hv, ref.sheet["vprev"]) and np.array_equal(hib, ref.sheet["ib"])
-        on = [np.count_nonzero(ref.w[c].reshape(-1)) for c in range(3)]
+        assert np.abs(hib).max() > 0 and np.array_equal(hv, ref.sheets.vprev) and np.array_equal(hib, ref.sheets.ib)
+        on = [np.count_nonzero(ref.debye.w[c].reshape(-1)) for c in range(3)]
         assert min(on) > 0
     if name == "pec-uniform":
         assert s.debye.lo[0][0] == 3 and s.debye.hi[0][0] == 9 and s.grid.shape[0] % 4 != 0
@@ -176,7 +177,7 @@ def test_every_instantiation_and_many_blocks(hip_lib, oracle_lib, name, nsteps):
     """k_debye<true, 8> (three media of 8 / 3 / 1 poles; eight media of 8 poles) and a launch of 83 blocks whose components start at
     non-zero blocks, from seeded fields."""
     ref_sim, s = _sim(name, nsteps), _sim(name, nsteps)
-    ref = Restated(ref_sim, oracle_lib, seed=21)
+    ref = Restatement(ref_sim, oracle_lib, seed=21)
     e = s.build(hip_lib)
     seeded_fields(e, 21)
     ref.run(nsteps)
@@ -204,7 +205,7 @@ def test_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
     nsteps = 60
     ref_sim, s = _x_aligned_sim(x0, x1, nx, nsteps), _x_aligned_sim(x0, x1, nx, nsteps)
     assert s.debye.lo[0][0] == x0 and s.debye.hi[0][0] == x1 and s.debye.lo[1][0] == x0 and s.debye.hi[1][0] == min(x1 + 1, nx)
-    ref = Restated(ref_sim, oracle_lib, seed=x0 + 100 * x1)
+    ref = Restatement(ref_sim, oracle_lib, seed=x0 + 100 * x1)
     e = s.build(hip_lib)
     seeded_fields(e, x0 + 100 * x1)
     ref.run(nsteps)
@@ -224,7 +225,7 @@ def test_run_in_chunks(hip_lib, oracle_lib):
     chunks = (1, 2, 97, 100)
     n = sum(chunks)
     ref_sim, s, h = (_sim("media-and-sheets-mur", n) for _ in range(3))
-    ref = Restated(ref_sim, oracle_lib, seed=3)
+    ref = Restatement(ref_sim, oracle_lib, seed=3)
     e, eh = s.build(hip_lib), h.build(hip_lib)
     seeded_fields(e, 3)
     seeded_fields(eh, 3)
@@ -247,9 +248,9 @@ def test_media_on_grid_faces_under_both_mur_schedules(hip_lib, oracle_lib, monke
     (fdtd_hip_dispersion.h): fields, probe series and the states of EVERY edge agree among both schedules and the restatement."""
     nsteps = 120
     ref_sim = _sim(name, nsteps)
-    ref = Restated(ref_sim, oracle_lib, seed=8)
+    ref = Restatement(ref_sim, oracle_lib, seed=8)
     ref.run(nsteps)
-    held = sum(int(np.count_nonzero((ref_sim.debye.w[c] != 0) & (ref.vi[c] == 0))) for c in range(3))
+    held = sum(int(np.count_nonzero((ref_sim.debye.w[c] != 0) & (ref.debye.vi[c] == 0))) for c in range(3))
     assert held > 300, held                      # the edges in question exist, in numbers
     mur = name.endswith("mur")
     for apply_pass, want in ((None, 2), ("1", 3 if mur else 2)):
@@ -388,7 +389,7 @@ def test_schedules_without_and_with_media(hip_lib):
 
 def _plugin_pair(prepare, hip_lib, oracle_lib, tmp_path, monkeypatch, nsteps, f):
     s = pkg("solver_fdtd_hip")
-    restating_build(monkeypatch)
+    install(monkeypatch)
     out = []
     for lib, tag in ((hip_lib, "gpu"), (oracle_lib, "cpu")):
         prep = prepare(lib, str(tmp_path / tag))

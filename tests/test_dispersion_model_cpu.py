@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, pkg
+from restatement import Restatement
 from test_plugin_surface_cpu import _load, _params, _same
 
 EPS0 = pkg("constants").EPS0
@@ -27,112 +28,6 @@ def _graded(n=(15, 13, 14), h=1e-3, seed=3):
     """Node lines with cells between 0.7 h and 1.4 h."""
     rng = np.random.default_rng(seed)
     return pkg("grid").RectGrid(*[np.concatenate([[0.0], np.cumsum(h * rng.uniform(0.7, 1.4, k - 1))]) for k in n])
-
-
-# ---- the restatement: oracle half-steps + dispersion.correction (+ sheet.correction) ------------------------------------------
-class Restated:
-    """An engine of `lib` (no Debye / sheet entry points needed) stepped by half-steps, with the corrections of the Debye media and —
-    after them, as the header orders — of the conducting sheets applied in numpy between the E phase and the H update.  A simulation
-    with sheets and no media skips the Debye part (test_sheet_model_cpu.restated_run is this class).  Edges the operator holds at zero
-    (vi == 0: grid faces, metal) are no dispersive edges, as in fdtd_debye_set: their w is taken as 0.  `seed`: seeded noise in all six
-    field components before the first step (helpers.seeded_fields); the states start at zero either way."""
-
-    def __init__(self, sim, lib, flags=0, seed=None):
-        saved = sim.debye, sim.sheets
-        sim.debye = sim.sheets = None            # the folded operator only: kappa_cells / sheet_lumped stay what they are
-        try:
-            self.e = sim.build(lib, flags=flags)
-        finally:
-            sim.debye, sim.sheets = saved
-        self.sim, d = sim, sim.debye
-        self.K = 0
-        self.sl, self.vi, self.w, self.tab, self.u, self.vprev = [], [], [], [], [], []
-        if d is not None:
-            alpha, oma, beta = _disp().tables(d.media, sim.dt)
-            vi_all = self.e.get_operator()[1]
-            self.K = alpha.shape[1]
-        for c in range(3 if d is not None else 0):
-            (i0, j0, k0), (i1, j1, k1) = d.lo[c], d.hi[c]
-            sl = (slice(k0, k1), slice(j0, j1), slice(i0, i1))
-            self.sl.append(sl)
-            self.vi.append(vi_all[c][sl].copy())
-            self.w.append(np.where(self.vi[c] == 0, np.float32(0), d.w[c].astype(np.float32)))
-            m = d.med[c].astype(np.int64)
-            self.tab.append(tuple(np.moveaxis(t[m], -1, 0).copy() for t in (alpha, oma, beta)))     # [K] + box shape
-            self.u.append(np.zeros((self.K,) + self.w[c].shape, np.float32))
-            self.vprev.append(np.zeros(self.w[c].shape, np.float32))
-        self.sheet = None
-        if sim.sheets is not None:
-            idx, comp, vi, cls, al, b = sim.sheet_tables()
-            self.sheet = dict(idx=idx, vi=vi, al=al[cls].T.copy(), b=b[cls].T.copy(), vprev=np.zeros(idx.size, np.float32),
-                              ib=np.zeros((al.shape[1], idx.size), np.float32), by_c=[np.nonzero(comp == c)[0] for c in range(3)])
-        if seed is not None:
-            from helpers import seeded_fields
-            seeded_fields(self.e, seed)
-        # which states have been off zero at a checkpoint (after the first step, every eighth, the end of every run()): "the wave reached
-        # this edge".  Asked at checkpoints and not of the final values alone because a + b of the u_k update cancels to exactly 0.0f
-        # about once in 2^24 state updates — twice in 800 drawn cases of ~5e7 states (one step earlier and later the state was ~5e-6).
-        self.nstep = 0
-        self.u_moved = [np.zeros(u.shape, bool) for u in self.u]
-        self.vprev_moved = [np.zeros(v.shape, bool) for v in self.vprev]
-        self.ib_moved = None if self.sheet is None else np.zeros(self.sheet["ib"].shape, bool)
-
-    def note_moved(self):
-        for c in range(len(self.u)):
-            self.u_moved[c] |= self.u[c] != 0
-            self.vprev_moved[c] |= self.vprev[c] != 0
-        if self.sheet is not None:
-            if self.ib_moved is None or self.ib_moved.shape != self.sheet["ib"].shape:      # (a test put its own edge set in)
-                self.ib_moved = np.zeros(self.sheet["ib"].shape, bool)
-            self.ib_moved |= self.sheet["ib"] != 0
-
-    def step(self):
-        e = self.e
-        e.half_step(0)
-        Vs = [e.get_field(0, c) for c in range(3)]
-        for c in range(len(self.w)):
-            if self.w[c].size:
-                al, om, be = self.tab[c]
-                Vs[c][self.sl[c]] = _disp().correction(Vs[c][self.sl[c]], self.vi[c], self.w[c], self.vprev[c], self.u[c], al, om, be)
-        if self.sheet is not None:
-            s = self.sheet
-            V = np.empty(s["idx"].size, np.float32)
-            for c in range(3):
-                V[s["by_c"][c]] = Vs[c].reshape(-1)[s["idx"][s["by_c"][c]]]
-            vnew = pkg("sheet").correction(V, s["vi"], s["vprev"], s["ib"], s["al"], s["b"])
-            s["vprev"] = vnew
-            for c in range(3):
-                Vs[c].reshape(-1)[s["idx"][s["by_c"][c]]] = vnew[s["by_c"][c]]
-        for c in range(3):
-            e.set_field(0, c, Vs[c])
-        self.V = Vs
-        e.half_step(1)
-        self.nstep += 1
-        if self.nstep == 1 or self.nstep % 8 == 0:
-            self.note_moved()
-
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
-        self.note_moved()
-
-
-def restating_build(monkeypatch):
-    """Simulation.build -> an engine of the given (oracle) library whose run() is the restatement: the checker the plugin tests use."""
-    Sim = pkg("simulation").Simulation
-    orig = Sim.build
-
-    def build(self, lib, **kw):
-        if self.debye is None or pkg("_capi").has_dispersion(lib):
-            return orig(self, lib, **kw)
-        r = Restated(self, lib, flags=kw.get("flags", 0))
-        r.e.run = r.run
-        self.engine, self.lib = r.e, lib
-        self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
-        self.restated = r
-        return r.e
-
-    monkeypatch.setattr(Sim, "build", build)
 
 
 # ---- fit -------------------------------------------------------------------------------------------------------------------
@@ -377,7 +272,7 @@ def test_port_edge_inside_medium_equals_restatement(oracle_lib):
     s.add_lumped_port(1, 50.0, [x[6], y[5], z[3]], [x[6], y[5], z[6]], "z", 1.0)
     v = sc.voxelize(s, g)
     run = sim.Simulation(g, v, f0=9e9, fc=5e9, boundary="PEC", nr_ts=400, end_criteria=0.0)
-    r = Restated(run, oracle_lib)
+    r = Restatement(run, oracle_lib)
     le = v.lumped[0]
     k, j, i = le.k, le.j, le.i
     (i0, j0, k0) = v.debye.lo[2]
@@ -389,13 +284,13 @@ def test_port_edge_inside_medium_equals_restatement(oracle_lib):
     C = EPS0 * m.eps_inf * A_l
     G = run.kappa_cells[k, j, i] * A_l + le.G
     vi_want = run.dt / (C * (1 + 0.5 * run.dt * G / C))
-    assert le.G > 0 and abs(r.vi[2][b] / vi_want - 1) < 1e-6
+    assert le.G > 0 and abs(r.debye.vi[2][b] / vi_want - 1) < 1e-6
     alpha, beta = m.discretise(run.dt)
     resid, scale = [], []
     for n in range(400):
         Vold = r.e.get_field(0, 2)[k, j, i] if n else np.float32(0)
         Is = [r.e.get_field(1, c) for c in range(3)]
-        u_old = r.u[2][(slice(None),) + b].astype(np.float64)
+        u_old = r.debye.u[2][(slice(None),) + b].astype(np.float64)
         r.step()
         Vnew = float(r.V[2][k, j, i])
         curl = (Is[1][k, j, i] - Is[1][k, j, i - 1]) - (Is[0][k, j, i] - Is[0][k, j - 1, i])
@@ -403,7 +298,7 @@ def test_port_edge_inside_medium_equals_restatement(oracle_lib):
         lhs = C * (Vnew - float(Vold)) / run.dt + G * 0.5 * (Vnew + float(Vold)) - w_e * float(np.sum(beta * u_old))
         resid.append(lhs - float(curl) - src * C * (1 + 0.5 * run.dt * G / C) / run.dt)
         scale.append(abs(float(curl)) + abs(C * Vnew / run.dt))
-    assert max(scale) > 0 and np.abs(r.u[2]).max() > 0
+    assert max(scale) > 0 and np.abs(r.debye.u[2]).max() > 0
     assert np.max(np.abs(resid)) <= 2e-5 * max(scale), (np.max(np.abs(resid)), max(scale))
 
 
@@ -460,14 +355,14 @@ def test_stability_and_passivity_graded_cavity(oracle_lib):
     assert 0 < drift < 1e-3
     run, v = _cavity(g, med=med, nr_ts=nsteps)
     assert run.dt == free.dt and len(v.debye) > 0
-    r = Restated(run, oracle_lib)
+    r = Restatement(run, oracle_lib)
     r.run(stop)
     I_prev = r.e.fields()[1]
     en = []
     for n in range(stop, nsteps):
         r.step()
         I_now = np.stack([r.e.get_field(1, c) for c in range(3)])
-        en.append(_discrete_energy(C, L, np.stack(r.V), I_now, I_prev) + d.branch_energy(v.debye, r.u))
+        en.append(_discrete_energy(C, L, np.stack(r.V), I_now, I_prev) + d.branch_energy(v.debye, r.debye.u))
         I_prev = I_now
     en = np.array(en)
     assert np.all(np.isfinite(en)) and en[0] > 0
@@ -536,7 +431,7 @@ def test_cavity_q_flat_with_debye_and_falling_with_kappa(oracle_lib):
                 stepper = lambda: e.run(1)
             else:
                 run, v = _cavity(g, med=med, port=False, f0=f1_t, fc=f1_t / 2, nr_ts=10)
-                r = Restated(run, oracle_lib)
+                r = Restatement(run, oracle_lib)
                 e = r.e
                 stepper = r.step
             wdt = 2 * np.pi * f2_t * run.dt

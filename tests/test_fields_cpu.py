@@ -104,8 +104,9 @@ def test_plane_wave_impedance_and_phase_in_cell_mode(oracle_lib, monkeypatch):
     """An empty TF/SF box at lambda / 20, an E and an H dump in cell mode inside it: |E| / |H| is eta0 within 2 % (the second-order
     averaging error is (k delta)^2 / 8 = 1.2 %), and E x H* is real: |Im| / Re < 0.03 (without the half-step twiddle of H the phase
     of half a timestep would show, about 0.09)."""
-    from test_planewave_model_cpu import EMPTY_CASES, F_EMPTY, empty_sim, restating_build
-    restating_build(monkeypatch)
+    from restatement import install
+    from test_planewave_model_cpu import EMPTY_CASES, F_EMPTY, empty_sim
+    install(monkeypatch)
     direction, e0 = EMPTY_CASES["axis"]
     lam = 299792458.0 / F_EMPTY
     sim = empty_sim(40, 16, lam / 20, direction, e0, F_EMPTY)

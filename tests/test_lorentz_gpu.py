@@ -10,7 +10,8 @@ from conftest import pkg
 from helpers import seeded_fields
 from test_dispersion_model_cpu import _fr4, _graded
 from test_sheet_model_cpu import _grid
-from test_lorentz_model_cpu import TWO_PI, RestatedLorentz, lorentz_cavity, lorentz_patch, restating_build
+from restatement import Restatement, install
+from test_lorentz_model_cpu import TWO_PI, lorentz_cavity, lorentz_patch
 
 N_SMALL, N_BIG = (14, 13, 12), (26, 24, 22)
 
@@ -56,9 +57,9 @@ CASES = [("pec-blocks-classes", _cavity_case(True), True),
 def _same_state(e, ref):
     for c in range(3):
         vp, x, vi = e.lorentz_state(c)
-        assert np.array_equal(vp, ref.lor["vprev"][c]), c
-        assert np.array_equal(x, ref.lor["x"][c]), c
-        assert np.array_equal(vi, ref.lor["vi"][c]), c
+        assert np.array_equal(vp, ref.lorentz.vprev[c]), c
+        assert np.array_equal(x, ref.lorentz.x[c]), c
+        assert np.array_equal(vi, ref.lorentz.vi[c]), c
 
 
 @pytest.mark.gpu
@@ -66,7 +67,7 @@ def _same_state(e, ref):
 def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, classes):
     nsteps = 400
     ref_sim = make(nsteps)
-    ref = RestatedLorentz(ref_sim, oracle_lib)
+    ref = Restatement(ref_sim, oracle_lib)
     ref.run(nsteps)
     s = make(nsteps)
     e = s.build(hip_lib)
@@ -75,27 +76,27 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, cl
     info = e.schedule_info()
     assert not info["resident"] and info["launches_per_timestep"] in (2, 3), info
     e.run(nsteps)
-    assert np.abs(ref.e.fields()).max() > 0 and min(np.abs(x).max() for x in ref.lor["x"]) > 0
-    assert min(np.abs(v).max() for v in ref.lor["vprev"]) > 0
+    assert np.abs(ref.e.fields()).max() > 0 and min(np.abs(x).max() for x in ref.lorentz.x) > 0
+    assert min(np.abs(v).max() for v in ref.lorentz.vprev) > 0
     if "debye" in name:
-        assert ref.sheet is not None and np.abs(ref.sheet["ib"]).max() > 0 and max(np.abs(u).max() for u in ref.u) > 0
-        assert np.abs(ref.lumped["x"]).max() > 0 and max(np.abs(p).max() for p in ref.mag["iprev"]) > 0
+        assert ref.sheets is not None and np.abs(ref.sheets.ib).max() > 0 and max(np.abs(u).max() for u in ref.debye.u) > 0
+        assert np.abs(ref.elements.x).max() > 0 and max(np.abs(p).max() for p in ref.magnetic.iprev) > 0
     else:
         assert len(s.lorentz.media) == 2
     assert np.array_equal(e.fields(), ref.e.fields())
     _same_state(e, ref)
-    if ref.lumped is not None:
-        assert np.array_equal(e.lumped_state()[1], ref.lumped["x"])
-    if ref.sheet is not None:
-        assert np.array_equal(e.sheet_state()[1], ref.sheet["ib"])
-    if ref.w:
+    if ref.elements is not None:
+        assert np.array_equal(e.lumped_state()[1], ref.elements.x)
+    if ref.sheets is not None:
+        assert np.array_equal(e.sheet_state()[1], ref.sheets.ib)
+    if ref.debye:
         for c in range(3):
-            assert np.array_equal(e.debye_state(c)[1], ref.u[c])
-    if ref.mag is not None:
+            assert np.array_equal(e.debye_state(c)[1], ref.debye.u[c])
+    if ref.magnetic is not None:
         for c in range(3):
-            assert np.array_equal(e.magnetic_state(c)[0], ref.mag["iprev"][c])
+            assert np.array_equal(e.magnetic_state(c)[0], ref.magnetic.iprev[c])
     got = s.port_series()
-    want = [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]
+    want = [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]
     assert len(got) == len(want) == 1
     for (pu, pi), (qu, qi) in zip(got, want):
         assert np.abs(qu).max() > 0 and np.abs(qi).max() > 0
@@ -147,7 +148,7 @@ def test_block_and_vector_boundaries_through_the_raw_abi(hip_lib, oracle_lib, n,
     phi, gam, h_ = _lor().tables(_raw_media(K, nmedia), sim0.dt, K=K)
     assert phi.shape == (nmedia, K, 2, 2)
     tables = (phi, gam, h_, lo, hi, w, med if nmedia > 1 else None)
-    ref = RestatedLorentz(sim0, oracle_lib, seed=9, lorentz=tables)
+    ref = Restatement(sim0, oracle_lib, seed=9, tables={"lorentz": tables})
     ref.run(nsteps)
     e = mk().build(hip_lib)
     seeded_fields(e, 9)
@@ -193,10 +194,10 @@ def test_v_probe_and_v_dft_box_read_the_voltage_before_the_correction(hip_lib, o
     nsamp = nsteps // every + 1
     tw_v = exc.dft_twiddles(freqs, sims[0].dt, every, nsamp, 0.0)
     tw_i = exc.dft_twiddles(freqs, sims[0].dt, every, nsamp, 0.5)
-    ref = RestatedLorentz(sims[0], oracle_lib, seed=4)
+    ref = Restatement(sims[0], oracle_lib, seed=4)
     e_run, e_half = sims[1].build(hip_lib), sims[2].build(hip_lib)
     pids, bids = [], []
-    for e in (ref.e, e_run, e_half):
+    for e in (ref, e_run, e_half):
         pids.append(e.add_probe(capi.KIND_V, idx, comp, w))
     for e in (e_run, e_half):
         e.set_dft(every, tw_v, tw_i)
@@ -206,20 +207,21 @@ def test_v_probe_and_v_dft_box_read_the_voltage_before_the_correction(hip_lib, o
     sl = (slice(lo[2], hi[2] + 1), slice(lo[1], hi[1] + 1), slice(lo[0], hi[0] + 1))
     acc = np.zeros((2,) + tuple(s.stop - s.start for s in sl), np.complex128)
     acc_after = np.zeros_like(acc)
-    after_series = []
+    after_series, seen = [], ref.record("lorentz")
     for n in range(nsteps):
         ref.step()
-        after_series.append(sum(float(wq) * float(ref.V_after[c].reshape(-1)[q]) for wq, c, q in zip(w, comp, idx)))
+        V_before, V_after = seen["lorentz"]
+        after_series.append(sum(float(wq) * float(V_after[c].reshape(-1)[q]) for wq, c, q in zip(w, comp, idx)))
         if n % every == 0:
             t = tw_v[n // every, :, 0] + 1j * tw_v[n // every, :, 1]
-            acc += t[:, None, None, None] * ref.V_before[1][sl].astype(np.float64)[None]
-            acc_after += t[:, None, None, None] * ref.V_after[1][sl].astype(np.float64)[None]
+            acc += t[:, None, None, None] * V_before[1][sl].astype(np.float64)[None]
+            acc_after += t[:, None, None, None] * V_after[1][sl].astype(np.float64)[None]
     e_run.run(70)
     e_run.run(80)
     for _ in range(nsteps):
         e_half.half_step(0)
         e_half.half_step(1)
-    want = ref.e.get_probe(pids[0])[:nsteps]
+    want = ref.get_probe(pids[0])[:nsteps]
     assert want.size == nsteps and np.abs(want).max() > 0
     assert np.max(np.abs(want - np.array(after_series))) > 1e-3 * np.abs(want).max()      # the correction does change these voltages
     assert np.array_equal(e_half.get_probe(pids[2])[:nsteps], want)
@@ -260,13 +262,13 @@ def test_lorentz_media_on_grid_faces_under_both_mur_schedules(hip_lib, oracle_li
     v_prev, states and vi of EVERY edge agree among both schedules and the restatement, bit for bit."""
     nsteps = 120
     ref_sim = _face_sim(name, nsteps)
-    ref = RestatedLorentz(ref_sim, oracle_lib, seed=8)
+    ref = Restatement(ref_sim, oracle_lib, seed=8)
     ref.run(nsteps)
     d = ref_sim.lorentz
-    held = sum(int(np.count_nonzero((np.asarray(d.w[c]).reshape(ref.lor["vi"][c].shape) != 0) & (ref.lor["vi"][c] == 0))) for c in range(3))
+    held = sum(int(np.count_nonzero((np.asarray(d.w[c]).reshape(ref.lorentz.vi[c].shape) != 0) & (ref.lorentz.vi[c] == 0))) for c in range(3))
     assert held > 300, held                      # the edges in question exist, in numbers
     fo = ref.e.fields()
-    assert np.all(np.isfinite(fo)) and np.abs(fo).max() > 0 and min(np.abs(x).max() for x in ref.lor["x"]) > 0
+    assert np.all(np.isfinite(fo)) and np.abs(fo).max() > 0 and min(np.abs(x).max() for x in ref.lorentz.x) > 0
     mur = name.endswith("mur")
     for apply_pass, want in ((None, 2), ("1", 3 if mur else 2)):
         if apply_pass is None:
@@ -285,7 +287,7 @@ def test_lorentz_media_on_grid_faces_under_both_mur_schedules(hip_lib, oracle_li
             vp, x, vi = e.lorentz_state(c)
             rest = vi == 0
             assert rest.any() and np.all(vp[rest] == 0) and np.all(x[:, :, rest] == 0)
-        for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
+        for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
             assert np.abs(qu).max() > 0 and np.abs(qi).max() > 0 and np.array_equal(pu[:nsteps], qu[:nsteps]) and np.array_equal(pi[:nsteps], qi[:nsteps])
         e.close()
 
@@ -356,7 +358,7 @@ def test_schedules_and_refusals_with_lorentz_media(hip_lib, oracle_lib):
 
 @pytest.mark.gpu
 def test_s11_of_a_patch_under_a_lorentz_superstrate_through_openems_api(hip_lib, oracle_lib, tmp_path, monkeypatch):
-    restating_build(monkeypatch)
+    install(monkeypatch)
     freq = np.linspace(3e9, 9e9, 13)
     s11 = []
     for lib, tag in ((hip_lib, "hip"), (oracle_lib, "oracle")):

@@ -2,7 +2,7 @@
 present, the resonances of a filled cavity against their closed forms, passivity, the float32 budget of the correction, the fold into
 the operator, the voxeliser's refusals and the API mirror.  The per-timestep correction is restated in numpy (lorentz.correction) on
 top of the oracle's half-steps — the oracle knows nothing of dispersion — behind the Debye media's correction and in front of the
-sheets' (RestatedLorentz), which is also what the GPU tests compare the HIP path with, bit for bit."""
+sheets' (restatement.Restatement), which is also what the GPU tests compare the HIP path with, bit for bit."""
 import ctypes
 import os
 
@@ -11,9 +11,9 @@ import pytest
 
 from conftest import ROOT, pkg
 from helpers import load_oracle_f64, rel_l2, stage_f64_tables
+from restatement import Restatement, install
 from test_dispersion_model_cpu import _discrete_energy, _edge_CL, _fr4, _graded, _grid
 from test_lumped_model_cpu import pec_cavity
-from test_magnetic_model_cpu import RestatedMagnetic
 from test_oracle_kat_cpu import _peak
 
 C0 = 299792458.0
@@ -27,142 +27,6 @@ FP32_BUDGET_CAP = 10.0
 
 def _lor():
     return pkg("lorentz")
-
-
-# ---- the restatement: RestatedMagnetic + lorentz.correction behind the E half-step --------------------------------------------
-class RestatedLorentz(RestatedMagnetic):
-    """test_magnetic_model_cpu.RestatedMagnetic with the Lorentz media's correction (lorentz.correction) right behind the E half-step.
-    include/fdtd_hip_lorentz.h puts it behind the Debye media's; the base class applies that one later, on the voltages it reads back —
-    the two act on disjoint sets of edges (checked here; the scene layer refuses a shared edge) and each touches its own edges only,
-    so their order leaves every bit where it is.  The sheets' and the elements' corrections follow, as the header orders.
-    `lorentz`: (phi, gam, h, lo, hi, w, med) of fdtd_lorentz_set, default the simulation's own.
-    `f64`: the double-precision oracle library when `lib` is that one — voltages and the operator go through its double entry points
-    and the correction runs in float64, on the float32-rounded tables (`round32`) or on the float64 ones; such a restatement knows
-    Lorentz media only."""
-
-    def __init__(self, sim, lib, flags=0, seed=None, tables=None, magnetic=None, lorentz=None, f64=None, round32=True):
-        saved = sim.lorentz
-        sim.lorentz = None                                   # the folded operator only: the oracle has no fdtd_lorentz_set
-        try:
-            super().__init__(sim, lib, flags=flags, seed=seed, tables=tables, magnetic=magnetic)
-        finally:
-            sim.lorentz = saved
-        self.f64, self.lor = f64, None
-        if f64 is not None:
-            assert lib is f64 and not self.w and self.sheet is None and self.lumped is None and self.mag is None
-            for fn in (f64.fdtd_oracle_get_field_f64, f64.fdtd_oracle_set_field_f64):
-                fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-            f64.fdtd_oracle_get_operator_f64.restype = ctypes.c_int
-            f64.fdtd_oracle_get_operator_f64.argtypes = [ctypes.c_void_p] * 5
-        if lorentz is None and sim.lorentz is not None:
-            d = sim.lorentz
-            ty = np.float32 if round32 else np.float64
-            lorentz = _lor().tables(d.media, sim.dt, dtype=ty) + (d.lo, d.hi, [w.astype(ty) for w in d.w], d.med)
-        if lorentz is not None:
-            self.set_lorentz(lorentz)
-
-    # -- voltages and vi in the restatement's precision
-    def _get_V(self, c):
-        if self.f64 is None:
-            return self.e.get_field(0, c)
-        out = np.zeros(self.e.local_shape, np.float64)
-        assert self.f64.fdtd_oracle_get_field_f64(self.e._ctx, 0, c, out.ctypes.data) == 0
-        return out
-
-    def _set_V(self, c, a):
-        if self.f64 is None:
-            return self.e.set_field(0, c, a)
-        a = np.ascontiguousarray(a, np.float64)
-        assert self.f64.fdtd_oracle_set_field_f64(self.e._ctx, 0, c, a.ctypes.data) == 0
-
-    def _vi(self):
-        if self.f64 is None:
-            return self.e.get_operator()[1]
-        out = [np.zeros((3,) + self.e.local_shape, np.float64) for _ in range(4)]
-        assert self.f64.fdtd_oracle_get_operator_f64(self.e._ctx, *[a.ctypes.data for a in out]) == 0
-        return out[1]
-
-    def set_lorentz(self, tables):
-        phi, gam, h, lo, hi, w, med = tables
-        ty = np.float32 if self.f64 is None else np.float64
-        phi, gam, h = np.asarray(phi), np.asarray(gam), np.asarray(h)
-        vi_all = self._vi()
-        L = dict(K=phi.shape[1], sl=[], vi=[], w=[], tab=[], x=[], vprev=[])
-        for c in range(3):
-            sl = (slice(lo[c][2], hi[c][2]), slice(lo[c][1], hi[c][1]), slice(lo[c][0], hi[c][0]))
-            shape = tuple(max(s.stop - s.start, 0) for s in sl)
-            empty = 0 in shape
-            vi = np.zeros(shape, ty) if empty else vi_all[c][sl].astype(ty)
-            wc = np.zeros(shape, ty) if empty else np.where(vi == 0, ty(0), np.asarray(w[c], ty).reshape(shape))
-            m = np.zeros(shape, np.int64) if (empty or med is None) else np.asarray(med[c], np.int64).reshape(shape)
-            L["sl"].append(sl); L["vi"].append(vi); L["w"].append(wc)
-            L["tab"].append((np.moveaxis(phi[m], (-3, -2, -1), (0, 1, 2)).astype(ty), np.moveaxis(gam[m], (-2, -1), (0, 1)).astype(ty),
-                             np.moveaxis(h[m], (-2, -1), (0, 1)).astype(ty)))           # [K][2][2] / [K][2] + box shape
-            L["x"].append(np.zeros((L["K"], 2) + shape, ty))
-            L["vprev"].append(np.zeros(shape, ty))
-            if c < len(self.w) and self.w[c].size and not empty:                        # no edge is a Debye edge as well
-                both = np.zeros(self.e.local_shape, bool)
-                both[self.sl[c]] = self.w[c] != 0
-                assert not np.any(both[sl] & (wc != 0))
-        self.lor = L
-        self.x_moved = [np.zeros(x.shape, bool) for x in L["x"]]
-
-    def _lorentz_correction(self):
-        L = self.lor
-        self.V_before, self.V_after = [], []
-        for c in range(3):
-            V = self._get_V(c)
-            self.V_before.append(V.copy())
-            if L["w"][c].size:
-                phi, gam, h = L["tab"][c]
-                V[L["sl"][c]] = _lor().correction(V[L["sl"][c]], L["vi"][c], L["w"][c], L["vprev"][c], L["x"][c], phi, gam, h)
-                self._set_V(c, V)
-            self.V_after.append(V)
-
-    def step(self):
-        if self.lor is None:
-            return super().step()
-        e = self.e
-        if self.f64 is not None:
-            e.half_step(0)
-            self._lorentz_correction()
-            e.half_step(1)
-            self.nstep += 1
-            return
-        real = e.half_step
-
-        def half_step(phase):
-            real(phase)
-            if phase == 0:
-                self._lorentz_correction()
-        e.half_step = half_step
-        try:
-            super().step()
-        finally:
-            e.__dict__.pop("half_step", None)
-
-    def note_moved(self):
-        super().note_moved()
-        if getattr(self, "lor", None) is not None:
-            for c in range(3):
-                self.x_moved[c] |= self.lor["x"][c] != 0
-
-
-def restating_build(monkeypatch):
-    """Simulation.build -> for a library without Lorentz entry points (the oracle) an engine whose run() is the restatement."""
-    Sim = pkg("simulation").Simulation
-    orig = Sim.build
-
-    def build(self, lib, **kw):
-        if self.lorentz is None or pkg("_capi").has_lorentz(lib):
-            return orig(self, lib, **kw)
-        r = RestatedLorentz(self, lib, flags=kw.get("flags", 0))
-        r.e.run = r.run
-        self.engine, self.lib = r.e, lib
-        self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
-        self.restated = r
-        return r.e
-    monkeypatch.setattr(Sim, "build", build)
 
 
 def lorentz_cavity(add, *, n=(14, 13, 12), nr_ts=400, boundary="PEC", use_classes=True, f0=10e9, fc=4e9):
@@ -241,7 +105,7 @@ def _kat_cavity(medium, nsteps, *, lines=(41, 25, 33)):
 
 
 def _kat_series(run, g, lib, nsteps):
-    r = RestatedLorentz(run, lib)
+    r = Restatement(run, lib)
     assert g.shape == (41, 25, 33)                      # the KAT's mesh: its source and probe nodes
     r.e.add_source([g.flat(13, 10, 9)], [1], [1.0])
     pid = r.e.add_probe(0, [g.flat(25, 12, 20)], [1], [1.0])
@@ -273,7 +137,7 @@ def test_filled_cavity_resonances_against_closed_forms(oracle_lib):
     r, v = _kat_series(run, g, oracle_lib, nsteps)
     want = np.sqrt(fc ** 2 + fp ** 2)
     e_drude = abs(_peak(v, dt, 0.9 * want, 1.1 * want, pad=64) / want - 1)
-    assert max(np.abs(x).max() for x in r.lor["x"]) > 0
+    assert max(np.abs(x).max() for x in r.lorentz.x) > 0
     lines.append(f"Drude f_p = {fp / 1e9:.2f} GHz, eps_inf = 1: sqrt(f_c^2 + f_p^2) = {want / 1e9:.5f} GHz, relative error {e_drude:.2e}")
     # Lorentz: x = w^2 solves x^2 - x (w0^2 + wp^2 + wc^2 / eps_inf) + w0^2 wc^2 / eps_inf = 0
     lor = lo.LorentzMedium(einf, 0.0, [TWO_PI * fp], [TWO_PI * f0])
@@ -309,7 +173,7 @@ def _energy_run(medium, nsteps, lib64, seed=5):
     c u^2)) after each of nsteps timesteps of the KAT cavity on a 20 x 12 x 16-cell mesh from seeded fields, everything in double."""
     run, g = _kat_cavity(medium, nsteps, lines=(21, 13, 17))
     stage_f64_tables(run, lib64)
-    r = RestatedLorentz(run, lib64, f64=lib64, round32=False)
+    r = Restatement(run, lib64, f64=lib64, round32=False)
     e = r.e
     op = [np.zeros((3,) + e.local_shape, np.float64) for _ in range(4)]
     lib64.fdtd_oracle_get_operator_f64.restype = ctypes.c_int
@@ -330,7 +194,7 @@ def _energy_run(medium, nsteps, lib64, seed=5):
         F = _f64_fields(e, lib64)
         q = 0.5 * float(np.sum(C * F[0] ** 2)) + 0.5 * float(np.sum(L * F[1] * I_prev))
         if medium is not None:
-            q += _lor().branch_energy(run.lorentz, r.lor["x"])
+            q += _lor().branch_energy(run.lorentz, r.lorentz.x)
         en.append(q)
         I_prev = F[1]
     return np.array(en), r
@@ -348,7 +212,7 @@ def test_passivity_in_double(oracle_lib):
     free = lo.LorentzMedium(1.5, 0.0, TWO_PI * np.array([2e9, 3e9]), TWO_PI * np.array([0.0, 3e9]), [0.0, 0.0])
     en, r = _energy_run(free, nsteps, lib64)
     got = float(np.max(np.abs(en / en[0] - 1)))
-    branch = lo.branch_energy(r.sim.lorentz, r.lor["x"])
+    branch = lo.branch_energy(r.sim.lorentz, r.lorentz.x)
     print(f"loss-free Drude + Lorentz poles: drift {got:.2e} (bound {bound:.2e}); branches hold {branch / en[-1]:.3f} of the energy")
     assert branch > 0.01 * en[-1]
     assert got <= bound
@@ -382,7 +246,7 @@ def budget_reference(lib32, lib64, seed, nsteps):
     """(fields of the float64 restatement on the float32-rounded tables, e_plain: rel. L2 of the float32 oracle against the float64
     oracle on the plain scene), from the same seeded fields."""
     from helpers import seeded_fields
-    ref = RestatedLorentz(budget_sim(nsteps), lib64, seed=seed, f64=lib64)
+    ref = Restatement(budget_sim(nsteps), lib64, seed=seed, f64=lib64)
     ref.run(nsteps)
     want = _f64_fields(ref.e, lib64)
     plain = []
@@ -400,11 +264,11 @@ def test_fp32_budget_of_the_correction(oracle_lib):
     nsteps, lines, worst = 300, [], 0.0
     for seed in (1, 2, 3):
         want, e_plain = budget_reference(oracle_lib, lib64, seed, nsteps)
-        r = RestatedLorentz(budget_sim(nsteps), oracle_lib, seed=seed)
+        r = Restatement(budget_sim(nsteps), oracle_lib, seed=seed)
         r.run(nsteps)
         e_lor = rel_l2(r.e.fields().astype(np.float64), want)
         lines.append(f"seed {seed}: float32 restatement against float64 {e_lor:.3e}; plain materials of eps_inf {e_plain:.3e}; ratio {e_lor / e_plain:.2f}")
-        assert 0 < e_plain < 1e-4 and max(np.abs(x).max() for x in r.lor["x"]) > 0
+        assert 0 < e_plain < 1e-4 and max(np.abs(x).max() for x in r.lorentz.x) > 0
         worst = max(worst, e_lor / e_plain)
     lines.append(f"largest ratio {worst:.2f}; cap {FP32_BUDGET_CAP:g}")
     print("\n".join(lines))
@@ -603,7 +467,7 @@ def lorentz_patch(lib, nr_ts=1500):
 
 
 def test_lorentz_superstrate_reaches_the_simulation(oracle_lib, tmp_path, monkeypatch):
-    restating_build(monkeypatch)
+    install(monkeypatch)
     f, port = lorentz_patch(oracle_lib, nr_ts=200)
     f.Run(str(tmp_path / "l"), verbose=0)
     d = f.sim.lorentz
@@ -611,7 +475,7 @@ def test_lorentz_superstrate_reaches_the_simulation(oracle_lib, tmp_path, monkey
     st = f.stats.lorentz
     assert st["K"] == 2 and st["poles"] == 2 and st["edges"] == [int(np.count_nonzero(w)) for w in d.w] and sum(st["edges"]) == len(d) > 0
     assert st["media"][0]["names"] == ["super"] and np.allclose(st["media"][0]["plasma_hz"], [3e9, 5e9]) and np.allclose(st["media"][0]["gamma"], [5e9, 1e9])
-    assert max(np.abs(x).max() for x in f.sim.restated.lor["x"]) > 0
+    assert max(np.abs(x).max() for x in f.sim.restated.lorentz.x) > 0
     # a scene without a Lorentz material reports none
     from test_magnetic_model_cpu import magnetic_patch
     f2, _ = magnetic_patch(oracle_lib, nr_ts=20, mue=1.0)

@@ -8,7 +8,8 @@ import pytest
 from conftest import pkg
 from test_dispersion_model_cpu import _fr4
 from test_sheet_model_cpu import _grid, cavity_sim
-from test_lumped_model_cpu import RestatedLumped, pec_cavity
+from restatement import Restatement, install
+from test_lumped_model_cpu import pec_cavity
 
 N_BIG = (26, 24, 22)
 
@@ -51,7 +52,7 @@ CASES = [("pec-parallel-L-classes", _cavity_case("parallel", True), True),
 def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, classes):
     nsteps = 400
     ref_sim = make(nsteps)
-    ref = RestatedLumped(ref_sim, oracle_lib)
+    ref = Restatement(ref_sim, oracle_lib)
     ref.run(nsteps)
     s = make(nsteps)
     e = s.build(hip_lib)
@@ -62,15 +63,15 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, cl
     info = e.schedule_info()
     assert not info["resident"] and info["launches_per_timestep"] in (2, 3), info
     e.run(nsteps)
-    assert np.abs(ref.e.fields()).max() > 0 and np.all(np.abs(ref.lumped["x"]).max(axis=1)[:1] > 0)
+    assert np.abs(ref.e.fields()).max() > 0 and np.all(np.abs(ref.elements.x).max(axis=1)[:1] > 0)
     if "debye" in name:
-        assert ref.sheet is not None and np.abs(ref.sheet["ib"]).max() > 0 and max(np.abs(u).max() for u in ref.u) > 0
+        assert ref.sheets is not None and np.abs(ref.sheets.ib).max() > 0 and max(np.abs(u).max() for u in ref.debye.u) > 0
     assert np.array_equal(e.fields(), ref.e.fields())
     hv, hx = e.lumped_state()
-    assert np.array_equal(hv, ref.lumped["vprev"]) and np.array_equal(hx, ref.lumped["x"])
-    if ref.sheet is not None:
-        assert np.array_equal(e.sheet_state()[1], ref.sheet["ib"])
-    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
+    assert np.array_equal(hv, ref.elements.vprev) and np.array_equal(hx, ref.elements.x)
+    if ref.sheets is not None:
+        assert np.array_equal(e.sheet_state()[1], ref.sheets.ib)
+    for (pu, pi), (qu, qi) in zip(s.port_series(), [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]):
         assert np.array_equal(pu, qu) and np.array_equal(pi, qi)
 
 
@@ -101,19 +102,18 @@ def test_edge_counts_across_block_boundaries(hip_lib, oracle_lib, n):
     mk = lambda: pec_cavity(None, nr_ts=nsteps)
     edges = [(c, i, j, k) for k in range(3, 9) for j in range(3, 10) for i in range(3, 11) for c in (2, 0, 1)][:n]
     assert len(edges) == n
-    ref = RestatedLumped(mk(), oracle_lib, seed=9)
-    tables = _raw_tables(ref.e, edges, ref.sim.dt)
-    ref.set_lumped(tables)
+    tables = _raw_tables(mk().build(oracle_lib), edges, mk().dt)
+    ref = Restatement(mk(), oracle_lib, seed=9, tables={"elements": tables})
     ref.run(nsteps)
     e = mk().build(hip_lib)
     e.set_lumped(*tables)
     from helpers import seeded_fields
     seeded_fields(e, 9)
     e.run(nsteps)
-    assert np.all(np.isfinite(ref.lumped["x"])) and np.all(np.abs(ref.lumped["x"][0]) > 0)
+    assert np.all(np.isfinite(ref.elements.x)) and np.all(np.abs(ref.elements.x[0]) > 0)
     assert np.array_equal(e.fields(), ref.e.fields())
     hv, hx = e.lumped_state()
-    assert np.array_equal(hv, ref.lumped["vprev"]) and np.array_equal(hx, ref.lumped["x"])
+    assert np.array_equal(hv, ref.elements.vprev) and np.array_equal(hx, ref.elements.x)
     assert not hx[1][tables[3] != 1].any() and (n < 2 or hx[1][tables[3] == 1].any())
 
 
@@ -129,9 +129,9 @@ def test_v_probe_on_a_lumped_edge_is_sampled_before_the_correction(hip_lib, orac
     idx, comp = sims[0].lumped_tables()[:2]
     assert idx.size == 3
     w = np.array([1.0, -0.5, 2.0], np.float32)
-    ref = RestatedLumped(sims[0], oracle_lib, seed=4)
+    ref = Restatement(sims[0], oracle_lib, seed=4)
     e_run, e_half = sims[1].build(hip_lib), sims[2].build(hip_lib)
-    pids = [e.add_probe(capi.KIND_V, idx, comp, w) for e in (ref.e, e_run, e_half)]
+    pids = [e.add_probe(capi.KIND_V, idx, comp, w) for e in (ref, e_run, e_half)]
     for e in (e_run, e_half):
         seeded_fields(e, 4)
     assert e_run.schedule_info()["launches_per_timestep"] == 2
@@ -141,15 +141,15 @@ def test_v_probe_on_a_lumped_edge_is_sampled_before_the_correction(hip_lib, orac
     for _ in range(nsteps):
         e_half.half_step(0)
         e_half.half_step(1)
-    want = ref.e.get_probe(pids[0])[:nsteps]
-    assert np.abs(want).max() > 0 and np.abs(ref.lumped["x"]).max() > 0
+    want = ref.get_probe(pids[0])[:nsteps]
+    assert np.abs(want).max() > 0 and np.abs(ref.elements.x).max() > 0
     # (the correction does change what the probe would read: sampled after it, the series differs)
     after = sum(float(wq) * float(ref.V[c].reshape(-1)[g]) for wq, c, g in zip(w, comp, idx))
     assert after != want[-1]
     assert np.array_equal(e_half.get_probe(pids[2])[:nsteps], want)
     assert np.array_equal(e_run.get_probe(pids[1])[:nsteps], want)
-    assert np.array_equal(e_run.fields(), ref.e.fields()) and np.array_equal(e_run.lumped_state()[1], ref.lumped["x"])
-    assert np.array_equal(e_half.fields(), ref.e.fields()) and np.array_equal(e_half.lumped_state()[1], ref.lumped["x"])
+    assert np.array_equal(e_run.fields(), ref.e.fields()) and np.array_equal(e_run.lumped_state()[1], ref.elements.x)
+    assert np.array_equal(e_half.fields(), ref.e.fields()) and np.array_equal(e_half.lumped_state()[1], ref.elements.x)
 
 
 @pytest.mark.gpu
@@ -163,12 +163,11 @@ def test_lumped_edges_on_a_mur_face_node_plane(hip_lib, oracle_lib, monkeypatch)
     edges = [(1, 0, j, k) for j in range(3, 9) for k in range(3, 9)] + [(2, 5, 0, k) for k in range(3, 8)] + \
             [(1, 6, j, k) for j in range(3, 9) for k in range(4, 7)] + [(0, i, 5, 5) for i in range(3, 9)]
     mk = lambda: cavity_sim(1.0, 1.0, sheet=False, boundary="MUR", nr_ts=nsteps)
-    ref = RestatedLumped(mk(), oracle_lib, seed=6)
-    tables = _raw_tables(ref.e, edges, ref.sim.dt)
+    tables = _raw_tables(mk().build(oracle_lib), edges, mk().dt)
     assert np.count_nonzero(tables[2] == 0) == 36 + 5 and np.count_nonzero(tables[2]) == 18 + 6
-    ref.set_lumped(tables)
+    ref = Restatement(mk(), oracle_lib, seed=6, tables={"elements": tables})
     ref.run(nsteps)
-    assert np.all(np.abs(ref.lumped["x"][0]) > 0)
+    assert np.all(np.abs(ref.elements.x[0]) > 0)
     for apply_pass in (None, "1"):
         if apply_pass is None:
             monkeypatch.delenv("FDTD_MUR_APPLY_PASS", raising=False)
@@ -184,7 +183,7 @@ def test_lumped_edges_on_a_mur_face_node_plane(hip_lib, oracle_lib, monkeypatch)
         e.run(nsteps)
         assert np.array_equal(e.fields(), ref.e.fields())
         hv, hx = e.lumped_state()
-        assert np.array_equal(hv, ref.lumped["vprev"]) and np.array_equal(hx, ref.lumped["x"])
+        assert np.array_equal(hv, ref.elements.vprev) and np.array_equal(hx, ref.elements.x)
         e.close()
 
 
@@ -249,18 +248,7 @@ def _loaded_strip(lib):
 
 @pytest.mark.gpu
 def test_s11_of_a_loaded_strip_through_openems_api(hip_lib, oracle_lib, tmp_path, monkeypatch):
-    Sim = pkg("simulation").Simulation
-    orig = Sim.build
-
-    def build(self, lib, **kw):                   # the oracle library steps through the restatement
-        if pkg("_capi").has_lumped(lib) or not self.element_stepped.size:
-            return orig(self, lib, **kw)
-        r = RestatedLumped(self, lib, flags=kw.get("flags", 0))
-        r.e.run = r.run
-        self.engine, self.lib = r.e, lib
-        self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
-        return r.e
-    monkeypatch.setattr(Sim, "build", build)
+    install(monkeypatch)                          # the oracle library steps through the restatement
     freq = np.linspace(3e9, 9e9, 13)
     s11 = []
     for lib, tag in ((hip_lib, "hip"), (oracle_lib, "oracle")):

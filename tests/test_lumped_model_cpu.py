@@ -1,15 +1,16 @@
 """Lumped R-L-C elements (lumped.py, scene.add_lumped_element): the discretisation's algebra, the admittance an element presents to
 the engine's edge, stability and passivity, what folds into the operator alone, the voxeliser's geometry and refusals, and the API
 mirror.  The per-timestep correction is restated in numpy (lumped.correction) on top of the oracle's half-steps — the oracle knows
-nothing of elements — behind the corrections of the Debye media and the sheets (RestatedLumped), which is also what the GPU tests
-compare the HIP path with, bit for bit."""
+nothing of elements — behind the corrections of the Debye media and the sheets (restatement.Restatement), which is also what the GPU
+tests compare the HIP path with, bit for bit."""
 import os
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, pkg
-from test_dispersion_model_cpu import Restated, _discrete_energy, _edge_CL
+from restatement import Restatement
+from test_dispersion_model_cpu import _discrete_energy, _edge_CL
 from test_sheet_model_cpu import _grid
 
 EPS0 = pkg("constants").EPS0
@@ -17,62 +18,6 @@ EPS0 = pkg("constants").EPS0
 
 def _lumped():
     return pkg("lumped")
-
-
-# ---- the restatement: Restated + lumped.correction behind the sheets' ----------------------------------------------------------
-class RestatedLumped(Restated):
-    """test_dispersion_model_cpu.Restated with the lumped elements' correction after the sheets', as include/fdtd_hip_lumped.h orders:
-    applied to the voltages the base class has just written, in front of the H half-step.  `tables`: (idx, comp, vi, cls, phi, gam,
-    h) of fdtd_lumped_set, default the simulation's own."""
-
-    def __init__(self, sim, lib, flags=0, seed=None, tables=None):
-        saved = sim.element_stepped
-        sim.element_stepped = np.zeros(0, np.int64)          # the folded operator only: the oracle has no fdtd_lumped_set
-        try:
-            super().__init__(sim, lib, flags=flags, seed=seed)
-        finally:
-            sim.element_stepped = saved
-        self.lumped = None
-        if tables is None and sim.element_stepped.size:
-            tables = sim.lumped_tables()
-        if tables is not None:
-            self.set_lumped(tables)
-
-    def set_lumped(self, tables):
-        idx, comp, vi, cls, phi, gam, h = tables
-        idx, comp, cls = np.asarray(idx, np.int64), np.asarray(comp, np.int8), np.asarray(cls, np.int64)
-        self.lumped = dict(idx=idx, comp=comp, vi=np.asarray(vi, np.float32), phi=np.moveaxis(np.asarray(phi, np.float32)[cls], 0, -1).copy(),
-                           gam=np.asarray(gam, np.float32)[cls].T.copy(), h=np.asarray(h, np.float32)[cls].T.copy(),
-                           vprev=np.zeros(idx.size, np.float32), x=np.zeros((2, idx.size), np.float32),
-                           by_c=[np.nonzero(comp == c)[0] for c in range(3)])
-
-    def _lumped_correction(self):
-        s = self.lumped
-        V = np.empty(s["idx"].size, np.float32)
-        for c in range(3):
-            V[s["by_c"][c]] = self.V[c].reshape(-1)[s["idx"][s["by_c"][c]]]
-        v = _lumped().correction(V, s["vi"], s["vprev"], s["x"], s["phi"], s["gam"], s["h"])
-        s["vprev"] = v
-        for c in range(3):
-            if s["by_c"][c].size:
-                self.V[c].reshape(-1)[s["idx"][s["by_c"][c]]] = v[s["by_c"][c]]
-                self.e.set_field(0, c, self.V[c])
-
-    def step(self):
-        if self.lumped is None:
-            return super().step()
-        e = self.e
-        real = e.half_step
-
-        def half_step(phase):
-            if phase == 1:
-                self._lumped_correction()
-            return real(phase)
-        e.half_step = half_step
-        try:
-            super().step()
-        finally:
-            del e.half_step
 
 
 # ---- discretisation algebra ----------------------------------------------------------------------------------------------------
@@ -203,8 +148,8 @@ def measure_identity(lib, element):
     dt = run.dt
     C0 = dt * (1 + vv0) / (2 * vi0)
     G0 = 2 * C0 * (1 - vv0) / (1 + vv0) / dt
-    r = RestatedLumped(run, lib)
-    assert r.lumped is not None and r.lumped["idx"].size == 1
+    r = Restatement(run, lib)
+    assert r.elements is not None and r.elements.idx.size == 1
     curl, vm, up = [], [], []
     vold, peak = 0.0, 0.0
     for n in range(run.nr_ts):
@@ -282,7 +227,7 @@ def _energy_series(run, lib, nsteps, every=10):
         for le in run.element_lumped:
             C[le.comp, le.k, le.j, le.i] += le.C
         weights = np.stack([el.elements[m].energy_weights() for m in el.elem[run.element_stepped]], axis=1)
-    r = RestatedLumped(run, lib)
+    r = Restatement(run, lib)
     stop = len(run.signal) + 1
     r.run(stop)
     en, en_el = [], []
@@ -291,7 +236,7 @@ def _energy_series(run, lib, nsteps, every=10):
         r.step()
         if before is not None:
             now = np.stack([r.e.get_field(1, c) for c in range(3)])
-            en_el.append(lm.stored_energy(weights, r.lumped["x"]) if weights is not None else 0.0)
+            en_el.append(lm.stored_energy(weights, r.elements.x) if weights is not None else 0.0)
             en.append(_discrete_energy(C, L, np.stack(r.V), now, before) + en_el[-1])
     return np.array(en), np.array(en_el), r
 
@@ -314,7 +259,7 @@ def test_loss_free_element_never_gains_energy(oracle_lib, kind, name, L, C):
     assert run.element_stepped.size == 1 and run.dt == run.grid.courant_dt()
     nsteps = 20000
     en, en_el, r = _energy_series(run, oracle_lib, nsteps)
-    assert np.all(np.isfinite(en)) and en[0] > 0 and np.abs(r.lumped["x"]).max() > 0
+    assert np.all(np.isfinite(en)) and en[0] > 0 and np.abs(r.elements.x).max() > 0
     w = en[:en.size // 20 * 20].reshape(-1, 20).max(axis=1)
     rise = float(np.max(np.diff(w)) / w[0])
     above = float(np.max(w) / w[0] - 1)
@@ -503,9 +448,9 @@ def test_caps_on_conducting_sheet_edges_are_metal_not_sheet(oracle_lib):
         assert np.array_equal(run.sheet_vi(), vi_op[run.sheets.comp.astype(np.int64), run.sheets.idx])
         idx, comp = run.lumped_tables()[:2]
         assert idx.size == 4 and np.array_equal(run.lumped_vi(), vi_op[comp.astype(np.int64), idx]) and np.all(run.lumped_vi() != 0)
-    r = RestatedLumped(run1, oracle_lib)
+    r = Restatement(run1, oracle_lib)
     r.run(300)
-    assert np.all(np.isfinite(r.e.fields())) and np.abs(r.lumped["x"]).max() > 0 and np.abs(r.sheet["ib"]).max() > 0
+    assert np.all(np.isfinite(r.e.fields())) and np.abs(r.elements.x).max() > 0 and np.abs(r.sheets.ib).max() > 0
 
 
 def test_caps_that_would_short_a_port_are_refused():

@@ -10,8 +10,9 @@ from conftest import pkg
 from helpers import seeded_fields
 from test_dispersion_model_cpu import _fr4
 from test_sheet_model_cpu import _grid
-from test_magnetic_model_cpu import (BUDGET_SEEDS, FP32_BUDGET_F, RestatedMagnetic, budget_case, budget_sim, magnetic_cavity,
-                                     magnetic_patch, restating_build)
+from restatement import Restatement, install
+from test_magnetic_model_cpu import (BUDGET_SEEDS, FP32_BUDGET_F, budget_case, budget_sim, magnetic_cavity,
+                                     magnetic_patch)
 
 N_SMALL, N_BIG = (14, 13, 12), (26, 24, 22)
 
@@ -51,8 +52,8 @@ CASES = [("pec-blocks-classes", _cavity_case(True), True),
 def _same_state(e, ref):
     for c in range(3):
         ip, iv0 = e.magnetic_state(c)
-        assert np.array_equal(ip, ref.mag["iprev"][c]), c
-        assert np.array_equal(iv0, ref.e.get_operator()[3][c][ref.mag["sl"][c]]), c
+        assert np.array_equal(ip, ref.magnetic.iprev[c]), c
+        assert np.array_equal(iv0, ref.e.get_operator()[3][c][ref.magnetic.sl[c]]), c
 
 
 @pytest.mark.gpu
@@ -60,7 +61,7 @@ def _same_state(e, ref):
 def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, classes):
     nsteps = 400
     ref_sim = make(nsteps)
-    ref = RestatedMagnetic(ref_sim, oracle_lib)
+    ref = Restatement(ref_sim, oracle_lib)
     ref.run(nsteps)
     s = make(nsteps)
     e = s.build(hip_lib)
@@ -69,20 +70,20 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, cl
     info = e.schedule_info()
     assert not info["resident"] and info["launches_per_timestep"] in (2, 3), info
     e.run(nsteps)
-    assert np.abs(ref.e.fields()).max() > 0 and max(np.abs(p).max() for p in ref.mag["iprev"]) > 0
+    assert np.abs(ref.e.fields()).max() > 0 and max(np.abs(p).max() for p in ref.magnetic.iprev) > 0
     if "debye" in name:
-        assert ref.sheet is not None and np.abs(ref.sheet["ib"]).max() > 0 and max(np.abs(u).max() for u in ref.u) > 0
-        assert np.abs(ref.lumped["x"]).max() > 0
+        assert ref.sheets is not None and np.abs(ref.sheets.ib).max() > 0 and max(np.abs(u).max() for u in ref.debye.u) > 0
+        assert np.abs(ref.elements.x).max() > 0
     assert np.array_equal(e.fields(), ref.e.fields())
     _same_state(e, ref)
     # the base operator is what fdtd_get_operator keeps returning: ii = 1 everywhere
     assert np.all(e.get_operator()[2] == 1.0)
-    if ref.lumped is not None:
-        assert np.array_equal(e.lumped_state()[1], ref.lumped["x"])
-    if ref.sheet is not None:
-        assert np.array_equal(e.sheet_state()[1], ref.sheet["ib"])
+    if ref.elements is not None:
+        assert np.array_equal(e.lumped_state()[1], ref.elements.x)
+    if ref.sheets is not None:
+        assert np.array_equal(e.sheet_state()[1], ref.sheets.ib)
     got = s.port_series()
-    want = [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]
+    want = [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]
     assert len(got) == len(want) == 1
     for (pu, pi), (qu, qi) in zip(got, want):
         assert np.abs(qi).max() > 0
@@ -142,7 +143,7 @@ def test_block_and_vector_boundaries_through_the_raw_abi(hip_lib, oracle_lib, n)
         lo.append(l); hi.append(h); cls.append(q)
     assert threads == n
     tables = (np.array([0.97, 1.0], np.float32), np.array([0.5, 0.25], np.float32), lo, hi, cls)
-    ref = RestatedMagnetic(mk(), oracle_lib, seed=9, magnetic=tables)
+    ref = Restatement(mk(), oracle_lib, seed=9, tables={"magnetic": tables})
     seed_I = [ref.e.get_field(1, c) for c in range(3)]
     ref.run(nsteps)
     e = mk().build(hip_lib)
@@ -156,9 +157,9 @@ def test_block_and_vector_boundaries_through_the_raw_abi(hip_lib, oracle_lib, n)
     for c in range(len(BOXES[n])):
         ip = e.magnetic_state(c)[0]
         off = cls[c] == 0
-        assert np.array_equal(ip[off], seed_I[c][ref.mag["sl"][c]][off])         # faces of class 0 keep their bits
+        assert np.array_equal(ip[off], seed_I[c][ref.magnetic.sl[c]][off])         # faces of class 0 keep their bits
         if cls[c].size > 2:
-            assert off.any() and np.any(ip[~off] != seed_I[c][ref.mag["sl"][c]][~off])
+            assert off.any() and np.any(ip[~off] != seed_I[c][ref.magnetic.sl[c]][~off])
 
 
 def _order_sim(n):
@@ -185,10 +186,10 @@ def test_i_probe_and_i_dft_box_read_the_corrected_current(hip_lib, oracle_lib):
     nsamp = nsteps // every + 1
     tw_v = exc.dft_twiddles(freqs, sims[0].dt, every, nsamp, 0.0)
     tw_i = exc.dft_twiddles(freqs, sims[0].dt, every, nsamp, 0.5)
-    ref = RestatedMagnetic(sims[0], oracle_lib, seed=4)
+    ref = Restatement(sims[0], oracle_lib, seed=4)
     e_run, e_half = sims[1].build(hip_lib), sims[2].build(hip_lib)
     pids, bids = [], []
-    for e in (ref.e, e_run, e_half):
+    for e in (ref, e_run, e_half):
         pids.append(e.add_probe(capi.KIND_I, idx, comp, w))
     for e in (e_run, e_half):
         e.set_dft(every, tw_v, tw_i)
@@ -201,20 +202,21 @@ def test_i_probe_and_i_dft_box_read_the_corrected_current(hip_lib, oracle_lib):
     sl = (slice(None), slice(lo[2], hi[2] + 1), slice(lo[1], hi[1] + 1), slice(lo[0], hi[0] + 1))
     acc = np.zeros((2,) + tuple(s.stop - s.start for s in sl[1:]), np.complex128)
     acc_raw = np.zeros_like(acc)
-    raw_series = []
+    raw_series, seen = [], ref.record("magnetic")
     for n in range(nsteps):
         ref.step()
-        raw_series.append(sum(float(wq) * float(ref.I_uncorrected[c].reshape(-1)[q]) for wq, c, q in zip(w, comp, idx)))
+        uncorrected = seen["magnetic"][0]
+        raw_series.append(sum(float(wq) * float(uncorrected[c].reshape(-1)[q]) for wq, c, q in zip(w, comp, idx)))
         if n % every == 0:
             t = tw_i[n // every, :, 0] + 1j * tw_i[n // every, :, 1]
             acc += t[:, None, None, None] * ref.I[1][sl[1:]].astype(np.float64)[None]
-            acc_raw += t[:, None, None, None] * ref.I_uncorrected[1][sl[1:]].astype(np.float64)[None]
+            acc_raw += t[:, None, None, None] * uncorrected[1][sl[1:]].astype(np.float64)[None]
     e_run.run(70)
     e_run.run(80)
     for _ in range(nsteps):
         e_half.half_step(0)
         e_half.half_step(1)
-    want = ref.e.get_probe(pids[0])
+    want = ref.get_probe(pids[0])
     assert want.size == nsteps and np.abs(want).max() > 0
     assert np.max(np.abs(want - np.array(raw_series))) > 1e-3 * np.abs(want).max()      # the correction does change what the probe reads
     assert np.array_equal(e_half.get_probe(pids[2])[:nsteps], want)
@@ -233,7 +235,7 @@ def test_set_field_reprimes_i_prev(hip_lib, oracle_lib):
     """fdtd_set_field(FDTD_KIND_I) after fdtd_magnetic_set loads i_prev again: a run from seeded fields equals the restatement, and
     i_prev holds the seeded currents before the first step."""
     nsteps = 120
-    ref = RestatedMagnetic(_order_sim(nsteps), oracle_lib)
+    ref = Restatement(_order_sim(nsteps), oracle_lib)
     e = _order_sim(nsteps).build(hip_lib)
     assert all(not e.magnetic_state(c)[0].any() for c in range(3))
     rng = np.random.default_rng(21)
@@ -243,7 +245,7 @@ def test_set_field_reprimes_i_prev(hip_lib, oracle_lib):
             e.set_field(kind, c, a)
             ref.set_field(kind, c, a)
             if kind == 1:
-                assert np.array_equal(e.magnetic_state(c)[0], a[ref.mag["sl"][c]])
+                assert np.array_equal(e.magnetic_state(c)[0], a[ref.magnetic.sl[c]])
     ref.run(nsteps)
     e.run(nsteps)
     assert np.array_equal(e.fields(), ref.e.fields())
@@ -302,7 +304,7 @@ def test_schedules_with_magnetic_faces(hip_lib, oracle_lib):
 
 @pytest.mark.gpu
 def test_s11_of_a_patch_on_a_magnetic_substrate_through_openems_api(hip_lib, oracle_lib, tmp_path, monkeypatch):
-    restating_build(monkeypatch)
+    install(monkeypatch)
     freq = np.linspace(3e9, 9e9, 13)
     s11 = []
     for lib, tag in ((hip_lib, "hip"), (oracle_lib, "oracle")):

@@ -7,8 +7,8 @@ import pytest
 
 from conftest import pkg
 from helpers import rel_l2
+from restatement import Restatement, install
 from test_dispersion_model_cpu import _discrete_energy, _edge_CL, _graded
-from test_lumped_model_cpu import RestatedLumped
 from test_oracle_kat_cpu import _peak
 
 C0 = 299792458.0
@@ -55,106 +55,6 @@ def build_raw(sim, lib, magnetic="own"):
     finally:
         sim.magnetic, sim.device_operator, sim.use_classes = saved
         sim._op = op
-
-
-class RestatedMagnetic(RestatedLumped):
-    """test_lumped_model_cpu.RestatedLumped with the magnetic faces' correction after the H half-step, as include/fdtd_hip_magnetic.h
-    orders: the six fp32 statements (magnetic.correction) on the currents the oracle has just written.  i_prev is loaded from the I
-    arrays when the set is made (after `seed`), as fdtd_magnetic_set does.  The oracle samples its I-probes inside the H half-step,
-    i.e. BEFORE this correction, so the I-probe series are kept here (get_probe of the engine returns them): sum_e w_e I_e in double,
-    in the probe's edge order — the products are exact in double, so this is the oracle's fma chain.  `tables`: as RestatedLumped;
-    `magnetic`: (a, b, lo, hi, cls) of fdtd_magnetic_set, default the simulation's own."""
-
-    def __init__(self, sim, lib, flags=0, seed=None, tables=None, magnetic=None):
-        saved = sim.magnetic
-        sim.magnetic = None                                  # the base operator only: the oracle has no fdtd_magnetic_set
-        try:
-            super().__init__(sim, lib, flags=flags, seed=seed, tables=tables)
-        finally:
-            sim.magnetic = saved
-        self.mag = None
-        self.i_probes, self.i_series = {}, {}
-        e = self.e
-        for p, (_, iid) in zip(sim.vox.ports, sim._port_probe_ids):
-            self.i_probes[iid] = (np.asarray(p.i_idx, np.int64), np.asarray(p.i_comp, np.int64), np.asarray(p.i_w, np.float32))
-        real_add, real_get = e.add_probe, e.get_probe
-
-        def add_probe(kind, idx, comp, w):
-            pid = real_add(kind, idx, comp, w)
-            if kind == 1:
-                self.i_probes[pid] = (np.asarray(idx, np.int64), np.asarray(comp, np.int64), np.asarray(w, np.float32))
-            return pid
-
-        def get_probe(pid):
-            if self.mag is not None and pid in self.i_probes:
-                return np.array(self.i_series.get(pid, []), np.float64)
-            return real_get(pid)
-        e.add_probe, e.get_probe = add_probe, get_probe
-        if magnetic is None and sim.magnetic is not None:
-            magnetic = sim.magnetic.tables()
-        if magnetic is not None:
-            self.set_magnetic(magnetic)
-
-    def set_magnetic(self, tables):
-        ta, tb, lo, hi, cls = tables
-        sl = [(slice(lo[c][2], hi[c][2]), slice(lo[c][1], hi[c][1]), slice(lo[c][0], hi[c][0])) for c in range(3)]
-        cls = [np.asarray(cls[c], np.uint8).reshape([s.stop - s.start for s in sl[c]]) for c in range(3)]
-        self.mag = dict(ta=np.asarray(ta, np.float32), tb=np.asarray(tb, np.float32), sl=sl, cls=cls,
-                        iprev=[self.e.get_field(1, c)[sl[c]].copy() for c in range(3)])
-
-    def set_field(self, kind, comp, a):
-        """fdtd_set_field, with the re-priming of i_prev the header promises for FDTD_KIND_I."""
-        self.e.set_field(kind, comp, a)
-        if kind == 1 and self.mag is not None:
-            self.mag["iprev"][comp] = np.asarray(a, np.float32)[self.mag["sl"][comp]].copy()
-
-    def _magnetic_correction(self):
-        m, e = self.mag, self.e
-        self.I_uncorrected = [e.get_field(1, c) for c in range(3)]
-        Is = [a.copy() for a in self.I_uncorrected]
-        for c in range(3):
-            if m["cls"][c].size:
-                Is[c][m["sl"][c]] = _mag().correction(Is[c][m["sl"][c]], m["iprev"][c], m["cls"][c], m["ta"], m["tb"])
-                e.set_field(1, c, Is[c])
-        self.I = Is
-        for pid, (idx, comp, w) in self.i_probes.items():
-            s = 0.0
-            for g, c, wq in zip(idx, comp, w):
-                s = float(wq) * float(Is[c].reshape(-1)[g]) + s
-            self.i_series.setdefault(pid, []).append(s)
-
-    def step(self):
-        if self.mag is None:
-            return super().step()
-        e = self.e
-        real = e.half_step
-
-        def half_step(phase):
-            real(phase)
-            if phase == 1:
-                self._magnetic_correction()
-        e.half_step = half_step
-        try:
-            super().step()
-        finally:
-            e.__dict__.pop("half_step", None)
-
-
-def restating_build(monkeypatch):
-    """Simulation.build -> for a library without magnetic entry points (the oracle) an engine whose run() is the restatement."""
-    Sim = pkg("simulation").Simulation
-    orig = Sim.build
-
-    def build(self, lib, **kw):
-        if self.magnetic is None or pkg("_capi").has_magnetic(lib):
-            return orig(self, lib, **kw)
-        r = RestatedMagnetic(self, lib, flags=kw.get("flags", 0))
-        r.e.run = r.run
-        self.engine, self.lib = r.e, lib
-        self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
-        self.restated = r
-        return r.e
-    monkeypatch.setattr(Sim, "build", build)
 
 
 def magnetic_cavity(add, *, n=(14, 13, 12), nr_ts=400, boundary="PEC", use_classes=True, f0=10e9, fc=4e9):
@@ -355,7 +255,7 @@ def _block(mu_r, sigma_m=0.0):
 def _energy_windows(run, lib, nsteps, every=10):
     C, _ = _edge_CL(run.grid, run.vox.eps_r)
     L = _mag().inductance(run.grid, run.magnetic.s)
-    r = RestatedMagnetic(run, lib)
+    r = Restatement(run, lib)
     stop = len(run.signal) + 1
     r.run(stop)
     en = []
@@ -384,7 +284,7 @@ def test_loss_free_block_never_gains_energy(oracle_lib):
     rise, above = float(np.max(np.diff(w)) / w[0]), float(np.max(w) / w[0] - 1)
     print(f"loss-free block: energy {en[0]:.4e} -> {en[-1]:.4e}; largest rise between window maxima {rise:.2e} (bound {400 * per_step:.2e}), "
           f"most above the start {above:.2e} (bound {(nsteps - len(run.signal)) * per_step:.2e}); spread {np.ptp(en) / en[0]:.2e}")
-    assert np.all(np.isfinite(en)) and en[0] > 0 and max(np.abs(p).max() for p in r.mag["iprev"]) > 0
+    assert np.all(np.isfinite(en)) and en[0] > 0 and max(np.abs(p).max() for p in r.magnetic.iprev) > 0
     assert rise <= 400 * per_step and above <= (nsteps - len(run.signal)) * per_step
     # ... and it is CONSTANT within the same accumulated rounding, sample by sample: with another L (mu0 A / l~ without s) the sum
     # swings with the field between the block and the air around it
@@ -440,7 +340,7 @@ def test_restatement_agrees_with_the_raw_operator(oracle_lib):
     lib64 = load_oracle_f64()
 
     def stepper(sim, seed, nsteps):
-        r = RestatedMagnetic(sim, oracle_lib, seed=seed)
+        r = Restatement(sim, oracle_lib, seed=seed)
         r.run(nsteps)
         return r.e.fields()
     worst = 0.0
@@ -472,7 +372,7 @@ def magnetic_patch(lib, nr_ts=1500, mue=2.0, sigma=0.0):
 
 
 def test_mue_and_sigma_reach_the_simulation(oracle_lib, tmp_path, monkeypatch):
-    restating_build(monkeypatch)
+    install(monkeypatch)
     f, port = magnetic_patch(oracle_lib, nr_ts=200, mue=2.0, sigma=150.0)
     f.Run(str(tmp_path / "m"), verbose=0)
     m = f.sim.magnetic
@@ -480,7 +380,7 @@ def test_mue_and_sigma_reach_the_simulation(oracle_lib, tmp_path, monkeypatch):
     st = f.stats.magnetic
     assert st["media"] == ["sub"] and st["classes"] == m.ncls >= 2 and st["faces"] == m.faces() and sum(st["faces"]) == len(m) > 0
     assert st["lo"][2] == [5, 5, 8] and st["hi"][2] == [20, 18, 11] and st["lo"][0] == [5, 5, 8] and st["hi"][0] == [21, 18, 10]
-    assert f.sim.restated.mag is not None and max(np.abs(p).max() for p in f.sim.restated.mag["iprev"]) > 0
+    assert f.sim.restated.magnetic is not None and max(np.abs(p).max() for p in f.sim.restated.magnetic.iprev) > 0
     # unknown keywords stay as tolerant as they were, and a plain material stays plain
     f2, _ = magnetic_patch(oracle_lib, nr_ts=20, mue=1.0)
     f2.GetCSX().AddMaterial("odd", epsilon=1.0, density=3.0).AddBox([1, 1, 1], [2, 2, 2])

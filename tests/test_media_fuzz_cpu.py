@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 
 import fuzz_parity
-from test_dispersion_model_cpu import Restated
-from test_sheet_model_cpu import MU0, _sheet, cavity_sim, restated_run
+from restatement import Restatement
+from test_sheet_model_cpu import MU0, _sheet, cavity_sim
 
 WANTED = ({f"k_debye<{m},{k}>" for m in ("false", "true") for k in (4, 8)} | {"8 media"} | {f"x0 mod 4 = {r}" for r in range(4)}
           | {f"x1 mod 4 = {r}" for r in range(4)} | {f"nx mod 4 = {r}" for r in range(4)}
@@ -115,25 +115,25 @@ def test_reference_side_of_the_first_cases_moves_everywhere(oracle_lib):
 def test_reference_side_of_the_directed_scenes(oracle_lib, name):
     import test_dispersion_gpu as tg
     sim = tg._sim(name, 40)
-    r = Restated(sim, oracle_lib, seed=21)
+    r = Restatement(sim, oracle_lib, seed=21)
     r.run(12)
     assert fuzz_parity.media_reference_problems(r) == []
     if name.startswith(("slab", "filled")):       # dispersive cells on face nodes: edges the operator holds are at rest, and they exist
-        held = [(sim.debye.w[c] != 0) & (r.vi[c] == 0) for c in range(3)]
+        held = [(sim.debye.w[c] != 0) & (r.debye.vi[c] == 0) for c in range(3)]
         assert sum(int(h.sum()) for h in held) > 300
-        assert all(np.all(r.u[c][:, held[c]] == 0) and np.all(r.vprev[c][held[c]] == 0) for c in range(3))
+        assert all(np.all(r.debye.u[c][:, held[c]] == 0) and np.all(r.debye.vprev[c][held[c]] == 0) for c in range(3))
 
 
 def test_reference_side_of_the_alignment_scenes(oracle_lib):
     import test_dispersion_gpu as tg
     for x0, x1, nx in (tg.X_ALIGN[0], tg.X_ALIGN[7], tg.X_ALIGN[16], tg.X_ALIGN[18]):
-        r = Restated(tg._x_aligned_sim(x0, x1, nx, 20), oracle_lib, seed=1)
+        r = Restatement(tg._x_aligned_sim(x0, x1, nx, 20), oracle_lib, seed=1)
         r.run(8)
         assert fuzz_parity.media_reference_problems(r) == []
 
 
 def _sheet_run_as_it_was(sim, lib, nsteps):
-    """The sheets-only restatement as test_sheet_model_cpu.restated_run spelt it before it became a wrapper of Restated."""
+    """The sheets-only restatement spelt out on its own, as the sheet tests first had it: an independent check of restatement.Restatement."""
     saved, sim.sheets = sim.sheets, None
     try:
         e = sim.build(lib)
@@ -163,12 +163,18 @@ def _sheet_run_as_it_was(sim, lib, nsteps):
 def test_one_checker_equals_the_sheets_only_one(oracle_lib):
     n = 300
     e0, v0, i0 = _sheet_run_as_it_was(cavity_sim(3e5, 1e-3, nr_ts=n), oracle_lib, n)
-    e1, v1, i1, en = restated_run(cavity_sim(3e5, 1e-3, nr_ts=n), oracle_lib, n, energy_every=100)
-    r = Restated(cavity_sim(3e5, 1e-3, nr_ts=n), oracle_lib)
-    assert r.K == 0 and r.w == [] and r.sheet is not None
+    r1, en = Restatement(cavity_sim(3e5, 1e-3, nr_ts=n), oracle_lib), []
+    for q in range(n):                               # step by step, with the energy every 100 timesteps
+        r1.step()
+        if (q + 1) % 100 == 0:
+            sv, si = r1.e.energy()
+            en.append(8.854187817e-12 * sv + MU0 * si)
+    e1, v1, i1, en = r1.e, r1.sheets.vprev, r1.sheets.ib, np.array(en)
+    r = Restatement(cavity_sim(3e5, 1e-3, nr_ts=n), oracle_lib)
+    assert r.debye is None and r.sheets is not None
     r.run(n)
     assert np.abs(i0).max() > 0 and np.abs(e0.fields()).max() > 0
-    for e, v, i in ((e1, v1, i1), (r.e, r.sheet["vprev"], r.sheet["ib"])):
+    for e, v, i in ((e1, v1, i1), (r.e, r.sheets.vprev, r.sheets.ib)):
         assert np.array_equal(e.fields(), e0.fields()) and np.array_equal(v, v0) and np.array_equal(i, i0)
     sv, si = e0.energy()
     want = 8.854187817e-12 * sv + MU0 * si      # (a threaded reduction: equal to rounding, not to the bit)

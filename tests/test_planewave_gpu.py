@@ -10,10 +10,11 @@ import pytest
 
 from conftest import ROOT, pkg
 from helpers import seeded_fields
+from restatement import Restatement
 from test_dispersion_model_cpu import _fr4
 from test_sheet_model_cpu import _grid
-from test_lumped_model_cpu import RestatedLumped, pec_cavity
-from test_planewave_model_cpu import RestatedPlaneWave, SPHERE, SPHERE_KA, sphere_csx, sphere_freqs
+from test_lumped_model_cpu import pec_cavity
+from test_planewave_model_cpu import SPHERE, SPHERE_KA, sphere_csx, sphere_freqs
 
 N_BIG = (26, 24, 22)
 OBLIQUE = dict(e0=(2, -2, 1), direction=(1, 2, 2))
@@ -54,13 +55,13 @@ CASES = [("pec-oblique-classes", _cavity_case(True), True),
 def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, classes):
     nsteps = 300
     ref_sim = make(nsteps)
-    ref = RestatedPlaneWave(ref_sim, oracle_lib, make=lambda s, l: RestatedLumped(s, l))
+    ref = Restatement(ref_sim, oracle_lib)
     ref.run(nsteps)
     s = make(nsteps)
     e = s.build(hip_lib)
     assert e.operator_form()[0].startswith("classes") == classes, e.operator_form()
     # the tables the host hands fdtd_planewave_set come from the device operator, and equal the restatement's from the oracle's
-    for a, b in zip(s.planewave_tables.args(), ref.tables.args()):
+    for a, b in zip(s.planewave_tables.args(), ref.pw_e.tables.args()):
         assert np.array_equal(a, b)
     assert s.planewave_tables.E[0].size > 256 and s.planewave_tables.H[0].size > 256
     info = e.schedule_info()
@@ -71,10 +72,10 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, cl
     assert all(np.abs(V[c][tot[c]]).max() > 0 for c in range(3))             # the wave is in the box
     assert np.array_equal(e.fields(), ref.e.fields())
     if "debye" in name:
-        r = ref.inner
-        assert r.sheet is not None and np.abs(r.sheet["ib"]).max() > 0 and max(np.abs(u).max() for u in r.u) > 0 and np.abs(r.lumped["x"]).max() > 0
-        assert np.array_equal(e.sheet_state()[1], r.sheet["ib"]) and np.array_equal(e.lumped_state()[1], r.lumped["x"])
-    series = list(zip(s.port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in ref_sim._port_probe_ids]))
+        r = ref
+        assert r.sheets is not None and np.abs(r.sheets.ib).max() > 0 and max(np.abs(u).max() for u in r.debye.u) > 0 and np.abs(r.elements.x).max() > 0
+        assert np.array_equal(e.sheet_state()[1], r.sheets.ib) and np.array_equal(e.lumped_state()[1], r.elements.x)
+    series = list(zip(s.port_series(), [(ref.get_probe(u), ref.get_probe(i)) for u, i in ref_sim._port_probe_ids]))
     assert len(series) == 1
     for (pu, pi), (qu, qi) in series:
         assert np.abs(qu).max() > 0 and np.array_equal(pu, qu) and np.array_equal(pi, qi)
@@ -108,7 +109,7 @@ def test_entry_counts_across_block_boundaries(hip_lib, oracle_lib, n):
     mk = lambda: pec_cavity(None, nr_ts=nsteps)
     tables = _hand_tables(n)
     assert tables.E[0].size == n and tables.H[0].size == n and 2 * nsteps > tables.sig2.size
-    ref = RestatedPlaneWave(mk(), oracle_lib, tables=tables)
+    ref = Restatement(mk(), oracle_lib, tables={"pw": tables})
     seeded_fields(ref.e, 9)
     ref.run(nsteps)
     e = mk().build(hip_lib)
@@ -201,7 +202,7 @@ def test_replacing_and_removing_the_set(hip_lib, oracle_lib):
     t1, t2 = _hand_tables(300, seed=3), _hand_tables(129, seed=5)
     empty = [a[:0] for a in t1.E] + [a[:0] for a in t1.H] + [None]
     # a second set replaces the first
-    ref = RestatedPlaneWave(mk(), oracle_lib, tables=t2)
+    ref = Restatement(mk(), oracle_lib, tables={"pw": t2})
     seeded_fields(ref.e, 2)
     ref.run(nsteps)
     e = mk().build(hip_lib)

@@ -2,7 +2,7 @@
 two entry lists, the empty box (the analytic pulse inside, the leakage outside and its second-order convergence), a PEC sphere against
 the Mie series, the placement refusals and the API mirror.  The per-timestep corrections are restated in numpy (planewave.apply) on
 top of the oracle's half-steps — the oracle knows nothing of plane waves — last behind each half-step, as include/fdtd_hip_planewave.h
-orders (RestatedPlaneWave); that is also what the GPU tests compare the HIP path with, bit for bit.
+orders (restatement.Restatement); that is also what the GPU tests compare the HIP path with, bit for bit.
 
 The restatement runs on the float32 oracle: the ABI reads and writes fields in float32, and the leakage levels measured here (1e-2 ...
 1e-3 of the incident wave) lie four orders above float32 rounding.  The table algebra is checked in float64, in numpy."""
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, pkg
+from restatement import Restatement, install
 
 C0 = 299792458.0
 ETA0 = 376.730313668
@@ -49,95 +50,6 @@ def _uniform(n, h=1e-3):
 def _graded(n=(12, 11, 10), h=1e-3, seed=7):
     rng = np.random.default_rng(seed)
     return pkg("grid").RectGrid(*[np.concatenate([[0.0], np.cumsum(h * rng.uniform(0.7, 1.4, k - 1))]) for k in n])
-
-
-# ---- the restatement: any other restatement (or a bare engine) + planewave.apply last behind each half-step --------------------------
-class _Bare:
-    """The oracle's own half-steps, nothing else: the innermost `inner` of RestatedPlaneWave for a scene without other corrections."""
-
-    def __init__(self, sim, lib, flags=0):
-        self.e = sim.build(lib, flags=flags)
-
-    def step(self):
-        self.e.half_step(0)
-        self.e.half_step(1)
-
-
-class RestatedPlaneWave:
-    """A restatement `inner` (test_*_model_cpu.Restated..., RestatedConformal, or None for the bare oracle) with the plane wave's two
-    corrections (planewave.apply, the fp32 statements of include/fdtd_hip_planewave.h): the edge list on the voltages right in front of
-    the H half-step, i.e. behind every other correction of the E side, the face list on the currents right behind the H half-step.
-    `make(sim, lib)` builds `inner` while the simulation's plane wave is hidden (the oracle has no fdtd_planewave_set).  The other
-    restatements' H-side corrections and the oracle's own I-probes come before / inside the H half-step; the placement rules keep all of
-    them off the corrected elements, so every bit stays where the header's order puts it.  `tables`: planewave.Tables, default the
-    simulation's own from the engine's operator."""
-
-    def __init__(self, sim, lib, make=None, tables=None, flags=0):
-        saved = sim.plane_wave
-        sim.plane_wave = None
-        try:
-            self.inner = _Bare(sim, lib, flags) if make is None else make(sim, lib)
-        finally:
-            sim.plane_wave = saved
-        self.sim, self.e = sim, self.inner.e
-        if tables is None:
-            op = self.e.get_operator()
-            tables = _pw().tables(sim.grid, sim.plane_wave, sim.dt, op[1], op[3], sim.signal2)
-        self.tables = tables
-
-    def _correct(self, kind, n):
-        tab = self.tables
-        comps = np.unique((tab.E if kind == 0 else tab.H)[1])
-        F = [self.e.get_field(kind, c) if c in comps else None for c in range(3)]
-        _pw().apply([f if f is not None else np.zeros(0, np.float32) for f in F], tab, n, kind)
-        for c in comps:
-            self.e.set_field(kind, int(c), F[c])
-            v = getattr(self.inner, "V", None) if kind == 0 else None
-            if v is not None:
-                v[c] = F[c]              # (a restatement that reads its own copy of the voltages after the H half-step: RestatedConformal)
-
-    def step(self):
-        e = self.e
-        real = e.half_step
-
-        def half_step(phase):
-            if phase != 1:
-                return real(phase)
-            n = int(e.step)
-            self._correct(0, n)
-            real(1)
-            self._correct(1, n)
-        e.half_step = half_step
-        try:
-            self.inner.step()
-        finally:
-            e.__dict__.pop("half_step", None)
-
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
-
-
-def restating_build(monkeypatch, make=None):
-    """Simulation.build -> for a library without the plane-wave entry point (the oracle) an engine whose run() is the restatement."""
-    Sim = pkg("simulation").Simulation
-    orig = Sim.build
-
-    def build(self, lib, **kw):
-        if self.plane_wave is None or pkg("_capi").has_planewave(lib):
-            return orig(self, lib, **kw)
-        mk = make
-        if mk is None and self.conformal is not None:
-            from test_conformal_model_cpu import RestatedConformal
-            mk = lambda s, l: RestatedConformal(s, l)
-        r = RestatedPlaneWave(self, lib, make=mk)
-        r.e.run = r.run
-        self.engine, self.lib = r.e, lib
-        self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
-        self.planewave_tables = r.tables
-        self.restated = r
-        return r.e
-    monkeypatch.setattr(Sim, "build", build)
 
 
 # ---- scenes shared with test_planewave_gpu.py ----------------------------------------------------------------------------------------
@@ -230,7 +142,7 @@ _SPHERE_RUNS = {}
 def restated_sphere(oracle_lib, monkeypatch, conformal=True):
     """The sphere scene stepped by the restatement on the oracle, once per session: [(back, forward)] per frequency."""
     if conformal not in _SPHERE_RUNS:
-        restating_build(monkeypatch)
+        install(monkeypatch)
         sim = sphere_sim(conformal=conformal)
         sim.build(oracle_lib)
         sim.run()
@@ -387,7 +299,7 @@ LEAK_DB = {"axis": -35.27, "oblique": -52.31}
 def _empty_run(oracle_lib, N, box, h, direction, e0, centre=False):
     pwm = _pw()
     sim = empty_sim(N, box, h, direction, e0, F_EMPTY)
-    r = RestatedPlaneWave(sim, oracle_lib)
+    r = Restatement(sim, oracle_lib)
     g, pw = sim.grid, sim.plane_wave
     tot = pwm.total_masks(g.shape, pw.lo, pw.hi)[0]
     nsteps = len(sim.signal) + int(pw.far_delay(g) / sim.dt) + 20
@@ -624,7 +536,7 @@ def test_add_excitation_surface(oracle_lib, monkeypatch, tmp_path):
     call = FDTD.calls[-3]
     assert call["name"] == "plane_wave" and call["exc_type"] == 10 and call["exc_val"] == [0.0, 1.0, 1.0] and call["delay"] == 0.0
     assert FDTD.calls[-2] == {"op": "SetPropagationDir", "prop": "plane_wave", "val": [0.0, 0.0, 2.0]}
-    restating_build(monkeypatch)
+    install(monkeypatch)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)
         FDTD.Run(str(tmp_path), verbose=0)                   # a scene with a plane wave and no port builds and runs

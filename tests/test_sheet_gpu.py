@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import pkg
-from test_sheet_model_cpu import MU0, _grid, cavity_sim, restated_run
+from restatement import Restatement
+from test_sheet_model_cpu import MU0, _grid, cavity_sim
 
 
 def _resolved_sim(boundary, nr_ts):
@@ -35,7 +36,9 @@ def test_hip_matches_restatement_bit_for_bit(hip_lib, oracle_lib, name, make, cl
     nsteps = 400
     ref_sim = make(nsteps)
     ref_sim.use_classes = classes
-    ref, vprev, ib, _ = restated_run(ref_sim, oracle_lib, nsteps)
+    r = Restatement(ref_sim, oracle_lib)
+    r.run(nsteps)
+    ref, vprev, ib = r.e, r.sheets.vprev, r.sheets.ib
     s = make(nsteps)
     s.use_classes = classes
     e = s.build(hip_lib)
@@ -64,12 +67,7 @@ def _raw_sheet_tables(e, edges):
 
 
 def _restated_with_raw_sheets(sim, lib, tables, seed):
-    from test_dispersion_model_cpu import Restated
-    r = Restated(sim, lib, seed=seed)
-    idx, comp, vi, cls, al, b = tables
-    r.sheet = dict(idx=idx, vi=vi, al=al[cls].T.copy(), b=b[cls].T.copy(), vprev=np.zeros(idx.size, np.float32),
-                   ib=np.zeros((al.shape[1], idx.size), np.float32), by_c=[np.nonzero(comp == c)[0] for c in range(3)])
-    return r
+    return Restatement(sim, lib, seed=seed, tables={"sheets": tables})
 
 
 @pytest.mark.gpu
@@ -78,16 +76,15 @@ def test_v_probe_on_a_sheet_edge_is_sampled_before_the_correction(hip_lib, oracl
     such restriction, so a probe added there must read the voltage BEFORE k_sheet changed it, under fdtd_run as under fdtd_half_step
     and in the restatement (with fused sources fdtd_run used to sample it in update_H's probe block, after the correction)."""
     from helpers import seeded_fields
-    from test_dispersion_model_cpu import Restated
     capi = pkg("_capi")
     nsteps = 150
     sims = [cavity_sim(3e5, 1e-3, nr_ts=nsteps) for _ in range(3)]
     sh = sims[0].sheets
     on = [int(q) for q in np.nonzero(sims[0].sheet_vi() != 0)[0][[3, 40, 77]]]                  # three sheet edges, live ones
     idx, comp, w = sh.idx[on], sh.comp[on], np.array([1.0, -0.5, 2.0], np.float32)
-    ref = Restated(sims[0], oracle_lib, seed=4)
+    ref = Restatement(sims[0], oracle_lib, seed=4)
     e_run, e_half = sims[1].build(hip_lib), sims[2].build(hip_lib)
-    pids = [e.add_probe(capi.KIND_V, idx, comp, w) for e in (ref.e, e_run, e_half)]
+    pids = [e.add_probe(capi.KIND_V, idx, comp, w) for e in (ref, e_run, e_half)]
     for e in (e_run, e_half):
         seeded_fields(e, 4)
     ref.run(nsteps)
@@ -96,15 +93,15 @@ def test_v_probe_on_a_sheet_edge_is_sampled_before_the_correction(hip_lib, oracl
     for _ in range(nsteps):
         e_half.half_step(0)
         e_half.half_step(1)
-    want = ref.e.get_probe(pids[0])[:nsteps]
-    assert np.abs(want).max() > 0 and np.abs(ref.sheet["ib"]).max() > 0
+    want = ref.get_probe(pids[0])[:nsteps]
+    assert np.abs(want).max() > 0 and np.abs(ref.sheets.ib).max() > 0
     # (the correction does change what the probe would read: sampled after it, the series differs)
     after = sum(float(wq) * float(ref.V[c].reshape(-1)[g]) for wq, c, g in zip(w, comp, idx))
     assert after != want[-1]
     assert np.array_equal(e_half.get_probe(pids[2])[:nsteps], want)
     assert np.array_equal(e_run.get_probe(pids[1])[:nsteps], want)
-    assert np.array_equal(e_run.fields(), ref.e.fields()) and np.array_equal(e_run.sheet_state()[1], ref.sheet["ib"])
-    for (pu, pi), (qu, qi) in zip(sims[1].port_series(), [(ref.e.get_probe(u), ref.e.get_probe(i)) for u, i in sims[0]._port_probe_ids]):
+    assert np.array_equal(e_run.fields(), ref.e.fields()) and np.array_equal(e_run.sheet_state()[1], ref.sheets.ib)
+    for (pu, pi), (qu, qi) in zip(sims[1].port_series(), [(ref.get_probe(u), ref.get_probe(i)) for u, i in sims[0]._port_probe_ids]):
         assert np.array_equal(pu, qu) and np.array_equal(pi, qi)
 
 
@@ -120,13 +117,12 @@ def test_sheet_edges_on_a_mur_face_node_plane(hip_lib, oracle_lib, monkeypatch):
             [(1, 6, j, k) for j in range(3, 9) for k in range(4, 7)] + [(0, i, 5, 5) for i in range(3, 9)]
     mk = lambda: cavity_sim(1.0, 1.0, sheet=False, boundary="MUR", nr_ts=nsteps)
     ref_sim = mk()
-    from test_dispersion_model_cpu import Restated
-    probe = Restated(ref_sim, oracle_lib)
+    probe = Restatement(ref_sim, oracle_lib)
     tables = _raw_sheet_tables(probe.e, edges)
     assert np.count_nonzero(tables[2] == 0) == 36 + 5 and np.count_nonzero(tables[2]) == 18 + 6
     ref = _restated_with_raw_sheets(mk(), oracle_lib, tables, seed=6)
     ref.run(nsteps)
-    assert np.all(np.abs(ref.sheet["ib"]).max(axis=0) > 0)
+    assert np.all(np.abs(ref.sheets.ib).max(axis=0) > 0)
     for apply_pass in (None, "1"):
         if apply_pass is None:
             monkeypatch.delenv("FDTD_MUR_APPLY_PASS", raising=False)
@@ -143,7 +139,7 @@ def test_sheet_edges_on_a_mur_face_node_plane(hip_lib, oracle_lib, monkeypatch):
         e.run(nsteps)
         assert np.array_equal(e.fields(), ref.e.fields())
         hv, hib = e.sheet_state()
-        assert np.array_equal(hv, ref.sheet["vprev"]) and np.array_equal(hib, ref.sheet["ib"])
+        assert np.array_equal(hv, ref.sheets.vprev) and np.array_equal(hib, ref.sheets.ib)
         e.close()
 
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg
+from restatement import Restatement
 from test_plugin_surface_cpu import _load, _params, _same
 
 MU0 = 4e-7 * np.pi
@@ -231,20 +232,6 @@ def cavity_sim(sigma, t, *, n=(14, 13, 12), boundary="PEC", nr_ts=2000, sheet=Tr
     return sim.Simulation(g, v, f0=f0, fc=fc, boundary=boundary, nr_ts=nr_ts, end_criteria=0.0)
 
 
-def restated_run(sim, lib, nsteps, *, flags=0, energy_every=0):
-    """Oracle half-steps + the numpy correction: (engine, v_prev, branch currents, energies).  The stepping is the one checker the
-    Debye tests use too (test_dispersion_model_cpu.Restated, which skips the media a simulation does not have)."""
-    from test_dispersion_model_cpu import Restated
-    r = Restated(sim, lib, flags=flags)
-    energies = []
-    for n in range(nsteps):
-        r.step()
-        if energy_every and (n + 1) % energy_every == 0:
-            sv, si = r.e.energy()
-            energies.append(8.854187817e-12 * sv + MU0 * si)
-    return r.e, r.sheet["vprev"], r.sheet["ib"], np.array(energies)
-
-
 def test_high_conductivity_matches_pec(oracle_lib):
     nsteps = 600
     pec = cavity_sim(1.0, 1.0, sheet=False, nr_ts=nsteps)
@@ -253,8 +240,9 @@ def test_high_conductivity_matches_pec(oracle_lib):
     ref = e.fields()
     s = cavity_sim(1e12, 1e-3, nr_ts=nsteps)
     assert len(s.sheets) > 0
-    es, _, _, _ = restated_run(s, oracle_lib, nsteps)
-    got = es.fields()
+    r = Restatement(s, oracle_lib)
+    r.run(nsteps)
+    got = r.e.fields()
     assert np.abs(ref).max() > 0
     assert np.abs(got - ref).max() <= 1e-4 * np.abs(ref).max()
 
@@ -264,7 +252,13 @@ def test_lossy_cavity_energy_decays(oracle_lib):
     windows: the leapfrog energy of a single instant oscillates within a period) and it falls by decades."""
     s = cavity_sim(1e5, 1e-3, nr_ts=20000, f0=20e9, fc=10e9)
     tail = len(s.signal)
-    _, _, ib, en = restated_run(s, oracle_lib, 20000, energy_every=10)
+    r, en = Restatement(s, oracle_lib), []
+    for n in range(20000):
+        r.step()
+        if (n + 1) % 10 == 0:
+            sv, si = r.e.energy()
+            en.append(8.854187817e-12 * sv + MU0 * si)
+    ib, en = r.sheets.ib, np.array(en)
     after = en[(tail + 9) // 10:]
     assert after[0] > 0 and np.all(np.isfinite(after))
     w = after[:after.size // 20 * 20].reshape(-1, 20).max(axis=1)
