@@ -1,6 +1,7 @@
 // kernel_common.hpp — device helpers of the update kernels (kernels.hip) and of the mailbox self-test (api.hip).
 #pragma once
 #include "fdtd_ctx.h"
+#include "wait_sets.hpp"
 
 namespace {
 
@@ -263,79 +264,61 @@ __device__ __forceinline__ void wf_wait_probes(const DevParams& p, const int kin
   if ((int)threadIdx.x < p.nprobe && p.probes[threadIdx.x].kind == kind) wf_poll(p, p.wf_prb_done + threadIdx.x, target);
   __syncthreads();
 }
-// E block (k, strip, pb) of a LATER timestep of a multi-step launch: wait for the H blocks of the previous timestep that wrote
-// the I values it reads and read the V values it overwrites (the same set): threads t - P4 - 1 .. t + 255 of the strip-plane
-// (its own cells, the row below, the element left of a group) — running into the previous strip's last rows at a strip's
-// start — and the same block of plane k - 1.  The mirror image of wf_wait below.
-__device__ __forceinline__ void wf_wait_back(const DevParams& p, const int k, const int strip, const int pb, const unsigned target) {
-  if (threadIdx.x < 64u) {
-    const int hop = 1 + p.P4 / FDTD_BLOCK;
-    const int first = pb * FDTD_BLOCK - p.P4 - 1;                 // first strip-linear thread whose data is read (may be negative)
-    const int t = (int)threadIdx.x;
-    const unsigned* f = nullptr;
-    const size_t row = ((size_t)k * p.nstrips + strip) * p.nbs;
-    if (t <= hop) {                                               // same strip-plane: this block and the ones before it
-      if (pb - t >= 0 && (pb - t + 1) * FDTD_BLOCK - 1 >= first) f = p.wf_flagsH + row + pb - t;
-    } else if (t <= 2 * hop + 1) {                                // previous strip's last blocks (always a full strip)
-      const int q = t - hop - 1, Tp = p.tys * p.P4, lastb = (Tp - 1) / FDTD_BLOCK;
-      if (first < 0 && strip > 0 && lastb - q >= 0 && min((lastb - q + 1) * FDTD_BLOCK, Tp) - 1 >= Tp + first) f = p.wf_flagsH + row - p.nbs + lastb - q;
-    } else if (t == 2 * hop + 2) {                                // plane below
-      if (k > 0) f = p.wf_flagsH + row - (size_t)p.nstrips * p.nbs + pb;
-    }
-    if (f) wf_poll(p, f, target);
-  }
-  __syncthreads();
+// Which flags a block waits for is integer arithmetic of its own (wait_sets.hpp, proven on the host against the stencil, cell by cell:
+// tests/test_wait_sets_cpu.py); here only the poll and the barrier.  DevParams has the members of the geometry but the Mur faces (a kernel argument).
+__device__ __forceinline__ WsGeom wf_geom(const DevParams& p, const MurH& m) {
+  return WsGeom{p.P4, p.ny, p.tys, p.nstrips, p.nbs, p.nk, {p.fd_P4.mul, p.fd_P4.shr, p.fd_P4.d}, {m.b[0], m.b[1], m.b[2], m.b[3], m.b[4], m.b[5]}};
 }
-// H block (k, strip, pb): wait for the E blocks whose output it reads / whose input it overwrites.  Threads t .. t+255 of
-// the strip-plane read rows j and j+1 (thread t + P4) and the element right of their group (thread t + 1): strip-linear
-// threads [pb*256, pb*256 + 256 + P4] at plane k — running into the next strip's first rows at a strip's end — and the
-// same block at plane k + 1.  One lane per flag, wave 0 polls, the block meets.
-__device__ __forceinline__ void wf_wait(const DevParams& p, const int k, const int strip, const int pb, const unsigned target) {
+#ifdef FDTD_WF_DIAG
+// diagnostic build only (make diag; tests/test_wait_sets_gpu.py): per block of a k_step launch (blockIdx.x) six words — start, start and end of its flag
+// wait, end, identity (flag index | H << 40 | delayed << 41 | 1 << 42), timestep —, and which blocks spin for g_wf_delay_ticks before they touch memory:
+// one bit per [timestep & 7][E, H][flag index].  Plain stores of thread 0, no atomics, no extra barrier.
+#define FDTD_WF_DIAG_SLOTS 65536
+__device__ unsigned long long g_wf_stamp[FDTD_WF_DIAG_SLOTS * 6];
+__device__ unsigned g_wf_delay_mask[8 * 2 * FDTD_WF_DIAG_SLOTS / 32];
+__device__ unsigned long long g_wf_delay_ticks;
+#define WF_DIAG_STAMP(word) do { if (threadIdx.x == 0 && blockIdx.x < FDTD_WF_DIAG_SLOTS) g_wf_stamp[(size_t)blockIdx.x * 6 + (word)] = wall_clock64(); } while (0)
+#else
+#define WF_DIAG_STAMP(word) do { } while (0)
+#endif
+// E block (k, strip, pb) of a LATER timestep of a multi-step launch: wait for the H blocks of the previous timestep that wrote
+// the I values it reads and read the V values it overwrites (the same set, wf_wait_back_flag).  One lane per flag, wave 0 polls, the block meets.
+__device__ __forceinline__ void wf_wait_back(const DevParams& p, const int k, const int strip, const int pb, const unsigned target) {
+  WF_DIAG_STAMP(1);
   if (threadIdx.x < 64u) {
-    const int hop = 1 + p.P4 / FDTD_BLOCK;
-    const int rows = min(p.tys, p.ny - strip * p.tys);
-    const int T = rows * p.P4;                                   // threads of this strip-plane
-    const int last = pb * FDTD_BLOCK + FDTD_BLOCK + p.P4;        // last strip-linear thread whose data is read
-    const int t = (int)threadIdx.x;
-    const unsigned* f = nullptr;
-    const size_t row = ((size_t)k * p.nstrips + strip) * p.nbs;
-    if (t <= hop) {                                              // same strip, this block and the ones behind it
-      if ((pb + t) * FDTD_BLOCK <= min(last, T - 1)) f = p.wf_flags + row + pb + t;
-    } else if (t <= 2 * hop + 1) {                               // next strip's first blocks
-      const int q = t - hop - 1;
-      if (last >= T && strip + 1 < p.nstrips && q < p.nbs && q * FDTD_BLOCK <= last - T) f = p.wf_flags + row + p.nbs + q;
-    } else if (t == 2 * hop + 2) {                               // plane above
-      if (k + 1 < p.nk) f = p.wf_flags + row + (size_t)p.nstrips * p.nbs + pb;
-    }
-    if (f) wf_poll(p, f, target);
+    const long long f = wf_wait_back_flag(p, k, strip, pb, (int)threadIdx.x);
+    if (f >= 0) wf_poll(p, p.wf_flagsH + f, target);
   }
   __syncthreads();
+  WF_DIAG_STAMP(2);
+}
+// H block (k, strip, pb): wait for the E blocks whose output it reads / whose input it overwrites (wf_wait_flag).
+__device__ __forceinline__ void wf_wait(const DevParams& p, const int k, const int strip, const int pb, const unsigned target) {
+  WF_DIAG_STAMP(1);
+  if (threadIdx.x < 64u) {
+    const long long f = wf_wait_flag(p, k, strip, pb, (int)threadIdx.x);
+    if (f >= 0) wf_poll(p, p.wf_flags + f, target);
+  }
+  __syncthreads();
+  WF_DIAG_STAMP(2);
 }
 
 // Mur faces inside the one-launch schedule: an H block also reads CANDIDATES that E blocks wrote — those of the inner nodes, one row / plane away
 // from the boundary nodes it loads (kernels.hip mur_load_V): the row behind it, the whole reach at plane k + 1, plane k - 1 under the upper z face.
-// Waited for generously: every block of strips s - 1 .. s + 1 at planes k - 1 .. k + 1 (9 nbs flags, one thread each; the host takes this schedule only
-// while they fit the workgroup).  All of them are E blocks of the SAME timestep: earlier in dispatch order (all E blocks, then all H blocks).
+// Waited for generously (wf_wait_mur_flag).  All of them are E blocks of the SAME timestep: earlier in dispatch order (all E blocks, then all H blocks).
 __device__ __forceinline__ void wf_wait_mur(const DevParams& p, const int k, const int strip, const unsigned target) {
+  WF_DIAG_STAMP(1);
   {
-    const int t = (int)threadIdx.x, nbs = p.nbs;
-    const int dk = t / (3 * nbs) - 1, r = t - (dk + 1) * 3 * nbs, ds = r / nbs - 1, q = r - (ds + 1) * nbs;
-    const int kk = k + dk, ss = strip + ds;
-    if (t < 9 * nbs && kk >= 0 && kk < p.nk && ss >= 0 && ss < p.nstrips)
-      wf_poll(p, p.wf_flags + ((size_t)kk * p.nstrips + ss) * nbs + q, target);
+    const long long f = wf_wait_mur_flag(p, k, strip, (int)threadIdx.x);
+    if (f >= 0) wf_poll(p, p.wf_flags + f, target);
   }
   __syncthreads();
+  WF_DIAG_STAMP(2);
 }
 
 // ... and the per-thread part.  Returns false for threads beyond the strip.
 __device__ __forceinline__ bool decode_thread(const DevParams& p, int strip, int pb, int& j, int& i0) {
-  const int t = pb * FDTD_BLOCK + (int)threadIdx.x;
-  const int rows = min(p.tys, p.ny - strip * p.tys);
-  if (t >= rows * p.P4) return false;
-  const int jj = (int)fd_div((unsigned)t, p.fd_P4);
-  j = strip * p.tys + jj;
-  i0 = (t - jj * p.P4) * 4;
-  return true;
+  return ws_decode_thread(p, strip, pb, (int)threadIdx.x, j, i0);
 }
 
 // Soft sources of one strip-plane, staged once per block: (flat offset | comp << 29 is avoided: two arrays).  Up to SRC_SCAN_MAX of them every

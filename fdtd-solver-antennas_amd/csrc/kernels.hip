@@ -573,14 +573,7 @@ __device__ __forceinline__ void body_H(const DevParams& p, const int strip, cons
     // whose upper x face starts a four-cell group (the inner node belongs to the thread before), takes the wide set (wf_wait_mur).  The wide set for
     // ALL blocks cost 2.3 us per timestep on 143x129x89 (the E -> H turn of a grid of one residency round).
     bool wide = false;
-    if (MUR) {
-      const MurH& m = *mh;
-      const int rows = min(p.tys, p.ny - strip * p.tys);
-      const int jlo = strip * p.tys + (int)fd_div((unsigned)(pb * FDTD_BLOCK), p.fd_P4);
-      const int jhi = strip * p.tys + min(rows - 1, (int)fd_div((unsigned)(pb * FDTD_BLOCK + FDTD_BLOCK - 1), p.fd_P4));
-      wide = k == m.b[4] || k == m.b[5] || (m.b[2] >= jlo && m.b[2] <= jhi) || (m.b[3] >= jlo && m.b[3] <= jhi) ||
-             (m.b[1] >= 0 && (m.b[1] & 3) == 0);
-    }
+    if (MUR) wide = wf_mur_wide(wf_geom(p, *mh), k, strip, pb);
     if (wide) wf_wait_mur(p, k, strip, wf_target + p.wf_wait_bias);
     else wf_wait(p, k, strip, pb, wf_target + p.wf_wait_bias);
     if (MULTI) {
@@ -804,8 +797,27 @@ __global__ __launch_bounds__(FDTD_BLOCK, (P2P || MUR) ? FDTD_WF_MINBLOCKS - 1 : 
   // 32-byte slot of a per-launch table (two tables, alternating with the step): plain stores, no atomics, no extra barrier
   const unsigned long long t_begin = wall_clock64();
 #endif
+#ifdef FDTD_WF_DIAG   // diagnostic builds only (tests/test_wait_sets_gpu.py): a block whose bit is set spins for a bounded time (at most 1 ms of the 100 MHz
+  // clock) right after its decode, before it loads or stores anything; polls, flags and arithmetic are unchanged
+  const unsigned long long d_begin = wall_clock64();
+  const unsigned d_flag = ((unsigned)k * (unsigned)p.nstrips + strip) * (unsigned)p.nbs + (unsigned)pb;
+  bool d_delayed = false;
+  if (d_flag < FDTD_WF_DIAG_SLOTS) {
+    d_delayed = ((g_wf_delay_mask[(((unsigned)step & 7u) * 2u + (is_h ? 1u : 0u)) * (FDTD_WF_DIAG_SLOTS / 32) + (d_flag >> 5)] >> (d_flag & 31u)) & 1u) != 0u;
+    const unsigned long long d_ticks = g_wf_delay_ticks < 100000ull ? g_wf_delay_ticks : 100000ull;
+    if (d_delayed) while ((unsigned long long)wall_clock64() - d_begin < d_ticks) __builtin_amdgcn_s_sleep(8);
+  }
+#endif
   if (!is_h) body_E<COEF, PML, true, P2P, true, MUR, MULTI>(p, (int)strip, k, pb, step, s_lut, s_psi, s_xc, s_src, wf_target, MUR ? &mur : nullptr, ts ? wf_target - 1u : 0u);
   else body_H<COEF == 0, PML, P2P, true, MULTI, MUR>(p, (int)strip, k, pb, step, s_psi, s_xc, wf_target, ts ? wf_target - 1u : 0u, MUR ? &mh : nullptr);
+#ifdef FDTD_WF_DIAG
+  if (threadIdx.x == 0 && blockIdx.x < FDTD_WF_DIAG_SLOTS) {
+    unsigned long long* const slot = g_wf_stamp + (size_t)blockIdx.x * 6;
+    slot[0] = d_begin; slot[3] = wall_clock64();
+    slot[4] = (unsigned long long)d_flag | (is_h ? 1ull << 40 : 0ull) | (d_delayed ? 1ull << 41 : 0ull) | (1ull << 42);
+    slot[5] = (unsigned long long)step;
+  }
+#endif
   if (p.xstamp && threadIdx.x == 0) p.xstamp[b] = wall_clock64();   // ... and when this block (its first wave) was done
 #ifdef FDTD_XCD_TRACE
   if (threadIdx.x == 0 && b < FDTD_XCD_TRACE_MAX) {
@@ -1668,5 +1680,82 @@ extern "C" int fdtd_debug_xcd_trace(long long step, unsigned long long* out) {
   }
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_xcd_trace), (size_t)FDTD_XCD_TRACE_MAX * 4 * sizeof(unsigned long long),
                              (size_t)(step & 1) * FDTD_XCD_TRACE_MAX * 4 * sizeof(unsigned long long)) == hipSuccess ? 0 : -3;
+}
+#endif
+
+#ifdef FDTD_WF_DIAG
+// diagnostic build only (make diag -> _diag/libfdtd_hip.so; tests/test_wait_sets_gpu.py): what the device computes for the wait sets of this
+// context — compared as integers with the host build of the same header (wait_sets_shim.cpp: ws_dump, the same layout) — and the probe
+// tables of the one-launch schedule as the device holds them.
+namespace {
+// one block per (k, strip, pb), in flag order; out[5][n], n = blocks * 256: wf_wait_flag, wf_wait_back_flag (lanes < 64, else -1), wf_wait_mur_flag,
+// wf_mur_wide, and the thread decode (j << 32 | i0, -1 beyond the strip)
+__global__ __launch_bounds__(FDTD_BLOCK) void k_debug_wait_sets(const DevParams p, const MurH mh, long long* const out, const size_t n) {
+  const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+  const int pb = b % p.nbs, strip = (b / p.nbs) % p.nstrips, k = b / (p.nbs * p.nstrips);
+  const size_t e = (size_t)b * FDTD_BLOCK + (size_t)t;
+  if (k >= p.nk || e >= n) return;
+  out[e] = t < 64 ? wf_wait_flag(p, k, strip, pb, t) : -1;
+  out[n + e] = t < 64 ? wf_wait_back_flag(p, k, strip, pb, t) : -1;
+  out[2 * n + e] = wf_wait_mur_flag(p, k, strip, t);
+  out[3 * n + e] = wf_mur_wide(wf_geom(p, mh), k, strip, pb) ? 1 : 0;
+  int j = 0, i0 = 0;
+  out[4 * n + e] = decode_thread(p, strip, pb, j, i0) ? ((long long)j << 32) | (long long)i0 : -1;
+}
+}  // namespace
+// geom[14]: P4, ny, tys, nstrips, nbs, nk, the six Mur face indices of the H blocks (-1 = off), nx, P.  out: 5 * nk * nstrips * nbs * 256 words, or null
+extern "C" int fdtd_debug_wait_sets(fdtd_ctx* c, int* geom, long long* out) {
+  if (!c || !geom || c->p.tys <= 0 || c->p.nbs <= 0) return -1;
+  const int g[14] = {c->p.P4, c->p.ny, c->p.tys, c->p.nstrips, c->p.nbs, c->p.nk, c->h_murh.b[0], c->h_murh.b[1], c->h_murh.b[2], c->h_murh.b[3],
+                     c->h_murh.b[4], c->h_murh.b[5], c->p.nx, c->p.P};
+  for (int q = 0; q < 14; ++q) geom[q] = g[q];
+  if (!c->any_mur) for (int q = 6; q < 12; ++q) geom[q] = -1;
+  if (!out) return 0;
+  MurH mh = c->h_murh;
+  if (!c->any_mur) for (int f = 0; f < 6; ++f) mh.b[f] = -1;
+  const size_t blocks = (size_t)c->p.nk * c->p.nstrips * c->p.nbs, n = blocks * FDTD_BLOCK;
+  long long* d = nullptr;
+  if (hipSetDevice(c->d.device) != hipSuccess || hipMalloc(&d, 5 * n * sizeof(long long)) != hipSuccess) return -3;
+  hipLaunchKernelGGL(k_debug_wait_sets, dim3((unsigned)blocks), dim3(FDTD_BLOCK), 0, 0, c->p, mh, d, n);
+  const bool ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d, 5 * n * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess;
+  hipFree(d);
+  return ok ? 0 : -3;
+}
+// The probe tables of the one-launch schedule, from the device (built by the first step of that schedule after a probe was added): sp, spV
+// [nk * nstrips] (strip-planes that hold I- / V-probe cells), rng [2 * FDTD_MAX_PROBES] and the owner lists blk (at most blk_cap words).
+// Returns the length of blk, < 0: no tables yet / blk_cap too small / device error
+extern "C" int fdtd_debug_probe_waits(fdtd_ctx* c, int* sp, int* spV, int* rng, int* blk, int blk_cap) {
+  if (!c || !sp || !spV || !rng || !blk) return -1;
+  if (c->wf_prb_dirty || !c->wf_prb_sp || !c->wf_prbV_sp || !c->wf_prb_rng || !c->wf_prb_blk) return -2;
+  const size_t nsp = (size_t)c->p.nk * c->p.nstrips;
+  if (hipSetDevice(c->d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -3;
+  if (hipMemcpy(sp, c->wf_prb_sp, nsp * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -3;
+  if (hipMemcpy(spV, c->wf_prbV_sp, nsp * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -3;
+  if (hipMemcpy(rng, c->wf_prb_rng, 2 * FDTD_MAX_PROBES * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -3;
+  int nblk = 0;
+  for (int q = 0; q < c->nprobe; ++q) nblk = std::max(nblk, rng[2 * q + 1]);
+  if (nblk > blk_cap) return -4;
+  if (nblk > 0 && hipMemcpy(blk, c->wf_prb_blk, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -3;
+  return nblk;
+}
+// Which blocks of the next launches spin, and how long (ticks of the 100 MHz clock, capped at 1 ms on the device): mask = 8 * 2 * 2048 words,
+// [timestep & 7][E, H][flag index] one bit each; null clears it.  The stamp table is cleared as well.
+extern "C" int fdtd_debug_wf_delay(const unsigned* mask, unsigned long long ticks) {
+  void *qm = nullptr, *qs = nullptr;
+  if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&qm, HIP_SYMBOL(g_wf_delay_mask)) != hipSuccess ||
+      hipGetSymbolAddress(&qs, HIP_SYMBOL(g_wf_stamp)) != hipSuccess) return -3;
+  const size_t mbytes = sizeof(unsigned) * 8 * 2 * FDTD_WF_DIAG_SLOTS / 32;
+  if ((mask ? hipMemcpy(qm, mask, mbytes, hipMemcpyHostToDevice) : hipMemset(qm, 0, mbytes)) != hipSuccess) return -3;
+  if (hipMemset(qs, 0, sizeof(unsigned long long) * FDTD_WF_DIAG_SLOTS * 6) != hipSuccess) return -3;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_wf_delay_ticks), &ticks, sizeof(ticks)) == hipSuccess ? 0 : -3;
+}
+// the stamps of the first nslots blocks of the last launch (six words each); clear: zero the table afterwards
+extern "C" int fdtd_debug_wf_stamps(unsigned long long* out, int nslots, int clear) {
+  if (!out || nslots < 0 || nslots > FDTD_WF_DIAG_SLOTS) return -1;
+  void* qs = nullptr;
+  if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&qs, HIP_SYMBOL(g_wf_stamp)) != hipSuccess) return -3;
+  if (hipMemcpy(out, qs, sizeof(unsigned long long) * 6 * (size_t)nslots, hipMemcpyDeviceToHost) != hipSuccess) return -3;
+  if (clear && hipMemset(qs, 0, sizeof(unsigned long long) * FDTD_WF_DIAG_SLOTS * 6) != hipSuccess) return -3;
+  return 0;
 }
 #endif

@@ -78,3 +78,49 @@ def build_f64(sim, lib64, *, double_tables=True):
     if double_tables:
         stage_f64_tables(sim, lib64)
     return sim.build(lib64)
+
+
+# ---- the wait-set arithmetic of the one-launch schedule on the host (csrc/wait_sets.hpp behind csrc/wait_sets_shim.cpp) ----------------
+class WsGeom(__import__("ctypes").Structure):
+    """csrc/wait_sets.hpp: WsGeom"""
+    import ctypes as _c
+    _fields_ = [("P4", _c.c_int), ("ny", _c.c_int), ("tys", _c.c_int), ("nstrips", _c.c_int), ("nbs", _c.c_int), ("nk", _c.c_int),
+                ("fd_mul", _c.c_uint), ("fd_shr", _c.c_uint), ("fd_d", _c.c_uint), ("b", _c.c_int * 6)]
+
+
+class WsFail(__import__("ctypes").Structure):
+    """csrc/wait_sets_model.hpp: WsFail (what: 1 forward flag missing, 2 backward, 3 Mur candidate, 4 plain flag of a block of a Mur grid,
+    5 lane budget, 6 flag outside the table, 7 thread decode)"""
+    import ctypes as _c
+    _fields_ = [("what", _c.c_int), ("k", _c.c_int), ("strip", _c.c_int), ("pb", _c.c_int), ("thread", _c.c_int), ("flag", _c.c_longlong)]
+
+    def __repr__(self):
+        return f"what {self.what} at block (k {self.k}, strip {self.strip}, pb {self.pb}) thread {self.thread}, flag {self.flag}"
+
+
+def load_wait_sets(drop=0):
+    """libfdtd_waitsets.so — or the library without clause `drop` (the negative control) —, built on demand by g++ (make waitsets_host)."""
+    import ctypes, os, subprocess
+    from conftest import ROOT
+    csrc = os.path.join(ROOT, "fdtd-solver-antennas_amd", "csrc")
+    so = os.path.join(csrc, f"libfdtd_waitsets_drop{drop}.so" if drop else "libfdtd_waitsets.so")
+    srcs = [os.path.join(csrc, f) for f in ("wait_sets.hpp", "wait_sets_model.hpp", "wait_sets_shim.cpp", "Makefile")]
+    if not os.path.isfile(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):
+        subprocess.check_call(["make", "-s", "-B", "-C", csrc, "waitsets_host"] + ([f"DROP={drop}"] if drop else []))
+    lib = ctypes.CDLL(so)
+    G, I, LL = ctypes.POINTER(WsGeom), ctypes.c_int, ctypes.c_longlong
+    IP = ctypes.POINTER(ctypes.c_int)
+    for name, res, args in (("ws_drop", I, []), ("ws_geom", None, [G, I, I, I, I, IP]), ("ws_wait_flag", LL, [G, I, I, I, I]),
+                            ("ws_wait_back_flag", LL, [G, I, I, I, I]), ("ws_wait_mur_flag", LL, [G, I, I, I]), ("ws_mur_wide", I, [G, I, I, I]),
+                            ("ws_decode", I, [G, I, I, I, IP, IP]), ("ws_dump", None, [G, ctypes.c_void_p]),
+                            ("ws_check", I, [G, I, I, ctypes.POINTER(WsFail)]), ("ws_check_mur_faces", I, [I, I, I, I, IP, ctypes.POINTER(WsFail)])):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
+    assert lib.ws_drop() == drop
+    return lib
+
+
+def ws_geom(lib, P4, ny, tys, nk, b=None):
+    import ctypes
+    g = WsGeom()
+    lib.ws_geom(ctypes.byref(g), P4, ny, tys, nk, (ctypes.c_int * 6)(*b) if b is not None else None)
+    return g

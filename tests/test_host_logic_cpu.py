@@ -212,8 +212,10 @@ def test_backward_flag_set_covers_every_block_an_e_block_reads():
     """Several timesteps per launch: an E block of timestep s + 1 waits for the H flags of `wf_wait_back`'s block set
     (csrc/kernel_common.hpp).  Brute force over tilings — rows shorter and longer than a block, short last strips, one-row
     strips: every thread whose I values a block's threads read (own cell group, the row below, the group to the left)
-    lies in a block of that set.  (The plane below is the same block index, trivially.)  The arithmetic below restates the
-    device code's; the geometry it is checked against is enumerated cell by cell."""
+    lies in a block of that set.  (The plane below is the same block index, trivially.)  The set is the device's own function
+    (csrc/wait_sets.hpp: wf_wait_back_flag, compiled for the host); the geometry it is checked against is enumerated cell by cell."""
+    from helpers import load_wait_sets, ws_geom
+    lib = load_wait_sets()
     B = 256
     for P4, ny, tys in ((14, 52, 13), (75, 300, 17), (50, 200, 40), (257, 9, 4), (600, 12, 5), (16, 9, 9), (100, 400, 40), (9, 60, 1)):
         nstrips = (ny + tys - 1) // tys
@@ -226,17 +228,15 @@ def test_backward_flag_set_covers_every_block_an_e_block_reads():
                 lo, hi = pb * B, min((pb + 1) * B, T)
                 if lo >= T:
                     continue
-                # what the device waits for: (strip delta, block) pairs
-                first = pb * B - P4 - 1
-                dev = set()
-                for t in range(hop + 1):
-                    if pb - t >= 0 and (pb - t + 1) * B - 1 >= first:
-                        dev.add((0, pb - t))
+                # what the device waits for: (strip delta, block) pairs, from the flag words of lanes 0 .. 63 at plane 0 (no plane below)
+                g = ws_geom(lib, P4, ny, tys, 2)
+                assert (g.nstrips, g.nbs) == (nstrips, nbs)
                 Tp = tys * P4
-                lastb = (Tp - 1) // B
-                for q in range(hop + 1):
-                    if first < 0 and strip > 0 and lastb - q >= 0 and min((lastb - q + 1) * B, Tp) - 1 >= Tp + first:
-                        dev.add((-1, lastb - q))
+                dev = set()
+                for lane in range(64):
+                    f = lib.ws_wait_back_flag(g, 0, strip, pb, lane)
+                    if f >= 0:
+                        dev.add((f // nbs - strip, f % nbs))
                 # what the block's threads read, thread by thread
                 need = set()
                 for t in range(lo, hi):
