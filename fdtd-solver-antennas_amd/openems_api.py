@@ -32,6 +32,7 @@ from .grid import RectGrid
 from .mesher import mesh_hint_from_box, smooth_mesh_lines, unique_lines
 from .scene import Scene, Box as SceneBox, voxelize
 from . import primitives as _prims
+from . import ports as _ports
 from .simulation import Simulation, BoundarySpec
 from .nf2ff import calc_nf2ff, NF2FFResult
 
@@ -639,6 +640,83 @@ class LumpedPort:
         return self
 
 
+class _ModalPort:
+    """What WaveguidePort and MSLPort share: the spectra of the probe series (dft_uniform, the half-step phase on I, as
+    LumpedPort.CalcPort) and the wave split with Z_ref and the reference-plane shift (ports.waves)."""
+
+    def _spectra(self, freq, signal_type):
+        us, is_, dt = self._fdtd._port_all_series(self.number)
+        self.freq = np.atleast_1d(np.asarray(freq, float))
+        scale = 2.0 * (dt if signal_type == "pulse" else 1.0 / us[0].size)
+        uf = [dft_uniform(self.freq, u, dt) * scale for u in us]
+        jf = [dft_uniform(self.freq, i, dt) * np.exp(-1j * np.pi * self.freq * dt) * scale for i in is_]
+        return us, is_, dt, uf, jf
+
+    def _finish(self, uf_tot, if_tot, ref_impedance, ref_plane_shift):
+        self.Z_ref = self.ZL if ref_impedance is None else ref_impedance
+        shift = None if ref_plane_shift is None else float(ref_plane_shift) * self._fdtd._csx.GetGrid().GetDeltaUnit()
+        (self.uf_tot, self.if_tot, self.uf_inc, self.if_inc, self.uf_ref, self.if_ref) = _ports.waves(uf_tot, if_tot, self.Z_ref, self.beta, shift)
+        self.P_inc = 0.5 * np.real(self.uf_inc * np.conj(self.if_inc))
+        self.P_ref = 0.5 * np.real(self.uf_ref * np.conj(self.if_ref))
+        self.P_acc = 0.5 * np.real(self.uf_tot * np.conj(self.if_tot))
+        return self
+
+
+class WaveguidePort(_ModalPort):
+    """Result side of AddWaveGuidePort (ports.py): modal voltage and current -> incident / reflected waves with the analytic beta and
+    ZL of the mode.  E_func, H_func: callables (x, y) -> (c_P, c_PP), metres from the box's minimum corner."""
+
+    def __init__(self, fdtd, number, start, stop, p_dir, E_func, H_func, kc, excite, eps_r=1.0, mode=None):
+        self._fdtd, self.number = fdtd, number
+        self.start, self.stop = np.asarray(start, float), np.asarray(stop, float)
+        self.exc_ny, self.excite = p_dir, excite
+        self.E_func, self.H_func, self.kc, self.eps_r, self.mode = E_func, H_func, float(kc), float(eps_r), mode
+
+    def _to_scene(self, sc, csx_metals):
+        sc.add_waveguide_port(self.number, self.start, self.stop, self.exc_ny, self.E_func, self.H_func, self.kc, self.excite, self.eps_r, mode=self.mode)
+
+    def CalcPort(self, sim_path, freq, ref_impedance=None, ref_plane_shift=None, signal_type="pulse"):
+        us, is_, dt, uf, jf = self._spectra(freq, signal_type)
+        self.u_data, self.i_data = UIData(np.arange(us[0].size) * dt, us[0]), UIData((np.arange(is_[0].size) + 0.5) * dt, is_[0])
+        self.beta, self.ZL = _ports.waveguide_beta_zl(self.freq, self.kc, self.eps_r)
+        return self._finish(uf[0], jf[0], ref_impedance, ref_plane_shift)
+
+
+class RectWGPort(WaveguidePort):
+    """Result side of AddRectWaveGuidePort: the TEmn port of an a x b guide, built on the general waveguide port."""
+
+    def __init__(self, fdtd, number, start, stop, p_dir, a, b, mode_name, excite, eps_r=1.0):
+        e_func, h_func, kc = _ports.rect_te_mode(a, b, mode_name, f"rectangular waveguide port {number}")
+        super().__init__(fdtd, number, start, stop, p_dir, e_func, h_func, kc, excite, eps_r, mode=str(mode_name).upper())
+        self.a, self.b = float(a), float(b)
+
+
+class MSLPort(_ModalPort):
+    """Result side of AddMSLPort (ports.py): three voltages and two currents on the line -> beta and ZL extracted from the run, and the
+    incident / reflected waves at the measurement plane (or shifted along the line)."""
+
+    def __init__(self, fdtd, number, metal_prop, start, stop, prop_dir, exc_dir, excite, feed_shift, meas_plane_shift, feed_R, priority):
+        self._fdtd, self.number, self.metal_prop = fdtd, number, metal_prop
+        self.start, self.stop = np.asarray(start, float), np.asarray(stop, float)
+        self.prop_ny, self.exc_ny, self.excite = prop_dir, exc_dir, excite
+        self.feed_shift, self.measplane_shift, self.feed_R, self.priority = feed_shift, meas_plane_shift, feed_R, priority
+
+    def _to_scene(self, sc, csx_metals):
+        metal = csx_metals.get(id(self.metal_prop))
+        if metal is None:
+            raise ValueError(f"MSL port {self.number}: its metal property '{getattr(self.metal_prop, 'name', self.metal_prop)}' is not a metal of "
+                             f"this structure (AddMetal / AddConductingSheet)")
+        sc.add_msl_port(self.number, metal, self.start, self.stop, self.prop_ny, self.exc_ny, self.excite, self.feed_shift, self.measplane_shift,
+                        self.feed_R, self.priority, add_strip=False)      # (AddMSLPort drew the strip into the CSX property)
+
+    def CalcPort(self, sim_path, freq, ref_impedance=None, ref_plane_shift=None, signal_type="pulse"):
+        us, is_, dt, uf, jf = self._spectra(freq, signal_type)
+        self.u_data, self.i_data = UIData(np.arange(us[1].size) * dt, us[1]), UIData((np.arange(is_[0].size) + 0.5) * dt, 0.5 * (is_[0] + is_[1]))
+        info = self._fdtd._port_info(self.number)
+        Et, Ht, self.beta, self.ZL = _ports.msl_beta_zl(uf[0], uf[1], uf[2], jf[0], jf[1], info["dist_AC"], info["dist_loops"])
+        return self._finish(Et, Ht, ref_impedance, ref_plane_shift)
+
+
 class nf2ff:
     def __init__(self, fdtd, name="nf2ff", start=None, stop=None):
         self._fdtd, self.name = fdtd, name
@@ -703,7 +781,8 @@ class openEMS:
         self._bc = ["PEC"] * 6
         self._f0 = self._fc = None
         self._edge_hints = []
-        self._ports: List[LumpedPort] = []
+        self._ports: List[LumpedPort] = []      # LumpedPort, WaveguidePort and MSLPort, in the order they were added
+        self._u_i_all = None
         self._nf2ff: Optional[nf2ff] = None
         self.sim: Optional[Simulation] = None
         self.stats = None
@@ -774,6 +853,49 @@ class openEMS:
                     self._csx.GetGrid()._lines[a].extend(hint[a])
         return port
 
+    def AddWaveGuidePort(self, port_nr, start, stop, p_dir, E_func, H_func, kc, excite=0, **kw):
+        """A modal port (ports.py): E_func, H_func Python callables (x, y) -> (c_P, c_PP), x and y in metres from the box's minimum
+        corner along the axes (p + 1) % 3 and (p + 2) % 3; strings (upstream's weight functions) are refused.  eps_r= the filling."""
+        self.calls_log.add("AddWaveGuidePort", port_nr=port_nr, start=list(start), stop=list(stop), p_dir=p_dir, kc=kc, excite=excite,
+                           eps_r=kw.get("eps_r", 1.0))
+        return self._add_waveguide(WaveguidePort(self, port_nr, start, stop, _AX[p_dir], E_func, H_func, kc, excite, kw.get("eps_r", 1.0)))
+
+    def AddRectWaveGuidePort(self, port_nr, start, stop, p_dir, a, b, mode_name, excite=0, **kw):
+        """The TEmn port of a rectangular guide, a and b in metres along (p + 1) % 3 and (p + 2) % 3; TM modes are refused."""
+        self.calls_log.add("AddRectWaveGuidePort", port_nr=port_nr, start=list(start), stop=list(stop), p_dir=p_dir, a=a, b=b, mode_name=mode_name,
+                           excite=excite, eps_r=kw.get("eps_r", 1.0))
+        return self._add_waveguide(RectWGPort(self, port_nr, start, stop, _AX[p_dir], a, b, mode_name, excite, kw.get("eps_r", 1.0)))
+
+    def _add_waveguide(self, port):
+        who = f"waveguide port {port.number}"
+        _ports.check_funcs(who, port.E_func, port.H_func)
+        if port.start[port.exc_ny] == port.stop[port.exc_ny]:
+            raise ValueError(f"{who}: start and stop coincide along {'xyz'[port.exc_ny]}: the port has no direction (d = 0)")
+        self._ports.append(port)
+        return port
+
+    def AddMSLPort(self, port_nr, metal_prop, start, stop, prop_dir, exc_dir, excite=0, FeedShift=0, MeasPlaneShift=None, Feed_R=np.inf,
+                   priority=0, **kw):
+        """A microstrip-line port (ports.py): the strip, a zero-thickness box on the plane stop[exc_dir], is added to metal_prop here."""
+        self.calls_log.add("AddMSLPort", port_nr=port_nr, metal=getattr(metal_prop, "name", None), start=list(start), stop=list(stop),
+                           prop_dir=prop_dir, exc_dir=exc_dir, excite=excite, FeedShift=FeedShift, MeasPlaneShift=MeasPlaneShift,
+                           Feed_R=None if Feed_R is None or not np.isfinite(Feed_R) else Feed_R, priority=priority)
+        who = f"MSL port {port_nr}"
+        if not isinstance(metal_prop, CSProperty) or metal_prop.kind not in ("Metal", "ConductingSheet"):
+            raise ValueError(f"{who}: metal_prop must be a metal of the structure (AddMetal / AddConductingSheet)")
+        port = MSLPort(self, port_nr, metal_prop, start, stop, _AX[prop_dir], _AX[exc_dir], excite, FeedShift, MeasPlaneShift,
+                       np.inf if Feed_R is None else Feed_R, priority)
+        if port.prop_ny == port.exc_ny:
+            raise ValueError(f"{who}: the propagation and the excitation direction are both {'xyz'[port.prop_ny]}")
+        for a in range(3):
+            if port.start[a] == port.stop[a]:
+                raise ValueError(f"{who}: its box has zero extent along {'xyz'[a]}")
+        strip_start = port.start.copy()
+        strip_start[port.exc_ny] = port.stop[port.exc_ny]
+        metal_prop.AddBox(strip_start, port.stop, priority=priority)
+        self._ports.append(port)
+        return port
+
     def CreateNF2FFBox(self, name="nf2ff", start=None, stop=None, **kw):
         self.calls_log.add("CreateNF2FFBox")
         self._nf2ff = nf2ff(self, name, start, stop)
@@ -827,6 +949,7 @@ class openEMS:
         lines = [unique_lines(csx.GetGrid()._lines[a]) * unit for a in range(3)]
         grid = RectGrid(*lines)
         sc = Scene(unit=unit)
+        metals = {}                            # id of a CSX metal property -> the scene's metal (an MSL port names its strip's metal)
         for p in csx.properties:
             if p.kind == "LorentzMaterial":
                 q = p.params
@@ -869,10 +992,14 @@ class openEMS:
             else:
                 m = (sc.add_conducting_sheet(p.name, p.params["conductivity"], p.params["thickness"]) if p.kind == "ConductingSheet"
                      else sc.add_metal(p.name))
+                metals[id(p)] = m
                 for b in p.boxes:
                     self._draw(m, b)
         for port in self._ports:
-            sc.add_lumped_port(port.number, port.R, port.start, port.stop, port.exc_ny, port.excite, port.priority)
+            if isinstance(port, LumpedPort):
+                sc.add_lumped_port(port.number, port.R, port.start, port.stop, port.exc_ny, port.excite, port.priority)
+            else:
+                port._to_scene(sc, metals)
         return grid, sc
 
     @staticmethod
@@ -935,7 +1062,8 @@ class openEMS:
             return
         allreduce = self._comm.allreduce if self._comm is not None else None
         self.stats = self.sim.run(verbose=int(verbose or 0), allreduce=allreduce)
-        self._u_i = self.sim.port_series(allreduce)
+        self._u_i_all = self.sim.port_probe_series(allreduce)
+        self._u_i = [(us[0], is_[0]) for us, is_ in self._u_i_all]      # (what Simulation.port_series gives: the first probe of each kind)
         self._allreduce = allreduce
         self._boxes = None
         if self._nf2ff is not None and self.sim.nf2ff_mode == "dft":
@@ -975,6 +1103,8 @@ class openEMS:
                                "halo_transport": getattr(self._comm, "transport_used", None),
                                "halo_transports_failed": list(self.stats.transports_failed),
                                "schedule_fallback": self.stats.schedule_fallback,
+                               **({"ports": [{"number": q.port.number, **{k: v for k, v in q.info.items() if k not in ("dist_AC", "dist_loops", "meas_pos")}}
+                                             for q in vox.ports if q.info is not None]} if any(q.info is not None for q in vox.ports) else {}),
                                **({"sar": self.stats.sar} if self.stats.sar else {}),
                                **({"fields": field_report} if field_report else {}),
                                **({"disc_materials": _disc_summary(sc, grid, vox)} if vox.cell_voxel is not None else {})}, fh)
@@ -999,6 +1129,21 @@ class openEMS:
         for port, (u, i) in zip(self._ports, self._u_i):
             if port.number == number:
                 return u, i, self.sim.dt
+        raise KeyError(number)
+
+    def _port_all_series(self, number):
+        """([u(t) of every V-probe], [i(t) of every I-probe], dt) of port `number`."""
+        if self.sim is None or self._u_i_all is None:
+            raise RuntimeError("Run() first")
+        for port, (us, is_) in zip(self._ports, self._u_i_all):
+            if port.number == number:
+                return us, is_, self.sim.dt
+        raise KeyError(number)
+
+    def _port_info(self, number):
+        for port, p in zip(self._ports, self.sim.vox.ports):
+            if port.number == number:
+                return p.info
         raise KeyError(number)
 
     def GetSAR(self, name, freq=None, normalise_to=None):

@@ -361,12 +361,13 @@ def check_placement(grid: RectGrid, pw: PlaneWave, *, cpml_cells: Sequence[int] 
             raise ValueError(f"{who}: the outer face {at(k)} next to the box is a conformal (cut) face: keep curved metal off the box surface")
     for p in ports:
         nr = p.port.number
+        kind = {"waveguide": "waveguide", "msl": "MSL"}.get(getattr(p.port, "kind", None), "lumped")
         k = hit(edges, [le.comp for le in p.lumped], [(le.k * ny + le.j) * nx + le.i for le in p.lumped]) or hit(edges, p.src_comp, p.src_idx)
         if k:
-            raise ValueError(f"{who}: the surface edge {at(k)} is an edge of lumped port {nr}: a port lies inside the box (receive mode) or outside it")
+            raise ValueError(f"{who}: the surface edge {at(k)} is an edge of {kind} port {nr}: a port lies inside the box (receive mode) or outside it")
         k = hit(edges, p.v_comp, p.v_idx) or hit(faces, p.i_comp, p.i_idx)
         if k:
-            raise ValueError(f"{who}: the {'surface edge' if k in edges else 'outer face'} {at(k)} is sampled by a probe of lumped port {nr}: probes "
+            raise ValueError(f"{who}: the {'surface edge' if k in edges else 'outer face'} {at(k)} is sampled by a probe of {kind} port {nr}: probes "
                              f"sample before the corrections and would read a mixed field")
     for kind, comp, blo, bhi in dft_boxes:
         for c, g in sorted(edges if kind == 0 else faces):

@@ -10,6 +10,7 @@ Yee grid (what [EXT] openEMS does when ``FDTD.Run`` sets up its operator):
     surface become sheet edges (surface impedance, stepped by the engine); interior edges stay PEC.  Where metals overlap, the
     highest box priority wins, as for materials;
   * lumped port  -> per-edge conductance, soft-source edges, voltage line and current loop;
+  * waveguide and microstrip-line ports (ports.py) -> one source list, V-probes and I-probes of the same kind, built once the metals are known;
   * lumped element (``add_lumped_element``: R, L, C in parallel or in series, lumped.py) -> the edges of its box along its
     direction, each with its share of the element; with ``caps`` the two end planes of a box with a cross-section become PEC.
 
@@ -32,6 +33,8 @@ from . import conformal as _conformal
 from . import primitives as _prims
 from . import planewave as _planewave
 from . import discmaterial as _discmaterial
+from . import ports as _ports
+from .ports import Probe, WaveguidePort, MSLPort
 
 
 @dataclass
@@ -258,6 +261,40 @@ class Scene:
         self.ports.append(p)
         return p
 
+    def add_waveguide_port(self, number, start, stop, direction, e_func, h_func, kc, excite=0.0, eps_r=1.0, mode=None) -> WaveguidePort:
+        """A modal port (ports.py): e_func, h_func callables (x, y) -> (c_P, c_PP), x and y in metres from the box's minimum corner."""
+        who = f"waveguide port {number}"
+        _ports.check_funcs(who, e_func, h_func)
+        p = WaveguidePort(int(number), tuple(map(float, start)), tuple(map(float, stop)), _ports._axis(direction, who), e_func, h_func,
+                          float(kc), float(excite), float(eps_r), mode=mode)
+        if p.start[p.direction] == p.stop[p.direction]:
+            raise ValueError(f"{who}: start and stop coincide along {'xyz'[p.direction]}: the port has no direction (d = 0)")
+        self.ports.append(p)
+        return p
+
+    def add_rect_waveguide_port(self, number, start, stop, direction, a, b, mode, excite=0.0, eps_r=1.0) -> WaveguidePort:
+        """A TEmn port of an a x b [m] rectangular guide, a along (p + 1) % 3, b along (p + 2) % 3 (ports.py)."""
+        e_func, h_func, kc = _ports.rect_te_mode(a, b, mode, f"rectangular waveguide port {number}")
+        return self.add_waveguide_port(number, start, stop, direction, e_func, h_func, kc, excite, eps_r, mode=str(mode).upper())
+
+    def add_msl_port(self, number, metal: "Metal", start, stop, prop_dir, exc_dir, excite=0.0, feed_shift=0.0, meas_plane_shift=None,
+                     feed_R=float("inf"), priority=0, add_strip=True) -> MSLPort:
+        """A microstrip-line port (ports.py); its strip is added to `metal` here, as a zero-thickness box on the plane stop[exc]
+        (add_strip=False: the caller has drawn it)."""
+        who = f"MSL port {number}"
+        if not isinstance(metal, Metal):
+            raise ValueError(f"{who}: the strip needs a metal of this scene (add_metal / add_conducting_sheet)")
+        p = MSLPort(int(number), metal, tuple(map(float, start)), tuple(map(float, stop)), _ports._axis(prop_dir, who), _ports._axis(exc_dir, who),
+                    float(excite), float(feed_shift), None if meas_plane_shift is None else float(meas_plane_shift), float(feed_R), int(priority))
+        if p.prop == p.exc:
+            raise ValueError(f"{who}: the propagation and the excitation direction are both {'xyz'[p.prop]}")
+        for a in range(3):
+            if p.start[a] == p.stop[a]:
+                raise ValueError(f"{who}: its box has zero extent along {'xyz'[a]}")
+        if add_strip:
+            metal.add_box(*_ports.msl_strip_box(p), priority=p.priority)
+        self.ports.append(p)
+        return p
 
     def add_lumped_element(self, name, direction, R=None, C=None, L=None, kind="parallel", caps=True) -> LumpedElement:
         """R [ohm], L [H], C [F] in parallel (kind "parallel" / 0: Y = 1/R + sC + 1/(sL)) or in series ("series" / 1:
@@ -283,17 +320,25 @@ class Scene:
 
 @dataclass
 class PortOnGrid:
-    port: LumpedPort
+    """A port on the grid: optional resistor edges, one source list, a list of V-probes and a list of I-probes (ports.Probe).  A
+    lumped port has one probe of each kind; v_idx ... i_w read the first of each.  `pec`: edges the port makes metal (an MSL port
+    with feed_R = 0); `info`: the summary of a waveguide / MSL port (ports.PortLists.info), None for a lumped port."""
+    port: object              # LumpedPort, ports.WaveguidePort or ports.MSLPort
     lumped: List[LumpedEdge]
     src_idx: np.ndarray       # global flat node indices
     src_comp: np.ndarray
     src_amp: np.ndarray
-    v_idx: np.ndarray
-    v_comp: np.ndarray
-    v_w: np.ndarray
-    i_idx: np.ndarray
-    i_comp: np.ndarray
-    i_w: np.ndarray
+    v_probes: List[Probe]
+    i_probes: List[Probe]
+    pec: Optional[Tuple[np.ndarray, np.ndarray]] = None
+    info: Optional[dict] = None
+
+    v_idx = property(lambda self: self.v_probes[0].idx)
+    v_comp = property(lambda self: self.v_probes[0].comp)
+    v_w = property(lambda self: self.v_probes[0].w)
+    i_idx = property(lambda self: self.i_probes[0].idx)
+    i_comp = property(lambda self: self.i_probes[0].comp)
+    i_w = property(lambda self: self.i_probes[0].w)
 
 
 @dataclass
@@ -483,7 +528,7 @@ def _voxelize(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
                 sl = [slice(off[2], off[2] + edge.shape[0]), slice(off[1], off[1] + edge.shape[1]),
                       slice(off[0], off[0] + edge.shape[2])]
                 pec[c][tuple(sl)] |= edge
-    ports = [_port_on_grid(p, grid, u) for p in scene.ports]
+    ports = _ports_on_grid(scene, grid, pec)
     return VoxelScene(eps, kap, pec, ports, debye=debye, lorentz=lorentz, elements=_elements_on_grid(scene, grid, pec, ports, None), **magnetic)
 
 
@@ -546,7 +591,6 @@ def _sheets_from_owners(scene: Scene, grid: RectGrid, eps, kap, eown, node_masks
     nx, ny, nz = grid.shape
     u = scene.unit
     pec = eown >= 0
-    ports = [_port_on_grid(p, grid, u) for p in scene.ports]
     sh = _sheet.SheetEdges()
     parts = []
     # The surface of a metal is taken from all sheet metals of the same conductivity and thickness together: where two of them meet
@@ -569,7 +613,9 @@ def _sheets_from_owners(scene: Scene, grid: RectGrid, eps, kap, eown, node_masks
                               np.full(flat.size, q, np.int32)))
     if parts:
         sh.idx, sh.comp, sh.scale, sh.metal = (np.concatenate([p[t] for p in parts]) for t in range(4))
-    # edges the correction must not touch: port edges (sources, lumped resistors) and voltage-probe lines
+    # edges the correction must not touch: port edges (sources, lumped resistors) and voltage-probe lines (the ports come after the
+    # sheets: a waveguide or MSL port leaves PEC edges out of its lists, and a sheet edge is not PEC)
+    ports = _ports_on_grid(scene, grid, pec)
     key = sh.idx * 3 + sh.comp
     for p in ports:
         for what, idx, comp in (("voltage-probe line", p.v_idx, p.v_comp), ("port edge", p.src_idx, p.src_comp)):
@@ -578,7 +624,7 @@ def _sheets_from_owners(scene: Scene, grid: RectGrid, eps, kap, eown, node_masks
                 e = int(np.argmax(hit))
                 k, r = divmod(int(sh.idx[e]), nx * ny)
                 raise ValueError(f"conducting sheet '{sh.metals[sh.metal[e]].name}': the edge at node {(r % nx, r // nx, k)} "
-                                 f"({'xyz'[sh.comp[e]]}) is a {what} of lumped port {p.port.number}")
+                                 f"({'xyz'[sh.comp[e]]}) is a {what} of {_ports.label(p.port)}")
     return VoxelScene(eps, kap, pec, ports, sh)
 
 
@@ -640,9 +686,23 @@ def _port_on_grid(port: LumpedPort, grid: RectGrid, u: float) -> PortOnGrid:
         port=port, lumped=lumped,
         src_idx=np.array(s_idx, np.int64), src_comp=np.full(len(s_idx), d, np.int8),
         src_amp=np.array(s_amp, np.float32),
-        v_idx=np.array(v_idx, np.int64), v_comp=np.full(len(v_idx), d, np.int8),
-        v_w=np.full(len(v_idx), -sign, np.float32),
-        i_idx=i_idx, i_comp=i_comp, i_w=i_w)
+        v_probes=[Probe(np.array(v_idx, np.int64), np.full(len(v_idx), d, np.int8), np.full(len(v_idx), -sign, np.float32))],
+        i_probes=[Probe(i_idx, i_comp, i_w)])
+
+
+def _ports_on_grid(scene: "Scene", grid: RectGrid, pec: np.ndarray) -> List[PortOnGrid]:
+    """Every port of the scene on the grid, in the order they were added.  A waveguide or MSL port reads `pec` (its lists leave metal
+    edges out) and may add to it (an MSL port with feed_R = 0), so the metals come first."""
+    out = []
+    for p in scene.ports:
+        if isinstance(p, LumpedPort):
+            out.append(_port_on_grid(p, grid, scene.unit))
+            continue
+        pl = _ports.lists(grid, pec, p, scene.unit)
+        if pl.pec[0].size:
+            pec.reshape(3, -1)[pl.pec[1].astype(np.int64), pl.pec[0]] = True
+        out.append(PortOnGrid(p, pl.lumped, pl.src.idx, pl.src.comp, pl.src.w, pl.v_probes, pl.i_probes, pl.pec, pl.info))
+    return out
 
 
 def _elements_on_grid(scene: Scene, grid: RectGrid, pec: np.ndarray, ports, sheets) -> Optional[_lumped.LumpedEdges]:
@@ -711,7 +771,7 @@ def _elements_on_grid(scene: Scene, grid: RectGrid, pec: np.ndarray, ports, shee
                     kk = int(pk[int(np.argmax(hit))])
                     k, r = divmod(kk // 3, nx * ny)
                     raise ValueError(f"lumped element '{cap_of[kk]}': its cap edge at node {(r % nx, r // nx, k)} ({'xyz'[kk % 3]}) is a "
-                                     f"{what} of lumped port {p.port.number}: the port would be shorted (caps=False leaves the end planes open)")
+                                     f"{what} of {_ports.label(p.port)}: the port would be shorted (caps=False leaves the end planes open)")
         if sheets is not None and len(sheets):
             keep = ~np.isin(sheets.idx * 3 + sheets.comp, ckey)
             sheets.idx, sheets.comp, sheets.scale, sheets.metal = sheets.idx[keep], sheets.comp[keep], sheets.scale[keep], sheets.metal[keep]
@@ -727,7 +787,7 @@ def _elements_on_grid(scene: Scene, grid: RectGrid, pec: np.ndarray, ports, shee
         for what, pidx, pcomp in (("voltage-probe line", p.v_idx, p.v_comp), ("source edge", p.src_idx, p.src_comp)):
             hit = np.isin(key, np.asarray(pidx, np.int64) * 3 + np.asarray(pcomp, np.int64))
             if hit.any():
-                raise ValueError(f"{where(int(np.argmax(hit)))} is a {what} of lumped port {p.port.number}")
+                raise ValueError(f"{where(int(np.argmax(hit)))} is a {what} of {_ports.label(p.port)}")
     return out
 
 
@@ -813,6 +873,6 @@ def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene
         vs.elements = _elements_on_grid(scene, grid, vs.pec, vs.ports, vs.sheets)
         return vs
     pec = emet >= 0
-    ports = [_port_on_grid(p, grid, u) for p in scene.ports]
+    ports = _ports_on_grid(scene, grid, pec)
     return VoxelScene(eps, kap, pec, ports, debye=debye, lorentz=lorentz, elements=_elements_on_grid(scene, grid, pec, ports, None),
                       mu_r=mur, sigma_m=sgm, cell_material=cmat, material_names=names, cell_voxel=cvox)

@@ -25,6 +25,7 @@ from . import conformal as _conformal
 from . import sar as _sar
 from . import planewave as _planewave
 from . import fields as _fields
+from . import ports as _ports
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox, calc_nf2ff
@@ -337,7 +338,14 @@ class Simulation:
         self.lib = None
         self.external_transport = None     # distributed.SlabComm when halos travel through the host
         self._port_probe_ids = []
+        self._port_probe_lists = []     # per port ([V-probe ids], [I-probe ids]); _port_probe_ids holds the first of each
         self._nf_ids = []
+        # waveguide and MSL ports: their planes against the walls and against every correction list of this run (ports.py)
+        for p in vox.ports:
+            if p.info is not None:
+                _ports.check_placement(grid, p.port, p.info, _ports.Probe(p.src_idx, p.src_comp, p.src_amp), p.v_probes, p.i_probes, pec=vox.pec,
+                                       kinds=self.bc.kinds, debye=self.debye, lorentz=self.lorentz, sheets=self.sheets, elements=self.elements,
+                                       conformal=self.conformal, plane_wave=self.plane_wave)
 
     def _check_plane_wave(self):
         """planewave.check_placement against the scene as this simulation holds it (again when a SAR box is added)."""
@@ -434,13 +442,15 @@ class Simulation:
             e.set_mur(self.mur_enable, self.mur_coeff)
         e.set_signal(self.signal)
         self._port_probe_ids = []
-        for p in self.vox.ports:
+        self._port_probe_lists = []
+        for p in self.vox.ports:      # a port = optional resistor edges (in the operator above), one source list, V-probes, I-probes
             if p.port.excite != 0:
                 e.add_source(p.src_idx, p.src_comp, p.src_amp,
                              np.full(p.src_idx.size, p.port.delay_steps, np.int32))
-            uid = e.add_probe(KIND_V, p.v_idx, p.v_comp, p.v_w)
-            iid = e.add_probe(KIND_I, p.i_idx, p.i_comp, p.i_w)
-            self._port_probe_ids.append((uid, iid))
+            uids = [e.add_probe(KIND_V, q.idx, q.comp, q.w) for q in p.v_probes]
+            iids = [e.add_probe(KIND_I, q.idx, q.comp, q.w) for q in p.i_probes]
+            self._port_probe_ids.append((uids[0], iids[0]))
+            self._port_probe_lists.append((uids, iids))
         if self.nf2ff_box is not None or self.sar_boxes or self.field_boxes:
             if self.nf2ff_mode == "record":
                 try:
@@ -1005,6 +1015,11 @@ class Simulation:
                 u, i = allreduce(u), allreduce(i)
             out.append((u, i))
         return out
+
+    def port_probe_series(self, allreduce=None):
+        """[([u_A(t), ...], [i_1(t), ...])] per port: every V-probe and every I-probe of it (a lumped port has one of each)."""
+        get = (lambda q: self.engine.get_probe(q)) if allreduce is None else (lambda q: allreduce(self.engine.get_probe(q)))
+        return [([get(q) for q in uids], [get(q) for q in iids]) for uids, iids in self._port_probe_lists]
 
     def nf2ff_boxes(self, allreduce=None, freqs=None):
         """Frequency-domain surface data [nfreq][k][j][i] per recording request.  `freqs`: recorder mode only — any
