@@ -45,7 +45,9 @@ priority = 0)
              lumped port's; 0: those edges become PEC; inf: nothing.
 
 Out of scope: coaxial, circular-waveguide, CPW, stripline and curve ports, TM modes, weight functions given as strings.  The lists use
-global node indices and reach the ranks of a decomposed run through the same calls as a lumped port's; world > 1 is not tested.
+global node indices and reach the ranks of a decomposed run through the same calls as a lumped port's; world > 1 is tested on the
+waveguide scene cut at its ports' planes (2 and 3 slabs of one process: mailbox transport with two launches and with one launch per
+timestep, linked contexts), not on the microstrip ports.
 """
 from __future__ import annotations
 

@@ -192,17 +192,53 @@ def raw_engine(name, lib, flags=0):
     return e, ids
 
 
+# The guide (65 node planes) as z-slabs of one process.  Cut at plane 24: port 1's source plane and V-plane become the bottom plane of
+# the slab above the cut (every cell waits for the H halo) and its I half-planes, 23 and 24, straddle the cut; the second cut at 40
+# does the same to port 2's V-plane.
+WG_CUTS = {"2slabs": ((0, 24), (24, 41)), "3slabs": ((0, 24), (24, 16), (40, 25))}
+WG_SLAB_TRANSPORTS = ("p2p-two", "p2p-one", "linked-split")
+
+
+def slab_engines(name, lib, cuts, flags=0):
+    """([engine of every rank], probe ids in list order) of a RAW scene on the slabs `cuts` = [(k0, nk)], every rank built by
+    Simulation.build with the port lists unchanged (the library keeps what the rank owns)."""
+    sim, _ = raw(name)
+    sim.slabs = lambda world, partition="cost": list(cuts)      # (Simulation.slabs cuts by cost or evenly: these cuts are the test's)
+    try:
+        engines = [sim.build(lib, rank=r, world=len(cuts), flags=flags) for r in range(len(cuts))]
+    finally:
+        del sim.slabs
+    assert [(e.k0, e.nk) for e in engines] == [tuple(s) for s in cuts]
+    return engines, [q for uids, iids in sim._port_probe_lists for q in uids + iids]
+
+
+def s_from_series(name, series, freqs):
+    """(S11, S21) of a RAW guide scene from probe series in list order, through the ports' own post-processing (CalcPort)."""
+    sim, _ = raw(name)
+    fd, (p1, p2) = RAW[name](None)
+    fd.sim, fd._u_i_all, at = sim, [], 0
+    for p in sim.vox.ports:
+        nu, ni = len(p.v_probes), len(p.i_probes)
+        fd._u_i_all.append((list(series[at:at + nu]), list(series[at + nu:at + nu + ni])))
+        at += nu + ni
+    assert at == len(series)
+    return s_params(p1, p2, freqs)
+
+
 _RAW_REF = {}
 
 
 def raw_reference(name, oracle_lib):
     """The oracle's run of a RAW scene, computed once: final fields, its own probe series, and per probe the series of probe_block's
-    sums (source_probe_cases.tree_sum) over the oracle's fields, taken half-step by half-step."""
+    sums (source_probe_cases.tree_sum) over the oracle's fields, taken half-step by half-step.  WG: likewise per rank of every cut of
+    WG_CUTS, every list clipped to the rank's planes ("slab_trees": {cut name: [rank][probe]})."""
     import source_probe_cases as spc
     if name not in _RAW_REF:
         _, case = raw(name)
         e, ids = raw_engine(name, oracle_lib)
         tree = [np.zeros(RAW_STEPS) for _ in case.probes]
+        slabs = {cut: [[(np.zeros(RAW_STEPS), spc.clip_to_planes(case, p, s)) for p in case.probes] for s in cuts]
+                 for cut, cuts in (WG_CUTS.items() if name == "WG" else ())}
         for step in range(RAW_STEPS):
             for phase, kind in ((0, spc.KIND_V), (1, spc.KIND_I)):
                 e.half_step(phase)
@@ -210,8 +246,14 @@ def raw_reference(name, oracle_lib):
                 for q, (k, idx, comp, w) in enumerate(case.probes):
                     if k == kind:
                         tree[q][step] = spc.tree_sum(w, F[comp.astype(np.int64), idx])
-        ref = {"fields": e.fields(), "own": [e.get_probe(q) for q in ids], "tree": tree, "step": e.step}
-        for a in [ref["fields"]] + ref["own"] + ref["tree"]:
+                for ranks in slabs.values():
+                    for probes in ranks:
+                        for out, (k, idx, comp, w) in probes:
+                            if k == kind:
+                                out[step] = spc.tree_sum(w, F[comp.astype(np.int64), idx])
+        ref = {"fields": e.fields(), "own": [e.get_probe(q) for q in ids], "tree": tree, "step": e.step,
+               "slab_trees": {cut: [[out for out, _ in probes] for probes in ranks] for cut, ranks in slabs.items()}}
+        for a in [ref["fields"]] + ref["own"] + ref["tree"] + [t for ranks in ref["slab_trees"].values() for probes in ranks for t in probes]:
             a.setflags(write=False)
         _RAW_REF[name] = ref
     return _RAW_REF[name]

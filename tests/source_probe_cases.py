@@ -1,6 +1,7 @@
 """Soft sources and probes through the raw C ABI: the cases of tests/test_sources_probes_cpu.py (oracle against numpy restatements, and
 where every case sits relative to the thresholds of the kernels) and tests/test_sources_probes_gpu.py (libfdtd_hip.so under every
-schedule against the oracle).  No test functions here.
+schedule against the oracle) — and, cut into z-slabs of one process under every halo transport, of
+tests/test_slab_sources_probes_gpu.py (run_slabs, tree_series with planes=, the S cases, the drawn slab batch).  No test functions here.
 
 A node is addressed by its global flat index (k * ny + j) * nx + i, an edge / face by (node, component)."""
 from dataclasses import dataclass, field
@@ -62,6 +63,7 @@ class Case:
     max_steps: int = 0           # 0: eight more than the calls take
     seed: Optional[int] = None   # seeded initial fields (helpers.seeded_fields)
     scene: int = 5               # seed of the materials
+    keep_frames: bool = False    # reference() keeps the oracle's fields of every timestep (the cases that are cut into slabs)
     env: dict = field(default_factory=dict)      # knobs read by fdtd_create ($FDTD_TYS ...)
     expect: dict = field(default_factory=dict)   # where the case is meant to sit: keys of regimes(), checked without a GPU
 
@@ -103,11 +105,21 @@ def prb(kind, idx, comp, w):
     return (int(kind), np.asarray(idx, np.int64), np.asarray(comp, np.int8), np.asarray(w, np.float32))
 
 
+def seeded_slab_fields(engine, seed, scale=1e-3):
+    """helpers.seeded_fields' arrays of the WHOLE grid, the engine's planes of them: a slab starts from its slice of the single slab's
+    initial fields."""
+    rng = np.random.default_rng(seed)
+    for kind in (0, 1):
+        for c in range(3):
+            g = (scale * rng.standard_normal((engine.nz, engine.ny, engine.nx))).astype(np.float32)
+            engine.set_field(kind, c, np.ascontiguousarray(g[engine.k0:engine.k0 + engine.nk]))
+
+
 def apply(case, engine, without=None):
     """Signal, initial fields, the sources (but call number `without`) and the probes of before the first timestep."""
     engine.set_signal(case.signal)
     if case.seed is not None:
-        seeded_fields(engine, case.seed)
+        seeded_slab_fields(engine, case.seed)
     for n, s in enumerate(case.sources):
         if n != without:
             engine.add_source(*s)
@@ -140,6 +152,63 @@ def series_of(case, engine):
     return [engine.get_probe(q) for q in range(len(case.all_probes()))]
 
 
+# ---- z-slabs in one process -----------------------------------------------------------------------------------------------------------
+TRANSPORTS = ("p2p-two", "p2p-one", "linked-split", "linked-nosplit", "half-steps")
+# what fdtd_schedule_info reports as the halo transport (linked: once fdtd_run_linked has linked the contexts)
+TRANSPORT_REPORTED = {"p2p-two": "p2p", "p2p-one": "p2p", "linked-split": "linked", "linked-nosplit": "linked", "half-steps": "external"}
+
+
+def transport_flags(transport):
+    capi = pkg("_capi")
+    return {"p2p-two": capi.FLAG_KERNEL_DIRECT, "p2p-one": capi.FLAG_KERNEL_WAVEFRONT, "linked-split": capi.FLAG_OVERLAP_ON,
+            "linked-nosplit": capi.FLAG_OVERLAP_OFF, "half-steps": 0}[transport]
+
+
+def slab_stepper(engines, transport):
+    """step(n): n timesteps of adjacent slabs of one process under `transport`.  The mailbox transports attach here (before the first
+    timestep); "half-steps" carries the halos through the host, the H halo of "step -1" (the initial fields) before the first timestep."""
+    capi = pkg("_capi")
+    if transport.startswith("p2p"):
+        blobs = [e.p2p_export() for e in engines]
+        for r, e in enumerate(engines):
+            e.p2p_attach(blobs[r - 1] if r > 0 else None, blobs[r + 1] if r + 1 < len(engines) else None)
+    if transport != "half-steps":
+        return lambda n: capi.run_linked(engines, n)
+    pairs = list(zip(engines[:-1], engines[1:]))
+
+    def h_up():
+        for lo, hi in pairs:
+            hi.halo_put(capi.HALO_H_UP, lo.halo_get(capi.HALO_H_UP))
+
+    def step(n):
+        if engines[0].step == 0:
+            h_up()
+        for _ in range(n):
+            for e in engines:
+                e.half_step(capi.PHASE_E)
+            for lo, hi in pairs:
+                lo.halo_put(capi.HALO_E_DOWN, hi.halo_get(capi.HALO_E_DOWN))
+            for e in engines:
+                e.half_step(capi.PHASE_H)
+            h_up()
+    return step
+
+
+def run_slabs(case, lib, cuts, transport):
+    """The case on the slabs `cuts` = [(k0, nk)] of one process, coupled by `transport`: every rank takes the whole lists (the library
+    keeps what it owns), its slice of the seeded fields, and the later additions between the calls.  Returns the engines."""
+    world = len(cuts)
+    engines = [engine_for(case, lib, transport_flags(transport), rank=r, world=world, slab=tuple(s)) for r, s in enumerate(cuts)]
+    step = slab_stepper(engines, transport)
+    for c, n in enumerate(case.calls):
+        step(n)
+        for after, what, call in case.later:
+            if after == c + 1:
+                for e in engines:
+                    (e.add_probe if what == "probe" else e.add_source)(*call)
+    return engines
+
+
 # ---- references -------------------------------------------------------------------------------------------------------------------
 def tree_sum(w, f):
     """probe_block's sum (csrc/kernel_common.hpp) in float64: thread t adds its cells t, t + 256, ... in order, s = fma(w, f, s) — the
@@ -158,10 +227,24 @@ def tree_sum(w, f):
     return float(s[0])
 
 
-def tree_series(case, fields_per_step):
+def in_planes(case, idx, planes):
+    """Which nodes of `idx` lie in the planes (k0, nk): the entries to_local (csrc/api.hip) keeps of a list on the slab of those planes."""
+    k = np.asarray(idx, np.int64) // (case.shape[0] * case.shape[1])
+    return (k >= planes[0]) & (k < planes[0] + planes[1])
+
+
+def clip_to_planes(case, probe, planes):
+    """A probe (kind, idx, comp, w) with the entries a slab keeps of it, in list order."""
+    keep = in_planes(case, probe[1], planes)
+    return (probe[0], probe[1][keep], probe[2][keep], probe[3][keep])
+
+
+def tree_series(case, fields_per_step, planes=None):
     """Per probe the series of probe_block's sums from `fields_per_step`: per timestep (V, I), float32 [3][nz][ny][nx], V after the E
-    half-step (Mur passes and sources applied), I after the H half-step.  Zero before a probe was added and nothing beyond max_steps."""
-    probes = case.all_probes()
+    half-step (Mur passes and sources applied), I after the H half-step.  Zero before a probe was added and nothing beyond max_steps.
+    `planes` = (k0, nk): the series of the rank that owns those planes — every list clipped to them, so that thread t takes the
+    entries t, t + 256, ... of the CLIPPED list (all zero where the rank owns no cell)."""
+    probes = [(first, p if planes is None else clip_to_planes(case, p, planes)) for first, p in case.all_probes()]
     out = [np.zeros(min(case.nsteps, case.cap)) for _ in probes]
     for step, (V, I) in enumerate(fields_per_step):
         if step >= case.cap:
@@ -196,8 +279,29 @@ def reference(case, oracle_lib):
         ref = {"fields": e.fields(), "own": series_of(case, e), "tree": tree_series(case, frames), "step": e.step}
         for a in [ref["fields"]] + ref["own"] + ref["tree"]:
             a.setflags(write=False)
+        if case.keep_frames:      # every cut of the case is cut from this one run (slab_trees)
+            for V, I in frames:
+                V.setflags(write=False), I.setflags(write=False)
+            ref["frames"], ref["slab_trees"] = frames, {}
         _REF[case.name] = ref
     return _REF[case.name]
+
+
+def forget(case):
+    """Drop a case's reference (the drawn slab cases keep the fields of every timestep: not for the whole session)."""
+    _REF.pop(case.name, None)
+
+
+def slab_trees(case, oracle_lib, cuts):
+    """Per rank of `cuts` = [(k0, nk)] the tree_series of that rank, from the frames of the case's one oracle run."""
+    ref = reference(case, oracle_lib)
+    key = tuple(cuts)
+    if key not in ref["slab_trees"]:
+        ref["slab_trees"][key] = [tree_series(case, ref["frames"], planes=s) for s in cuts]
+        for t in ref["slab_trees"][key]:
+            for a in t:
+                a.setflags(write=False)
+    return ref["slab_trees"][key]
 
 
 # ---- where a case sits: the host logic of csrc/ restated (integer arithmetic) -------------------------------------------------------
@@ -631,11 +735,145 @@ def _d7():
     li, lj = np.array([20, 19, 20, 20] * 2), np.array([12, 12, 12, 11] * 2)      # Iy right / left of the edge (20, 12), Ix above / below it
     loop = prb(KIND_I, node(shape, li, lj, [7] * 4 + [8] * 4), [1, 1, 0, 0] * 2, [1, -1, -1, 1] * 2)
     vline = prb(KIND_V, node(shape, 20, 12, np.arange(6, 10)), [2] * 4, [-1.0] * 4)
-    case = Case("D7", shape, ("CPML",) * 6, 3, signal(), [line], [vline, loop], (1, 59), expect={"fusable": True})
-    DIRECTED[case.name] = case       # (its runs are the slab test's)
+    case = Case("D7", shape, ("CPML",) * 6, 3, signal(), [line], [vline, loop], (1, 59), expect={"fusable": True}, keep_frames=True)
+    DIRECTED[case.name] = case       # (its runs are the slab tests')
 
 
 _d7()
+
+
+# ---- the directed slab cases: D7's grid (40 x 24 x 16), cut at and around planes 7 | 8 ------------------------------------------------
+SLAB_SHAPE = (40, 24, 16)
+CUT_2 = ((0, 8), (8, 8))
+CUT_3 = ((0, 7), (7, 2), (9, 7))              # a two-plane slab: both of its planes wait for a halo
+CUT_4 = ((0, 6), (6, 2), (8, 2), (10, 6))
+SLAB_RUNS = []     # (case name, cuts, transport, "ok" | "refused: <the library's text>")
+
+
+def _slab_runs(name, cuts, transports=TRANSPORTS):
+    for c in cuts:
+        for t in transports:
+            SLAB_RUNS.append((name, c, t, "ok"))
+
+
+def _inner_edges(planes, rows):
+    """Every edge (c, k, j, i) of the rows and planes, three cells off the x faces."""
+    return np.array([(c, k, j, i) for k in planes for c in range(3) for j in rows for i in range(3, 37)])
+
+
+def _s1():
+    """S1 (and S2: the same lists on thinner slabs): strips of 4 rows; 200 distinct source edges of all three components in rows 8..11
+    of plane 8 and 200 in plane 7 (one strip-plane each: the dense LDS image on both sides of the cut 7 | 8), a few of them never
+    firing; a V-probe and an I-probe of 300 cells over planes 6..9; a V-probe of 280 cells wholly in plane 8 (the bottom plane of the
+    slab above the cut: every cell waits for the H halo) and an I-probe of 270 cells wholly in plane 7 (the top plane of the slab below:
+    every cell waits for the E halo), both longer than one block; an I-probe wholly in planes 2..4, of which the upper slabs own
+    nothing.  Seeded fields, so that the halo of the initial fields counts."""
+    shape = SLAB_SHAPE
+    rng = np.random.default_rng(8100)
+    sources = []
+    for plane in (8, 7):
+        e = _inner_edges([plane], range(8, 12))
+        c, k, j, i = e[rng.permutation(len(e))[:200]].T
+        delay = rng.integers(-3, 41, 200)
+        delay[[3, 77, 150]] = [500, 81, 300]        # never fire in the 80 timesteps
+        sources.append(src(node(shape, i, j, k), c, _amps(rng, 200), delay))
+
+    def cells(kind, n, planes, rows=range(2, 22)):
+        e = _inner_edges(planes, rows)
+        c, k, j, i = e[rng.permutation(len(e))[:n]].T
+        return prb(kind, node(shape, i, j, k), c, _weights(rng, n))
+    probes = [cells(KIND_V, 300, range(6, 10)), cells(KIND_I, 300, range(6, 10)), cells(KIND_V, 280, [8]), cells(KIND_I, 270, [7]),
+              cells(KIND_I, 20, range(2, 5))]
+    case = Case("S1", shape, ("CPML",) * 6, 3, signal(), sources, probes, (1, 79), seed=11, env={"FDTD_TYS": "4"}, keep_frames=True,
+                expect={"tys": 4, "sp_max": 200, "dup": False, "path": "dense", "fusable": True, "blocks_per_strip_plane": 1,
+                        "probe_cells_max": 300, "nprobes": 5})
+    DIRECTED[case.name] = case
+    _slab_runs("S1", [CUT_2, CUT_3, CUT_4])       # (CUT_3, CUT_4: the issue's S2)
+
+
+_s1()
+
+
+def _s3():
+    """S3: D6's pattern on this grid.  Calls of 1, 7, 40 and 12 timesteps with series of 55 entries (the last five timesteps are not
+    recorded); after the second call 40 more source entries on planes 7 and 8 — one edge of plane 8 listed twice, with another amplitude
+    and delay (src_dense_ok = 0, the chain of k_post) — and two more probes on planes 7 and 8."""
+    shape = SLAB_SHAPE
+    rng = np.random.default_rng(8300)
+
+    def some(n, kind, klo=1, khi=15):
+        i, j, k = rng.integers(3, 37, n), rng.integers(1, 23, n), rng.integers(klo, khi, n)
+        return prb(kind, node(shape, i, j, k), rng.integers(0, 3, n), _weights(rng, n))
+    probes = [some(n, q % 2) for q, n in enumerate([1, 3, 9, 17, 40, 64])] + [some(12, KIND_V, 7, 9), some(12, KIND_I, 7, 9)]
+    sources = [src(node(shape, [20, 20, 21, 21], [12, 13, 12, 13], [7, 7, 8, 8]), [2, 2, 1, 0], [1.0, -0.5, 0.7, -0.9], [0, 2, 1, -1])]
+    e = _inner_edges([7, 8], range(9, 13))
+    c, k, j, i = e[rng.permutation(len(e))[:39]].T
+    idx, amp, delay = node(shape, i, j, k), _amps(rng, 39), rng.integers(-3, 41, 39)
+    at = int(np.flatnonzero(k == 8)[2])           # this edge again, right behind its first entry
+    idx, c = np.insert(idx, at + 1, idx[at]), np.insert(c, at + 1, c[at])
+    amp, delay = np.insert(amp, at + 1, np.float32(-0.75) * amp[at] + np.float32(0.3)), np.insert(delay, at + 1, delay[at] + 2)
+    more = src(idx, c, amp, delay)
+    case = Case("S3", shape, ("CPML",) * 6, 3, signal(), sources, probes, (1, 7, 40, 12), max_steps=55, seed=4, keep_frames=True,
+                later=[(2, "source", more), (2, "probe", some(33, KIND_V, 7, 9)), (2, "probe", some(21, KIND_I, 7, 9))],
+                expect={"dup": True, "path": "scan", "fusable": True, "nprobes": 10})
+    DIRECTED[case.name] = case
+    _slab_runs("S3", [CUT_2, CUT_3])
+
+
+_s3()
+
+
+def _s4(zkind):
+    """S4: Mur faces on x and y, the z faces CPML or Mur.  One source edge next to the x-low face in plane 8 and more well inside, in
+    planes 7 and 8: the post, apply and source passes are launches of their own; a V-probe with cells ON the x-low node plane (the
+    tangential edges the apply pass writes) in planes 7 and 8, and an I-probe round them.  Linked contexts and half-steps only: the mailbox
+    transport takes no Mur face."""
+    shape = SLAB_SHAPE
+    rng = np.random.default_rng(8400)
+    sources = [src(node(shape, [1, 20, 20, 21], [12, 12, 13, 12], [8, 8, 7, 7]), [2, 2, 1, 0], [1.0, -0.8, 0.6, 0.9], [0, 1, -2, 3])]
+    jj = np.array([5, 9, 12, 12, 16, 20])
+    on_face = prb(KIND_V, node(shape, 0, np.concatenate([jj, jj]), [7] * 6 + [8] * 6), [1, 2] * 6, _weights(rng, 12))
+    near = prb(KIND_I, node(shape, [0, 1] * 6, np.concatenate([jj, jj]), [7] * 6 + [8] * 6), [2, 1] * 6, _weights(rng, 12))
+    inner = prb(KIND_V, node(shape, 20, 12, np.arange(5, 11)), [2] * 6, [-1.0] * 6)
+    kinds = ("MUR",) * 4 + (zkind,) * 2
+    case = Case(f"S4-z{zkind.lower()}", shape, kinds, 3 if zkind == "CPML" else 0, signal(), sources, [on_face, near, inner], (1, 69), seed=6, scene=21,
+                keep_frames=True, expect={"near_mur": True, "fusable": False})
+    DIRECTED[case.name] = case
+    _slab_runs(case.name, [CUT_2, CUT_3, CUT_4], ("linked-split", "linked-nosplit", "half-steps"))
+    SLAB_RUNS.append((case.name, CUT_2, "p2p-two", "refused: fdtd_run_linked: every context must use the p2p transport (no Mur)"))
+
+
+_s4("CPML")
+_s4("MUR")
+_slab_runs("D7", [CUT_2])
+SLAB_CASES = sorted({r[0] for r in SLAB_RUNS})
+
+
+def slab_facts(case, cuts):
+    """Where the lists of a case sit on the slabs `cuts`: per rank the source entries of its fullest strip-plane and whether that
+    strip-plane takes the dense path on the rank, per rank and probe the cells it owns, and of those the ones in its bottom plane (V: they
+    wait for the H halo from below) and in its top plane (I: they wait for the E halo from above)."""
+    nx, ny, _ = case.shape
+    tys = tys_of(case)
+    nstrips = -(-ny // tys)
+    out = []
+    for r, (k0, nk) in enumerate(cuts):
+        sidx = np.concatenate([s[0] for _, s in case.all_sources()])
+        scomp = np.concatenate([s[1] for _, s in case.all_sources()]).astype(np.int64)
+        own = in_planes(case, sidx, (k0, nk))
+        sidx, scomp = sidx[own], scomp[own]
+        k, j, _ = _kji(case, sidx)
+        sp = np.bincount((k - k0) * nstrips + j // tys, minlength=nk * nstrips)
+        dup = np.unique(sidx * 4 + scomp).size < sidx.size
+        cells, bottom, top = [], [], []
+        for _, p in case.all_probes():
+            pk = _kji(case, clip_to_planes(case, p, (k0, nk))[1])[0]
+            cells.append(int(pk.size))
+            bottom.append(int(np.sum(pk == k0)) if (p[0] == KIND_V and r > 0) else 0)
+            top.append(int(np.sum(pk == k0 + nk - 1)) if (p[0] == KIND_I and r + 1 < len(cuts)) else 0)
+        out.append({"sp_max": int(sp.max()) if sidx.size else 0, "dense": bool(sidx.size and sp.max() > SRC_SCAN_MAX and not dup), "dup": bool(dup),
+                    "sp": sp.reshape(nk, nstrips), "cells": cells, "halo_cells_V": bottom, "halo_cells_I": top})
+    return out
 
 
 # ---- the randomised batch -------------------------------------------------------------------------------------------------------------
@@ -722,3 +960,66 @@ def drawn(n):
 
 
 N_DRAWN = 24
+
+# ---- the randomised slab batch --------------------------------------------------------------------------------------------------------
+N_SLAB_DRAWN = 16
+SLAB_SEED = 20268420      # (the first of 20261020, 20261120, ... whose batch meets every floor of test_drawn_slab_batch_covers_what_it_claims)
+
+
+def draw_slabs(rng):
+    """(case, cuts, transport): a case of draw() with at least 8 planes, cut into 2..4 slabs of at least 2 planes — every cut with
+    probability 1/2 placed ON a plane that holds a source or probe cell (that plane becomes the bottom plane of the slab above the cut or
+    the top plane of the slab below it) — and the transport it runs under, drawn first: a mailbox transport takes the next case without a
+    Mur face (and without more than 256 entries with a repeated edge in one strip-plane: it refuses both), so a case with Mur faces runs
+    on linked contexts or half-steps."""
+    transport = TRANSPORTS[int(rng.integers(0, len(TRANSPORTS)))]
+    while True:
+        case, _ = draw(rng)
+        if case.shape[2] >= 8 and not (transport.startswith("p2p") and ("MUR" in case.boundary or regimes(case)["path"] == "post")):
+            break
+    nz = case.shape[2]
+    nodes = np.concatenate([s[0] for _, s in case.all_sources()] + [p[1] for _, p in case.all_probes()])
+    held = np.unique(nodes // (case.shape[0] * case.shape[1]))
+    while True:
+        world = int(rng.integers(2, 5))
+        first = []                 # the first plane of every slab but the lowest
+        for _ in range(world - 1):
+            if rng.random() < 0.5:
+                first.append(int(rng.choice(held)) + int(rng.integers(0, 2)))
+            else:
+                first.append(int(rng.integers(2, nz - 1)))
+        b = [0] + sorted(first) + [nz]
+        if all(hi - lo >= 2 for lo, hi in zip(b[:-1], b[1:])):
+            break
+    cuts = tuple((lo, hi - lo) for lo, hi in zip(b[:-1], b[1:]))
+    case.keep_frames = True
+    return case, cuts, transport
+
+
+def drawn_slabs(n):
+    case, cuts, transport = draw_slabs(np.random.default_rng(SLAB_SEED + n))
+    case.name = f"slabs-{n:02d}"
+    return case, cuts, transport
+
+
+def slab_batch_coverage():
+    """What the drawn slab batch reaches, by the arithmetic of slab_facts: the floors tests/test_sources_probes_cpu.py asserts."""
+    tally = {"transports": {t: 0 for t in TRANSPORTS}, "two_plane_slabs": 0, "probes_across_a_cut": 0, "rank_probe_pairs_without_cells": 0,
+             "slabs_with_a_dense_strip_plane": 0, "mur_cases": 0, "cuts_on_a_held_plane": 0, "cuts": 0}
+    for n in range(N_SLAB_DRAWN):
+        case, cuts, transport = drawn_slabs(n)
+        facts = slab_facts(case, cuts)
+        tally["transports"][transport] += 1
+        tally["two_plane_slabs"] += sum(nk == 2 for _, nk in cuts)
+        tally["mur_cases"] += "MUR" in case.boundary
+        tally["slabs_with_a_dense_strip_plane"] += sum(f["dense"] for f in facts)
+        for q in range(len(case.all_probes())):
+            owners = sum(f["cells"][q] > 0 for f in facts)
+            tally["probes_across_a_cut"] += owners >= 2
+            tally["rank_probe_pairs_without_cells"] += len(cuts) - owners
+        nodes = np.concatenate([s[0] for _, s in case.all_sources()] + [p[1] for _, p in case.all_probes()])
+        held = set((nodes // (case.shape[0] * case.shape[1])).tolist())
+        for k0, _ in cuts[1:]:
+            tally["cuts"] += 1
+            tally["cuts_on_a_held_plane"] += (k0 in held) or (k0 - 1 in held)
+    return tally

@@ -378,3 +378,36 @@ def test_msl_refusals():
     fd, _ = pc.msl(None)
     with pytest.raises(ValueError, match="MSL port 3: metal_prop must be a metal of the structure"):
         fd.AddMSLPort(3, fd.GetCSX().AddMaterial("fr4", epsilon=4.4), [16, 8, 0], [24, 38, 4], "y", "z", 1)
+
+
+@pytest.mark.parametrize("cut", sorted(pc.WG_CUTS))
+def test_the_guide_on_oracle_slabs_is_the_guide_on_one_slab(oracle_lib, cut):
+    """WG cut at plane 24 (port 1's source and V-plane the bottom plane of the upper slab, its I half-planes on both sides of the cut) and
+    at planes 24 and 40, the oracle half-stepped with the halos carried by the host: the single slab's fields (every value, and the bits
+    of every non-zero one: the sign of a zero on a dead edge depends on what lies below plane 0, tests/test_sources_probes_cpu.py); every
+    rank's series the sums of the cells it owns; the ranks' series added up and handed to the ports' post-processing give the single
+    slab's S11 and S21 over the band to 1e-12 relative."""
+    import source_probe_cases as spc
+    from helpers import rel_l2
+    cuts = pc.WG_CUTS[cut]
+    _, case = pc.raw("WG")
+    ref = pc.raw_reference("WG", oracle_lib)
+    engs, ids = pc.slab_engines("WG", oracle_lib, cuts)
+    spc.slab_stepper(engs, "half-steps")(pc.RAW_STEPS)
+    got, want = np.concatenate([e.fields() for e in engs], axis=2), ref["fields"]
+    assert np.array_equal(got, want) and np.array_equal(got[want != 0].view(np.uint32), want[want != 0].view(np.uint32))
+    trees = ref["slab_trees"][cut]
+    owners = []
+    for q, pid in enumerate(ids):
+        parts = [e.get_probe(pid) for e in engs]
+        for r, part in enumerate(parts):
+            assert len(part) == pc.RAW_STEPS and part.any() == trees[r][q].any() and rel_l2(part, trees[r][q]) < 1e-12, (cut, r, q)
+        owners.append([bool(p.any()) for p in parts])
+        assert rel_l2(sum(parts), ref["own"][q]) < 1e-12, (cut, q)
+    # port 1: V (120 cells, plane 24) the upper slab's alone, I (240 faces, planes 23 and 24) on both sides of the cut
+    assert [p[1].size for p in case.probes[:2]] == [120, 240] and owners[0][:2] == [False, True] and owners[1][:2] == [True, True], owners
+    f = pc.wg_freqs()
+    summed = pc.s_from_series("WG", [sum(e.get_probe(pid) for e in engs) for pid in ids], f)
+    single = pc.s_from_series("WG", ref["own"], f)
+    for a, b in zip(summed, single):
+        assert np.abs(b).min() > 0 and np.all(np.abs(a - b) <= 1e-12 * np.abs(b)), (cut, np.abs((a - b) / b).max())

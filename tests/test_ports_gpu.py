@@ -3,8 +3,8 @@ is new: a port is lists for fdtd_add_source and fdtd_add_probe — but a weighte
 walls (the dense source path), I-probes of 240 non-uniformly weighted faces over two half-planes, and ten probes in one scene are
 regimes of those paths that the engine's own tests do not reach.  Fields bit for bit; every probe series EQUAL to probe_block's
 reduction tree restated over the oracle's fields, and within 1e-12 relative L2 of the oracle's own (sequential) sums; the schedule a
-run was forced into is the one fdtd_schedule_info reports; a schedule that cannot run a scene refuses it with its stated reason.  And
-one run through the public API: S21 of the guide on the device against the same run on the oracle."""
+run was forced into is the one fdtd_schedule_info reports; a schedule that cannot run a scene refuses it with its stated reason.  The
+guide cut into z-slabs at its ports' planes, under the mailbox and the linked transports: the same, for every rank.  And one run through the public API: S21 of the guide on the device against the same run on the oracle."""
 import numpy as np
 import pytest
 
@@ -12,6 +12,7 @@ import ports_cases as pc
 import source_probe_cases as spc
 from conftest import pkg
 from helpers import rel_l2
+from test_slab_sources_probes_gpu import check_slabs
 from test_sources_probes_gpu import _flags, _knobs, _schedule_is, _fields_equal
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +48,31 @@ def test_port_lists_under_schedule(hip_lib, oracle_lib, monkeypatch, name, sched
         assert bad.size == 0, (name, sched, f"probe {q} ({case.probes[q][1].size} cells)", f"{bad.size} entries differ, first at {bad[:1]}",
                                f"rel L2 to the tree {rel_l2(got, tree):.3e}, to the oracle's series {rel_l2(got, own):.3e}")
         assert rel_l2(got, own) < 1e-12, (name, sched, q, rel_l2(got, own))
+
+
+SLAB_RUNS = [(cut, t) for cut in sorted(pc.WG_CUTS) for t in pc.WG_SLAB_TRANSPORTS]
+
+
+@pytest.mark.parametrize("cut,transport", SLAB_RUNS, ids=[f"WG-{c}-{t}" for c, t in SLAB_RUNS])
+def test_port_lists_on_slabs(hip_lib, oracle_lib, monkeypatch, cut, transport):
+    """WG as z-slabs of one process, every rank built by Simulation.build with the port lists unchanged.  Cut at plane 24: port 1's 120
+    source edges (the dense path) and its V-probe's 120 cells all lie in the bottom plane of the upper slab, which takes its V only after
+    the H halo has arrived, and the 240 faces of its I-probe in planes 23 — the lower slab's top plane, which takes its I only after the E
+    halo has arrived — and 24.  The second cut, at 40, does the same to port 2's V-plane.  Fields as the oracle's single slab; every
+    rank's series EQUAL to probe_block's tree over the cells it owns; the ranks' series add up to the oracle's within 1e-12."""
+    cuts = pc.WG_CUTS[cut]
+    _, case = pc.raw("WG")
+    _knobs(monkeypatch, case, extra={"FDTD_RESIDENT": "0"})
+    ref = pc.raw_reference("WG", oracle_lib)
+    engs, ids = pc.slab_engines("WG", hip_lib, cuts, spc.transport_flags(transport))
+    spc.slab_stepper(engs, transport)(pc.RAW_STEPS)
+    infos = [e.schedule_info() for e in engs]
+    print(f"SCHEDULE WG {cut} {transport} -> {infos}")
+    assert all(e.step == pc.RAW_STEPS == ref["step"] for e in engs)
+    for info in infos:
+        assert info["transport"] == spc.TRANSPORT_REPORTED[transport] and not info["resident"], info
+        assert info["launches_per_timestep"] == (1 if transport == "p2p-one" else 2), info
+    check_slabs(engs, cuts, [(0, p) for p in case.probes], ids, pc.RAW_STEPS, ref["fields"], ref["slab_trees"][cut], ref["own"], ("WG", cut, transport))
 
 
 def test_the_guide_source_takes_the_dense_path():
