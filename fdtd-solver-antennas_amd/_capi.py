@@ -54,6 +54,8 @@ CONFORMAL_SYMBOLS = ["fdtd_conformal_set", "fdtd_conformal_get", "fdtd_voxel_fra
 SAR_SYMBOLS = ["fdtd_sar_local", "fdtd_sar_average"]
 # include/fdtd_hip_planewave.h: plane-wave excitation on a total-field / scattered-field box, likewise
 PLANEWAVE_SYMBOLS = ["fdtd_planewave_set"]
+# include/fdtd_hip_excite.h: H-field excitations on listed faces, likewise
+EXCITE_SYMBOLS = ["fdtd_excite_set"]
 # include/fdtd_hip_fields.h: field dumps (E, H, J, rot-H on a point lattice) on the device, likewise
 FIELDS_SYMBOLS = ["fdtd_field_interp"]
 # FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
@@ -236,6 +238,13 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    excite_sig = {"fdtd_excite_set": (C.c_int, [p, C.c_int, p, p, p, p, C.c_int, p, p, p, p, p, C.c_int])}
+    assert sorted(excite_sig) == sorted(EXCITE_SYMBOLS)
+    for name, (res, args) in excite_sig.items():     # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     sar_sig = {
         "fdtd_sar_local": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p]),
         "fdtd_sar_average": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, p, p, p, p, C.c_double, C.c_int, p, p, p, p]),
@@ -264,6 +273,11 @@ def has_fields(lib: C.CDLL) -> bool:
 def has_sar(lib: C.CDLL) -> bool:
     """Whether `lib` exports the SAR entry points (include/fdtd_hip_sar.h)."""
     return all(hasattr(lib, n) for n in SAR_SYMBOLS)
+
+
+def has_excite(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the H-field excitation entry point (include/fdtd_hip_excite.h)."""
+    return all(hasattr(lib, n) for n in EXCITE_SYMBOLS)
 
 
 def has_planewave(lib: C.CDLL) -> bool:
@@ -658,6 +672,7 @@ class Engine:
         "magnetic": (has_magnetic, "magnetic materials (fdtd_magnetic_set / fdtd_magnetic_get)"),
         "conformal": (has_conformal, "conformal boundaries (fdtd_conformal_set / fdtd_conformal_get)"),
         "planewave": (has_planewave, "plane-wave excitation (fdtd_planewave_set)"),
+        "excite": (has_excite, "H-field excitations (fdtd_excite_set)"),
     }
 
     def _need(self, correction: str):
@@ -836,6 +851,23 @@ class Engine:
         for l in lists:
             args += [int(l[0].size)] + [_ptr(a) if a.size else None for a in l]
         self._ck(self.lib.fdtd_planewave_set(self._ctx, *args, _ptr(sig2) if sig2.size else None, int(sig2.size)), "planewave_set")
+
+    # -- H-field excitations (include/fdtd_hip_excite.h) ----------------------------------------------
+    def set_excite(self, idxH, compH, ampH, delayH, idxS, compS, ampS, delayS, sigH):
+        """The hard list and the soft list of field_excitation.ExcitationLists.h_args (per list idx int64 [n], comp int8 [n], amp float32 [n], delay
+        int32 [n]) and the pulse at the half-steps, sigH[m] = s((m + 1/2) dt).  Two empty lists remove the set."""
+        self._need("excite")
+        lists = []
+        for idx, comp, amp, delay in ((idxH, compH, ampH, delayH), (idxS, compS, ampS, delayS)):
+            l = (_arr(idx, np.int64).ravel(), _arr(comp, np.int8).ravel(), _arr(amp, np.float32).ravel(), _arr(delay, np.int32).ravel())
+            if not (l[0].size == l[1].size == l[2].size == l[3].size):
+                raise ValueError("excitation lists must be idx [n], comp [n], amp [n], delay [n]")
+            lists.append(l)
+        sigH = _arr(np.zeros(0) if sigH is None else sigH, np.float32).ravel()
+        args = []
+        for l in lists:
+            args += [int(l[0].size)] + [_ptr(a) if a.size else None for a in l]
+        self._ck(self.lib.fdtd_excite_set(self._ctx, *args, _ptr(sigH) if sigH.size else None, int(sigH.size)), "excite_set")
 
     def get_field(self, kind: int, comp: int) -> np.ndarray:
         out = np.empty(self.local_shape, np.float32)

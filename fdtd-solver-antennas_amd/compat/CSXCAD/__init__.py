@@ -14,6 +14,7 @@ class CSProperties:            # names probed by probe_openems_fixed (fixed.py:1
     CSProperties = _api.CSProperty
     CSPropMaterial = _api.CSProperty
     CSPropMetal = _api.CSProperty
+    CSPropProbeBox = _api.CSProbe      # what ContinuousStructure.AddProbe returns (probes.py)
 
 
 class CSPrimitives:

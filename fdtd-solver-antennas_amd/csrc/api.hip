@@ -272,6 +272,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   sheet_free(c);
   lumped_free(c);
   planewave_free(c);
+  excite_free(c);
   media_free(&c->debye);
   media_free(&c->lorentz);
   magnetic_free(c);
@@ -888,7 +889,8 @@ static CorrectionInfo correction(const fdtd_ctx* c, int which) {
     case CORR_LUMPED:   return {c->lumped.n > 0, "lumped elements", false, true};
     case CORR_MAGNETIC: return {c->mag_ncls > 0, "magnetic materials", true, true};
     case CORR_CONFORMAL: return {c->conf_n > 0, "conformal boundaries", true, true};
-    default:            return {c->pw[0].n > 0 || c->pw[1].n > 0, "plane-wave excitation", true, true};   // (its edge list runs behind the E phase as well)
+    case CORR_PLANEWAVE: return {c->pw[0].n > 0 || c->pw[1].n > 0, "plane-wave excitation", true, true};   // (its edge list runs behind the E phase as well)
+    default:            return {c->excite.n > 0, "H-field excitations", true, true};
   }
 }
 static bool any_correction(const fdtd_ctx* c) {
@@ -1211,7 +1213,8 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   }
   launch_magnetic(c, s);   // magnetic faces: after the whole H update, before anything samples I (no-op without faces)
   launch_conformal(c, s);  // conformal faces: likewise
-  launch_planewave(c, FDTD_KIND_I, step, s);   // plane wave: the faces just outside the box, last of the H side (no-op without one)
+  launch_planewave(c, FDTD_KIND_I, step, s);   // plane wave: the faces just outside the box (no-op without one)
+  launch_excite(c, step, s);                   // H-field excitations: last of the H side (no-op without a set)
   if (!pl.fused) launch_post(c, FDTD_KIND_I, step, false, s);
   launch_dft(c, FDTD_KIND_I, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_H, s));
@@ -1504,6 +1507,7 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_magnetic(c, s);
     launch_conformal(c, s);
     launch_planewave(c, FDTD_KIND_I, c->step, s);
+    launch_excite(c, c->step, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);
     launch_dft(c, FDTD_KIND_I, c->step, s);
     c->step++;

@@ -328,6 +328,11 @@ struct fdtd_ctx {
   unsigned pw_faces = 0;
   std::vector<int> pw_h_off;
   float* pw_sig2 = nullptr; int pw_nsig2 = 0;
+  // H-field excitations (excite.hip, include/fdtd_hip_excite.h): the distinct faces — per face its node offset, its component and whether
+  // it has a hard entry, its range of soft entries — the hard entries [n], the soft entries grouped by face, the pulse at the half-steps
+  struct ExciteSet { int n = 0; int4* face = nullptr; float* hamp = nullptr; int* hdelay = nullptr; float* samp = nullptr; int* sdelay = nullptr;
+                     float* sig = nullptr; int nsig = 0; };
+  ExciteSet excite;
   std::string err;
 };
 
@@ -374,7 +379,7 @@ int res_prepare(fdtd_ctx* c, int max_chunk);
 int launch_resident(fdtd_ctx* c, long long step, int nsteps, hipStream_t s);
 void res_free(fdtd_ctx* c);
 // The corrections between the E and H phases and behind the H update, in launch order.  api.hip lists what the planner knows of each.
-enum Correction { CORR_SHEET, CORR_DEBYE, CORR_LORENTZ, CORR_LUMPED, CORR_MAGNETIC, CORR_CONFORMAL, CORR_PLANEWAVE, CORR_COUNT };
+enum Correction { CORR_SHEET, CORR_DEBYE, CORR_LORENTZ, CORR_LUMPED, CORR_MAGNETIC, CORR_CONFORMAL, CORR_PLANEWAVE, CORR_EXCITE, CORR_COUNT };
 int correction_single_slab(fdtd_ctx* c, Correction which);   // api.hip: FDTD_OK, or the refusal of a decomposed / p2p / linked context
 inline int fdtd_fail_hip(fdtd_ctx* c, const char* who, hipError_t e) {   // a set function's allocation or copy failed
   return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
@@ -430,6 +435,10 @@ void conformal_free(fdtd_ctx* c);
 // launch_lumped; kind FDTD_KIND_I after the H update, behind launch_conformal (no-ops without a plane wave)
 void launch_planewave(fdtd_ctx* c, int kind, long long step, hipStream_t s);
 void planewave_free(fdtd_ctx* c);
+// excite.hip: H-field excitations — the sparse correction after the H update, behind launch_planewave(FDTD_KIND_I): last of the H side
+// (no-op without a set)
+void launch_excite(fdtd_ctx* c, long long step, hipStream_t s);
+void excite_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

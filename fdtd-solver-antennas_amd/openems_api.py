@@ -362,6 +362,26 @@ class CSExcitation(CSProperty):
         raise ValueError(f"Add{kind} on excitation '{self.name}': a plane wave takes one box only")
 
 
+class CSProbe(CSProperty):
+    """What ContinuousStructure.AddProbe returns: a stand-alone probe (probes.py), placed by one AddBox(start, stop)."""
+
+    def __init__(self, log: _CallLog, spec):
+        fn = spec.mode_function
+        super().__init__(log, "Probe", spec.name, p_type=spec.p_type, weight=spec.weight, norm_dir=spec.norm_dir,
+                         mode_function=None if fn is None else [getattr(f, "expression", None) or repr(f) for f in fn])
+        self.spec = spec
+
+    def AddBox(self, start=None, stop=None, priority=0, **kw):
+        if self.boxes:
+            raise ValueError(f"probe '{self.name}': one box per probe")
+        b = super().AddBox(start, stop, priority, **kw)
+        self.spec.start, self.spec.stop = tuple(float(v) for v in start), tuple(float(v) for v in stop)
+        return b
+
+    def _add(self, kind, priority, **kw):
+        raise ValueError(f"Add{kind} on probe '{self.name}': a probe takes one box only")
+
+
 def _take(kw, names, numbered):
     """Per-pole values out of the keywords `kw` (popped): the first of `names` present, as a sequence — else the keywords of
     `numbered` with the suffixes _1, _2, ... as far as they go."""
@@ -520,6 +540,18 @@ class ContinuousStructure:
         if any(p.kind == "Excitation" for p in self.properties):
             raise ValueError(f"AddExcitation '{name}': the structure already has a plane wave (one plane-wave box per scene)")
         p = CSExcitation(self._log, name, exc_type, np.asarray(exc_val, float).reshape(-1), delay)
+        self.properties.append(p)
+        return p
+
+    def AddProbe(self, name, p_type, weight=1, norm_dir=None, mode_function=None):
+        """CSXCAD's probe property (probes.py): ``p_type`` 0 voltage, 1 current, 2 E field, 3 H field, 10 / 11 mode-matching voltage /
+        current (``mode_function``: three per-component callables (x, y, z) or strings, coordinates in drawing units).  One
+        ``AddBox(start, stop)`` on the returned property places it; ``openEMS.GetProbe(name)`` returns its series after ``Run``,
+        which also writes upstream's ASCII probe file ``name`` into sim_path."""
+        from . import probes as _probes
+        if any(p.kind == "Probe" and p.name == str(name) for p in self.properties):
+            raise ValueError(f"AddProbe '{name}' is defined twice")
+        p = CSProbe(self._log, _probes.make(name, p_type, weight, norm_dir, mode_function))
         self.properties.append(p)
         return p
 
@@ -789,6 +821,8 @@ class openEMS:
         self._sar = {}                 # (dump name, frequency) -> sar.SARResult of the last Run
         self._field_dumps = {}         # name -> the arguments of AddFieldDump
         self._fields = {}              # (dump name, frequency or timestep taken) -> fields.FieldDump of the last Run
+        self._field_excitations = []   # field_excitation.FieldExcitation, in the order of AddFieldExcitation
+        self._probes = {}              # probe name -> {"t", "val"} of the last Run
 
     @property
     def calls(self):
@@ -938,6 +972,22 @@ class openEMS:
                                        timesteps=None if timesteps is None else [int(v) for v in np.atleast_1d(timesteps)],
                                        sub_sampling=tuple(sub_sampling), file_type=int(file_type), dump_type=int(dump_type))
 
+    def AddFieldExcitation(self, name, exc_type, exc_val, start, stop, *, weight=None, delay=0, priority=0):
+        """An E- or H-field excitation over a box, a plane, a line or a point, start / stop in drawing units (field_excitation.py).
+        ``exc_type`` as upstream: 0 soft E, 1 hard E, 2 soft H, 3 hard H; ``exc_val`` the field vector; ``weight`` None, one callable
+        (x, y, z) or three per-component callables or strings (upstream's weight functions; coordinates in drawing units); ``delay``
+        in seconds.  CSX.AddExcitation keeps refusing these types, and CSExcitation.SetWeightFunction stays refused: its box and
+        weights come after the call, and a scene is built from them."""
+        from . import field_excitation as _fexc
+        if any(e.name == str(name) for e in self._field_excitations):
+            raise ValueError(f"AddFieldExcitation '{name}' is defined twice")
+        ex = _fexc.make(name, exc_type, exc_val, start, stop, weight, delay, priority)
+        self.calls_log.add("AddFieldExcitation", name=name, exc_type=exc_type, exc_val=[float(v) for v in ex.exc_val], start=list(ex.start),
+                           stop=list(ex.stop), weight=[None if f is None else getattr(f, "expression", None) or repr(f) for f in ex.weight],
+                           delay=float(delay), priority=int(priority))
+        self._field_excitations.append(ex)
+        return ex
+
     # -- run ------------------------------------------------------------------------------------------
     @staticmethod
     def _draw(m, b):
@@ -978,8 +1028,8 @@ class openEMS:
                 if len(p.boxes) != 1 or not np.allclose(p.boxes[0].matrix, np.eye(4)):
                     raise ValueError(f"excitation '{p.name}': takes exactly one box, without a transform")
                 sc.add_plane_wave(p.name, p.params["exc_val"], p.params["prop_dir"]).add_box(p.boxes[0].start, p.boxes[0].stop)
-            elif p.kind == "Dump":
-                continue                       # no part of the scene: Run hands the SAR boxes to Simulation.add_sar_box
+            elif p.kind in ("Dump", "Probe"):
+                continue                       # no part of the scene: Run hands the SAR boxes to Simulation.add_sar_box, the probes to add_probe
             elif p.kind == "LumpedElement":
                 m = sc.add_lumped_element(p.name, p.params["ny"], R=p.params["R"], C=p.params["C"], L=p.params["L"],
                                           kind=p.params["LEtype"], caps=p.params["caps"])
@@ -1000,6 +1050,7 @@ class openEMS:
                 sc.add_lumped_port(port.number, port.R, port.start, port.stop, port.exc_ny, port.excite, port.priority)
             else:
                 port._to_scene(sc, metals)
+        sc.field_excitations.extend(self._field_excitations)
         return grid, sc
 
     @staticmethod
@@ -1048,10 +1099,13 @@ class openEMS:
             for name, d in self._field_dumps.items():
                 sim.add_field_box(name, d["start"] * grid_unit, d["stop"] * grid_unit, d["kind"], mode=d["mode"], freqs=d["freqs"],
                                   timesteps=d["timesteps"], sub_sampling=d["sub_sampling"])
+            for p in self._csx.properties:
+                if p.kind == "Probe":
+                    sim.add_probe(p.spec, grid_unit)
             return sim
         grid_unit = self._csx.GetGrid().GetDeltaUnit()
         self.sim = make(freqs)
-        self._nf2ff_snap, self._box_cache, self._sar, self._fields = False, {}, {}, {}
+        self._nf2ff_snap, self._box_cache, self._sar, self._fields, self._probes = False, {}, {}, {}, {}
         if self._nf2ff is not None and self.sim.nf2ff_mode == "dft" and self._nf2ff_freqs is None:
             self.sim = make(nf2ff_comb(self._f0))     # no time-domain record: a comb, CalcNF2FF snaps to it
             self._nf2ff_snap = True
@@ -1065,6 +1119,8 @@ class openEMS:
         self._u_i_all = self.sim.port_probe_series(allreduce)
         self._u_i = [(us[0], is_[0]) for us, is_ in self._u_i_all]      # (what Simulation.port_series gives: the first probe of each kind)
         self._allreduce = allreduce
+        self._probes = {name: self.sim.probe_series(name, allreduce) for name in self.sim.probes}
+        probe_report = [{**info, "file": info["name"], "samples": int(np.shape(self._probes[info["name"]]["val"])[-1])} for info in self.stats.probes or []]
         self._boxes = None
         if self._nf2ff is not None and self.sim.nf2ff_mode == "dft":
             self._boxes = self.sim.nf2ff_boxes(allreduce)
@@ -1107,7 +1163,13 @@ class openEMS:
                                              for q in vox.ports if q.info is not None]} if any(q.info is not None for q in vox.ports) else {}),
                                **({"sar": self.stats.sar} if self.stats.sar else {}),
                                **({"fields": field_report} if field_report else {}),
+                               **({"excitations": self.stats.excitations} if self.stats.excitations else {}),
+                               **({"probes": probe_report} if probe_report else {}),
                                **({"disc_materials": _disc_summary(sc, grid, vox)} if vox.cell_voxel is not None else {})}, fh)
+                # the stand-alone probes as upstream's ASCII probe files: the time column, then the value column(s)
+                for name, r in self._probes.items():
+                    np.savetxt(os.path.join(sim_path, name), np.c_[r["t"], np.atleast_2d(r["val"]).T], fmt="%.17g",
+                               header=f"probe '{name}' ({self.sim.probes[name].info['kind']}): t [s], value" + ("s x, y, z" if np.ndim(r["val"]) == 2 else ""))
                 # a plane wave: the excitation signal as upstream's two-column `et` file (time, value), which its RCS post-processing
                 # reads for the incident spectrum (P_rad of CalcNF2FF over the spectrum of et)
                 if self.sim.plane_wave is not None:
@@ -1145,6 +1207,15 @@ class openEMS:
             if port.number == number:
                 return p.info
         raise KeyError(number)
+
+    def GetProbe(self, name):
+        """{"t", "val"} of the probe `name` (CSX.AddProbe) of the last Run: val is 1-D, or [3][n] for the field types 2 and 3; t [s]
+        carries the half-step for the current types 1, 3 and 11."""
+        if self.sim is None or self.stats is None:
+            raise RuntimeError("Run() first")
+        if name not in self._probes:
+            raise KeyError(f"no probe '{name}' (defined: {sorted(self._probes)})")
+        return self._probes[name]
 
     def GetSAR(self, name, freq=None, normalise_to=None):
         """The result of the SAR dump `name` (AddDump, dump_type 20 / 21 / 22) at `freq` (default: its first frequency): a

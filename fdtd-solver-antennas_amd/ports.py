@@ -210,6 +210,51 @@ def _mode_items(grid: RectGrid, lo, hi, p: int, func, faces: bool):
     return out
 
 
+def mode_lists(grid: RectGrid, pec: np.ndarray, lo, hi, p: int, who: str, *, e_func=None, h_func=None, s_src=None, excite=0.0, s_prb=None,
+               d: int = 1, dtype=np.float32):
+    """The mode-matching lists over the cross-section lo..hi of the planes along axis p — what a waveguide port's source and probes
+    are, and a stand-alone mode-matching probe (probes.py): (source list on node plane s_src, V-probe on node plane s_prb, I-probe on
+    the two half-planes adjoining s_prb), each a Probe or None where its function or plane is not given.  e_func, h_func: (x, y) ->
+    (c_P, c_PP), metres from the box's minimum corner."""
+    src = v = i = None
+    if e_func is not None:
+        e_items = _mode_items(grid, lo, hi, p, e_func, False)
+        e_max = max(float(np.max(np.abs(it[5]))) for it in e_items)
+    if h_func is not None:
+        h_items = _mode_items(grid, lo, hi, p, h_func, True)
+        h_max = max(float(np.max(np.abs(it[5]))) for it in h_items)
+    if not ((e_func is None or (e_max > 0 and np.isfinite(e_max))) and (h_func is None or (h_max > 0 and np.isfinite(h_max)))):
+        raise ValueError(f"{who}: its mode functions are zero (or not finite) on every edge of the cross-section")
+    pec_flat = pec.reshape(3, -1)
+
+    def edges(s):
+        """(idx, comp, e, len, w) of the live edges of node plane s."""
+        parts = []
+        for c, C, L, cell_ax, line_ax, val, ln, dual in e_items:
+            idx = _flat(grid, p, s, cell_ax, C, line_ax, L)
+            keep = (np.abs(val) > ZERO_WEIGHT * e_max) & ~pec_flat[c][idx]
+            parts.append((idx[keep], np.full(int(keep.sum()), c, np.int8), val[keep], ln[keep], dual[keep]))
+        return [np.concatenate([q[t] for q in parts]) for t in range(5)]
+    if e_func is not None and s_src is not None:
+        idx, comp, e, ln, w = edges(s_src)
+        src = _probe(idx, comp, excite * e * ln, dtype)
+    if e_func is not None and s_prb is not None:
+        idx, comp, e, ln, w = edges(s_prb)
+        n_e = float(np.sum(e * e * ln * w))
+        if not n_e > 0:
+            raise ValueError(f"{who}: every edge of its measurement plane (node {s_prb} along {AX[p]}) is metal (PEC)")
+        v = _probe(idx, comp, e * w / np.sqrt(n_e), dtype)
+    if h_func is not None and s_prb is not None:
+        parts, n_h = [], 0.0
+        for c, C, L, cell_ax, line_ax, val, ln, dual in h_items:
+            keep = np.abs(val) > ZERO_WEIGHT * h_max
+            n_h += float(np.sum(val[keep] ** 2 * ln[keep] * dual[keep]))
+            for s in (s_prb - 1, s_prb):
+                parts.append((_flat(grid, p, s, cell_ax, C, line_ax, L)[keep], np.full(int(keep.sum()), c, np.int8), 0.5 * d * val[keep] * ln[keep]))
+        i = _probe(np.concatenate([q[0] for q in parts]), np.concatenate([q[1] for q in parts]), np.concatenate([q[2] for q in parts]) / np.sqrt(n_h), dtype)
+    return src, v, i
+
+
 def waveguide_lists(grid: RectGrid, pec: np.ndarray, port: WaveguidePort, u: float, dtype=np.float32) -> PortLists:
     """The lists of a waveguide port; `dtype`: float32 is what the engine takes, float64 keeps the weights as computed (the tests of
     the mode functions' orthogonality read those)."""
@@ -230,36 +275,10 @@ def waveguide_lists(grid: RectGrid, pec: np.ndarray, port: WaveguidePort, u: flo
         raise ValueError(f"{who}: start and stop snap to the same mesh line along {AX[p]} (node {s_src}): the port has no length on this mesh")
     if s_prb < 1 or s_prb > grid.shape[p] - 2:
         raise ValueError(f"{who}: its measurement plane (node {s_prb} along {AX[p]}) lies on a grid face: the current probe needs a half-plane on either side")
-    e_items = _mode_items(grid, lo, hi, p, port.e_func, False)
-    h_items = _mode_items(grid, lo, hi, p, port.h_func, True)
-    e_max = max(float(np.max(np.abs(it[5]))) for it in e_items)
-    h_max = max(float(np.max(np.abs(it[5]))) for it in h_items)
-    if not (e_max > 0 and h_max > 0 and np.isfinite(e_max) and np.isfinite(h_max)):
-        raise ValueError(f"{who}: its mode functions are zero (or not finite) on every edge of the cross-section")
-    pec_flat = pec.reshape(3, -1)
-
-    def edges(s):
-        """(idx, comp, e, len, w) of the live edges of node plane s."""
-        parts = []
-        for c, C, L, cell_ax, line_ax, val, ln, dual in e_items:
-            idx = _flat(grid, p, s, cell_ax, C, line_ax, L)
-            keep = (np.abs(val) > ZERO_WEIGHT * e_max) & ~pec_flat[c][idx]
-            parts.append((idx[keep], np.full(int(keep.sum()), c, np.int8), val[keep], ln[keep], dual[keep]))
-        return [np.concatenate([q[t] for q in parts]) for t in range(5)]
-    idx, comp, e, ln, w = edges(s_src)
-    src = _probe(idx, comp, port.excite * e * ln, dtype) if port.excite != 0 else _probe([], [], [], dtype)
-    idx, comp, e, ln, w = edges(s_prb)
-    n_e = float(np.sum(e * e * ln * w))
-    if not n_e > 0:
-        raise ValueError(f"{who}: every edge of its measurement plane (node {s_prb} along {AX[p]}) is metal (PEC)")
-    v = _probe(idx, comp, e * w / np.sqrt(n_e), dtype)
-    parts, n_h = [], 0.0
-    for c, C, L, cell_ax, line_ax, val, ln, dual in h_items:
-        keep = np.abs(val) > ZERO_WEIGHT * h_max
-        n_h += float(np.sum(val[keep] ** 2 * ln[keep] * dual[keep]))
-        for s in (s_prb - 1, s_prb):
-            parts.append((_flat(grid, p, s, cell_ax, C, line_ax, L)[keep], np.full(int(keep.sum()), c, np.int8), 0.5 * d * val[keep] * ln[keep]))
-    i = _probe(np.concatenate([q[0] for q in parts]), np.concatenate([q[1] for q in parts]), np.concatenate([q[2] for q in parts]) / np.sqrt(n_h), dtype)
+    src, v, i = mode_lists(grid, pec, lo, hi, p, who, e_func=port.e_func, h_func=port.h_func, s_src=s_src if port.excite != 0 else None,
+                           excite=port.excite, s_prb=s_prb, d=d, dtype=dtype)
+    if src is None:
+        src = _probe([], [], [], dtype)
     info = {"kind": "waveguide" if port.mode is None else "rect_waveguide", "mode": port.mode, "direction": AX[p], "sign": d,
             "lo": [int(q) for q in lo], "hi": [int(q) for q in hi], "source_plane": int(s_src), "probe_plane": int(s_prb),
             "source_edges": int(src.idx.size), "v_probe_edges": [int(v.idx.size)], "i_probe_faces": [int(i.idx.size)], "resistor_edges": 0}

@@ -34,6 +34,8 @@ from . import primitives as _prims
 from . import planewave as _planewave
 from . import discmaterial as _discmaterial
 from . import ports as _ports
+from . import field_excitation as _fexc
+from . import probes as _probes
 from .ports import Probe, WaveguidePort, MSLPort
 
 
@@ -200,6 +202,7 @@ class Scene:
     ports: List[LumpedPort] = field(default_factory=list)
     elements: List[LumpedElement] = field(default_factory=list)
     plane_waves: List[PlaneWaveSource] = field(default_factory=list)
+    field_excitations: List["_fexc.FieldExcitation"] = field(default_factory=list)
 
     def add_material(self, name, eps_r=1.0, kappa=0.0, mu_r=1.0, sigma_m=0.0, density=0.0) -> Material:
         """mu_r >= 1 and sigma_m >= 0 (magnetic loss sigma* [ohm/m]) make the material magnetic (magnetic.py); anisotropic
@@ -318,6 +321,17 @@ class Scene:
         return pw
 
 
+    def add_field_excitation(self, name, exc_type, exc_val, start, stop, weight=None, delay=0.0, priority=0) -> "_fexc.FieldExcitation":
+        """An E- or H-field excitation over a box, a plane, a line or a point (field_excitation.py): exc_type 0 soft E, 1 hard E, 2 soft
+        H, 3 hard H; exc_val the field vector [V/m or A/m]; start, stop in drawing units; weight None, one callable (x, y, z) or
+        three per-component callables or strings (coordinates in drawing units); delay [s]."""
+        if any(e.name == str(name) for e in self.field_excitations):
+            raise ValueError(f"field excitation '{name}' is defined twice")
+        ex = _fexc.make(name, exc_type, exc_val, start, stop, weight, delay, priority)
+        self.field_excitations.append(ex)
+        return ex
+
+
 @dataclass
 class PortOnGrid:
     """A port on the grid: optional resistor edges, one source list, a list of V-probes and a list of I-probes (ports.Probe).  A
@@ -369,6 +383,10 @@ class VoxelScene:
     # voxel body models (None: the scene has no disc material): per cell the linear index of its voxel in the map of the disc
     # material that owns it (cell_material says which), -1 where another material or the background does
     cell_voxel: Optional[np.ndarray] = None
+    # field excitations (field_excitation.FieldExcitation, in scene order) and the scene's drawing unit: Simulation, which knows dt,
+    # turns them into lists
+    field_excitations: Optional[list] = None
+    unit: float = 1e-3
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -448,6 +466,8 @@ def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = Fa
         lo = tuple(grid.snap(a, min(bx.start[a], bx.stop[a]) * u) for a in range(3))
         hi = tuple(grid.snap(a, max(bx.start[a], bx.stop[a]) * u) for a in range(3))
         vs.plane_wave = _planewave.PlaneWave(src.name, src.spec.e0, src.spec.direction, lo, hi)
+    if getattr(scene, "field_excitations", None):
+        vs.field_excitations, vs.unit = list(scene.field_excitations), float(scene.unit)
     return vs
 
 
@@ -654,34 +674,19 @@ def _port_on_grid(port: LumpedPort, grid: RectGrid, u: float) -> PortOnGrid:
                 s_idx.append(grid.flat(*pos))
                 # field of -excite/length across the port => unit port voltage for excite = 1
                 s_amp.append(-sign * port.excite * grid.d[d][q] / length)
-    # voltage: U = -dir * sum of edge voltages along the centre line
+    # voltage: U = -dir * sum of edge voltages along the centre line (probes.voltage_path: a stand-alone voltage probe walks the same way)
     c1 = grid.snap(a1, 0.5 * (port.start[a1] + port.stop[a1]) * u)
     c2 = grid.snap(a2, 0.5 * (port.start[a2] + port.stop[a2]) * u)
-    v_idx = []
-    for q in range(lo[d], hi[d]):
-        pos = [0, 0, 0]
-        pos[d], pos[a1], pos[a2] = q, c1, c2
-        v_idx.append(grid.flat(*pos))
-    # current: loop of dual edges around the port cross-section at the middle edge
+    p0, p1 = [0, 0, 0], [0, 0, 0]
+    p0[d], p1[d] = (lo[d], hi[d]) if sign > 0 else (hi[d], lo[d])
+    p0[a1] = p1[a1] = c1
+    p0[a2] = p1[a2] = c2
+    v_idx, _, v_sign = _probes.voltage_path(grid, p0, p1)
+    assert np.all(v_sign == sign)
+    # current: loop of dual edges around the port cross-section at the middle edge (probes.current_loop)
     qm = lo[d] + (n_ser - 1) // 2
-    acc = {}
-
-    def add(comp, pos, w):
-        key = (comp, tuple(pos))
-        acc[key] = acc.get(key, 0.0) + w
-
-    for p1 in range(lo[a1], hi[a1] + 1):
-        for p2 in range(lo[a2], hi[a2] + 1):
-            pos = [0, 0, 0]
-            pos[d], pos[a1], pos[a2] = qm, p1, p2
-            pm1 = list(pos); pm1[a1] -= 1
-            pm2 = list(pos); pm2[a2] -= 1
-            add(a2, pos, +1.0); add(a2, pm1, -1.0)
-            add(a1, pos, -1.0); add(a1, pm2, +1.0)
-    items = [(k, w) for k, w in acc.items() if abs(w) > 0]
-    i_idx = np.array([grid.flat(*k[1]) for k, _ in items], np.int64)
-    i_comp = np.array([k[0] for k, _ in items], np.int8)
-    i_w = np.array([sign * w for _, w in items], np.float32)
+    i_idx, i_comp, i_w = _probes.current_loop(grid, lo, hi, d, qm)
+    i_w = (sign * i_w).astype(np.float32)
     return PortOnGrid(
         port=port, lumped=lumped,
         src_idx=np.array(s_idx, np.int64), src_comp=np.full(len(s_idx), d, np.int8),

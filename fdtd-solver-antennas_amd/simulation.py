@@ -26,6 +26,8 @@ from . import sar as _sar
 from . import planewave as _planewave
 from . import fields as _fields
 from . import ports as _ports
+from . import field_excitation as _fexc
+from . import probes as _probes
 from .cpml import CPMLSpec, build_cpml
 from .excitation import gauss_pulse, dft_twiddles
 from .nf2ff import NF2FFBox, calc_nf2ff
@@ -157,6 +159,8 @@ class RunStats:
     conformal: Optional[dict] = None          # conformal PEC boundaries (conformal.py): faces per component, R, dt factor, faces clamped
     planewave: Optional[dict] = None          # plane-wave excitation (planewave.py): direction, e0, the box in nodes, entries per list
     fields: Optional[dict] = None             # field boxes (fields.py): per name the kind, mode, box and points and, once Simulation.field has run, the interpolation time and device yes/no
+    excitations: Optional[list] = None        # field excitations (field_excitation.py): per excitation its type, edges / faces, metal edges dropped, delay
+    probes: Optional[list] = None             # stand-alone probes (openems_api: CSX.AddProbe): per probe its type, entries and file
     sar: Optional[dict] = None                # SAR boxes (sar.py): per name the voxels, tissue voxels, mass, method and, once Simulation.sar has run, status counts and averaging time
 
 
@@ -334,6 +338,18 @@ class Simulation:
                                            f"{reach - len(self.signal)} more to cross its box, but NrTS = {self.nr_ts}: the run ends before the pulse has left the box")
                 import warnings
                 warnings.warn(self.excitation_warning, RuntimeWarning, stacklevel=2)
+        # field excitations: the E types are source lists (a hard one also zeroes its edges' operator entries: _overrides), the H types
+        # the two lists of fdtd_excite_set with the pulse at the half-steps; all checked against every other list of this run
+        self.excitations = getattr(vox, "field_excitations", None) or None
+        self.excite_lists, self.excite_h_args, self.signal_h = None, None, None
+        if self.excitations is not None:
+            from .scene import _tol
+            self.excite_lists = _fexc.lists(grid, self.excitations, vox.unit, self.dt, vox.pec, _tol(grid))
+            self._check_field_excitations(1)
+            if self.excite_lists.any_h():
+                self.signal_h = _fexc.signal_h(self.f0, self.fc, self.dt, len(self.signal))
+                self.excite_h_args = self.excite_lists.h_args(self.signal_h)
+        self.probes, self._probe_ids = {}, {}          # stand-alone probes (probes.py): name -> probes.ProbeLists, -> device probe ids
         self.engine: Optional[Engine] = None
         self.lib = None
         self.external_transport = None     # distributed.SlabComm when halos travel through the host
@@ -356,6 +372,59 @@ class Simulation:
                                    elements=self.elements, debye=self.debye, lorentz=self.lorentz, conformal=self.conformal, ports=v.ports,
                                    dft_boxes=reqs, sar_boxes=self.sar_boxes, field_boxes=self.field_boxes)
 
+    def add_probe(self, spec: "_probes.ProbeSpec", unit: float = 1e-3) -> "_probes.ProbeLists":
+        """A stand-alone probe (before build): probes.ProbeSpec with its box in drawing units of `unit` metres.  One or three device
+        probes; a context takes probes.MAX_PROBES, the ports' included."""
+        from .scene import _tol
+        if self.engine is not None:
+            raise ValueError(f"probe '{spec.name}': add_probe comes before build")
+        if spec.name in self.probes:
+            raise ValueError(f"probe '{spec.name}' is defined twice")
+        pl = _probes.lists(self.grid, self.vox.pec, spec, unit, _tol(self.grid))
+        used = sum(len(p.v_probes) + len(p.i_probes) for p in self.vox.ports) + sum(len(q.lists) for q in self.probes.values())
+        if used + len(pl.lists) > _probes.MAX_PROBES:
+            raise ValueError(f"probe '{spec.name}': its {len(pl.lists)} device probe(s) would make {used + len(pl.lists)} probes, a context takes "
+                             f"{_probes.MAX_PROBES} (FDTD_MAX_PROBES), the ports' {sum(len(p.v_probes) + len(p.i_probes) for p in self.vox.ports)} included")
+        self.probes[spec.name] = pl
+        return pl
+
+    def probe_series(self, name, allreduce=None) -> dict:
+        """{"t", "val"} of probe `name` after the run: val 1-D, or [3][n] for the field types; t carries the half-step for the
+        current types."""
+        if name not in self.probes:
+            raise KeyError(f"no probe '{name}' (defined: {sorted(self.probes)})")
+        if self.engine is None or name not in self._probe_ids:
+            raise RuntimeError("probe series: build and run first")
+        pl = self.probes[name]
+        get = (lambda q: self.engine.get_probe(q)) if allreduce is None else (lambda q: allreduce(self.engine.get_probe(q)))
+        val = [get(q) / sc for q, sc in zip(self._probe_ids[name], pl.scale)]
+        t = (np.arange(val[0].size) + (0.5 if pl.kind == KIND_I else 0.0)) * self.dt
+        return {"t": t, "val": val[0] if len(val) == 1 else np.stack(val)}
+
+    def _check_field_excitations(self, world: int):
+        """field_excitation.check_placement against the scene as this simulation holds it."""
+        pw_elems = None
+        if self.plane_wave is not None:
+            g = self.grid
+            pw_elems = tuple(np.unique(np.array([g.flat(i, j, k) * 3 + n for n, i, j, k, *_ in _planewave.terms(g, self.plane_wave, phase)], np.int64))
+                             for phase in (0, 1))
+        _fexc.check_placement(self.grid, self.excitations, self.excite_lists, cpml_cells=self.bc.face_cells(),
+                              magnetic_classes=None if self.magnetic is None else self.magnetic.full_classes(self.grid.shape[::-1]),
+                              conformal=self.conformal, plane_wave_elems=pw_elems, ports=self.vox.ports, elements=self.elements, sheets=self.sheets,
+                              debye=self.debye, lorentz=self.lorentz, world=world)
+
+    def _overrides(self, dtype=np.float32):
+        """(edge, comp, vv, m) of the edges whose operator entries the host fixes: the lumped conductances and capacitances, and the
+        hard E edges of the field excitations with vv = m = 0 (their voltage is the source's alone)."""
+        v = self.vox
+        edge, comp, vv, m = lumped_overrides(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, dtype=dtype)
+        if self.excite_lists is not None and self.excite_lists.hard_e[0].size:
+            h = self.excite_lists.hard_e
+            key, first = np.unique(h[0] * 3 + h[1], return_index=True)
+            z = np.zeros(first.size, dtype)
+            edge, comp, vv, m = np.concatenate([edge, h[0][first]]), np.concatenate([comp, h[1][first]]), np.concatenate([vv, z]), np.concatenate([m, z])
+        return edge, comp, vv, m
+
     @property
     def op(self) -> ECOperator:
         """The operator in its host (numpy) formulation — built on first use; the default product path never asks."""
@@ -363,6 +432,10 @@ class Simulation:
             v = self.vox
             walls = {} if self.pmc is None else {"pmc": self.pmc}
             self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, **walls)
+            if self.excite_lists is not None and self.excite_lists.hard_e[0].size:      # hard E edges: vv = m = 0 (as _overrides)
+                h = self.excite_lists.hard_e
+                self._op.vv.reshape(3, -1)[h[1].astype(np.int64), h[0]] = 0.0
+                self._op.m.reshape(3, -1)[h[1].astype(np.int64), h[0]] = 0.0
         return self._op
 
     # ---------------------------------------------------------------------------------------------
@@ -402,13 +475,15 @@ class Simulation:
             raise _capi.FdtdError("SAR boxes need a single slab (world = 1): a decomposed run with SAR boxes is not supported")
         if self.field_boxes and world > 1:
             raise _capi.FdtdError("field boxes need a single slab (world = 1): a decomposed run with field boxes is not supported")
+        if self.excitations is not None and world > 1:
+            self._check_field_excitations(world)      # (an H-type excitation on a decomposed run: ValueError naming it)
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
         if self.device_operator:
             v = self.vox
             emet, hmet = pack_metric_tables(*metric_lists(g, self.dt, pmc=self.pmc), g, k0, nk)
             e.build_operator(g.d, v.eps_r, self.kappa_cells, v.pec, EPS0,
-                             lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped), emet, hmet,
+                             self._overrides(), emet, hmet,
                              prefer_classes=self.use_classes)
             self.operator_form = "raw" if e.operator_form()[0] == "raw" else "classes"
         else:
@@ -436,6 +511,8 @@ class Simulation:
             op = e.get_operator()
             self.planewave_tables = _planewave.tables(g, self.plane_wave, self.dt, op[1], op[3], self.signal2)
             e.set_planewave(*self.planewave_tables.args())
+        if self.excite_h_args is not None:
+            e.set_excite(*self.excite_h_args)
         if self.cpml is not None:
             e.set_cpml(*self.cpml.for_slab(k0, nk))
         if self.mur_enable.any():
@@ -451,6 +528,11 @@ class Simulation:
             iids = [e.add_probe(KIND_I, q.idx, q.comp, q.w) for q in p.i_probes]
             self._port_probe_ids.append((uids[0], iids[0]))
             self._port_probe_lists.append((uids, iids))
+        self._probe_ids = {name: [e.add_probe(pl.kind, q.idx, q.comp, q.w) for q in pl.lists] for name, pl in self.probes.items()}
+        if self.excite_lists is not None:             # the E types: soft list, then hard list (their edges hold vv = vi = 0)
+            for l in (self.excite_lists.soft_e, self.excite_lists.hard_e):
+                if l[0].size:
+                    e.add_source(l[0], l[1], l[2], l[3])
         if self.nf2ff_box is not None or self.sar_boxes or self.field_boxes:
             if self.nf2ff_mode == "record":
                 try:
@@ -999,6 +1081,8 @@ class Simulation:
         stats.magnetic = self.magnetic_info()
         stats.conformal = self.conformal_info()
         stats.planewave = self.planewave_info()
+        stats.excitations = None if self.excite_lists is None else self.excite_lists.info
+        stats.probes = [pl.info for pl in self.probes.values()] or None
         stats.fields = self._field_report if self.field_boxes else None  # Simulation.field fills in the seconds and device yes/no
         stats.sar = self._sar_report if self.sar_boxes else None      # Simulation.sar fills in the status counts and the averaging time
         stats.schedule = e.schedule_info()
