@@ -7,12 +7,16 @@ of 12 x 10 x 9 nodes with PEC faces (and again with a Mur face at x+, far from t
   edge B  x-directed at node (6, 6, 3): the same inside a Lorentz box;
           each under a V-probe of its own and inside a V-DFT box;
   face F  y-normal at node (6, 5, 4) (edge A is one of its four): magnetic class 1, a listed conformal face and on the plane wave's
-          H list, under an I-probe and inside an I-DFT box;
-  and a few more elements per list that overlap in pairs or not at all.
+          H list, under an I-probe and inside an I-DFT box; it also carries two soft entries of fdtd_excite_set, 1 and 1e-7 of a common
+          scale, whose order shows in float32;
+  face G  y-normal at node (7, 5, 4): magnetic class 2, on the plane wave's H list, and a hard entry of fdtd_excite_set: whatever the
+          other lists did, its current is amp * sigH[n - delay], under an I-probe and inside an I-DFT box of its own;
+  and a few more elements per list that overlap in pairs or not at all (include/fdtd_hip_excite.h leaves the placement to the caller:
+  the C ABI accepts an excited face that is a magnetic, conformal or plane-wave face, and the launch order decides the bits there).
 
 The reference is restatement.Restatement with these raw tables: the headers' statement lists in the headers' order on the oracle's
 half-steps: Debye, Lorentz, sheets, elements, plane wave (E list) between the E phase and the H update, magnetic, conformal, plane wave
-(H list) behind the H update.  V-probes and V-DFT boxes read in front of every E-side correction (the oracle's own E phase samples
+(H list), H-field excitations behind the H update.  V-probes and V-DFT boxes read in front of every E-side correction (the oracle's own E phase samples
 them there), I-probes and I-DFT boxes behind every H-side one (kept here: the oracle samples I inside its H half-step)."""
 import numpy as np
 
@@ -22,12 +26,13 @@ from restatement import E_SIDE, ORDER, Restatement
 N = (12, 10, 9)
 STEPS, CALLS, SEED = 60, (25, 35), 11
 EVERY, FREQS = 5, np.array([8e9, 11e9])
-NAMES = ORDER
-A, B, F = (2, 6, 5, 4), (0, 6, 6, 3), (1, 6, 5, 4)
+NAMES = ORDER[:-1] + ("excite_soft", "excite_hard")                   # what `dropped` can take out: the excitations' two lists singly
+A, B, F, G = (2, 6, 5, 4), (0, 6, 6, 3), (1, 6, 5, 4), (1, 7, 5, 4)
 V_PROBES = [([A], [1.0]), ([B], [-0.5])]
-I_PROBES = [([F], [1.0]), ([F, (2, 6, 5, 4)], [2.0, -1.0])]
+I_PROBES = [([F], [1.0]), ([F, (2, 6, 5, 4)], [2.0, -1.0]), ([G], [1.0])]
 V_BOXES = [(2, (5, 4, 3), (7, 6, 5)), (0, (5, 5, 2), (7, 7, 4))]      # (component, lo, hi) in nodes, inclusive: over A / over B
-I_BOXES = [(1, (5, 4, 3), (7, 6, 5))]                                 # over F
+I_BOXES = [(1, (5, 4, 3), (7, 6, 5)), (1, (7, 4, 4), (7, 6, 4))]      # over F (and G) / over G alone
+NSIG_H, HARD_G = 40, (2.5, 2)                                         # sigH's samples; (amplitude, delay) of the hard entry on G
 
 
 def flat(i, j, k):
@@ -58,7 +63,7 @@ def _box(rng, lo, hi, draw):
 
 
 def hand_tables(op, dt, seed=5):
-    """The argument tuples of the seven setters, keyed by NAMES' sets ("pw" holds both lists).  op: Engine.get_operator() of the scene."""
+    """The argument tuples of the eight setters, keyed by ORDER's sets ("pw" holds both lists, "excite" both of its).  op: Engine.get_operator() of the scene."""
     disp, lor, lum, pwm = pkg("dispersion"), pkg("lorentz"), pkg("lumped"), pkg("planewave")
     rng = np.random.default_rng(seed)
     vi, iv = op[1], op[3]
@@ -95,6 +100,7 @@ def hand_tables(op, dt, seed=5):
     mlo, mhi = (5, 4, 3), (8, 7, 6)
     cy = _box(rng, mlo, mhi, lambda r, s: r.integers(0, 3, s).astype(np.uint8))
     cy[F[3] - mlo[2], F[2] - mlo[1], F[1] - mlo[0]] = 1
+    cy[G[3] - mlo[2], G[2] - mlo[1], G[1] - mlo[0]] = 2
     xlo, xhi = (4, 4, 4), (6, 6, 6)
     cx = _box(rng, xlo, xhi, lambda r, s: r.integers(0, 3, s).astype(np.uint8))
     T["magnetic"] = (np.array([0.97, 0.9], np.float32), np.array([0.6, 0.85], np.float32), [xlo, mlo, empty[0]], [xhi, mhi, empty[1]], [cx, cy, z8])
@@ -113,6 +119,15 @@ def hand_tables(op, dt, seed=5):
         return i_, c_, coef, rng.integers(0, 41, (n, 2)).astype(np.int32), w_
     T["pw"] = pwm.Tables(hand([A, B, (1, 5, 5, 5), (2, 7, 5, 4), (0, 5, 6, 3)]), hand([F, (2, 6, 5, 4), (0, 5, 5, 5), (1, 7, 5, 4)]),
                          pwm.signal2(10e9, 4e9, 18e-12, 40))
+    # the H-field excitations (a generator of their own: the tables above are what they were): hard on G and on a face no other list has;
+    # soft twice on F — in float32 (I + t) + 1e-7 t is not (I + 1e-7 t) + t — and once on two other faces, one of them conformal
+    rx = np.random.default_rng(seed + 1000)
+    hard, soft = [G, (2, 3, 6, 5)], [F, (0, 6, 4, 3), F, (2, 4, 3, 6)]
+    hi_, hc_ = _list(hard)
+    si_, sc_ = _list(soft)
+    T["excite"] = (hi_, hc_, np.array([HARD_G[0], -0.8], np.float32), np.array([HARD_G[1], 0], np.int32),
+                   si_, sc_, np.array([0.9, 0.4, 0.9e-7, -0.6], np.float32), np.array([0, 3, 0, 30], np.int32),
+                   (1e-3 * rx.standard_normal(NSIG_H)).astype(np.float32))
     return T
 
 
@@ -120,6 +135,9 @@ def dropped(T, name):
     """The tables without one correction (the plane wave's two lists count singly)."""
     pwm = pkg("planewave")
     out = {k: v for k, v in T.items() if k != name}
+    if name in ("excite_soft", "excite_hard"):
+        x = T["excite"]
+        out["excite"] = tuple(a[:0] for a in x[:4]) + x[4:] if name == "excite_hard" else x[:4] + tuple(a[:0] for a in x[4:8]) + x[8:]
     if name in ("pw_e", "pw_h"):
         none = tuple(a[:0] for a in T["pw"].E)
         out["pw"] = pwm.Tables(none if name == "pw_e" else T["pw"].E, none if name == "pw_h" else T["pw"].H, T["pw"].sig2)
@@ -134,6 +152,8 @@ def set_tables(e, T):
             fn(*T[name])
     if "pw" in T:
         e.set_planewave(*T["pw"].args())
+    if "excite" in T:
+        e.set_excite(*T["excite"])
 
 
 def twiddles(dt):

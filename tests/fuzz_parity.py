@@ -15,8 +15,8 @@ the energy to 1e-12, the NF2FF face spectra to 1e-6 of their largest entry (floa
     python tests/fuzz_parity.py --media ...     # scenes with Debye media and / or conducting sheets (k_debye, k_sheet and their place in the step
                                                 # loop) against the oracle's half-steps plus the numpy restatement of the two corrections
                                                 # (draw_media_case / run_media_case below); tests/test_media_fuzz_cpu.py guards what the draw covers
-    python tests/fuzz_parity.py --corrections ...   # scenes with at least three of the seven corrections of the step loop, often all of them (Debye and
-                                                # Lorentz media, sheets, elements, magnetic faces, conformal faces, a plane wave), against
+    python tests/fuzz_parity.py --corrections ...   # scenes with at least three of the eight corrections of the step loop, often all of them (Debye and
+                                                # Lorentz media, sheets, elements, magnetic faces, conformal faces, a plane wave, H-field excitations), against
                                                 # tests/restatement.py (draw_corrections_case / run_corrections_case); tests/test_corrections_fuzz_cpu.py guards the draw
 
 Lives under tests/ because it loads the oracle (test infrastructure); tests/test_round3_gpu.py::test_randomised_cases_equal_the_oracle
@@ -511,9 +511,10 @@ def run_media_case(case, hip, oracle):
     return problems, info
 
 
-# ---- all seven corrections in one context ---------------------------------------------------------------------------------------------
+# ---- all eight corrections in one context ---------------------------------------------------------------------------------------------
 CORRECTIONS_BATCH = (24, 2)   # (cases, seed) of the batch in the -m gpu suite (tests/test_corrections_fuzz_gpu.py); test_corrections_fuzz_cpu.py guards its coverage
-CORRECTION_NAMES = ("debye", "lorentz", "sheets", "elements", "magnetic", "conformal", "planewave")      # (the order the cases are drawn in)
+DRAWN_NAMES = ("debye", "lorentz", "sheets", "elements", "magnetic", "conformal", "planewave")      # (the order the cases are drawn in)
+CORRECTION_NAMES = DRAWN_NAMES + ("excite",)      # H-field excitations: drawn last, from a generator of their own (draw_excitations)
 TWO_PI = 2 * np.pi
 
 
@@ -535,19 +536,74 @@ def _lorentz_poles(rng, K):
     return wp, w0, gamma
 
 
-def draw_corrections_case(rng):
-    """One scene with at least three of the seven corrections of the step loop (often all of them) as a plain dict: Debye media, Lorentz
-    / Drude media, conducting sheets, lumped elements, magnetic materials, a curved metal with conformal faces, a plane wave.  All
+def draw_excitations(case, g):
+    """H-field excitations for a drawn case, from the generator `g` alone: one to three hard faces, five to nine soft faces of which the
+    first is listed twice (two soft entries on one face), all three components, delays of 0 timesteps, inside the run and past its end
+    (such an entry never reads the table: a hard face is then held at zero throughout).  Each is a point box on a face that exists, is
+    no grid face, lies in no CPML layer and is no magnetic, conformal or plane-wave face — what field_excitation.check_placement demands,
+    asked of the scene without excitations — and that no NF2FF box samples: the reference's NF2FF sums are the oracle's own, taken
+    inside its H half-step in front of every H-side correction (boxes and recorder faces ACROSS excited faces: the observer tests of
+    test_excite_gpu.py, whose reference samples behind them).  None where that scene is refused or has no such faces."""
+    try:
+        sim = corrections_case_sim(dict(case, excite=None))
+    except ValueError:
+        return None
+    nx, ny, nz = n = case["shape"]
+    ok = np.ones((3, nz, ny, nx), bool)
+    cells = sim.bc.face_cells()
+    for c in range(3):
+        for a in range(3):      # along a: nodes lo <= p < hi (a == c: off the grid faces; else a cell along a; both: outside the layers)
+            lo, hi = max(cells[2 * a], 1 if a == c else 0), n[a] - 1 - cells[2 * a + 1]
+            p = np.arange(n[a])
+            ok[c] &= ((p >= lo) & (p < hi)).reshape([-1 if 2 - a == d else 1 for d in range(3)])
+    if sim.magnetic is not None:
+        ok &= sim.magnetic.full_classes((nz, ny, nx)) == 0
+    flat = ok.reshape(3, -1)
+    if sim.conformal is not None:
+        flat[np.asarray(sim.conformal.comp, np.int64), np.asarray(sim.conformal.idx, np.int64)] = False
+    if sim.plane_wave is not None:
+        pwm = _mod("planewave")
+        for f, i, j, k, *_ in pwm.terms(sim.grid, sim.plane_wave, 1):
+            ok[f, k, j, i] = False
+    for r in ([] if sim.nf2ff_box is None else sim.nf2ff_box.requests):
+        if r.kind == 1:
+            ok[r.comp, r.lo[2]:r.hi[2] + 1, r.lo[1]:r.hi[1] + 1, r.lo[0]:r.hi[0] + 1] = False
+    nh, ns = int(g.integers(1, 4)), int(g.integers(5, 10))
+    total = sum(case["calls"])
+    kinds = {"0": 0, "inside": int(g.integers(1, max(2, total // 2))), "past": total + 8 + int(g.integers(0, 5))}
+    out = []
+    for q in range(nh + ns):
+        c = q % 3 if q >= nh else int(g.integers(0, 3))
+        cand = np.argwhere(ok[c])
+        if not len(cand):
+            return None
+        k, j, i = (int(v) for v in cand[int(g.integers(0, len(cand)))])
+        ok[c, k, j, i] = False
+        how = ("0", "inside", "past")[(q - nh) % 3] if q >= nh else str(g.choice(["0", "inside", "past"]))
+        amp = round(float(g.uniform(0.2, 1.0)) * float(g.choice([-1.0, 1.0])), 3)
+        out.append({"type": 3 if q < nh else 2, "comp": c, "node": [i, j, k], "val": amp, "delay_steps": kinds[how], "delay": kinds[how] * float(sim.dt)})
+    first = out[nh]                  # the repeated face: its second entry 1e-7 of the first, so that the list order shows in float32
+    out.append(dict(first, val=round(-1e-7 * first["val"], 10)))
+    out.append(dict(first, val=-first["val"]))
+    return out
+
+
+def draw_corrections_case(rng, excite=None):
+    """One scene with at least three of the corrections of the step loop (often all of them) as a plain dict: Debye media, Lorentz
+    / Drude media, conducting sheets, lumped elements, magnetic materials, a curved metal with conformal faces, a plane wave — drawn from
+    `rng` — and H-field excitations: `excite` = (seed, case number) draws them (draw_excitations) from a generator of its own seeded
+    with that pair, into every case that holds the seven others and every second of the rest; `rng` is not touched by it, so every other
+    quantity of every case is what it is without.  All
     positions are node indices; a box owns the cells [lo, hi).  The media stand behind each other along y or z (the longer of the two
     inside the layers), the curved metal beside them along x, the plane wave's box one cell outside everything and the NF2FF box outside
     that.  What each item is there for: the table in docs/HISTORY.md (randomised corrections)."""
     touchy = False
     if rng.random() < 0.3:
-        want = dict.fromkeys(CORRECTION_NAMES, True)
+        want = dict.fromkeys(DRAWN_NAMES, True)
     else:
         touchy = bool(rng.random() < 0.4)      # media up to the grid faces along x: no plane wave, no NF2FF box, no CPML there
         while True:
-            want = {k: bool(rng.random() < 0.55) for k in CORRECTION_NAMES}
+            want = {k: bool(rng.random() < 0.55) for k in DRAWN_NAMES}
             if touchy:
                 want["planewave"] = False
             if sum(want.values()) >= 3:
@@ -811,10 +867,23 @@ def draw_corrections_case(rng):
     if wave is not None and sum(calls) < 40:      # (the pulse's first timesteps lie below float32 rounding of the seeded fields)
         calls[-1] += 40 - sum(calls)
     sets = [(int(rng.integers(0, 2)), int(rng.integers(0, 3)), int(rng.integers(1, 1 << 30))) if rng.random() < 0.4 else None for _ in calls[1:]]
-    return {"shape": tuple(n), "graded": int(rng.integers(1, 1 << 20)) if rng.random() < 0.6 else 0, "kinds": kinds, "cells": cells,
+    case = {"shape": tuple(n), "graded": int(rng.integers(1, 1 << 20)) if rng.random() < 0.6 else 0, "kinds": kinds, "cells": cells,
             "classes": bool(rng.random() < 0.7), "debye": debye, "lorentz": lorentz, "sheets": sheets, "elements": elements, "magnetic": magnetic,
             "metal": metal, "planewave": wave, "port": port, "nf2ff": nf, "drive": str(rng.choice(["auto", "direct", "half"])), "env": env,
-            "calls": calls, "sets": sets, "seed": int(rng.integers(1, 1 << 30))}
+            "calls": calls, "sets": sets, "seed": int(rng.integers(1, 1 << 30)), "excite": None}
+    if excite is not None:
+        g = np.random.default_rng([int(excite[0]), int(excite[1])])
+        everything = bool(debye and lorentz and sheets and elements and magnetic and metal is not None and wave is not None)
+        if everything or g.random() < 0.5:
+            case["excite"] = draw_excitations(case, g)
+    return case
+
+
+def corrections_batch(ncases=None, seed=None):
+    """The drawn cases of a batch (default: CORRECTIONS_BATCH), excitations included."""
+    ncases, seed = CORRECTIONS_BATCH if ncases is None else (ncases, seed)
+    rng = np.random.default_rng(seed)
+    return [draw_corrections_case(rng, excite=(seed, q)) for q in range(ncases)]
 
 
 def corrections_case_sim(case):
@@ -862,6 +931,12 @@ def corrections_case_sim(case):
     pw = case["planewave"]
     if pw is not None:
         s.add_plane_wave("pw", pw["e0"], pw["dir"]).add_box(at(pw["lo"]), at(pw["hi"]))
+    for q, x in enumerate(case.get("excite") or []):      # H-field excitations: point boxes at the face centres
+        c, p = x["comp"], x["node"]
+        centre = [1e3 * (float(lines[a][p[a]]) if a == c else 0.5 * float(lines[a][p[a]] + lines[a][p[a] + 1])) for a in range(3)]
+        val = [0.0, 0.0, 0.0]
+        val[c] = x["val"]
+        s.add_field_excitation(f"x{q}", x["type"], val, centre, centre, delay=x["delay"])
     vox = sc.voxelize(s, grid, conformal=mt is not None)
     total = sum(case["calls"])
     return simm.Simulation(grid, vox, f0=MEDIA_F0, fc=MEDIA_FC, boundary=case["kinds"], cpml_cells=case["cells"], nr_ts=total + 8,
@@ -870,15 +945,16 @@ def corrections_case_sim(case):
 
 
 def corrections_present(sim):
-    """Which of the seven corrections the engine steps for this simulation."""
+    """Which of the eight corrections the engine steps for this simulation."""
     have = (sim.debye is not None, sim.lorentz is not None, sim.sheets is not None, sim.element_stepped.size > 0, sim.magnetic is not None,
-            sim.conformal is not None, sim.plane_wave is not None)
+            sim.conformal is not None, sim.plane_wave is not None, sim.excite_h_args is not None)
     return {name for name, h in zip(CORRECTION_NAMES, have) if h}
 
 
 def watch_plane_wave(ref):
-    """Hooks on a Restatement: did the plane wave's two lists change V / I on their elements?  The returned dict answers per list."""
-    changed, held = {name: False for name in ("pw_e", "pw_h") if name in ref.parts}, {}
+    """Hooks on a Restatement: did the plane wave's two lists change V / I on their elements, and the H-field excitations I on their
+    faces?  The returned dict answers per list ("pw_e", "pw_h", "excite")."""
+    changed, held = {name: False for name in ("pw_e", "pw_h", "excite") if name in ref.parts}, {}
 
     def before(name, kind, F):
         if name in changed and not changed[name]:
@@ -921,6 +997,14 @@ def corrections_reference_problems(r):
         problems.append("reference: i_prev of a listed conformal face is zero")
     if r.pw_e is not None and not all(r.pw_changed.values()):
         problems.append(f"reference: the plane wave's lists changed nothing (V: {r.pw_changed['pw_e']}, I: {r.pw_changed['pw_h']})")
+    if r.excite is not None:
+        if not r.pw_changed["excite"]:
+            problems.append("reference: the H-field excitations changed no current")
+        l = r.excite.lists
+        held = (l.hard[3].astype(np.int64) >= r.nstep) if r.nstep else np.zeros(0, bool)      # hard faces whose entry never read the table: amp * 0.0f
+        for g, c in zip(l.hard[0][held], l.hard[1][held]):
+            if r.e.get_field(1, int(c)).reshape(-1)[g] != 0:
+                problems.append(f"reference: the hard face at node {int(g)}, component {int(c)} is not held at zero")
     return problems
 
 
@@ -1051,7 +1135,7 @@ def run_batch(ncases, seed, hip, oracle, only=None, log=print, slabs=False, mur=
     rng = np.random.default_rng(seed)
     failed = []
     for n in range(ncases):
-        case = draw_corrections_case(rng) if corrections else draw_media_case(rng) if media else draw_slab_case(rng) if slabs else draw_case(rng, mur)
+        case = draw_corrections_case(rng, excite=(seed, n)) if corrections else draw_media_case(rng) if media else draw_slab_case(rng) if slabs else draw_case(rng, mur)
         if only is not None and n != only:
             continue
         t0 = time.perf_counter()
@@ -1088,7 +1172,7 @@ def main():
     ap.add_argument("--slabs", action="store_true", help="decomposed runs: 2 ... 6 P2P slabs in one process against one slab on the oracle")
     ap.add_argument("--mur", action="store_true", help="every case with Mur faces, mostly on the two / three launches per timestep")
     ap.add_argument("--media", action="store_true", help="scenes with Debye media and / or conducting sheets against the numpy restatement of their corrections")
-    ap.add_argument("--corrections", action="store_true", help="scenes with at least three of the seven corrections of the step loop (often all) in one context against tests/restatement.py")
+    ap.add_argument("--corrections", action="store_true", help="scenes with at least three of the eight corrections of the step loop (often all) in one context against tests/restatement.py")
     args = ap.parse_args()
     hip, oracle = load_libs()
     failed = run_batch(args.cases, args.seed, hip, oracle, args.only, log=lambda s: print(s, flush=True), slabs=args.slabs, mur=args.mur, media=args.media,

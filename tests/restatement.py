@@ -1,7 +1,8 @@
-"""The reference for the seven step-loop corrections: Debye media, Lorentz / Drude media, conducting sheets, lumped elements, magnetic
-faces, conformal faces and the plane wave.  oracle/fdtd_oracle.c has none of them, so the parity tests compare the HIP library, bit for
-bit, with the oracle's half-steps and the float32 statement lists of dispersion.py, lorentz.py, sheet.py, lumped.py, magnetic.py,
-conformal.py and planewave.py applied in numpy between them, in the order include/fdtd_hip_*.h give.  That order is ORDER, stated here
+"""The reference for the eight step-loop corrections: Debye media, Lorentz / Drude media, conducting sheets, lumped elements, magnetic
+faces, conformal faces, the plane wave and the H-field excitations.  oracle/fdtd_oracle.c has none of them, so the parity tests compare
+the HIP library, bit for bit, with the oracle's half-steps and the float32 statement lists of dispersion.py, lorentz.py, sheet.py,
+lumped.py, magnetic.py, conformal.py, planewave.py and excite_cases.HLists (the numpy statement of include/fdtd_hip_excite.h) applied in
+numpy between them, in the order include/fdtd_hip_*.h give.  That order is ORDER, stated here
 once; Restatement.step reads top to bottom as the headers do:
 
     half_step(E)        (the oracle samples its V-probes and V boxes here, in front of every E-side correction)
@@ -10,7 +11,7 @@ once; Restatement.step reads top to bottom as the headers do:
     write V back
     half_step(H)
     read I
-    magnetic -> conformal (reads the V just written) -> plane wave (face list)
+    magnetic -> conformal (reads the V just written) -> plane wave (face list) -> H-field excitations
     write I back; sample the kept I-probes
 
 It holds for any tables the setters of the C ABI accept, overlapping ones included (corrections_overlap_cases.py)."""
@@ -22,20 +23,22 @@ import numpy as np
 from conftest import pkg
 from helpers import seeded_fields
 
-ORDER = ("debye", "lorentz", "sheets", "elements", "pw_e", "magnetic", "conformal", "pw_h")
+ORDER = ("debye", "lorentz", "sheets", "elements", "pw_e", "magnetic", "conformal", "pw_h", "excite")
 E_SIDE, H_SIDE = ORDER[:5], ORDER[5:]
 # what a Simulation holds of each correction, and the _capi question whether a library can step it
 HELD = {"debye": lambda s: s.debye is not None, "lorentz": lambda s: s.lorentz is not None, "sheets": lambda s: s.sheets is not None,
         "elements": lambda s: s.element_stepped.size > 0, "magnetic": lambda s: s.magnetic is not None,
-        "conformal": lambda s: s.conformal is not None, "pw": lambda s: s.plane_wave is not None}
+        "conformal": lambda s: s.conformal is not None, "pw": lambda s: s.plane_wave is not None,
+        "excite": lambda s: s.excite_h_args is not None}
 HAS = {"debye": "has_dispersion", "lorentz": "has_lorentz", "sheets": "has_sheets", "elements": "has_lumped", "magnetic": "has_magnetic",
-       "conformal": "has_conformal", "pw": "has_planewave"}
+       "conformal": "has_conformal", "pw": "has_planewave", "excite": "has_excite"}
 
 
 @contextlib.contextmanager
 def corrections_hidden(sim):
-    """`sim` without its seven corrections, so that sim.build makes the folded / base operator alone: the oracle has no setter for any."""
-    saved = {k: getattr(sim, k) for k in ("debye", "lorentz", "sheets", "element_stepped", "magnetic", "conformal", "plane_wave")}
+    """`sim` without its eight corrections, so that sim.build makes the folded / base operator alone: the oracle has no setter for any.
+    (The E side of a field excitation is source lists and operator overrides, which the oracle has: it stays.)"""
+    saved = {k: getattr(sim, k) for k in ("debye", "lorentz", "sheets", "element_stepped", "magnetic", "conformal", "plane_wave", "excite_h_args")}
     for k in saved:
         setattr(sim, k, np.zeros(0, np.int64) if k == "element_stepped" else None)
     try:
@@ -206,19 +209,32 @@ class PlaneWaveList:
         pkg("planewave").apply(F, self.tables, r.n, self.kind)
 
 
+class Excite:
+    """The nine arguments of fdtd_excite_set (the hard list, the soft list, sigH) at timestep r.n; .lists is the excite_cases.HLists whose
+    apply is the numpy statement of include/fdtd_hip_excite.h.  No state."""
+
+    def __init__(self, r, *args):
+        from excite_cases import HLists
+        assert len(args) == 9
+        self.lists = HLists(args[0:4], args[4:8], args[8])
+
+    def apply(self, F, r):
+        self.lists.apply(F, r.n)
+
+
 # ---- the stepper ----------------------------------------------------------------------------------------------------------------------
 class Restatement:
     """An engine of `lib` (the oracle: no correction entry points needed) built from `sim` with its corrections hidden and stepped by
     half-steps, with the corrections applied in numpy in ORDER.  Each is an object above, None where absent: .debye, .lorentz, .sheets,
-    .elements, .magnetic, .conformal, and .pw_e / .pw_h for the plane wave's two lists.
-    `tables`: {name: the argument tuple of the C ABI setter} for "debye", "lorentz", "sheets", "elements", "magnetic", "conformal", and
-    "pw": planewave.Tables.  A correction not named there takes the simulation's own tables, if the simulation holds it.
+    .elements, .magnetic, .conformal, .excite, and .pw_e / .pw_h for the plane wave's two lists.
+    `tables`: {name: the argument tuple of the C ABI setter} for "debye", "lorentz", "sheets", "elements", "magnetic", "conformal",
+    "excite", and "pw": planewave.Tables.  A correction not named there takes the simulation's own tables, if the simulation holds it.
     `seed`: seeded noise in all six field components (helpers.seeded_fields) in front of priming i_prev; the other states start at zero.
     `before`, `after`: hooks called with (name, kind, fields) in front of and behind each correction held; `fields` are the three live
     arrays of that kind (0: V, 1: I) — copy what you keep (record() does).  After a step .V and, with an H-side correction, .I hold the
     fields as written back.
-    The oracle samples its I-probes inside the H half-step, in front of the H-side corrections, so with magnetic or conformal faces the
-    I-probe series are kept here — sum_e w_e I_e in double in the probe's edge order: the products are exact in double, so this is the
+    The oracle samples its I-probes inside the H half-step, in front of the H-side corrections, so with magnetic or conformal faces or
+    H-field excitations the I-probe series are kept here — sum_e w_e I_e in double in the probe's edge order: the products are exact in double, so this is the
     oracle's fma chain — and get_probe returns them; otherwise it returns the oracle's own.
     `f64`: the double-precision oracle library when `lib` is that one — fields and vi go through its double entry points and the
     correction runs in float64, on the simulation's float32-rounded tables (`round32`) or on the float64 ones; Lorentz media only."""
@@ -236,14 +252,16 @@ class Restatement:
         if seed is not None:
             seeded_fields(e, seed)
         own = {"debye": sim.debye_tables, "lorentz": sim.lorentz_tables, "sheets": sim.sheet_tables, "elements": sim.lumped_tables,
-               "magnetic": lambda: sim.magnetic.tables(), "conformal": sim.conformal_tables, "pw": self._planewave_tables}
+               "magnetic": lambda: sim.magnetic.tables(), "conformal": sim.conformal_tables, "pw": self._planewave_tables,
+               "excite": lambda: sim.excite_h_args}
         if f64 is not None and not round32:
             d = sim.lorentz
             own["lorentz"] = lambda: pkg("lorentz").tables(d.media, sim.dt, dtype=np.float64) + (d.lo, d.hi, d.w, d.med)
         given = dict(tables or {})
         T = {k: given[k] if k in given else own[k]() for k in own if k in given or HELD[k](sim)}
         assert f64 is None or set(T) <= {"lorentz"}
-        make = {"debye": Debye, "lorentz": Lorentz, "sheets": Sheets, "elements": Elements, "magnetic": Magnetic, "conformal": Conformal}
+        make = {"debye": Debye, "lorentz": Lorentz, "sheets": Sheets, "elements": Elements, "magnetic": Magnetic, "conformal": Conformal,
+                "excite": Excite}
         self.parts = {}
         for name in ORDER:
             key = "pw" if name in ("pw_e", "pw_h") else name
@@ -304,7 +322,7 @@ class Restatement:
         return pid
 
     def get_probe(self, pid):
-        if pid in self.i_probes and (self.magnetic or self.conformal):
+        if pid in self.i_probes and (self.magnetic or self.conformal or self.excite):
             return np.array(self.i_series.get(pid, []), np.float64)
         return self.e.get_probe(pid)
 
@@ -344,7 +362,7 @@ class Restatement:
         if any(name in self.parts for name in H_SIDE):
             self.I = [self.get(1, c) for c in range(3)]
             self._apply(H_SIDE, 1, self.I)
-        if self.magnetic or self.conformal:
+        if self.magnetic or self.conformal or self.excite:      # behind every H-side correction, the excitations included
             for pid, (idx, comp, w) in self.i_probes.items():
                 s = 0.0
                 for g, c, wq in zip(idx, comp, w):
@@ -378,9 +396,10 @@ class _Engine:
         return getattr(self._r.e, name)
 
 
-def install(monkeypatch):
+def install(monkeypatch, tables=None):
     """Simulation.build -> the restatement's engine when the simulation holds a correction whose entry points the library lacks (the
-    oracle), the real build otherwise: the checker of the plugin-level tests.  The restatement is sim.restated."""
+    oracle), the real build otherwise: the checker of the plugin-level tests.  The restatement is sim.restated.
+    `tables(sim)`: raw tables that replace the simulation's own (Restatement's `tables`)."""
     Sim = pkg("simulation").Simulation
     orig = Sim.build
 
@@ -388,7 +407,11 @@ def install(monkeypatch):
         capi = pkg("_capi")
         if not any(held(self) and not getattr(capi, HAS[name])(lib) for name, held in HELD.items()):
             return orig(self, lib, **kw)
-        r = Restatement(self, lib, flags=kw.get("flags", 0))
+        r = Restatement(self, lib, flags=kw.get("flags", 0), tables=None if tables is None else tables(self))
+        for name, pl in self.probes.items():          # the stand-alone current probes: kept like the ports' (sampled behind the H side)
+            if pl.kind == 1:
+                for pid, q in zip(self._probe_ids[name], pl.lists):
+                    r.i_probes[pid] = (np.asarray(q.idx, np.int64), np.asarray(q.comp, np.int64), np.asarray(q.w, np.float32))
         self.engine, self.lib = r.engine, lib
         self.rank, self.world, self.device, self._build_flags = 0, 1, 0, 0
         if r.pw_e is not None:

@@ -19,10 +19,11 @@ SCHEDULES = ("DIRECT", "WF1", "WFM", "RESIDENT", "AUTO")   # WF1: WAVEFRONT with
 
 
 # ---- engines ----------------------------------------------------------------------------------------------------------------------
-def raw_engine(lib, grid_case, boundary, flags=0, max_steps=8, *, cpml_cells=3, rank=0, world=1, slab=None):
+def raw_engine(lib, grid_case, boundary, flags=0, max_steps=8, *, cpml_cells=3, rank=0, world=1, slab=None, hard=None):
     """An engine on the uniform random-material scene `grid_case` = (seed, (nx, ny, nz)) (opbuild_cases.random_scene without PEC or
     lumped edges), its operator built by the library, `boundary` one kind or six ('PEC' / 'MUR' / 'CPML') set the way
-    Simulation.build sets them.  The engine carries .grid and .dt."""
+    Simulation.build sets them.  `hard`: (idx, comp) of hard E edges — overrides with vv = m = 0 on every rank, as Simulation._overrides
+    makes them (fdtd_build_operator keeps those of its slab).  The engine carries .grid and .dt."""
     capi, eco, const, cp, simm = pkg("_capi"), pkg("ecoperator"), pkg("constants"), pkg("cpml"), pkg("simulation")
     from opbuild_cases import random_scene
     seed, shape = grid_case
@@ -32,7 +33,12 @@ def raw_engine(lib, grid_case, boundary, flags=0, max_steps=8, *, cpml_cells=3, 
     k0, nk = (0, nz) if slab is None else slab
     e = capi.Engine(lib, nx, ny, nz, dt, k0=k0, nk=nk, rank=rank, world=world, max_steps=max_steps, flags=flags)
     emet, hmet = eco.pack_metric_tables(*eco.metric_lists(grid, dt), grid, k0, nk)
-    e.build_operator(grid.d, eps, kap, pec, const.EPS0, eco.lumped_overrides(grid, eps, kap, pec, dt, []), emet, hmet)
+    over = eco.lumped_overrides(grid, eps, kap, pec, dt, [])
+    if hard is not None:
+        z = np.zeros(len(hard[0]), np.float32)
+        over = (np.concatenate([over[0], np.asarray(hard[0], np.int64)]), np.concatenate([over[1], np.asarray(hard[1], np.int8)]),
+                np.concatenate([over[2], z]), np.concatenate([over[3], z]))
+    e.build_operator(grid.d, eps, kap, pec, const.EPS0, over, emet, hmet)
     bc = simm.BoundarySpec.parse(boundary, cpml_cells)
     cells = bc.face_cells()
     if any(cells):
@@ -66,6 +72,8 @@ class Case:
     keep_frames: bool = False    # reference() keeps the oracle's fields of every timestep (the cases that are cut into slabs)
     env: dict = field(default_factory=dict)      # knobs read by fdtd_create ($FDTD_TYS ...)
     expect: dict = field(default_factory=dict)   # where the case is meant to sit: keys of regimes(), checked without a GPU
+    hard: Optional[tuple] = None                 # hard E edges (idx, comp, amp, delay), each once: operator overrides vv = m = 0 and a source
+                                                 # list behind `sources`, as Simulation adds them
 
     @property
     def nsteps(self):
@@ -77,7 +85,7 @@ class Case:
 
     def all_sources(self):
         """[(first timestep, call)] in the order the engine's list holds them."""
-        out = [(0, s) for s in self.sources]
+        out = [(0, s) for s in self.sources] + ([(0, self.hard)] if self.hard is not None else [])
         for after, what, call in self.later:
             if what == "source":
                 out.append((int(sum(self.calls[:after])), call))
@@ -120,7 +128,7 @@ def apply(case, engine, without=None):
     engine.set_signal(case.signal)
     if case.seed is not None:
         seeded_slab_fields(engine, case.seed)
-    for n, s in enumerate(case.sources):
+    for n, s in enumerate(case.sources + ([case.hard] if case.hard is not None else [])):
         if n != without:
             engine.add_source(*s)
     return [engine.add_probe(*p) for p in case.probes]
@@ -128,7 +136,7 @@ def apply(case, engine, without=None):
 
 def run(case, engine, runner=None, without=None):
     """The run calls, the later additions between them.  `runner(engine, n)` steps n timesteps (default: one fdtd_run)."""
-    n_src = len(case.sources)
+    n_src = len(case.sources) + (case.hard is not None)
     for c, n in enumerate(case.calls):
         (runner or (lambda e, m: e.run(m)))(engine, n)
         for after, what, call in case.later:
@@ -143,7 +151,8 @@ def run(case, engine, runner=None, without=None):
 
 
 def engine_for(case, lib, flags=0, without=None, **kw):
-    e = raw_engine(lib, (case.scene, case.shape), case.boundary, flags, case.cap, cpml_cells=case.cpml_cells, **kw)
+    e = raw_engine(lib, (case.scene, case.shape), case.boundary, flags, case.cap, cpml_cells=case.cpml_cells,
+                   hard=None if (case.hard is None or kw.pop("soft_operator", False)) else case.hard[:2], **kw)
     apply(case, e, without)
     return e
 
@@ -846,6 +855,141 @@ def _s4(zkind):
 _s4("CPML")
 _s4("MUR")
 _slab_runs("D7", [CUT_2])
+
+
+# ---- E-type field excitations and probes.py lists on the slabs: hard edges (Case.hard) on and next to the cut planes -------------------
+HARD_CASES = ("H1-line", "H2-plate", "H2-plate-mur")
+HARD_PLANES = {"H1-line": (6, 7, 8, 9), "H2-plate": (7, 8, 9), "H2-plate-mur": (7, 8, 9)}      # the planes each case claims for its hard edges
+
+
+def _grid_of(case):
+    from opbuild_cases import random_scene
+    return random_scene(case.scene, case.shape, False, 3, n_lumped=0, pec_frac=0.0)[0]
+
+
+def _h1():
+    """H1: a z-directed hard E line at (20, 12) over the planes 6 ... 9 — for every cut k0 in 7, 8, 9 an edge on plane k0 - 1 (the top
+    plane of the rank below: its H update reads the E halo) and one on k0 —, one delay per edge; a V-probe on every hard edge, an I-probe
+    on the faces round the line and a V-probe through it, both over planes 5 ... 10."""
+    shape = SLAB_SHAPE
+    rng = np.random.default_rng(8500)
+    ks = np.array(HARD_PLANES["H1-line"])
+    hard = src(node(shape, 20, 12, ks), [2] * 4, [1.0, -0.8, 0.6, 0.9], [0, 3, 1, 25])
+    on = [prb(KIND_V, [g], [2], [1.0]) for g in hard[0]]
+    kk = np.arange(5, 11)
+    ring = prb(KIND_I, node(shape, np.tile([19, 20], 6), np.repeat(12, 12), np.repeat(kk, 2)), [1] * 12, _weights(rng, 12))
+    through = prb(KIND_V, node(shape, 20, 12, kk), [2] * 6, _weights(rng, 6))
+    case = Case("H1-line", shape, ("CPML",) * 6, 3, signal(), [], on + [ring, through], (1, 7, 72), seed=13, keep_frames=True, hard=hard,
+                expect={"fusable": True})
+    DIRECTED[case.name] = case
+    _slab_runs(case.name, [CUT_2, CUT_3])
+
+
+def _h2(mur):
+    """H2: hard E plates of x and y edges IN the planes 7, 8 and 9 (i 18 ... 22, j 10 ... 14): the cut plane k0 belongs to the rank above,
+    the rank below reads its voltages as a halo; 40 edges per plane, more than the 32 a strip-plane scans (the dense image), 24 of
+    them in rows 12 ... 14.  A V-probe on six of them, an I-probe and a V-probe over planes 6 ... 10 around the plates.  With Mur faces on
+    x and y: linked contexts and half-steps, and the mailbox's refusal."""
+    shape = SLAB_SHAPE
+    rng = np.random.default_rng(8600)
+    ex = [(0, k, j, i) for k in HARD_PLANES["H2-plate"] for j in range(10, 15) for i in range(18, 22)]
+    ey = [(1, k, j, i) for k in HARD_PLANES["H2-plate"] for j in range(10, 14) for i in range(18, 23)]
+    c, k, j, i = np.array(ex + ey).T
+    amp = (0.5 + 0.1 * (i - 18) - 0.07 * (j - 10)) * np.where(c == 0, 1.0, -1.0)
+    hard = src(node(shape, i, j, k), c, amp, np.where(k == 8, 2, k - 7))
+    pick = [0, 21, 47, 60, 88, 119]
+    on = [prb(KIND_V, [hard[0][q]], [hard[1][q]], [1.0]) for q in pick]
+    n = 60
+    pi, pj, pk = rng.integers(16, 25, n), rng.integers(8, 17, n), rng.integers(6, 11, n)
+    around_i = prb(KIND_I, node(shape, pi, pj, pk), rng.integers(0, 3, n), _weights(rng, n))
+    around_v = prb(KIND_V, node(shape, pi[::-1], pj, pk), rng.integers(0, 3, n), _weights(rng, n))
+    kinds = ("MUR",) * 4 + ("CPML",) * 2 if mur else ("CPML",) * 6
+    case = Case("H2-plate-mur" if mur else "H2-plate", shape, kinds, 3, signal(), [], on + [around_i, around_v], (1, 7, 72), seed=14,
+                scene=21 if mur else 5, keep_frames=True, hard=hard, expect={"fusable": True, "path": "dense"})
+    DIRECTED[case.name] = case
+    if mur:
+        _slab_runs(case.name, [CUT_2, CUT_3], ("linked-split", "linked-nosplit", "half-steps"))
+        SLAB_RUNS.append((case.name, CUT_2, "p2p-two", "refused: fdtd_run_linked: every context must use the p2p transport (no Mur)"))
+    else:
+        _slab_runs(case.name, [CUT_2, CUT_3])
+
+
+def _h3():
+    """H3: a soft E list as a weighted, delayed field excitation makes it — three delays, graded amplitudes, z edges over planes 5 ... 10
+    and x edges in planes 7, 8, 9, one edge listed twice — spanning both (all three) slabs; and the four list kinds of probes.py, built
+    by probes.lists itself for boxes that straddle the cuts: a voltage line from plane 5 to plane 11, a current loop with normal x
+    over planes 6 ... 10, E-field and H-field point probes at nodes of the planes 7 and 8 (a point has one node: one on either side of
+    the cut 7 | 8, and the z edge of the one on plane 7 ends on plane 8)."""
+    probes_mod = pkg("probes")
+    shape = SLAB_SHAPE
+    kk = np.repeat(np.arange(5, 11), 3)
+    ii = np.tile([14, 15, 16], 6)
+    z_idx, z_amp, z_delay = node(shape, ii, 9, kk), 0.2 + 0.1 * (kk - 5) - 0.05 * (ii - 14), np.tile([0, 4, 9], 6)
+    xk = np.repeat([7, 8, 9], 4)
+    xi = np.tile([13, 14, 15, 16], 3)
+    x_idx, x_amp, x_delay = node(shape, xi, 10, xk), -0.3 + 0.08 * (xi - 13) + 0.05 * (xk - 7), np.repeat([9, 0, 4], 4)
+    idx = np.concatenate([z_idx, x_idx, z_idx[[10]]])
+    comp = np.concatenate([np.full(18, 2), np.full(12, 0), [2]])
+    soft = src(idx, comp, np.concatenate([z_amp, x_amp, [-0.45]]), np.concatenate([z_delay, x_delay, [4]]))
+    case = Case("H3-soft-and-probes", shape, ("CPML",) * 6, 3, signal(), [soft], [], (1, 7, 72), seed=15, keep_frames=True,
+                expect={"fusable": True, "dup": True})
+    g = _grid_of(case)
+    pec = np.zeros((3, shape[2], shape[1], shape[0]), bool)
+    at = lambda i, j, k: (float(g.x[i]), float(g.y[j]), float(g.z[k]))
+    mid = lambda a, q: 0.5 * float(g.lines[a][q] + g.lines[a][q + 1])
+    specs = []
+    for name, t, start, stop, nd in (("ut", 0, at(15, 9, 5), at(15, 9, 11), None),
+                                     ("it", 1, (mid(0, 15), float(g.y[8]), float(g.z[6])), (mid(0, 15), float(g.y[11]), float(g.z[10])), 0),
+                                     ("et7", 2, at(15, 10, 7), at(15, 10, 7), None), ("et8", 2, at(15, 10, 8), at(15, 10, 8), None),
+                                     ("ht7", 3, at(16, 11, 7), at(16, 11, 7), None), ("ht8", 3, at(16, 11, 8), at(16, 11, 8), None)):
+        sp = probes_mod.make(name, t, norm_dir=nd)
+        sp.start, sp.stop = start, stop
+        specs.append(sp)
+    case.probe_names = []
+    for sp in specs:
+        pl = probes_mod.lists(g, pec, sp, 1.0, 1e-9)
+        for q in pl.lists:
+            case.probes.append(prb(pl.kind, q.idx, q.comp, q.w))
+            case.probe_names.append(sp.name)
+    DIRECTED[case.name] = case
+    _slab_runs(case.name, [CUT_2, CUT_3])
+
+
+def _h4():
+    """H4 (single slab): D2-tys8's grid, 130 x 17 x 10 with strips of 8 rows — 40 hard x and z edges in row 15 of plane 5 (threads
+    231 ... 263 of the strip-plane: two blocks), 20 of them at i >= 100, in the second block; a V-probe on six of them."""
+    shape = (130, 17, 10)
+    rng = np.random.default_rng(8700)
+    i = np.concatenate([rng.choice(np.arange(2, 100), 20, replace=False), rng.choice(np.arange(100, 128), 20, replace=False)])
+    comp = rng.integers(0, 2, 40) * 2
+    hard = src(node(shape, i, 15, 5), comp, _amps(rng, 40), rng.integers(0, 12, 40))
+    on = [prb(KIND_V, [hard[0][q]], [hard[1][q]], [1.0]) for q in (0, 7, 19, 20, 31, 39)]
+    around = prb(KIND_I, node(shape, np.arange(97, 109), 14, 5), [0] * 12, _weights(rng, 12))
+    case = Case("H4-second-block", shape, ("PEC",) * 6, 0, signal(), [], on + [around], (1, 7, 52), seed=16, hard=hard, env={"FDTD_TYS": "8"},
+                expect={"tys": 8, "sp_max": 40, "dup": False, "path": "dense", "fusable": True, "blocks_per_strip_plane": 2, "src_blocks": [0, 1]})
+    _add(case, [("DIRECT", "two"), ("WF1", "one"), ("RESIDENT", "resident")])
+
+
+_h1()
+_h2(False)
+_h2(True)
+_h3()
+_h4()
+# the slab cases once on ONE slab under the resident, the one-launch and the two-launch schedule
+for _name in ("H1-line", "H2-plate", "H3-soft-and-probes"):
+    for _sched, _outcome in (("RESIDENT", "resident"), ("WF1", "one"), ("DIRECT", "two")):
+        RUNS.append((_name, _sched, _outcome, {}))
+HARD_CASES = HARD_CASES + ("H4-second-block",)
+HARD_PLANES["H4-second-block"] = (5,)
+
+
+def hard_table(case, q):
+    """What hard edge q holds, per recorded timestep: float32(amp * sig[n - delay]) inside the table, 0.0 outside."""
+    idx, comp, amp, delay = case.hard
+    n = np.arange(min(case.nsteps, case.cap)) - int(delay[q])
+    inside = (n >= 0) & (n < len(case.signal))
+    s = np.where(inside, case.signal.astype(np.float32)[np.clip(n, 0, len(case.signal) - 1)], np.float32(0.0)).astype(np.float32)
+    return (amp[q] * s).astype(np.float64)
 SLAB_CASES = sorted({r[0] for r in SLAB_RUNS})
 
 

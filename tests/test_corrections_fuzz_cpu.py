@@ -1,4 +1,4 @@
-"""Guards of the randomised parity run of all seven corrections in one context (tests/fuzz_parity.py --corrections) that need no GPU: the
+"""Guards of the randomised parity run of all eight corrections in one context (tests/fuzz_parity.py --corrections) that need no GPU: the
 fixed-seed batch of the -m gpu suite is accepted by the host layer and covers, together, what it was written to reach; the same seed
 gives the same cases; the reference side of the first cases moves every state of every correction present; raw tables handed
 to the restatement give the bits of the simulation's own."""
@@ -25,7 +25,13 @@ WANTED = ({f"k_debye<{m},{k}>" for m in ("false", "true") for k in (4, 8)} | {f"
              "port loop through a magnetic material", "mu_r only", "sigma_m only", "mu_r and sigma_m", "box at x = 0", "box on the last column",
              "medium on a Mur face node, no apply pass", "medium on a Mur face node, apply pass", "set_field of a V component", "set_field of an I component",
              ">= 3 calls", "nf2ff none", "nf2ff dft", "nf2ff record", "raw operator", "graded", "uniform", "plane wave", "no plane wave",
-             "oblique plane wave", "axis-aligned plane wave", "sphere", "tilted cylinder", "R, L and C in one element"})
+             "oblique plane wave", "axis-aligned plane wave", "sphere", "tilted cylinder", "R, L and C in one element"}
+          | {f"excited {what} face of component {c}" for what in ("soft", "hard") for c in "xyz"}
+          | {f"{what} excitation delay {d}" for what in ("soft", "hard") for d in ("0", "inside the run", "past the run")}
+          | {"one face with three soft entries", "excitations", "no excitations", "excitations with magnetic faces", "excitations with conformal faces",
+             "excitations with a plane wave", "excitations under drive half", "excitations under drive direct", "excitations under drive auto",
+             "excitations with Mur faces, apply pass", "excitations with Mur faces, no apply pass", "excitations with nf2ff record", "excitations with nf2ff dft",
+             "set_field of an I component with excitations"})
 
 
 def _edge_mask(d, shape):
@@ -138,15 +144,64 @@ def features(case, sim):
         out |= {"plane wave", "axis-aligned plane wave" if sorted(map(abs, case["planewave"]["dir"]))[1] == 0 else "oblique plane wave"}
     else:
         out.add("no plane wave")
+    if sim.excite_h_args is None:
+        out.add("no excitations")
+    else:
+        total = sum(case["calls"])
+        hard, soft = sim.excite_h_args[0:4], sim.excite_h_args[4:8]
+        assert hard[0].size == sum(x["type"] == 3 for x in case["excite"]) and soft[0].size == sum(x["type"] == 2 for x in case["excite"])
+        for what, l in (("hard", hard), ("soft", soft)):
+            for c, d in zip(l[1].tolist(), l[3].tolist()):
+                out |= {f"excited {what} face of component {'xyz'[c]}",
+                        f"{what} excitation delay " + ("0" if d == 0 else "inside the run" if d < total else "past the run")}
+        if np.unique(soft[0] * 3 + soft[1], return_counts=True)[1].max() == 3:
+            out.add("one face with three soft entries")
+        out |= {"excitations", f"excitations under drive {case['drive']}"}
+        if sim.magnetic is not None:
+            out.add("excitations with magnetic faces")
+        if sim.conformal is not None:
+            out.add("excitations with conformal faces")
+        if sim.plane_wave is not None:
+            out.add("excitations with a plane wave")
+        if "MUR" in case["kinds"]:
+            out.add("excitations with Mur faces, " + ("apply pass" if case["env"].get("FDTD_MUR_APPLY_PASS") == "1" else "no apply pass"))
+        if case["nf2ff"] != "none":
+            out.add(f"excitations with nf2ff {case['nf2ff']}")
+        if any(st is not None and st[0] == 1 for st in case["sets"]):
+            out.add("set_field of an I component with excitations")
     return out
+
+
+def _excited_faces_are_free(sim):
+    """What field_excitation.check_placement demands of the excited faces, asked again here of the lists the simulation holds."""
+    n = sim.grid.shape
+    key = np.concatenate([sim.excite_h_args[0] * 3 + sim.excite_h_args[1], sim.excite_h_args[4] * 3 + sim.excite_h_args[5]]).astype(np.int64)
+    g, c = key // 3, key % 3
+    pos = np.stack([g % n[0], g // n[0] % n[1], g // (n[0] * n[1])])
+    for a in range(3):
+        assert np.all(pos[a][c != a] < n[a] - 1) and np.all((pos[a][c == a] > 0) & (pos[a][c == a] < n[a] - 1))
+    if sim.magnetic is not None:
+        assert not sim.magnetic.full_classes(n[::-1]).reshape(3, -1)[c, g].any()
+    if sim.conformal is not None:
+        assert not np.isin(key, np.asarray(sim.conformal.idx, np.int64) * 3 + np.asarray(sim.conformal.comp, np.int64)).any()
+    if sim.plane_wave is not None:
+        pw = np.array([sim.grid.flat(i, j, k) * 3 + f for f, i, j, k, *_ in pkg("planewave").terms(sim.grid, sim.plane_wave, 1)], np.int64)
+        assert pw.size and not np.isin(key, pw).any()
+    for r in ([] if sim.nf2ff_box is None else sim.nf2ff_box.requests):      # (no NF2FF box samples one: fuzz_parity.draw_excitations says why)
+        on = (c == r.comp) & np.all([(pos[a] >= r.lo[a]) & (pos[a] <= r.hi[a]) for a in range(3)], axis=0)
+        assert r.kind == 0 or not on.any()
 
 
 def test_fixed_seed_batch_is_accepted_and_covers_what_it_is_for():
     ncases, seed = fuzz_parity.CORRECTIONS_BATCH
     rng = np.random.default_rng(seed)
+    bare = np.random.default_rng(seed)
     seen, accepted, refused, count, how_many = set(), 0, [], collections.Counter(), []
     for q in range(ncases):
-        case = fuzz_parity.draw_corrections_case(rng)
+        case = fuzz_parity.draw_corrections_case(rng, excite=(seed, q))
+        # the excitations come from a generator of their own: without them the case is what draw_corrections_case(rng) draws — the
+        # parent commit's case (test_batch_without_excitations_is_the_recorded_one holds that to the record)
+        assert {k: v for k, v in case.items() if k != "excite"} == {k: v for k, v in fuzz_parity.draw_corrections_case(bare).items() if k != "excite"}
         nx, ny, nz = case["shape"]
         assert 14 <= nx <= 70 and 12 <= ny <= 36 and 12 <= nz <= 28 and 2 <= case["cells"] <= 6
         assert 1 <= len(case["calls"]) <= 5 and all(1 <= k <= 60 for k in case["calls"]) and sum(case["calls"]) <= 150
@@ -165,10 +220,15 @@ def test_fixed_seed_batch_is_accepted_and_covers_what_it_is_for():
         count.update(have)
         how_many.append(len(have))
         seen |= features(case, sim)
+        assert ("excite" in have) == (case["excite"] is not None)
+        if case["excite"] is not None:
+            assert 7 <= len(case["excite"]) <= 14
+            _excited_faces_are_free(sim)
     print(f"{accepted} of {ncases} accepted; refused: {refused}; cases per correction: {dict(count)}; corrections per case: {sorted(how_many)}")
     assert 6 * accepted >= 5 * ncases, refused
+    assert accepted == ncases == 24 and refused == []      # this batch: every case, with its excitations, is accepted by the host layer
     assert all(count[name] >= 4 for name in NAMES), count
-    assert how_many.count(7) >= 2 and 3 * sum(h >= 5 for h in how_many) >= accepted, how_many
+    assert how_many.count(8) >= 8 and 3 * sum(h >= 5 for h in how_many) >= accepted, how_many
     assert not WANTED - seen, sorted(WANTED - seen)
 
 
@@ -176,15 +236,26 @@ def test_same_seed_same_cases():
     first = fuzz_parity.draw_corrections_case(np.random.default_rng(5))
     rng = np.random.default_rng(5)
     assert fuzz_parity.draw_corrections_case(rng) == first and fuzz_parity.draw_corrections_case(rng) != first
+    a, b = fuzz_parity.corrections_batch(6, 5), fuzz_parity.corrections_batch(6, 5)
+    assert a == b and a[0] == dict(first, excite=a[0]["excite"]) and any(c["excite"] is not None for c in a)
+
+
+def test_batch_without_excitations_is_the_recorded_one():
+    """The descriptions of the fixed-seed batch with the excitation part removed, against tests/golden/corrections_batch_seed2.json: the
+    repr() of each case as the commit before the excitations drew it (written there by that commit's draw_corrections_case)."""
+    import json
+    import os
+    from conftest import ROOT
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "corrections_batch_seed2.json")))
+    got = [repr({k: v for k, v in c.items() if k != "excite"}) for c in fuzz_parity.corrections_batch()]
+    assert len(want) == 24 and got == want
 
 
 def test_reference_side_of_the_first_cases_moves_everywhere(oracle_lib):
     """The first cases of the batch stepped on the restatement alone: finite, non-zero, every state of every correction present
     off zero, the plane wave's lists changing V and I on their elements."""
-    rng = np.random.default_rng(fuzz_parity.CORRECTIONS_BATCH[1])
-    ran, have = 0, set()
-    for q in range(8):
-        case = fuzz_parity.draw_corrections_case(rng)
+    ran, have, acted = 0, set(), 0
+    for q, case in enumerate(fuzz_parity.corrections_batch()[:8]):
         try:
             problems, _ = fuzz_parity.run_corrections_case(case, None, oracle_lib)
         except ValueError:
@@ -192,7 +263,15 @@ def test_reference_side_of_the_first_cases_moves_everywhere(oracle_lib):
         assert problems == [], (q, case, problems)
         have |= fuzz_parity.corrections_present(fuzz_parity.corrections_case_sim(case))
         ran += 1
-    assert ran >= 7 and have == set(NAMES), (ran, have)
+        if case["excite"] is not None:      # the set acts: the same case without it ends with other fields
+            fields = []
+            for c in (case, dict(case, excite=None)):
+                ref = fuzz_parity.corrections_reference(fuzz_parity.corrections_case_sim(c), oracle_lib, seed=case["seed"])
+                ref.run(case["calls"][0])
+                fields.append(ref.e.fields())
+            assert not np.array_equal(fields[0][1], fields[1][1]), q
+            acted += 1
+    assert ran >= 7 and have == set(NAMES) and acted >= 4, (ran, have, acted)
 
 
 def test_composed_with_conformal_faces_alone_is_restated_conformal(oracle_lib):
@@ -250,8 +329,8 @@ def test_composed_with_a_plane_wave_and_conformal_faces_is_the_pair_it_was(oracl
 def test_overlap_reference_tells_every_correction_apart(oracle_lib, mur):
     """The hand tables of corrections_overlap_cases.py on the reference alone: the lists do overlap where the case says, the run is
     finite and every state moves, the V-probes kept here are the oracle's own (sampled in front of every E-side correction), the
-    I-probes are not (sampled behind every H-side one), and dropping any one correction changes the values the GPU test compares on the
-    shared edge or face itself."""
+    I-probes are not (sampled behind every H-side one), and dropping any one of the ten lists (the plane wave's two and the
+    excitations' two counted singly) changes the values the GPU test compares on the shared edge or face itself."""
     ref = oc.reference(oracle_lib, mur)
     T = ref.T
     key = lambda el: (int(el[0]), oc.flat(*el[1:]))
@@ -265,6 +344,11 @@ def test_overlap_reference_tells_every_correction_apart(oracle_lib, mur):
     lo = T["magnetic"][2][c]
     assert T["magnetic"][4][c][k - lo[2], j - lo[1], i - lo[0]] != 0
     assert key(oc.F) in listed(T["conformal"][1], T["conformal"][0]) & listed(*T["pw"].H[:2])
+    x = T["excite"]
+    assert list(zip(x[5].tolist(), x[4].tolist())).count(key(oc.F)) == 2 and key(oc.F) not in listed(*x[:2])
+    c, i, j, k = oc.G
+    assert T["magnetic"][4][c][k - lo[2], j - lo[1], i - lo[0]] != 0 and key(oc.G) in listed(*T["pw"].H[:2]) & listed(*x[:2])
+    assert key(oc.G) not in listed(x[4], x[5]) and key(oc.G) not in listed(T["conformal"][1], T["conformal"][0])
     assert np.isfinite(ref.fields).all() and all(np.abs(a).max() > 0 for name in ref.state for a in ref.state[name])
     for pid, s in zip(ref.own_v, ref.v_series):
         assert np.array_equal(ref.e.get_probe(pid)[:oc.STEPS], np.array(s)) and np.abs(s).max() > 0
@@ -272,12 +356,53 @@ def test_overlap_reference_tells_every_correction_apart(oracle_lib, mur):
     for name in oc.NAMES:
         d = oc.reference(oracle_lib, mur, name)
         assert not np.array_equal(d.fields, ref.fields), name
-        if name in ("magnetic", "conformal", "pw_h"):
+        if name in ("magnetic", "conformal", "pw_h", "excite_soft"):
             assert at(d, 1, oc.F) != at(ref, 1, oc.F) and not np.array_equal(d.i_series[0], ref.i_series[0]), name
             assert np.abs(d.i_acc[0] - ref.i_acc[0]).max() > 1e-6 * np.abs(ref.i_acc[0]).max(), name
+        elif name == "excite_hard":
+            assert not np.array_equal(d.i_series[2], ref.i_series[2])
+            assert np.abs(d.i_acc[1] - ref.i_acc[1]).max() > 1e-6 * np.abs(ref.i_acc[1]).max()
+            assert not np.array_equal(d.state["magnetic"][1], ref.state["magnetic"][1])      # i_prev of G restarts from another current
         else:
             shared = [oc.A, oc.B] if name in ("sheets", "elements", "pw_e") else [oc.A] if name == "debye" else [oc.B]
             for q, el in enumerate([oc.A, oc.B]):
                 if el in shared:
                     assert at(d, 0, el) != at(ref, 0, el), (name, el)
                     assert not np.array_equal(d.v_series[q], ref.v_series[q]), (name, el)
+
+
+def _hard_series(T, amp_delay=oc.HARD_G):
+    """float32(amp * sigH[n - delay]), 0.0 outside the table: what a hard face holds, per timestep."""
+    amp, d = amp_delay
+    sig = np.concatenate([np.zeros(d, np.float32), T["excite"][8], np.zeros(oc.STEPS, np.float32)])[:oc.STEPS]
+    return (np.float32(amp) * sig).astype(np.float64)
+
+
+@pytest.mark.parametrize("mur", [False, True], ids=["pec", "one-mur-face"])
+def test_overlap_reference_tells_the_excitations_place_in_the_order(oracle_lib, monkeypatch, mur):
+    """The reference alone: the hard face G holds amp * sigH[n - delay] whatever the magnetic faces and the plane wave did there; the
+    two soft entries on F in the other list order give other bits; and with the excitations in front of the plane wave's face list
+    instead of behind it (restatement.H_SIDE swapped) both faces read other bits — F by float32 association ((I + pw) + t against
+    (I + t) + pw), G because the plane wave then adds to the hard value."""
+    import restatement
+    ref = oc.reference(oracle_lib, mur)
+    T = ref.T
+    want = _hard_series(T)
+    assert np.array_equal(np.array(ref.i_series[2]), want) and np.count_nonzero(want) == oc.NSIG_H and not want[:oc.HARD_G[1]].any() and not want[42:].any()
+    at = lambda r, el: r.fields[1][el[0]][el[3], el[2], el[1]]
+    # the soft list reversed: the same entries per face, F's two in the other order
+    x = T["excite"]
+    rev = dict(T, excite=x[:4] + tuple(a[::-1].copy() for a in x[4:8]) + x[8:])
+    r = oc.Ordered(oracle_lib, rev, mur).run()
+    assert not np.array_equal(r.i_series[0], ref.i_series[0]) and at(r, oc.F) != at(ref, oc.F)
+    assert np.array_equal(np.array(r.i_series[2]), want)
+    # plane wave (face list) <-> excitations
+    assert restatement.H_SIDE[-2:] == ("pw_h", "excite")
+    monkeypatch.setattr(restatement, "H_SIDE", restatement.H_SIDE[:-2] + ("excite", "pw_h"))
+    sw = oc.Ordered(oracle_lib, T, mur).run()
+    monkeypatch.undo()
+    assert not np.array_equal(sw.i_series[0], ref.i_series[0]) and at(sw, oc.F) != at(ref, oc.F)
+    got = np.array(sw.i_series[2])
+    assert not np.array_equal(got, want) and np.count_nonzero(got != want) >= 20      # the plane wave's term on top of the hard value
+    assert np.abs(sw.i_acc[1] - ref.i_acc[1]).max() > 1e-6 * np.abs(ref.i_acc[1]).max()
+    assert not np.array_equal(sw.state["magnetic"][1], ref.state["magnetic"][1])

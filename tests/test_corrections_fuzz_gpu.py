@@ -1,5 +1,5 @@
-"""All seven corrections of the step loop in one context on the GPU (Debye and Lorentz media, sheets, elements and the plane wave's edge
-list behind the E phase; magnetic faces, conformal faces and the plane wave's face list behind the H update): a fixed-seed batch of
+"""All eight corrections of the step loop in one context on the GPU (Debye and Lorentz media, sheets, elements and the plane wave's edge
+list behind the E phase; magnetic faces, conformal faces, the plane wave's face list and the H-field excitations behind the H update): a fixed-seed batch of
 tests/fuzz_parity.py --corrections against restatement.Restatement; lists that overlap, through the raw C ABI, against the headers'
 statement lists applied in the headers' order; fdtd_set_field of every component between two calls with everything present."""
 import numpy as np
@@ -13,10 +13,14 @@ from helpers import seeded_fields
 GROUP = 4      # cases per parametrised group of the batch
 
 
+_BATCH = []
+
+
 def _batch():
-    ncases, seed = fuzz_parity.CORRECTIONS_BATCH
-    rng = np.random.default_rng(seed)
-    return [fuzz_parity.draw_corrections_case(rng) for _ in range(ncases)]
+    """The drawn cases, once per session (drawing the excitations builds each case's scene); nobody changes them."""
+    if not _BATCH:
+        _BATCH.extend(fuzz_parity.corrections_batch())
+    return _BATCH
 
 
 @pytest.mark.gpu
@@ -57,7 +61,8 @@ def _hip_overlap(hip_lib, T, mur, drive):
 @pytest.mark.parametrize("mur", [False, True], ids=["pec", "one-mur-face"])
 def test_overlapping_lists_follow_the_headers_order(hip_lib, oracle_lib, monkeypatch, mur):
     """One edge listed for a sheet, an element and the plane wave inside a Debye box, another inside a Lorentz box; one face that is
-    magnetic, conformal and on the plane wave's face list (corrections_overlap_cases.py).  fdtd_run under AUTO and DIRECT in two calls
+    magnetic, conformal, on the plane wave's face list and twice on the soft list of the H-field excitations, a second one that is
+    magnetic, on the plane wave's face list and on the hard list (corrections_overlap_cases.py).  fdtd_run under AUTO and DIRECT in two calls
     and fdtd_half_step pairs give the bits of the headers' statement lists applied in the headers' order; with a Mur face, under both
     Mur schedules.  The setters accept every overlap."""
     ref = oc.reference(oracle_lib, mur)
@@ -85,6 +90,9 @@ def test_overlapping_lists_follow_the_headers_order(hip_lib, oracle_lib, monkeyp
             assert np.array_equal(e.get_probe(pid)[:oc.STEPS], np.array(want)), (tag, "V-probe")
         for pid, want in zip(ip, ref.i_series):      # currents behind every H-side one
             assert np.array_equal(e.get_probe(pid)[:oc.STEPS], np.array(want)), (tag, "I-probe")
+        # the hard face G: amp * sigH[n - delay] exactly, whatever the magnetic faces and the plane wave's list did there
+        hard = np.concatenate([np.zeros(oc.HARD_G[1], np.float32), T["excite"][8], np.zeros(oc.STEPS, np.float32)])[:oc.STEPS]
+        assert np.array_equal(e.get_probe(ip[2])[:oc.STEPS], (np.float32(oc.HARD_G[0]) * hard).astype(np.float64)), (tag, "hard face")
         for bid, want in list(zip(vb, ref.v_acc)) + list(zip(ib, ref.i_acc)):
             box = e.get_dft_box(bid)[0]
             assert box.shape == want.shape and np.abs(box - want).max() <= 1e-12 * np.abs(want).max(), (tag, "DFT box", np.abs(box - want).max() / np.abs(want).max())
@@ -95,7 +103,7 @@ def test_overlapping_lists_follow_the_headers_order(hip_lib, oracle_lib, monkeyp
 # ---- fdtd_set_field with everything present ---------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_set_field_of_every_component_with_all_seven_present(hip_lib, oracle_lib):
-    """The first drawn case with all seven corrections, two calls; between them fdtd_set_field of every V and every I component: i_prev
+    """The first drawn case with all eight corrections (the name is from when there were seven), two calls; between them fdtd_set_field of every V and every I component: i_prev
     of the magnetic and the conformal faces is re-primed from the new currents, the states of the Debye and Lorentz media, the sheets and
     the elements keep their bits, and everything equals the restatement, which does the same, after both calls."""
     case = next(c for c in _batch() if fuzz_parity.corrections_present(fuzz_parity.corrections_case_sim(c)) == set(fuzz_parity.CORRECTION_NAMES))

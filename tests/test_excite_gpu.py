@@ -12,7 +12,9 @@ import pytest
 
 from conftest import ROOT, pkg
 from helpers import seeded_fields
+import excite_cases as xc
 from excite_cases import ExciteRestatement, HLists, main_lists, main_sim, node
+from restatement import Restatement
 from test_dispersion_model_cpu import _fr4
 
 
@@ -154,6 +156,272 @@ def test_decomposed_and_linked_contexts_are_refused():
     said = json.loads(r.stdout.strip().splitlines()[-1])
     want = r"\(-5\).*H-field excitations: single slab only \(world = 1, no p2p transport, no linked contexts\)"
     assert len(said) == 2 and all(m is not None and re.search(want, m) for m in said), said
+
+
+# ---- list shapes of fdtd_excite_set and k_excite through the raw C ABI (excite_cases.py; CPU side: test_field_excitation_cpu.py) -------
+CALLS = (1, 7, 72)       # 80 timesteps
+
+
+def _parity(hip_lib, oracle_lib, lists, *, n=xc.MAIN_GRID, seed=4, use_classes=True, before=None):
+    """The HIP context with `lists` stepped in CALLS against the restatement: all six fields bit for bit.  -> (fields, engine)."""
+    ref = Restatement(main_sim(n=n, use_classes=use_classes), oracle_lib, seed=seed, tables={"excite": lists.args()})
+    ref.run(sum(CALLS))
+    e = main_sim(n=n, use_classes=use_classes).build(hip_lib)
+    if before is not None:
+        before(e)
+    e.set_excite(*lists.args())
+    seeded_fields(e, seed)
+    assert e.schedule_info()["launches_per_timestep"] == 2
+    for k in CALLS:
+        e.run(k)
+    f, fo = e.fields(), ref.e.fields()
+    assert np.isfinite(fo).all() and np.array_equal(f, fo), f"fields differ at {np.count_nonzero(f != fo)} entries, first {tuple(np.argwhere(f != fo)[0])}"
+    return f, e
+
+
+_BARE = {}
+
+
+def _bare(hip_lib, n=xc.MAIN_GRID, seed=4):
+    """The same seeded run without a set, once per grid."""
+    if n not in _BARE:
+        e = main_sim(n=n).build(hip_lib)
+        seeded_fields(e, seed)
+        e.run(sum(CALLS))
+        _BARE[n] = e.fields()
+        e.close()
+    return _BARE[n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hard", [False, True], ids=["soft", "hard"])
+@pytest.mark.parametrize("count", xc.PLANE_COUNTS)
+def test_distinct_faces_around_one_block(hip_lib, oracle_lib, count, hard):
+    """1, 255, 256 and 257 distinct faces on one node plane (one thread per face, blocks of 256), soft entries only and with a hard
+    entry on every face."""
+    lists = xc.plane_lists(count, hard)
+    assert lists.faces()[0].size == count and lists.hard[0].size == (count if hard else 0) and lists.soft[0].size == count
+    f, e = _parity(hip_lib, oracle_lib, lists)
+    e.close()
+    bare = _bare(hip_lib)
+    fi, fc = lists.faces()
+    for g, c in ((fi[0], fc[0]), (fi[-1], fc[-1])):         # the first and the last face of the grouped set did get their entries
+        assert f[1, c].reshape(-1)[g] != bare[1, c].reshape(-1)[g]
+
+
+@pytest.mark.gpu
+def test_one_face_with_300_soft_entries(hip_lib, oracle_lib):
+    """One thread walks 300 entries in list order (test_field_excitation_cpu: the reversed list gives other bits on the reference)."""
+    lists = xc.many_entries_lists()
+    assert lists.faces()[0].size == 1 and lists.soft[0].size == 300
+    _, e = _parity(hip_lib, oracle_lib, lists)
+    e.close()
+
+
+@pytest.mark.gpu
+def test_scattered_entries_of_a_face_are_grouped_in_list_order(hip_lib, oracle_lib):
+    """40 faces x 3 entries, listed face by face and entry by entry: the same grouped set, the same bits, those of the restatement."""
+    fields = []
+    for order in ("face-major", "entry-major"):
+        f, e = _parity(hip_lib, oracle_lib, xc.forty_faces_lists(order))
+        fields.append(f)
+        e.close()
+    assert np.array_equal(fields[0].view(np.uint32), fields[1].view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hard", [False, True], ids=["soft", "hard"])
+@pytest.mark.parametrize("nx", xc.NX_EXTREMES)
+def test_faces_at_the_grid_extremes(hip_lib, oracle_lib, nx, hard):
+    """The origin and the last existing face of every component along every axis, for every nx mod 4; the node one step further along a
+    transverse axis is a node of the grid without that face: refused by name, and the context keeps the set it had."""
+    capi = pkg("_capi")
+    n = (nx,) + xc.MAIN_GRID[1:]
+    lists = xc.extreme_lists(nx, hard)
+    f, e = _parity(hip_lib, oracle_lib, lists, n=n)
+    bare = _bare(hip_lib, n)
+    faces = xc.extreme_faces(n)
+    differ = [f[1, c, k, j, i] != bare[1, c, k, j, i] for c, i, j, k in faces]
+    assert all(differ), [fc for fc, d in zip(faces, differ) if not d]
+    e.close()
+    e = main_sim(n=n).build(hip_lib)
+    col = lambda fc, amp: ([node(*fc[1:], n)], [fc[0]], [amp], [0])
+    none = ([], [], [], [])
+    refused = 0
+    for fc in faces:
+        for b in xc.beyond(fc, n):
+            for args, what in (((*col(b, 1.0), *none), "hard"), ((*none, *col(b, 1.0)), "soft")):
+                with pytest.raises(capi.FdtdError, match=f"{what} face 0 does not exist"):
+                    e.set_excite(*args, lists.sigH)
+                refused += 1
+    assert refused == 2 * 12
+    e.close()
+
+
+@pytest.mark.gpu
+def test_main_case_on_the_raw_operator_form(hip_lib, oracle_lib):
+    lists = main_lists()
+    form = []
+    _, e = _parity(hip_lib, oracle_lib, lists, use_classes=False, before=lambda q: form.append(q.operator_form()))
+    e.close()
+    e = main_sim().build(hip_lib)
+    assert form[0] != e.operator_form(), form          # (the two forms do differ: the main case above runs on class bytes)
+    e.close()
+
+
+@pytest.mark.gpu
+def test_a_second_set_replaces_the_first(hip_lib, oracle_lib):
+    """fdtd_excite_set twice before the first timestep: the run is that of a context that only ever had the second set; after a
+    timestep the call is refused and the context steps on unchanged."""
+    capi = pkg("_capi")
+    first, second = main_lists(), xc.plane_lists(257, True)
+    assert first.faces()[0].size != second.faces()[0].size
+    f, e = _parity(hip_lib, oracle_lib, second, before=lambda q: q.set_excite(*first.args()))
+    e.close()
+    once, e = _parity(hip_lib, oracle_lib, second)
+    e.close()
+    assert np.array_equal(f.view(np.uint32), once.view(np.uint32))
+    e = main_sim().build(hip_lib)
+    e.set_excite(*second.args())
+    seeded_fields(e, 4)
+    e.run(CALLS[0])
+    with pytest.raises(capi.FdtdError, match="before the first timestep"):
+        e.set_excite(*first.args())
+    with pytest.raises(capi.FdtdError, match="before the first timestep"):
+        e.set_excite(*[a[:0] for a in first.hard], *[a[:0] for a in first.soft], None)      # (removing it is refused too)
+    for k in CALLS[1:]:
+        e.run(k)
+    assert np.array_equal(e.fields().view(np.uint32), once.view(np.uint32))
+    e.close()
+
+
+@pytest.mark.gpu
+def test_hard_faces_held_at_zero(hip_lib, oracle_lib):
+    """A hard entry with amp = +0.0 and one whose delay lies past the run, read with get_field after every timestep.  The second holds
+    +0.0 bits throughout (0.7f * 0.0f).  The first holds a zero in every timestep: +0.0 outside the table and, inside it, 0.0f * s —
+    the statement I = amp * s of the header in IEEE arithmetic, a zero with the sign of s; the bits are asked exactly so."""
+    nsteps = sum(CALLS)
+    lists = xc.held_lists(nsteps)
+    ref = Restatement(main_sim(), oracle_lib, seed=4, tables={"excite": lists.args()})
+    e = main_sim().build(hip_lib)
+    e.set_excite(*lists.args())
+    seeded_fields(e, 4)
+    (g0, g1), (c0, c1), d0 = lists.hard[0], lists.hard[1], int(lists.hard[3][0])
+    assert e.get_field(1, int(c0)).reshape(-1)[g0] != 0 and e.get_field(1, int(c1)).reshape(-1)[g1] != 0      # (seeded: not zero to begin with)
+    signs = set()
+    for n in range(nsteps):
+        e.run(1)
+        ref.step()
+        a0, a1 = e.get_field(1, int(c0)).reshape(-1)[g0], e.get_field(1, int(c1)).reshape(-1)[g1]
+        s = lists.sigH[n - d0] if 0 <= n - d0 < lists.sigH.size else np.float32(0.0)
+        want = np.float32(0.0) * s
+        assert a1.view(np.uint32) == 0, (n, a1)
+        assert a0 == 0 and a0.view(np.uint32) == want.view(np.uint32), (n, a0, s)
+        signs.add(int(a0.view(np.uint32) >> 31))
+    assert signs == {0, 1}                        # (the table has samples of both signs under the first face)
+    assert np.array_equal(e.fields(), ref.e.fields())
+    e.close()
+
+
+@pytest.mark.gpu
+def test_set_field_of_the_currents_between_two_calls(hip_lib, oracle_lib):
+    """fdtd_set_field(FDTD_KIND_I) of all three components between two calls: the correction keeps no state, so the run is the
+    restatement's given the same fields at the same timestep."""
+    lists = main_lists()
+    ref = Restatement(main_sim(), oracle_lib, seed=4, tables={"excite": lists.args()})
+    e = main_sim().build(hip_lib)
+    e.set_excite(*lists.args())
+    seeded_fields(e, 4)
+    rng = np.random.default_rng(23)
+    for q, k in enumerate((8, 30, 42)):
+        if q:
+            for c in range(3):
+                a = (1e-3 * rng.standard_normal(e.local_shape)).astype(np.float32)
+                ref.set_field(1, c, a)
+                e.set_field(1, c, a)
+        ref.run(k)
+        e.run(k)
+        assert np.array_equal(e.fields(), ref.e.fields()), q
+    e.close()
+
+
+# ---- what samples I behind the excitation: I-probe, I-DFT box, recorder face (excite_cases.observer_scene) ---------------------------
+def _observers(hip_lib, kind, mode, drive, late_at=None):
+    """The observer scene on the HIP library: `mode` "dft" or "record", `drive` "auto", "direct" or "half", in calls of 8 and 72
+    timesteps; late_at = 8: the second I-probe is added between the two calls.  -> (engine, probe id, box id, late probe id)."""
+    capi = pkg("_capi")
+    sc, sim = xc.observer_scene(kind), xc.observer_sim(kind)
+    e = sim.build(hip_lib, flags=capi.FLAG_KERNEL_DIRECT if drive == "direct" else 0)
+    e.set_excite(*sc["lists"].args())
+    if sc["source"] is not None:
+        e.add_source(*sc["source"])
+    tw_v, tw_i, _ = xc.observer_twiddles(sim.dt)
+    if mode == "dft":
+        e.set_dft(xc.OBS_EVERY, tw_v, tw_i)
+    else:
+        e.set_recorder(xc.OBS_EVERY, tw_i.shape[0])
+    pid = e.add_probe(capi.KIND_I, *sc["probe"])
+    bid = e.add_dft_box(capi.KIND_I, *sc["box"])
+    seeded_fields(e, 5)
+    late = None
+    for q, k in enumerate((8, xc.OBS_STEPS - 8)):
+        if q and late_at is not None:
+            late = e.add_probe(capi.KIND_I, *sc["late"])
+        if drive == "half":
+            for _ in range(k):
+                e.half_step(capi.PHASE_E)
+                e.half_step(capi.PHASE_H)
+        else:
+            e.run(k)
+    return e, pid, bid, late
+
+
+def _check_observers(e, ref, mode, pid, bid, late, tag):
+    tw_i, ident = xc.observer_twiddles(ref.sim.dt)[1:]
+    assert np.array_equal(e.fields(), ref.fields), tag
+    assert np.array_equal(e.get_probe(pid)[:xc.OBS_STEPS], ref.series), (tag, "I-probe")              # bit-equal, as the suite asks of I-probes
+    if late is not None:         # 0.0 before its first timestep, the restated series from there on
+        got = e.get_probe(late)[:xc.OBS_STEPS]
+        assert not got[:ref.late_at].any() and np.array_equal(got[ref.late_at:], ref.late), (tag, "late I-probe")
+    scale = np.abs(ref.acc).max()
+    if mode == "dft":            # 1e-12 of the largest entry, as the suite asks of I-DFT boxes
+        box = e.get_dft_box(bid)[0]
+        assert box.shape == ref.acc.shape and np.abs(box - ref.acc).max() <= 1e-12 * scale, (tag, np.abs(box - ref.acc).max() / scale)
+    else:                        # the record itself (the identity table: exact), and its transform
+        rec = e.rec_transform(bid, ident)[0]
+        ns = ref.rec.shape[0]
+        assert not rec.imag.any() and np.array_equal(rec.real[:ns], ref.rec.astype(np.float64)) and not rec.real[ns:].any(), (tag, "record")
+        box = e.rec_transform(bid, tw_i)[0]
+        assert box.shape == ref.acc.shape and np.abs(box - ref.acc).max() <= 1e-12 * scale, (tag, np.abs(box - ref.acc).max() / scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["pec", "mur", "mur-near"])
+def test_observers_sample_the_current_behind_the_excitation(hip_lib, oracle_lib, monkeypatch, kind):
+    """An I-probe, an I-DFT box (dft mode) and a recorder face (record mode), each over a hard and a soft H face: fdtd_run under AUTO
+    and DIRECT and fdtd_half_step pairs, in two calls; with six Mur faces under both Mur schedules (two launches, three with the apply
+    pass); "mur-near": an excited face one node from a Mur face plane, probes sampled by k_post.  The second I-probe is added between
+    the two calls."""
+    ref = xc.observed(oracle_lib, kind)
+    assert np.abs(ref.series).max() > 0 and np.abs(ref.late).max() > 0 and ref.late.size == xc.OBS_STEPS - ref.late_at
+    runs = [(None, drive) for drive in ("auto", "direct", "half")] + ([("1", "auto"), ("1", "direct")] if kind != "pec" else [])
+    launches = set()
+    for apply_pass, drive in runs:
+        if apply_pass is None:
+            monkeypatch.delenv("FDTD_MUR_APPLY_PASS", raising=False)
+        else:
+            monkeypatch.setenv("FDTD_MUR_APPLY_PASS", apply_pass)
+        for mode in ("dft", "record"):
+            tag = f"{kind}, {drive}, apply pass {apply_pass}, {mode}"
+            e, pid, bid, late = _observers(hip_lib, kind, mode, drive, late_at=ref.late_at)
+            info = e.schedule_info()
+            assert not info["resident"] and info["launches_per_timestep"] >= 2, (tag, info)
+            launches.add(info["launches_per_timestep"])
+            _check_observers(e, ref, mode, pid, bid, late, tag)
+            e.close()
+    # fused sources and probes: two launches, three with the Mur apply pass; "mur-near": more — the sources and the probes (k_post) and
+    # the Mur passes are launches of their own
+    assert launches == {2} if kind == "pec" else launches == {2, 3} if kind == "mur" else min(launches) > 3, launches
 
 
 # ---- hard E edges: no kernel of their own, every schedule --------------------------------------------------------------------------

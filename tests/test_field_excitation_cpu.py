@@ -449,3 +449,114 @@ def test_coaxial_line_without_a_port_class(oracle_lib):
         assert np.all(z.real > 0) and np.abs(z.imag).max() < 0.01 * z0          # a travelling wave towards +z
     assert dev[0] <= BAR and dev[1] <= BAR
     assert dev[1] < dev[0]
+
+
+# ---- the directed list shapes and the observer scene of test_excite_gpu.py, on the reference alone --------------------------------
+def _restated_fields(oracle_lib, lists, n=xc.MAIN_GRID, nsteps=80, seed=4):
+    from restatement import Restatement
+    r = Restatement(xc.main_sim(n=n), oracle_lib, seed=seed, tables=None if lists is None else {"excite": lists.args()})
+    r.run(nsteps)
+    return r.e.fields()
+
+
+def test_directed_lists_are_on_their_side_of_each_threshold():
+    """Integer arithmetic on the lists alone: the face counts around k_excite's block of 256, the one face with 300 entries before,
+    inside and past the table, the two listings of the 40 faces, and the faces at the grid's extremes."""
+    assert xc.PLANE_COUNTS == (1, 255, 256, 257)
+    for count in xc.PLANE_COUNTS:
+        for hard in (False, True):
+            l = xc.plane_lists(count, hard)
+            fi, fc = l.faces()
+            assert fi.size == count and (count + 255) // 256 == (1 if count <= 256 else 2)
+            assert np.all(fi // (xc.MAIN_GRID[0] * xc.MAIN_GRID[1]) == 5)                              # one node plane
+            assert all(xc.face_exists(int(c), *_ijk(int(g)), xc.MAIN_GRID) for g, c in zip(fi, fc))
+            assert l.hard[0].size == (count if hard else 0) and {0, 3, 57} >= set(l.soft[3].tolist())
+    l = xc.many_entries_lists()
+    amp, delay = l.soft[2], l.soft[3]
+    assert l.faces()[0].size == 1 and amp.size == 300 and (amp > 0).sum() > 100 and (amp < 0).sum() > 100
+    assert np.abs(amp).max() / np.abs(amp).min() > 3e5 and np.abs(amp).max() <= 1e-3
+    # 80 timesteps, 40 samples: read from the first timestep on; starting inside the run; never reached
+    assert (delay == 0).any() and ((delay > 0) & (delay < 40)).sum() > 50 and (delay >= 80).sum() > 50 and ((delay >= 40) & (delay < 80)).sum() > 50
+    a, b = xc.forty_faces_lists("face-major"), xc.forty_faces_lists("entry-major")
+    assert a.faces()[0].size == 40 and a.soft[0].size == 120 and set(a.faces()[1].tolist()) == {0, 1, 2}
+    ka, kb = a.soft[0] * 3 + a.soft[1], b.soft[0] * 3 + b.soft[1]
+    assert np.all(ka.reshape(40, 3) == ka.reshape(40, 3)[:, :1]) and np.all(kb.reshape(3, 40) == kb[:40]) and np.unique(kb[:40]).size == 40
+    oa, ob = np.argsort(ka, kind="stable"), np.argsort(kb, kind="stable")         # the host's grouping: a stable sort on 3 idx + comp
+    for q in range(4):
+        assert np.array_equal(a.soft[q][oa], b.soft[q][ob])
+    assert np.array_equal(a.rank[oa], b.rank[ob]) and np.array_equal(a.sigH, b.sigH)
+    for nx in xc.NX_EXTREMES:
+        n = (nx,) + xc.MAIN_GRID[1:]
+        faces = xc.extreme_faces(n)
+        assert len(set(faces)) == 15 and all(xc.face_exists(*f, n) for f in faces)
+        for c in range(3):
+            mine = [f for f in faces if f[0] == c]
+            assert (c, 0, 0, 0) in mine
+            for a_ in range(3):
+                assert max(f[1 + a_] for f in mine) == (n[a_] - 1 if a_ == c else n[a_] - 2)
+        far = [b_ for f in faces for b_ in xc.beyond(f, n)]
+        assert len(far) == 12 and all(0 <= p < n[a_] for b_ in far for a_, p in enumerate(b_[1:])) and not any(xc.face_exists(*b_, n) for b_ in far)
+        for hard in (False, True):
+            l = xc.extreme_lists(nx, hard)
+            assert l.faces()[0].size == 15 and (l.hard[0].size, l.soft[0].size) == ((15, 0) if hard else (0, 18))
+    assert {nx % 4 for nx in xc.NX_EXTREMES} == {0, 1, 2, 3}
+
+
+def _ijk(g, n=xc.MAIN_GRID):
+    return g % n[0], g // n[0] % n[1], g // (n[0] * n[1])
+
+
+def test_directed_lists_on_the_reference(oracle_lib):
+    """The reference side of the directed cases: 300 entries on one face in reversed list order give other bits; the 40 faces listed
+    face by face and entry by entry give the same bits, and with each face's entries reversed other ones; every face at the grid's
+    extremes ends the run with another current than without the set; the held faces read zero."""
+    bare = _restated_fields(oracle_lib, None)
+    fwd, rev = _restated_fields(oracle_lib, xc.many_entries_lists()), _restated_fields(oracle_lib, xc.many_entries_lists(reverse=True))
+    assert np.isfinite(fwd).all() and not np.array_equal(fwd, bare) and not np.array_equal(fwd, rev)
+    a, b = xc.forty_faces_lists("face-major"), xc.forty_faces_lists("entry-major")
+    fa, fb = _restated_fields(oracle_lib, a), _restated_fields(oracle_lib, b)
+    assert np.array_equal(fa.view(np.uint32), fb.view(np.uint32)) and not np.array_equal(fa, bare)
+    flipped = xc.HLists(a.hard, tuple(np.asarray(q).reshape(40, 3)[:, ::-1].ravel() for q in a.soft), a.sigH)
+    assert not np.array_equal(_restated_fields(oracle_lib, flipped), fa)
+    for nx in xc.NX_EXTREMES:
+        n = (nx,) + xc.MAIN_GRID[1:]
+        none = _restated_fields(oracle_lib, None, n=n)
+        for hard in (False, True):
+            f = _restated_fields(oracle_lib, xc.extreme_lists(nx, hard), n=n)
+            same = [fc for fc in xc.extreme_faces(n) if f[1, fc[0], fc[3], fc[2], fc[1]] == none[1, fc[0], fc[3], fc[2], fc[1]]]
+            assert np.isfinite(f).all() and not same, (nx, hard, same)
+    l = xc.held_lists(80)
+    f = _restated_fields(oracle_lib, l)
+    assert all(f[1, int(c)].reshape(-1)[g] == 0 for g, c in zip(l.hard[0], l.hard[1])) and not np.array_equal(f, bare)
+
+
+@pytest.mark.parametrize("kind", sorted(xc.OBS_KINDS))
+def test_observers_tell_behind_the_excitation_from_in_front_of_it(oracle_lib, kind):
+    """The observer scene on the reference alone: the I-probe, the box's running DFT sums and its record, read from the restated I in
+    front of `excite` instead of behind it, all change — so a library that samples one of them in front of k_excite cannot pass."""
+    sc = xc.observer_scene(kind)
+    n = xc.OBS_GRID
+    assert max(n[0] - 24, n[1] - 20, n[2] - 16) <= 0
+    c, lo, hi = sc["box"]
+    inside = lambda f: f[0] == c and all(lo[a] <= f[1 + a] <= hi[a] for a in range(3))
+    hk, sk = sc["lists"].hard[0] * 3 + sc["lists"].hard[1], sc["lists"].soft[0] * 3 + sc["lists"].soft[1]
+    key = lambda f: xc.node(*f[1:], n) * 3 + f[0]
+    assert inside(sc["hard"]) and inside(sc["soft"]) and key(sc["hard"]) in hk and key(sc["hard"]) not in sk and (sk == key(sc["soft"])).sum() == 2
+    for probe in (sc["probe"], sc["late"]):
+        pk = set((probe[0] * 3 + probe[1]).tolist())
+        assert {key(sc["hard"]), key(sc["soft"])} <= pk
+    if kind == "mur-near":
+        assert sc["hard"][1] == 1 and sc["soft"][2] == n[1] - 2 and sc["source"][0][0] % n[0] == 1      # one node from x-; the last cell row; the plane next to x-
+    ref = xc.observed(oracle_lib, kind)
+    assert np.isfinite(ref.fields).all() and ref.series.size == xc.OBS_STEPS and ref.late.size == xc.OBS_STEPS - ref.late_at
+    assert np.count_nonzero(ref.series != ref.series_front) > xc.OBS_STEPS // 2
+    scale = np.abs(ref.acc).max()
+    assert np.abs(ref.acc - ref.acc_front).max() > 1e-3 * scale
+    at = lambda a, f: a[..., f[3] - lo[2], f[2] - lo[1], f[1] - lo[0]]
+    for f in (sc["hard"], sc["soft"]):      # ... on both faces, in the sums and in the record
+        assert np.abs(at(ref.acc, f) - at(ref.acc_front, f)).max() > 1e-3 * scale
+        assert np.count_nonzero(at(ref.rec, f) != at(ref.rec_front, f)) >= 3
+    # the hard face reads the excitation itself
+    amp, d = sc["lists"].hard[2][0], int(sc["lists"].hard[3][0])
+    sig = np.concatenate([np.zeros(d, np.float32), sc["lists"].sigH, np.zeros(xc.OBS_STEPS, np.float32)])[:xc.OBS_STEPS]
+    assert np.array_equal(at(ref.rec, sc["hard"]), (amp * sig)[::xc.OBS_EVERY])

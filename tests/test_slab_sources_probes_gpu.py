@@ -76,6 +76,41 @@ def _run_and_check(case, cuts, transport, hip_lib, oracle_lib, monkeypatch):
     probes = case.all_probes()
     check_slabs(engs, cuts, probes, list(range(len(probes))), min(case.nsteps, case.cap), ref["fields"], spc.slab_trees(case, oracle_lib, cuts),
                 ref["own"], what)
+    if case.hard is not None:
+        _hard_edges_hold(case, engs, cuts, what)
+
+
+def _hard_edges_hold(case, engs, cuts, what):
+    """Every rank's operator shows vv = vi = 0 on the hard edges it owns (fdtd_build_operator keeps the overrides of its slab); on the
+    owning rank a V-probe on a hard edge reads float32(amp * sig[n - d]) exactly, 0.0 outside the table, and 0.0 on every other rank —
+    the check of test_excite_gpu.test_hard_e_under_all_three_schedules, per rank."""
+    idx, comp, amp, delay = case.hard
+    plane = case.shape[0] * case.shape[1]
+    owned_any = 0
+    for e, (k0, nk) in zip(engs, cuts):
+        own = spc.in_planes(case, idx, (k0, nk))
+        op = e.get_operator()
+        local = idx[own] - k0 * plane
+        assert op[0].shape[1] == nk and not op[0].reshape(3, -1)[comp[own].astype(int), local].any(), (what, "vv", k0)
+        assert not op[1].reshape(3, -1)[comp[own].astype(int), local].any(), (what, "vi", k0)
+        owned_any += int(own.sum())
+    assert owned_any == idx.size
+    checked = 0
+    for q, (first, (kind, pidx, pcomp, w)) in enumerate(case.all_probes()):
+        if kind != spc.KIND_V or pidx.size != 1:
+            continue
+        hit = np.flatnonzero((idx == pidx[0]) & (comp == pcomp[0]))
+        if not hit.size:
+            continue
+        want = spc.hard_table(case, int(hit[0]))
+        for e, planes in zip(engs, cuts):
+            got = e.get_probe(q)
+            if spc.in_planes(case, pidx, planes)[0]:
+                assert np.array_equal(got, want) and want.any(), (what, q, planes)
+            else:
+                assert not got.any(), (what, q, planes)
+        checked += 1
+    assert checked >= 4, what
 
 
 @pytest.mark.parametrize("name,cuts,transport,outcome", spc.SLAB_RUNS,

@@ -24,7 +24,8 @@ def _bits(a):
 def _twin_fields(case, lib):
     """The case without its sources, half-stepped, the sources added in numpy after every E half-step: in list order
     V = float32(V + float32(amp * sig[step - delay])) where 0 <= step - delay < nsig."""
-    e = spc.raw_engine(lib, (case.scene, case.shape), case.boundary, 0, case.cap, cpml_cells=case.cpml_cells)
+    e = spc.raw_engine(lib, (case.scene, case.shape), case.boundary, 0, case.cap, cpml_cells=case.cpml_cells,
+                       hard=None if case.hard is None else case.hard[:2])
     e.set_signal(case.signal)
     if case.seed is not None:
         spc.seeded_fields(e, case.seed)
@@ -243,3 +244,70 @@ def test_tree_sum_is_the_documented_order():
     f[0], f[1], f[256] = 1e16, 1.0, -1e16
     assert spc.tree_sum(w, f) == 1.0 and float(np.float32(1e16)) + 1.0 - float(np.float32(1e16)) == 0.0
     assert spc.tree_sum([], []) == 0.0
+
+
+# ---- hard E edges and probes.py lists on the slabs (source_probe_cases H1 ... H4) -------------------------------------------------------
+def test_hard_cases_sit_on_the_cut_planes():
+    """Integer arithmetic: every hard edge lies on a plane its case claims, each edge once; H1 has an edge on planes k0 - 1 and k0 of
+    every cut, H2 x and y edges IN every cut plane; H3's soft list spans every slab with three delays and one edge twice, and its
+    probes.py lists (voltage line, current loop) have cells on both sides of every cut, its point probes a node on either side of 7 | 8;
+    H4 has hard edges in the second block of a strip-plane."""
+    plane = spc.SLAB_SHAPE[0] * spc.SLAB_SHAPE[1]
+    for name in spc.HARD_CASES:
+        c = spc.DIRECTED[name]
+        idx, comp, amp, delay = c.hard
+        k = idx // (c.shape[0] * c.shape[1])
+        assert sorted(set(k.tolist())) == list(spc.HARD_PLANES[name]) and np.unique(idx * 3 + comp).size == idx.size and np.all(delay >= 0) and np.all(amp != 0)
+        for q in range(idx.size):
+            t = spc.hard_table(c, q)
+            assert t.any() and t.size == c.nsteps and not t[:int(delay[q])].any() and not t[int(delay[q]) + len(c.signal):].any()
+    cuts_k0 = sorted({k0 for cuts in (spc.CUT_2, spc.CUT_3) for k0, _ in cuts[1:]})
+    assert cuts_k0 == [7, 8, 9]
+    h1, h2 = spc.DIRECTED["H1-line"], spc.DIRECTED["H2-plate"]
+    k1 = set((h1.hard[0] // plane).tolist())
+    assert set(h1.hard[1].tolist()) == {2} and all({k0 - 1, k0} <= k1 for k0 in cuts_k0)
+    for k0 in cuts_k0:
+        on = h2.hard[0] // plane == k0
+        assert set(h2.hard[1][on].tolist()) == {0, 1} and on.sum() == 40 > spc.SRC_SCAN_MAX
+    assert np.array_equal(spc.DIRECTED["H2-plate-mur"].hard[0], h2.hard[0]) and spc.DIRECTED["H2-plate-mur"].boundary[:4] == ("MUR",) * 4
+    h3 = spc.DIRECTED["H3-soft-and-probes"]
+    idx, comp, amp, delay = h3.sources[0]
+    key = idx * 3 + comp
+    assert set(delay.tolist()) == {0, 4, 9} and np.unique(key).size == key.size - 1 and np.unique(amp).size > 20
+    for cuts in (spc.CUT_2, spc.CUT_3):
+        facts = spc.slab_facts(h3, cuts)
+        assert all(f["sp_max"] > 0 for f in facts) and any(f["dup"] for f in facts)
+        for q, pname in enumerate(h3.probe_names):
+            owners = sum(f["cells"][q] > 0 for f in facts)
+            assert owners == (len(cuts) if pname in ("ut", "it") else 1), (pname, cuts, owners)      # the line and the loop: cells on every slab
+    node_k = {pname: int(h3.probes[q][1][0] // plane) for q, pname in enumerate(h3.probe_names)}
+    assert (node_k["et7"], node_k["et8"], node_k["ht7"], node_k["ht8"]) == (7, 8, 7, 8)
+    assert [p[0] for p in h3.probes] == [0, 1] + [0] * 6 + [1] * 6 and h3.probes[0][1].size == 6 and h3.probes[1][1].size == 18
+    r = spc.regimes(spc.DIRECTED["H4-second-block"])
+    assert r["src_blocks"] == [0, 1] and r["blocks_per_strip_plane"] == 2
+    for name in ("H1-line", "H2-plate", "H3-soft-and-probes"):
+        assert {t for n, _, t, _ in spc.SLAB_RUNS if n == name} == set(spc.TRANSPORTS)
+        assert {(s, o) for n, s, o, _ in spc.RUNS if n == name} == {("RESIDENT", "resident"), ("WF1", "one"), ("DIRECT", "two")}
+    assert any(o.startswith("refused") for n, _, _, o in spc.SLAB_RUNS if n == "H2-plate-mur")
+
+
+@pytest.mark.parametrize("name", spc.HARD_CASES)
+def test_hard_edges_on_the_oracle(oracle_lib, name):
+    """The oracle's operator holds vv = vi = 0 on every hard edge and its V-probes on them read float32(amp * sig[n - d]) exactly; with
+    the override of ONE hard edge dropped the fields are others."""
+    case = spc.DIRECTED[name]
+    ref = spc.reference(case, oracle_lib)
+    e = spc.engine_for(case, oracle_lib)
+    op = e.get_operator()
+    idx, comp, amp, delay = case.hard
+    assert not op[0].reshape(3, -1)[comp.astype(int), idx].any() and not op[1].reshape(3, -1)[comp.astype(int), idx].any()
+    for q, (first, (kind, pidx, pcomp, w)) in enumerate(case.all_probes()):
+        hit = np.flatnonzero((idx == pidx[0]) & (comp == pcomp[0])) if pidx.size == 1 and kind == spc.KIND_V else []
+        if len(hit):
+            assert np.array_equal(ref["own"][q], spc.hard_table(case, int(hit[0]))) and np.array_equal(ref["tree"][q], ref["own"][q])
+    assert sum(1 for _, p in case.all_probes() if p[1].size == 1) >= 4
+    keep = np.arange(idx.size) != idx.size // 2
+    e2 = spc.raw_engine(oracle_lib, (case.scene, case.shape), case.boundary, 0, case.cap, cpml_cells=case.cpml_cells, hard=(idx[keep], comp[keep]))
+    spc.apply(case, e2)
+    spc.run(case, e2)
+    assert not np.array_equal(e2.fields(), ref["fields"])

@@ -88,6 +88,18 @@ def _run_and_compare(case, sched, outcome, env, hip_lib, oracle_lib):
     _schedule_is(info, outcome, case, sched, env)
     _fields_equal(e.fields(), ref["fields"], (case.name, sched, env))
     _series_equal(case, e, ref, (case.name, sched, env))
+    if case.hard is not None:      # hard E edges: the overridden operator, and on every hard edge under a V-probe amp * sig[n - d] exactly
+        idx, comp, amp, delay = case.hard
+        op = e.get_operator()
+        assert not op[0].reshape(3, -1)[comp.astype(int), idx].any() and not op[1].reshape(3, -1)[comp.astype(int), idx].any(), (case.name, sched)
+        checked = 0
+        for q, (first, (kind, pidx, pcomp, w)) in enumerate(case.all_probes()):
+            hit = np.flatnonzero((idx == pidx[0]) & (comp == pcomp[0])) if (kind == spc.KIND_V and pidx.size == 1) else np.zeros(0, int)
+            if hit.size:
+                want = spc.hard_table(case, int(hit[0]))
+                assert want.any() and np.array_equal(e.get_probe(q), want), (case.name, sched, q)
+                checked += 1
+        assert checked >= 4, (case.name, sched)
     return e
 
 
