@@ -16,6 +16,7 @@
 #include "host_tables.hpp"
 #include "../../include/fdtd_hip_traffic.h"
 #include "kernel_common.hpp"   // fdtd_ctx.h + the device helpers of the mailbox protocol (self-test kernels below)
+#include "corrections.hpp"     // the step-loop corrections: one row each, all this file knows of them
 
 static thread_local std::string g_err;
 
@@ -269,14 +270,7 @@ void fdtd_destroy(fdtd_ctx* c) {
   for (int b = 0; b < c->nbox; ++b) { hipFree(c->box[b].acc); hipFree(c->box[b].rec); }
   hipFree(c->d_probe); hipFree(c->d_box); hipFree(c->tw_v); hipFree(c->tw_i);
   hipFree(c->d_energy); hipFree(c->src_rng); hipFree(c->src_ids);
-  sheet_free(c);
-  lumped_free(c);
-  planewave_free(c);
-  excite_free(c);
-  media_free(&c->debye);
-  media_free(&c->lorentz);
-  magnetic_free(c);
-  conformal_free(c);
+  for (const CorrectionRow* k : corrections) k->release(c);
   if (c->peer_lo && c->peer_lo_ipc) hipIpcCloseMemHandle(c->peer_lo);
   if (c->peer_hi && c->peer_hi_ipc) hipIpcCloseMemHandle(c->peer_hi);
   hipFree(c->mbox);
@@ -863,49 +857,37 @@ static bool mur_post_fusable(const fdtd_ctx* c, bool multi, bool fused) {
 // voltages in memory are then the E update's own, and inside update_H they are being overwritten: whoever reads V there —
 // V-probes (sampled by update_H's extra block), NF2FF / DFT boxes (sampled between the two launches) — must not hold a
 // node of a Mur face.  (The reference's probes and boxes sit inside the grid.)  Needs the post pass inside update_E.
-// k_sheet runs between the two launches and reads and writes V: a sheet edge on the node plane of an enabled face takes the apply pass
-// too (the header's order: Mur passes, then the correction).  k_debye needs no such rule: the operator holds vi = 0 on every edge of a
-// grid face, and fdtd_debye_set leaves those edges out (their V is never the correction's to change, their states never act).
-// k_lumped is a sparse correction as k_sheet is, and so is k_planewave's edge list (fdtd_planewave_set takes any existing edge; the
-// operator holds vi = 0 on a face's node plane, but the list's coefficients are the caller's): the two questions the planner has are
-// asked of "a sheet, lumped or plane-wave edge".  The plane wave's FACE list is not asked: fused I-probes are sampled by the next
-// update_E's probe blocks or by the flush at the end of the call, both behind it, and the Mur passes never touch I.
-static bool correction_on_face(const fdtd_ctx* c, int f) { return ((c->sheet.faces | c->lumped.faces | c->pw_faces) >> f) & 1u; }   // (0 without edges)
-static bool correction_at(const fdtd_ctx* c, int off) {   // an edge of a sparse correction on the node at local offset `off`
-  for (const std::vector<int>* h : {&c->sheet.h_off, &c->lumped.h_off, &c->pw_h_off})
-    if (std::binary_search(h->begin(), h->end(), off)) return true;
+// A sparse E-side correction runs between the two launches and reads and writes V: a listed edge on the node plane of an enabled face
+// takes the apply pass too (the headers' order: Mur passes, then the correction).  The volume corrections need no such rule: the operator
+// holds vi = 0 on every edge of a grid face, and their set functions leave those edges out (their V is never the correction's to change,
+// their states never act).
+// Every sparse E-side list is asked the planner's two questions alike (the rows with edge_facts, corrections.hpp; a listed edge may be
+// any existing edge: the operator holds vi = 0 on a face's node plane, but a list's coefficients can be the caller's).  H-side lists are
+// not asked: fused I-probes are sampled by the next update_E's probe blocks or by the flush at the end of the call, both behind them,
+// and the Mur passes never touch I.
+static bool correction_on_face(const fdtd_ctx* c, int f) {   // an edge of a sparse correction on the node plane of grid face f
+  for (const CorrectionRow* k : corrections)
+    if (k->edge_facts && ((k->edge_facts(c)->faces >> f) & 1u)) return true;
+  return false;
+}
+static bool correction_at(const fdtd_ctx* c, int off) {   // ... on the node at local offset `off`
+  for (const CorrectionRow* k : corrections)
+    if (k->edge_facts && std::binary_search(k->edge_facts(c)->h_off.begin(), k->edge_facts(c)->h_off.end(), off)) return true;
   return false;
 }
 
-// What the planner knows of the corrections (enum Correction: their launch order, and the order of the refusals): is one set, its name in
-// the messages, whether it runs behind the H update (else between the E phase and the H update: either way two launches per timestep, no
-// k_step, no k_resident), and whether linked contexts are refused besides decomposed grids and the p2p transport.
-struct CorrectionInfo { bool active; const char* name; bool after_H; bool no_links; };
-static CorrectionInfo correction(const fdtd_ctx* c, int which) {
-  switch (which) {
-    case CORR_SHEET:    return {c->sheet.n > 0, "conducting sheets", false, false};
-    case CORR_DEBYE:    return {c->debye.nmedia > 0, "Debye media", false, true};
-    case CORR_LORENTZ:  return {c->lorentz.nmedia > 0, "Lorentz media", false, true};
-    case CORR_LUMPED:   return {c->lumped.n > 0, "lumped elements", false, true};
-    case CORR_MAGNETIC: return {c->mag_ncls > 0, "magnetic materials", true, true};
-    case CORR_CONFORMAL: return {c->conf_n > 0, "conformal boundaries", true, true};
-    case CORR_PLANEWAVE: return {c->pw[0].n > 0 || c->pw[1].n > 0, "plane-wave excitation", true, true};   // (its edge list runs behind the E phase as well)
-    default:            return {c->excite.n > 0, "H-field excitations", true, true};
-  }
-}
+// What the planner knows of the corrections is their rows (corrections.hpp; the table's order is the order of the refusals).  One that
+// is set means two launches per timestep, no k_step, no k_resident: it runs between the E phase and the H update, or behind the H update.
 static bool any_correction(const fdtd_ctx* c) {
-  for (int q = 0; q < CORR_COUNT; ++q)
-    if (correction(c, q).active) return true;
+  for (const CorrectionRow* k : corrections)
+    if (k->active(c)) return true;
   return false;
 }
-}  // extern "C" (the *_set functions of the other files call this one)
-int correction_single_slab(fdtd_ctx* c, Correction which) {
-  const CorrectionInfo k = correction(c, which);
-  if (c->d.world > 1 || c->p.p2p || (k.no_links && (c->link_lo || c->link_hi)))
-    return fdtd_fail(c, FDTD_E_UNSUPPORTED, k.no_links ? "%s: single slab only (world = 1, no p2p transport, no linked contexts)" : "%s: single slab only (world = 1)", k.name);
-  return FDTD_OK;
+// ... and their launches of one side, in that side's order (no-ops without a set)
+static void launch_corrections(fdtd_ctx* c, int kind, long long step, hipStream_t s) {
+  if (kind == FDTD_KIND_V) for (const Correction q : launch_order_E) corrections[q]->launch_E(c, step, s);
+  else for (const Correction q : launch_order_H) corrections[q]->launch_H(c, step, s);
 }
-extern "C" {
 static bool mur_direct_possible(const fdtd_ctx* c, bool multi, bool fused) {
   if (!c->mur_no_apply || !mur_post_fusable(c, multi, fused)) return false;
   for (int f = 0; f < 6; ++f)
@@ -1047,15 +1029,15 @@ struct StepPlan {
   bool probes_first = false;   // two launches, fused: the V-probes in a launch of their own in front of the corrections (probes_first)
 };
 
-// The corrections of the Debye media and the conducting sheets follow the V-probes (the headers' order).  With fused sources the V-probes
-// of a timestep are otherwise sampled by the probe blocks of update_H, i.e. after the corrections: wrong as soon as a correction changes
-// a voltage a probe reads.  Debye media are volumes (ports sit inside substrates): always.  Sheet edges are few and the scene layer keeps
-// them off the probe lines: only when a V-probe cell sits on the node of a sheet edge (whatever the components: cheap and on the safe side).
-// Lumped-element edges: as the sheets'.  The plane wave's edge list: as the sheets' (the scene layer keeps probes off the box surface, the
-// C ABI does not).
+// The E-side corrections follow the V-probes (the headers' order).  With fused sources the V-probes of a timestep are otherwise sampled
+// by the probe blocks of update_H, i.e. after the corrections: wrong as soon as a correction changes a voltage a probe reads.  Volumes
+// (dispersive media: ports sit inside substrates): always.  The edges of a sparse list are few and the scene layer keeps them off the
+// probe lines (the C ABI does not): only when a V-probe cell sits on the node of a listed edge (whatever the components: cheap and on
+// the safe side).
 static bool probes_first(const fdtd_ctx* c) {
   if (c->nprobe == 0) return false;
-  if (correction(c, CORR_DEBYE).active || correction(c, CORR_LORENTZ).active) return true;   // (Lorentz / Drude media are volumes as well)
+  for (const CorrectionRow* k : corrections)
+    if (k->volume && k->active(c)) return true;
   for (int q = 0; q < c->nprobe; ++q) {
     if (c->probe[q].kind != FDTD_KIND_V) continue;
     for (int off : c->h_prb_off[q])
@@ -1074,13 +1056,12 @@ static int plan_schedule(fdtd_ctx* c, bool linked, StepPlan* out) {
   const unsigned sel = c->d.flags & FDTD_FLAG_KERNEL_MASK;
   const bool multi = c->d.world > 1;
   const bool fused = sources_fusable(c);
-  for (int q = 0; q < CORR_COUNT; ++q) {
-    const CorrectionInfo k = correction(c, q);
-    if (!k.active) continue;
-    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)
-      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "%s: the two-launch schedule only (their correction runs between the %s)", k.name,
-                       k.after_H ? "H update and the next E phase" : "E phase and the H update");
-    if (int r = correction_single_slab(c, (Correction)q)) return r;
+  for (const CorrectionRow* k : corrections) {
+    if (!k->active(c)) continue;
+    if (sel == FDTD_FLAG_KERNEL_WAVEFRONT || sel == FDTD_FLAG_KERNEL_RESIDENT)   // (a correction of both sides is named by its H side)
+      return fdtd_fail(c, FDTD_E_UNSUPPORTED, "%s: the two-launch schedule only (their correction runs between the %s)", k->name,
+                       k->launch_H ? "H update and the next E phase" : "E phase and the H update");
+    if (int r = correction_single_slab(c, *k)) return r;
   }
   if (sel == FDTD_FLAG_KERNEL_RESIDENT) {
     const char* why = "";
@@ -1178,10 +1159,11 @@ static int phase_E(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
   if (!post_in_E) launch_mur(c, 1, s);          // post pass (a no-op without Mur faces)
   if (pl.mur != MUR_DIRECT) launch_mur(c, 2, s);   // apply pass, unless update_H takes the candidates itself
   if (!pl.fused) launch_post(c, FDTD_KIND_V, step, true, s);
-  // Debye media, a sheet, lumped or plane-wave edge under a V-probe: the correction follows the V-probes, so these cannot wait for the probe blocks of update_H
+  // a volume correction, or a listed edge under a V-probe: the correction follows the V-probes, so these cannot wait for the probe blocks of update_H
   // (phase_H leaves them out)
   else if (pl.probes_first) launch_post(c, FDTD_KIND_V, step, false, s);
   launch_dft(c, FDTD_KIND_V, step, s);
+  launch_corrections(c, FDTD_KIND_V, step, s);   // after the whole E phase and whatever samples its V, before the H update
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_E, s));
   return FDTD_OK;
 }
@@ -1211,10 +1193,7 @@ static int phase_H(fdtd_ctx* c, const StepPlan& pl, ProfEvents* pe, int n) {
     if (r) return r;
     launch_update_H(c, nk - 1, nk, step, false, s);
   }
-  launch_magnetic(c, s);   // magnetic faces: after the whole H update, before anything samples I (no-op without faces)
-  launch_conformal(c, s);  // conformal faces: likewise
-  launch_planewave(c, FDTD_KIND_I, step, s);   // plane wave: the faces just outside the box (no-op without one)
-  launch_excite(c, step, s);                   // H-field excitations: last of the H side (no-op without a set)
+  launch_corrections(c, FDTD_KIND_I, step, s);   // after the whole H update, before anything samples I
   if (!pl.fused) launch_post(c, FDTD_KIND_I, step, false, s);
   launch_dft(c, FDTD_KIND_I, step, s);
   if (multi && !pl.rccl_inline) HIPCK(c, hipEventRecord(c->ev_H, s));
@@ -1373,11 +1352,6 @@ static int step_loop(fdtd_ctx* c, int nsteps, ProfEvents* pe) {
   }
   for (int n = 0; n < nsteps; ++n) {
     if ((r = phase_E(c, pl, pe, n))) return r;
-    launch_debye(c, c->stream);   // Debye media: after the whole E phase, before the sheets' correction and the H update (no-op without media)
-    launch_lorentz(c, c->stream); // Lorentz / Drude media: behind the Debye media's correction (no-op without media)
-    launch_sheet(c, c->stream);   // conducting sheets: after the whole E phase, before the H update (no-op without sheets)
-    launch_lumped(c, c->stream);  // lumped elements: behind the sheets' correction, before the H update (no-op without elements)
-    launch_planewave(c, FDTD_KIND_V, c->step, c->stream);   // plane wave: the box surface's edges, last of the E side (no-op without one)
     if (multi && (r = exchange(c, FDTD_HALO_E_DOWN, pl.rccl_inline))) return r;
     if ((r = phase_H(c, pl, pe, n))) return r;
     if (multi && (r = exchange(c, FDTD_HALO_H_UP, pl.rccl_inline))) return r;
@@ -1497,17 +1471,10 @@ int fdtd_half_step(fdtd_ctx* c, int phase) {
     launch_mur(c, 2, s);
     launch_post(c, FDTD_KIND_V, c->step, true, s);
     launch_dft(c, FDTD_KIND_V, c->step, s);
-    launch_debye(c, s);
-    launch_lorentz(c, s);
-    launch_sheet(c, s);
-    launch_lumped(c, s);
-    launch_planewave(c, FDTD_KIND_V, c->step, s);
+    launch_corrections(c, FDTD_KIND_V, c->step, s);
   } else if (phase == FDTD_PHASE_H) {
     launch_update_H(c, 0, c->d.nk, c->step, false, s);
-    launch_magnetic(c, s);
-    launch_conformal(c, s);
-    launch_planewave(c, FDTD_KIND_I, c->step, s);
-    launch_excite(c, c->step, s);
+    launch_corrections(c, FDTD_KIND_I, c->step, s);
     launch_post(c, FDTD_KIND_I, c->step, false, s);
     launch_dft(c, FDTD_KIND_I, c->step, s);
     c->step++;
@@ -2054,10 +2021,10 @@ int fdtd_set_field(fdtd_ctx* c, int kind, int comp, const float* in) {
   float* dst = kind == FDTD_KIND_V ? c->p.V[comp] : c->p.I[comp];
   HIPCK(c, hipMemcpy2D(dst, (size_t)c->P * 4, in, (size_t)c->d.nx * 4, (size_t)c->d.nx * 4, (size_t)c->d.nk * c->d.ny,
                        hipMemcpyHostToDevice));
-  if (kind == FDTD_KIND_I) {   // magnetic and conformal faces: i_prev is the I the next H update starts from
-    const int r = magnetic_prime(c, comp);
-    return r ? r : conformal_prime(c, comp);
-  }
+  if (kind == FDTD_KIND_I)   // state a correction keeps of I (i_prev: the I the next H update starts from)
+    for (const CorrectionRow* k : corrections)
+      if (k->prime)
+        if (int r = k->prime(c, comp)) return r;
   return FDTD_OK;
 }
 

@@ -6,7 +6,7 @@
 // component, four coefficients: 32 bytes, two 16-byte loads) and i_prev read from consecutive memory by consecutive lanes, four
 // gathered voltages, one scattered current.  Every statement is one fp32 operation in the order the header spells
 // (-ffp-contract=off), so a host restatement on top of the oracle's half-steps reproduces it bit for bit.
-#include "fdtd_ctx.h"
+#include "corrections.hpp"
 #include "../../include/fdtd_hip_conformal.h"
 
 #include <algorithm>
@@ -63,15 +63,13 @@ ConfArgs conf_args(fdtd_ctx* c) {
                   c->conf_n, c->P, c->plane};
 }
 
-}  // namespace
-
 void conformal_free(fdtd_ctx* c) {
   hipFree(c->conf_face); hipFree(c->conf_coef); hipFree(c->conf_iprev);
   c->conf_face = nullptr; c->conf_coef = nullptr; c->conf_iprev = nullptr;
   c->conf_n = 0;
 }
 
-void launch_conformal(fdtd_ctx* c, hipStream_t s) {
+void launch_conformal(fdtd_ctx* c, long long, hipStream_t s) {
   if (c->conf_n <= 0) return;
   hipLaunchKernelGGL(k_conformal, dim3((unsigned)((c->conf_n + 255) / 256)), dim3(256), 0, s, conf_args(c));
 }
@@ -84,15 +82,21 @@ int conformal_prime(fdtd_ctx* c, int comp) {
   return FDTD_OK;
 }
 
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_conformal = {
+    "conformal boundaries", /*no_links*/ true, /*volume*/ false,
+    [](const fdtd_ctx* c) { return c->conf_n > 0; },
+    nullptr, launch_conformal, conformal_free, nullptr, conformal_prime};
+#endif
+
 extern "C" {
 
 int fdtd_conformal_set(fdtd_ctx* c, int n, const int8_t* comp, const int64_t* idx, const float* coef) {
   if (!c) return FDTD_E_ARG;
   if (n < 0 || (n > 0 && (!comp || !idx || !coef))) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: bad argument");
-  if (n > 0)
-    if (int r = correction_single_slab(c, CORR_CONFORMAL)) return r;
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_conformal_set: set the operator first");
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_conformal_set: before the first timestep");
+  if (int r = correction_set_begin(c, corr_conformal, "fdtd_conformal_set", n > 0)) return r;
   const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
   std::vector<int4> face((size_t)n);
   std::vector<float4> cf((size_t)n);
@@ -110,17 +114,12 @@ int fdtd_conformal_set(fdtd_ctx* c, int n, const int8_t* comp, const int64_t* id
     cf[f] = make_float4(coef[4 * (size_t)f], coef[4 * (size_t)f + 1], coef[4 * (size_t)f + 2], coef[4 * (size_t)f + 3]);
   }
   if (sparse_doubles(keys)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_conformal_set: a face given twice");
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  conformal_free(c);
+  if (int r = correction_set_replace(c, corr_conformal)) return r;
   if (n == 0) return FDTD_OK;
   hipError_t e = to_device(&c->conf_face, face);
   if (e == hipSuccess) e = to_device(&c->conf_coef, cf);
   if (e == hipSuccess) e = hipMalloc((void**)&c->conf_iprev, (size_t)n * sizeof(float));
-  if (e != hipSuccess) {
-    conformal_free(c);
-    return fdtd_fail_hip(c, "fdtd_conformal_set", e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, corr_conformal, "fdtd_conformal_set", e);
   c->conf_n = n;
   const int r = conformal_prime(c, -1);
   if (r) conformal_free(c);

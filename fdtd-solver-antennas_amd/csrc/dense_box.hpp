@@ -7,6 +7,7 @@
 // blocks [blk0, blk0 + ceil(nq / 256)) belong to a component.  Here: the host side of the box (check, widen, scatter, crop, an operator
 // array over it), the launch layout and the kernels' decode.
 #pragma once
+#include "corrections.hpp"
 #include "kernel_common.hpp"
 
 #include <vector>
@@ -135,7 +136,8 @@ void operator_over_box(const fdtd_ctx* c, const std::vector<float>& whole, int c
 }  // namespace
 
 // dispersion.hip: the host side of the Debye media, which the Lorentz media share.  `planes`: state planes per pole (1, 2); `tab`: the
-// packed table as the kernel reads it.  The exported setters check their own limits and pack their own tables.
-int media_set(fdtd_ctx* c, MediaBoxes* m, const char* who, Correction which, int planes, int nmedia, int K, const std::vector<float>& tab,
+// packed table as the kernel reads it; `row`: the caller's own.  The exported setters check their own limits and pack their own tables.
+void media_free(MediaBoxes* m);
+int media_set(fdtd_ctx* c, MediaBoxes* m, const CorrectionRow& row, const char* who, int planes, int nmedia, int K, const std::vector<float>& tab,
               const int32_t lo[3][3], const int32_t hi[3][3], const float* const w[3], const uint8_t* const med[3]);
 int media_get(fdtd_ctx* c, const MediaBoxes* m, const char* who, int planes, int comp, float* v_prev, float* u, float* vi);

@@ -118,7 +118,9 @@ void media_free(MediaBoxes* m) {
   *m = MediaBoxes{};
 }
 
-void launch_debye(fdtd_ctx* c, hipStream_t s) {
+namespace {
+
+void launch_debye(fdtd_ctx* c, long long, hipStream_t s) {
   const MediaBoxes& m = c->debye;
   if (m.nmedia <= 0) return;
   DebyeArgs a{};
@@ -137,12 +139,20 @@ void launch_debye(fdtd_ctx* c, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, a);
 }
 
-int media_set(fdtd_ctx* c, MediaBoxes* m, const char* who, Correction which, int planes, int nmedia, int K, const std::vector<float>& tab,
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_debye = {
+    "Debye media", /*no_links*/ true, /*volume*/ true,
+    [](const fdtd_ctx* c) { return c->debye.nmedia > 0; },
+    launch_debye, nullptr,
+    [](fdtd_ctx* c) { media_free(&c->debye); },
+    nullptr, nullptr};
+#endif
+
+int media_set(fdtd_ctx* c, MediaBoxes* m, const CorrectionRow& row, const char* who, int planes, int nmedia, int K, const std::vector<float>& tab,
               const int32_t lo[3][3], const int32_t hi[3][3], const float* const w[3], const uint8_t* const med[3]) {
-  if (nmedia > 0)
-    if (int r = correction_single_slab(c, which)) return r;
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "%s: set the operator first", who);
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "%s: before the first timestep", who);
+  if (int r = correction_set_begin(c, row, who, nmedia > 0)) return r;
   size_t nbox[3] = {0, 0, 0};
   for (int ci = 0; ci < 3 && nmedia > 0; ++ci) {
     if (int r = box_check(c, who, ci, lo[ci], hi[ci], false, "grid's edges", w[ci] && (nmedia == 1 || (med && med[ci])),
@@ -152,9 +162,7 @@ int media_set(fdtd_ctx* c, MediaBoxes* m, const char* who, Correction which, int
       for (size_t e = 0; e < nbox[ci]; ++e)
         if (med[ci][e] >= nmedia) return fdtd_fail(c, FDTD_E_ARG, "%s: component %d: medium id %d out of range", who, ci, (int)med[ci][e]);
   }
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  media_free(m);
+  if (int r = correction_set_replace(c, row)) return r;
   if (nmedia == 0 || nbox[0] + nbox[1] + nbox[2] == 0) return FDTD_OK;
   std::vector<float> vi;
   if (int r = operator_array(c, 1, &vi)) return r;
@@ -178,10 +186,7 @@ int media_set(fdtd_ctx* c, MediaBoxes* m, const char* who, Correction which, int
     if (e == hipSuccess) e = to_device(&b.u, std::vector<float>((size_t)planes * K * b.g.n, 0.f));
   }
   if (e == hipSuccess) e = to_device(&m->tab, tab);
-  if (e != hipSuccess) {
-    media_free(m);
-    return fdtd_fail_hip(c, who, e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, row, who, e);
   m->nmedia = nmedia; m->K = K;
   return FDTD_OK;
 }
@@ -214,7 +219,7 @@ int fdtd_debye_set(fdtd_ctx* c, int nmedia, int K, const float* alpha, const flo
   for (int t = 0; t < 3; ++t)
     for (int m = 0; m < nmedia; ++m)
       for (int k = 0; k < K; ++k) tab[(size_t)t * TAB + m * FDTD_DEBYE_MAX_K + k] = src[t][m * K + k];
-  return media_set(c, &c->debye, "fdtd_debye_set", CORR_DEBYE, 1, nmedia, K, tab, lo, hi, w, med);
+  return media_set(c, &c->debye, corr_debye, "fdtd_debye_set", 1, nmedia, K, tab, lo, hi, w, med);
 }
 
 int fdtd_debye_get(fdtd_ctx* c, int comp, float* v_prev, float* u, float* vi) {

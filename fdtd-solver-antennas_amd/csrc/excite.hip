@@ -8,7 +8,7 @@
 // store of the current.  The host has grouped the entries by face, the soft ones in list order, so the fp32 order the header
 // spells does not depend on the launch shape, and no face is written by two threads: no atomics.  Every statement is one fp32
 // operation (-ffp-contract=off), so a host restatement on top of the oracle's half-steps reproduces it bit for bit.  No state.
-#include "fdtd_ctx.h"
+#include "corrections.hpp"
 #include "../../include/fdtd_hip_excite.h"
 
 #include <algorithm>
@@ -53,8 +53,6 @@ __global__ __launch_bounds__(256) void k_excite(const ExciteArgs a) {
   if (changed) I[o] = v;
 }
 
-}  // namespace
-
 void excite_free(fdtd_ctx* c) {
   fdtd_ctx::ExciteSet& x = c->excite;
   hipFree(x.face); hipFree(x.hamp); hipFree(x.hdelay); hipFree(x.samp); hipFree(x.sdelay); hipFree(x.sig);
@@ -68,6 +66,15 @@ void launch_excite(fdtd_ctx* c, long long step, hipStream_t s) {
   hipLaunchKernelGGL(k_excite, dim3((unsigned)((x.n + 255) / 256)), dim3(256), 0, s, a);
 }
 
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_excite = {
+    "H-field excitations", /*no_links*/ true, /*volume*/ false,
+    [](const fdtd_ctx* c) { return c->excite.n > 0; },
+    nullptr, launch_excite, excite_free, nullptr, nullptr};
+#endif
+
 extern "C" {
 
 int fdtd_excite_set(fdtd_ctx* c, int nhard, const int64_t* idxH, const int8_t* compH, const float* ampH, const int32_t* delayH,
@@ -77,10 +84,7 @@ int fdtd_excite_set(fdtd_ctx* c, int nhard, const int64_t* idxH, const int8_t* c
   if (nhard < 0 || nsoft < 0 || (nhard > 0 && (!idxH || !compH || !ampH || !delayH)) || (nsoft > 0 && (!idxS || !compS || !ampS || !delayS)) ||
       ((nhard > 0 || nsoft > 0) && (!sigH || nsigH < 1)))
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_excite_set: bad argument");
-  if (nhard > 0 || nsoft > 0)
-    if (int r = correction_single_slab(c, CORR_EXCITE)) return r;
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_excite_set: set the operator first");
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_excite_set: before the first timestep");
+  if (int r = correction_set_begin(c, corr_excite, "fdtd_excite_set", nhard > 0 || nsoft > 0)) return r;
   const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
   // every entry: (key = 3 * index + component, local offset), checked
   const int ntot = nhard + nsoft;
@@ -126,9 +130,7 @@ int fdtd_excite_set(fdtd_ctx* c, int nhard, const int64_t* idxH, const int8_t* c
       samp.push_back(ampS[e - nhard]); sdelay.push_back(delayS[e - nhard]);
     }
   }
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  excite_free(c);
+  if (int r = correction_set_replace(c, corr_excite)) return r;
   if (ntot == 0) return FDTD_OK;
   fdtd_ctx::ExciteSet& x = c->excite;
   hipError_t e = to_device(&x.face, face);
@@ -137,10 +139,7 @@ int fdtd_excite_set(fdtd_ctx* c, int nhard, const int64_t* idxH, const int8_t* c
   if (e == hipSuccess) e = to_device(&x.samp, samp);
   if (e == hipSuccess) e = to_device(&x.sdelay, sdelay);
   if (e == hipSuccess) e = to_device(&x.sig, std::vector<float>(sigH, sigH + nsigH));
-  if (e != hipSuccess) {
-    excite_free(c);
-    return fdtd_fail_hip(c, "fdtd_excite_set", e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, corr_excite, "fdtd_excite_set", e);
   x.n = (int)face.size();
   x.nsig = nsigH;
   return FDTD_OK;

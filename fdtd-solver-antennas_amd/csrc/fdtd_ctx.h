@@ -164,14 +164,19 @@ struct ResHost {
   int capacity = -1, capacity_variant = -1;   // workgroups of k_resident the chip holds at once (occupancy query), for which kernel variant
 };
 
+// What the planner asks of a sparse E-side list (api.hip correction_on_face, correction_at): the grid faces whose node plane holds an edge
+// (bit f: x-, x+, y-, y+, z-, z+) and the edges' local offsets, sorted, on the host (does a V-probe cell sit on an edge's node?).
+// Filled by edge_facts_of (corrections.hpp).
+struct EdgeFacts {
+  unsigned faces = 0;
+  std::vector<int> h_off;
+};
 // The edge list of a sparse correction (conducting sheets, lumped elements): per edge its local offset, component, full vi, class and
-// v_prev on the device; for the planner (api.hip correction_on_face, correction_at) the grid faces whose node plane holds an edge
-// (bit f: x-, x+, y-, y+, z-, z+) and the offsets once more, sorted, on the host (does a V-probe cell sit on an edge's node?)
+// v_prev on the device
 struct EdgeList {
   int n = 0;
   int* off = nullptr; int8_t* comp = nullptr; float* vi = nullptr; int* cls = nullptr; float* vprev = nullptr;
-  unsigned faces = 0;
-  std::vector<int> h_off;
+  EdgeFacts facts;
 };
 // The box of a dense correction (Debye and Lorentz media: edges; magnetic materials: faces), per field component: laid out like the
 // field arrays, its x range widened to multiples of 4 so that a thread's four elements are one 16-byte vector (dense_box.hpp)
@@ -320,13 +325,11 @@ struct fdtd_ctx {
   float* conf_iprev = nullptr;
   // plane-wave excitation (planewave.hip, include/fdtd_hip_planewave.h): the edge list [0] and the face list [1] — per entry its node
   // offset and component and two terms (coefficient, whole half-steps of delay, fraction) — and the pulse at half-step resolution
-  struct PlaneWaveList { int n = 0; int* off = nullptr; int8_t* comp = nullptr; float2* coef = nullptr; int2* m0 = nullptr; float2* w = nullptr; };
+  // ... and, of the EDGE list alone, the planner's facts.  (The face list needs none: fused I-probes are sampled by the next update_E's
+  // probe blocks or by the flush at the end of the call, both behind it, and the Mur passes never touch I.)
+  struct PlaneWaveList { int n = 0; int* off = nullptr; int8_t* comp = nullptr; float2* coef = nullptr; int2* m0 = nullptr; float2* w = nullptr;
+                         EdgeFacts facts; };
   PlaneWaveList pw[2];
-  // ... and for the planner what an EdgeList keeps of its edges, of the EDGE list alone: the grid faces whose node plane holds one (bit f:
-  // x-, x+, y-, y+, z-, z+) and the offsets once more, sorted, on the host.  (The face list needs neither: fused I-probes are sampled by
-  // the next update_E's probe blocks or by the flush at the end of the call, both behind it, and the Mur passes never touch I.)
-  unsigned pw_faces = 0;
-  std::vector<int> pw_h_off;
   float* pw_sig2 = nullptr; int pw_nsig2 = 0;
   // H-field excitations (excite.hip, include/fdtd_hip_excite.h): the distinct faces — per face its node offset, its component and whether
   // it has a hard entry, its range of soft entries — the hard entries [n], the soft entries grouped by face, the pulse at the half-steps
@@ -378,9 +381,7 @@ bool res_possible(fdtd_ctx* c, const char** why);
 int res_prepare(fdtd_ctx* c, int max_chunk);
 int launch_resident(fdtd_ctx* c, long long step, int nsteps, hipStream_t s);
 void res_free(fdtd_ctx* c);
-// The corrections between the E and H phases and behind the H update, in launch order.  api.hip lists what the planner knows of each.
-enum Correction { CORR_SHEET, CORR_DEBYE, CORR_LORENTZ, CORR_LUMPED, CORR_MAGNETIC, CORR_CONFORMAL, CORR_PLANEWAVE, CORR_EXCITE, CORR_COUNT };
-int correction_single_slab(fdtd_ctx* c, Correction which);   // api.hip: FDTD_OK, or the refusal of a decomposed / p2p / linked context
+// The corrections between the E and H phases and behind the H update: corrections.hpp (one row each, defined in the correction's own file)
 inline int fdtd_fail_hip(fdtd_ctx* c, const char* who, hipError_t e) {   // a set function's allocation or copy failed
   return fdtd_fail(c, e == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
 }
@@ -393,16 +394,8 @@ inline hipError_t to_device(T** dst, const std::vector<T>& v) {
   if (v.empty()) return hipSuccess;
   return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
-// sheet.hip: conducting sheets — the sparse correction after the E phase (no-op without sheets)
-void launch_sheet(fdtd_ctx* c, hipStream_t s);
-void sheet_free(fdtd_ctx* c);
-// ... and what it shares with lumped.hip: the list's prologue (state checks, every edge inside the grid and existing, classes in range, no
-// edge twice; then the stream synchronised, `release` called, the list's arrays uploaded, the planner's facts kept) and its release
-int edge_list_set(fdtd_ctx* c, EdgeList* l, void (*release)(fdtd_ctx*), const char* who, int n, const int64_t* idx, const int8_t* comp,
-                  const float* vi, const int32_t* cls, int ncls);
-void edge_list_free(EdgeList* l);
-// ... and with conformal.hip: a listed flat node index -> (i, j, k) and the local offset (false: outside the grid, or no component), and
-// whether a key (3 * index + component) is listed twice
+// What the sparse lists share (sheet.hip, conformal.hip, planewave.hip, excite.hip): a listed flat node index -> (i, j, k) and the local
+// offset (false: outside the grid, or no component), and whether a key (3 * index + component) is listed twice
 inline bool sparse_decode(const fdtd_ctx* c, int64_t g, int comp, int64_t pos[3], int* off) {
   const int64_t gplane = (int64_t)c->d.nx * c->d.ny;
   if (g < 0 || g >= gplane * c->d.nz || comp < 0 || comp > 2) return false;
@@ -415,30 +408,6 @@ inline bool sparse_doubles(std::vector<int64_t>& keys) {
   std::sort(keys.begin(), keys.end());
   return std::adjacent_find(keys.begin(), keys.end()) != keys.end();
 }
-// lumped.hip: lumped R-L-C elements — the sparse correction after the E phase, behind launch_sheet (no-op without elements)
-void launch_lumped(fdtd_ctx* c, hipStream_t s);
-void lumped_free(fdtd_ctx* c);
-// dispersion.hip: Debye media — the dense correction after the E phase, in front of launch_sheet (no-op without media)
-void launch_debye(fdtd_ctx* c, hipStream_t s);
-void media_free(MediaBoxes* m);   // (Debye and Lorentz media alike)
-// lorentz.hip: Lorentz / Drude media — the dense correction behind launch_debye, in front of launch_sheet (no-op without media)
-void launch_lorentz(fdtd_ctx* c, hipStream_t s);
-// magnetic.hip: magnetic materials — the dense correction after the H update, in front of everything that samples I (no-op without faces)
-void launch_magnetic(fdtd_ctx* c, hipStream_t s);
-int magnetic_prime(fdtd_ctx* c, int comp);   // i_prev <- the component's I array (fdtd_magnetic_set, fdtd_set_field)
-void magnetic_free(fdtd_ctx* c);
-// conformal.hip: conformal PEC boundaries — the sparse correction after the H update, behind launch_magnetic (no-op without faces)
-void launch_conformal(fdtd_ctx* c, hipStream_t s);
-int conformal_prime(fdtd_ctx* c, int comp);  // i_prev <- the listed faces' currents (fdtd_conformal_set, fdtd_set_field; comp < 0: all)
-void conformal_free(fdtd_ctx* c);
-// planewave.hip: plane-wave excitation — the sparse corrections of the box surface: kind FDTD_KIND_V after the E phase, behind
-// launch_lumped; kind FDTD_KIND_I after the H update, behind launch_conformal (no-ops without a plane wave)
-void launch_planewave(fdtd_ctx* c, int kind, long long step, hipStream_t s);
-void planewave_free(fdtd_ctx* c);
-// excite.hip: H-field excitations — the sparse correction after the H update, behind launch_planewave(FDTD_KIND_I): last of the H side
-// (no-op without a set)
-void launch_excite(fdtd_ctx* c, long long step, hipStream_t s);
-void excite_free(fdtd_ctx* c);
 void xcd_shares_reset(fdtd_ctx* c);   // after the CPML layers or the tiling changed
 int xcd_stamp_arm(fdtd_ctx* c, hipStream_t s);   // the next k_step launch leaves its blocks' end times (calibration)
 int xcd_adapt(fdtd_ctx* c);              // after that launch has finished: per-XCD finish times -> new share fractions

@@ -125,9 +125,7 @@ __global__ __launch_bounds__(256) void k_lorentz(const LorentzArgs a) {
     }
 }
 
-}  // namespace
-
-void launch_lorentz(fdtd_ctx* c, hipStream_t s) {
+void launch_lorentz(fdtd_ctx* c, long long, hipStream_t s) {
   const MediaBoxes& m = c->lorentz;
   if (m.nmedia <= 0) return;
   LorentzArgs a{};
@@ -147,6 +145,17 @@ void launch_lorentz(fdtd_ctx* c, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, a);
 }
 
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_lorentz = {
+    "Lorentz media", /*no_links*/ true, /*volume*/ true,
+    [](const fdtd_ctx* c) { return c->lorentz.nmedia > 0; },
+    launch_lorentz, nullptr,
+    [](fdtd_ctx* c) { media_free(&c->lorentz); },
+    nullptr, nullptr};
+#endif
+
 extern "C" {
 
 int fdtd_lorentz_set(fdtd_ctx* c, int nmedia, int K, const float* phi, const float* gam, const float* h,
@@ -163,7 +172,7 @@ int fdtd_lorentz_set(fdtd_ctx* c, int nmedia, int K, const float* phi, const flo
       for (int q = 0; q < 4; ++q) row[q] = phi[((size_t)m * K + k) * 4 + q];
       for (int q = 0; q < 2; ++q) { row[4 + q] = gam[((size_t)m * K + k) * 2 + q]; row[6 + q] = h[((size_t)m * K + k) * 2 + q]; }
     }
-  return media_set(c, &c->lorentz, "fdtd_lorentz_set", CORR_LORENTZ, 2, nmedia, K, tab, lo, hi, w, med);
+  return media_set(c, &c->lorentz, corr_lorentz, "fdtd_lorentz_set", 2, nmedia, K, tab, lo, hi, w, med);
 }
 
 int fdtd_lorentz_get(fdtd_ctx* c, int comp, float* v_prev, float* x, float* vi) {

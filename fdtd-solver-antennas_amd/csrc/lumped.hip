@@ -6,7 +6,7 @@
 // The edges are few (one to a few thousand): the launch is a latency floor, not a bandwidth problem.  Every statement is one
 // fp32 operation in the order the header spells (-ffp-contract=off), so a host restatement on top of the oracle's half-steps
 // reproduces it bit for bit.
-#include "fdtd_ctx.h"
+#include "corrections.hpp"
 #include "../../include/fdtd_hip_lumped.h"
 
 #include <algorithm>
@@ -40,20 +40,29 @@ __global__ __launch_bounds__(256) void k_lumped(LumpedArgs a) {
   a.vprev[e] = v;
 }
 
-}  // namespace
-
 void lumped_free(fdtd_ctx* c) {
   edge_list_free(&c->lumped);
   hipFree(c->lumped_x); hipFree(c->lumped_phi); hipFree(c->lumped_gam); hipFree(c->lumped_h);
   c->lumped_x = nullptr; c->lumped_phi = nullptr; c->lumped_gam = nullptr; c->lumped_h = nullptr;
 }
 
-void launch_lumped(fdtd_ctx* c, hipStream_t s) {
+void launch_lumped(fdtd_ctx* c, long long, hipStream_t s) {
   const EdgeList& l = c->lumped;
   if (l.n <= 0) return;
   LumpedArgs a{c->p.V[0], c->p.V[1], c->p.V[2], l.off, l.comp, l.vi, l.cls, l.vprev, c->lumped_x, c->lumped_phi, c->lumped_gam, c->lumped_h, l.n};
   hipLaunchKernelGGL(k_lumped, dim3((unsigned)((l.n + 255) / 256)), dim3(256), 0, s, a);
 }
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_lumped = {
+    "lumped elements", /*no_links*/ true, /*volume*/ false,
+    [](const fdtd_ctx* c) { return c->lumped.n > 0; },
+    launch_lumped, nullptr, lumped_free,
+    [](const fdtd_ctx* c) { return &c->lumped.facts; },
+    nullptr};
+#endif
 
 extern "C" {
 
@@ -63,18 +72,15 @@ int fdtd_lumped_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, 
   if (n < 0 || (n > 0 && (!idx || !comp || !vi || !cls || !phi || !gam || !h)))
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_lumped_set: bad argument");
   if (n > 0 && ncls < 1) return fdtd_fail(c, FDTD_E_ARG, "fdtd_lumped_set: ncls must be >= 1");
-  // (this call's own wording; the planner refuses p2p and linked contexts when they step: api.hip corrections)
+  // (this call's own wording; the planner refuses p2p and linked contexts when they step: api.hip plan_schedule)
   if (c->d.world > 1) return fdtd_fail(c, FDTD_E_UNSUPPORTED, "lumped elements: single slab only (world = 1)");
-  const int r = edge_list_set(c, &c->lumped, lumped_free, "fdtd_lumped_set", n, idx, comp, vi, cls, ncls);
+  const int r = edge_list_set(c, &c->lumped, corr_lumped, "fdtd_lumped_set", n, idx, comp, vi, cls, ncls);
   if (r || n == 0) return r;
   hipError_t e = to_device(&c->lumped_x, std::vector<float>((size_t)2 * n, 0.f));
   if (e == hipSuccess) e = to_device(&c->lumped_phi, std::vector<float>(phi, phi + (size_t)ncls * 4));
   if (e == hipSuccess) e = to_device(&c->lumped_gam, std::vector<float>(gam, gam + (size_t)ncls * 2));
   if (e == hipSuccess) e = to_device(&c->lumped_h, std::vector<float>(h, h + (size_t)ncls * 2));
-  if (e != hipSuccess) {
-    lumped_free(c);
-    return fdtd_fail_hip(c, "fdtd_lumped_set", e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, corr_lumped, "fdtd_lumped_set", e);
   return FDTD_OK;
 }
 

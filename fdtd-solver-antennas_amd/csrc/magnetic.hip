@@ -58,8 +58,6 @@ __global__ __launch_bounds__(256) void k_magnetic(const MagArgs a) {
   *reinterpret_cast<float4*>(m.iprev + o) = p4;
 }
 
-}  // namespace
-
 void magnetic_free(fdtd_ctx* c) {
   for (auto& b : c->mag_box) {
     hipFree(b.iprev); hipFree(b.cls);
@@ -70,7 +68,7 @@ void magnetic_free(fdtd_ctx* c) {
   c->mag_ncls = 0;
 }
 
-void launch_magnetic(fdtd_ctx* c, hipStream_t s) {
+void launch_magnetic(fdtd_ctx* c, long long, hipStream_t s) {
   if (c->mag_ncls <= 0) return;
   MagArgs a{};
   const unsigned blocks = box_layout(c, c->mag_box, a.c);
@@ -98,6 +96,15 @@ int magnetic_prime(fdtd_ctx* c, int ci) {
   return FDTD_OK;
 }
 
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_magnetic = {
+    "magnetic materials", /*no_links*/ true, /*volume*/ false,
+    [](const fdtd_ctx* c) { return c->mag_ncls > 0; },
+    nullptr, launch_magnetic, magnetic_free, nullptr, magnetic_prime};
+#endif
+
 extern "C" {
 
 int fdtd_magnetic_set(fdtd_ctx* c, int ncls, const float* ta, const float* tb, const int32_t lo[3][3], const int32_t hi[3][3],
@@ -107,19 +114,14 @@ int fdtd_magnetic_set(fdtd_ctx* c, int ncls, const float* ta, const float* tb, c
   if (ncls > FDTD_MAGNETIC_MAX_CLASSES)
     return fdtd_fail(c, FDTD_E_UNSUPPORTED, "magnetic materials: %d distinct (a, b) classes, at most %d (one class byte per face)", ncls, FDTD_MAGNETIC_MAX_CLASSES);
   if (ncls > 0 && (!ta || !tb || !lo || !hi || !cls)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_magnetic_set: bad argument");
-  if (ncls > 0)
-    if (int r = correction_single_slab(c, CORR_MAGNETIC)) return r;
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_magnetic_set: set the operator first");
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_magnetic_set: before the first timestep");
+  if (int r = correction_set_begin(c, corr_magnetic, "fdtd_magnetic_set", ncls > 0)) return r;
   size_t nbox[3] = {0, 0, 0};
   for (int ci = 0; ci < 3 && ncls > 0; ++ci) {
     if (int r = box_check(c, "fdtd_magnetic_set", ci, lo[ci], hi[ci], true, "grid", cls[ci] != nullptr, "class bytes", &nbox[ci])) return r;
     for (size_t e = 0; e < nbox[ci]; ++e)
       if (cls[ci][e] > ncls) return fdtd_fail(c, FDTD_E_ARG, "fdtd_magnetic_set: component %d: class %d out of range", ci, (int)cls[ci][e]);
   }
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  magnetic_free(c);
+  if (int r = correction_set_replace(c, corr_magnetic)) return r;
   if (ncls == 0 || nbox[0] + nbox[1] + nbox[2] == 0) return FDTD_OK;
   hipError_t e = hipSuccess;
   for (int ci = 0; ci < 3 && e == hipSuccess; ++ci) {
@@ -134,10 +136,7 @@ int fdtd_magnetic_set(fdtd_ctx* c, int ncls, const float* ta, const float* tb, c
     for (int q = 0; q < ncls; ++q) tab[q + 1] = make_float2(ta[q], tb[q]);
     e = to_device(&c->mag_tab, tab);
   }
-  if (e != hipSuccess) {
-    magnetic_free(c);
-    return fdtd_fail_hip(c, "fdtd_magnetic_set", e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, corr_magnetic, "fdtd_magnetic_set", e);
   c->mag_ncls = ncls;
   for (int ci = 0; ci < 3; ++ci) {
     const int r = magnetic_prime(c, ci);

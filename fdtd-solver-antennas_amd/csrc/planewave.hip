@@ -8,7 +8,7 @@
 // load and store of the field.  No state, no atomics: the host merges the two terms of an element on a box edge into ONE entry, so
 // no element is written twice in a launch.  Every statement is one fp32 operation in the order the header spells
 // (-ffp-contract=off), so a host restatement on top of the oracle's half-steps reproduces it bit for bit.
-#include "fdtd_ctx.h"
+#include "corrections.hpp"
 #include "../../include/fdtd_hip_planewave.h"
 
 #include <algorithm>
@@ -57,7 +57,7 @@ void list_free(fdtd_ctx::PlaneWaveList* l) {
 }
 
 // one list checked and turned into the arrays the kernel reads (nothing on the device yet)
-struct HostList { std::vector<int> off; std::vector<int8_t> comp; std::vector<float2> coef, w; std::vector<int2> m0; unsigned planes = 0; };
+struct HostList { std::vector<int> off; std::vector<int8_t> comp; std::vector<float2> coef, w; std::vector<int2> m0; };
 int list_check(fdtd_ctx* c, const char* what, bool faces, int n, const int64_t* idx, const int8_t* comp, const float* coef,
                const int32_t* m0, const float* w, HostList* out) {
   const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
@@ -77,7 +77,6 @@ int list_check(fdtd_ctx* c, const char* what, bool faces, int n, const int64_t* 
       if (!(wq >= 0.f && wq < 1.f)) return fdtd_fail(c, FDTD_E_ARG, "fdtd_planewave_set: %s %d: the fraction of the delay must be in [0, 1)", what, e);
     }
     keys[e] = idx[e] * 3 + m;
-    for (int a = 0; a < 3; ++a) out->planes |= (pos[a] == 0 ? 1u : 0u) << (2 * a) | (pos[a] == nn[a] - 1 ? 1u : 0u) << (2 * a + 1);   // (as edge_list_set)
     out->off[e] = off; out->comp[e] = (int8_t)m;
     out->coef[e] = make_float2(coef[2 * (size_t)e], coef[2 * (size_t)e + 1]);
     out->m0[e] = make_int2(m0[2 * (size_t)e], m0[2 * (size_t)e + 1]);
@@ -96,12 +95,9 @@ hipError_t list_upload(fdtd_ctx::PlaneWaveList* l, const HostList& h) {
   return e;
 }
 
-}  // namespace
-
 void planewave_free(fdtd_ctx* c) {
   list_free(&c->pw[0]); list_free(&c->pw[1]);
   hipFree(c->pw_sig2); c->pw_sig2 = nullptr; c->pw_nsig2 = 0;
-  c->pw_faces = 0; c->pw_h_off.clear();
 }
 
 void launch_planewave(fdtd_ctx* c, int kind, long long step, hipStream_t s) {
@@ -111,6 +107,20 @@ void launch_planewave(fdtd_ctx* c, int kind, long long step, hipStream_t s) {
   PlaneWaveArgs a{F[0], F[1], F[2], l.off, l.comp, l.coef, l.m0, l.w, c->pw_sig2, 2 * step - (kind == FDTD_KIND_V ? 1 : 0), c->pw_nsig2, l.n};
   hipLaunchKernelGGL(k_planewave, dim3((unsigned)((l.n + 255) / 256)), dim3(256), 0, s, a);
 }
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+// (the one correction of both sides: its edge list runs behind the E phase, its face list behind the H update)
+const CorrectionRow corr_planewave = {
+    "plane-wave excitation", /*no_links*/ true, /*volume*/ false,
+    [](const fdtd_ctx* c) { return c->pw[0].n > 0 || c->pw[1].n > 0; },
+    [](fdtd_ctx* c, long long step, hipStream_t s) { launch_planewave(c, FDTD_KIND_V, step, s); },
+    [](fdtd_ctx* c, long long step, hipStream_t s) { launch_planewave(c, FDTD_KIND_I, step, s); },
+    planewave_free,
+    [](const fdtd_ctx* c) { return &c->pw[0].facts; },
+    nullptr};
+#endif
 
 extern "C" {
 
@@ -122,30 +132,20 @@ int fdtd_planewave_set(fdtd_ctx* c,
   if (nE < 0 || nH < 0 || (nE > 0 && (!idxE || !compE || !coefE || !m0E || !wE)) || (nH > 0 && (!idxH || !compH || !coefH || !m0H || !wH)) ||
       ((nE > 0 || nH > 0) && (!sig2 || nsig2 < 1)))
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_planewave_set: bad argument");
-  if (nE > 0 || nH > 0)
-    if (int r = correction_single_slab(c, CORR_PLANEWAVE)) return r;
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "fdtd_planewave_set: set the operator first");
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "fdtd_planewave_set: before the first timestep");
+  if (int r = correction_set_begin(c, corr_planewave, "fdtd_planewave_set", nE > 0 || nH > 0)) return r;
   HostList hE, hH;
   if (int r = list_check(c, "edge", false, nE, idxE, compE, coefE, m0E, wE, &hE)) return r;
   if (int r = list_check(c, "face", true, nH, idxH, compH, coefH, m0H, wH, &hH)) return r;
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  planewave_free(c);
+  if (int r = correction_set_replace(c, corr_planewave)) return r;
   if (nE == 0 && nH == 0) return FDTD_OK;
   hipError_t e = list_upload(&c->pw[0], hE);
   if (e == hipSuccess) e = list_upload(&c->pw[1], hH);
   if (e == hipSuccess) e = to_device(&c->pw_sig2, std::vector<float>(sig2, sig2 + nsig2));
-  if (e != hipSuccess) {
-    planewave_free(c);
-    return fdtd_fail_hip(c, "fdtd_planewave_set", e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, corr_planewave, "fdtd_planewave_set", e);
   c->pw_nsig2 = nsig2;
   // what the planner asks of the edge list (api.hip correction_on_face, correction_at): a V-probe cell on a listed edge is sampled in
   // front of the corrections, a listed edge on the node plane of a Mur face takes the apply pass as a launch of its own
-  c->pw_faces = hE.planes;
-  c->pw_h_off.swap(hE.off);
-  std::sort(c->pw_h_off.begin(), c->pw_h_off.end());
+  c->pw[0].facts = edge_facts_of(c, std::move(hE.off));
   return FDTD_OK;
 }
 

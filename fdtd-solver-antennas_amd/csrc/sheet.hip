@@ -4,7 +4,7 @@
 // sparse correction of the sheet edges once per timestep, between the E phase and the H update: one thread per edge, plain
 // vector loads and stores, state structure-of-arrays.  Every statement is one fp32 operation in the order the header spells
 // (-ffp-contract=off), so a host restatement on top of the oracle's half-steps reproduces it bit for bit.
-#include "fdtd_ctx.h"
+#include "corrections.hpp"
 #include "../../include/fdtd_hip_sheet.h"
 
 #include <algorithm>
@@ -42,43 +42,33 @@ __global__ __launch_bounds__(256) void k_sheet(SheetArgs a) {
 }  // namespace
 
 // The edge list of a sparse correction (conducting sheets here, lumped elements in lumped.hip)
-int edge_list_set(fdtd_ctx* c, EdgeList* l, void (*release)(fdtd_ctx*), const char* who, int n, const int64_t* idx, const int8_t* comp,
+int edge_list_set(fdtd_ctx* c, EdgeList* l, const CorrectionRow& row, const char* who, int n, const int64_t* idx, const int8_t* comp,
                   const float* vi, const int32_t* cls, int ncls) {
-  if (!c->have_op) return fdtd_fail(c, FDTD_E_STATE, "%s: set the operator first", who);
-  if (c->step != 0) return fdtd_fail(c, FDTD_E_STATE, "%s: before the first timestep", who);
+  if (int r = correction_set_state(c, who)) return r;
   const int64_t nn[3] = {c->d.nx, c->d.ny, c->d.nz};
   std::vector<int> off(n), cl(n);
   std::vector<int8_t> cp(n);
   std::vector<int64_t> keys(n);
-  unsigned faces = 0;
   for (int e = 0; e < n; ++e) {
     int64_t pos[3];
     if (!sparse_decode(c, idx[e], comp[e], pos, &off[e]) || cls[e] < 0 || cls[e] >= ncls)
       return fdtd_fail(c, FDTD_E_ARG, "%s: edge %d out of range", who, e);
     if (pos[comp[e]] >= nn[comp[e]] - 1) return fdtd_fail(c, FDTD_E_ARG, "%s: edge %d does not exist", who, e);
     keys[e] = idx[e] * 3 + comp[e];
-    for (int a = 0; a < 3; ++a) faces |= (pos[a] == 0 ? 1u : 0u) << (2 * a) | (pos[a] == nn[a] - 1 ? 1u : 0u) << (2 * a + 1);
     cp[e] = comp[e];
     cl[e] = cls[e];
   }
   if (sparse_doubles(keys)) return fdtd_fail(c, FDTD_E_ARG, "%s: an edge given twice", who);
-  HIPCK(c, hipSetDevice(c->d.device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  release(c);
+  if (int r = correction_set_replace(c, row)) return r;
   if (n == 0) return FDTD_OK;
   hipError_t e = to_device(&l->off, off);
   if (e == hipSuccess) e = to_device(&l->comp, cp);
   if (e == hipSuccess) e = to_device(&l->vi, std::vector<float>(vi, vi + n));
   if (e == hipSuccess) e = to_device(&l->cls, cl);
   if (e == hipSuccess) e = to_device(&l->vprev, std::vector<float>(n, 0.f));
-  if (e != hipSuccess) {
-    release(c);
-    return fdtd_fail_hip(c, who, e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, row, who, e);
   l->n = n;
-  l->faces = faces;
-  l->h_off.swap(off);
-  std::sort(l->h_off.begin(), l->h_off.end());
+  l->facts = edge_facts_of(c, std::move(off));
   return FDTD_OK;
 }
 
@@ -87,6 +77,8 @@ void edge_list_free(EdgeList* l) {
   *l = EdgeList{};
 }
 
+namespace {
+
 void sheet_free(fdtd_ctx* c) {
   edge_list_free(&c->sheet);
   hipFree(c->sheet_ib); hipFree(c->sheet_alpha); hipFree(c->sheet_b);
@@ -94,12 +86,23 @@ void sheet_free(fdtd_ctx* c) {
   c->sheet_K = c->sheet_ncls = 0;
 }
 
-void launch_sheet(fdtd_ctx* c, hipStream_t s) {
+void launch_sheet(fdtd_ctx* c, long long, hipStream_t s) {
   const EdgeList& l = c->sheet;
   if (l.n <= 0) return;
   SheetArgs a{c->p.V[0], c->p.V[1], c->p.V[2], l.off, l.comp, l.vi, l.cls, l.vprev, c->sheet_ib, c->sheet_alpha, c->sheet_b, l.n, c->sheet_K};
   hipLaunchKernelGGL(k_sheet, dim3((unsigned)((l.n + 255) / 256)), dim3(256), 0, s, a);
 }
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__   // (host data: corrections.hpp)
+const CorrectionRow corr_sheet = {
+    "conducting sheets", /*no_links*/ false, /*volume*/ false,
+    [](const fdtd_ctx* c) { return c->sheet.n > 0; },
+    launch_sheet, nullptr, sheet_free,
+    [](const fdtd_ctx* c) { return &c->sheet.facts; },
+    nullptr};
+#endif
 
 extern "C" {
 
@@ -110,16 +113,13 @@ int fdtd_sheet_set(fdtd_ctx* c, int n, const int64_t* idx, const int8_t* comp, c
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_sheet_set: bad argument");
   if (n > 0 && (K < 1 || K > FDTD_SHEET_MAX_K || ncls < 1))
     return fdtd_fail(c, FDTD_E_ARG, "fdtd_sheet_set: K must be 1..%d and ncls >= 1", FDTD_SHEET_MAX_K);
-  if (int r = correction_single_slab(c, CORR_SHEET)) return r;
-  const int r = edge_list_set(c, &c->sheet, sheet_free, "fdtd_sheet_set", n, idx, comp, vi, cls, ncls);
+  if (int r = correction_single_slab(c, corr_sheet)) return r;   // (asked of an empty list as well)
+  const int r = edge_list_set(c, &c->sheet, corr_sheet, "fdtd_sheet_set", n, idx, comp, vi, cls, ncls);
   if (r || n == 0) return r;
   hipError_t e = to_device(&c->sheet_ib, std::vector<float>((size_t)K * n, 0.f));
   if (e == hipSuccess) e = to_device(&c->sheet_alpha, std::vector<float>(alpha, alpha + (size_t)ncls * K));
   if (e == hipSuccess) e = to_device(&c->sheet_b, std::vector<float>(b, b + (size_t)ncls * K));
-  if (e != hipSuccess) {
-    sheet_free(c);
-    return fdtd_fail_hip(c, "fdtd_sheet_set", e);
-  }
+  if (e != hipSuccess) return correction_set_failed(c, corr_sheet, "fdtd_sheet_set", e);
   c->sheet_K = K; c->sheet_ncls = ncls;
   return FDTD_OK;
 }

@@ -3,7 +3,8 @@
 The Lorentz media and the magnetic faces go through the same widen / scatter / crop as the Debye media: their boxes walk the x
 alignments test_dispersion_gpu.test_box_alignment_in_x walks (X_ALIGN; test_box_alignment_cases_cover_every_residue there pins what
 the list covers), against the restatements of test_lorentz_model_cpu / test_magnetic_model_cpu, bit for bit.  And every refusal that
-now comes out of one place keeps its text."""
+now comes out of one place keeps its text, for all eight rows of the table (csrc/corrections.hpp); a set that is cleared leaves the
+context what it was, and a row's `prime` follows fdtd_set_field."""
 import numpy as np
 import pytest
 
@@ -98,8 +99,8 @@ def test_magnetic_box_alignment_in_x(hip_lib, oracle_lib, x0, x1, nx):
         assert np.array_equal(ip[cls[c] == 0], before[cls[c] == 0]) and np.any(ip[cls[c] != 0] != before[cls[c] != 0])
 
 
-# ---- the refusals: one context of 8 x 8 x 8 nodes per correction (all seven of the planner's table, correction() in csrc/api.hip), one
-# edge, one face or a box of one cell ------------------------------------------------------------------------------------------------
+# ---- the refusals: one context of 8 x 8 x 8 nodes per correction (all eight rows of the planner's table, corrections[] in
+# csrc/corrections.hpp), one edge, one face or a box of one cell; CLEAR: the same setters with an empty set ----------------------------
 E_PHASE = "their correction runs between the E phase and the H update"
 H_PHASE = "their correction runs between the H update and the next E phase"
 ONE = [(3, 3, 3)] * 3, [(4, 4, 4)] * 3
@@ -135,13 +136,29 @@ def _set_planewave(e):
     e.set_planewave(*EDGE, *one, *EDGE, *one, np.ones(4, np.float32))                # one edge, and the face at the same node
 
 
+def _set_excite(e):
+    e.set_excite(*EDGE, [1.0], [0], [], [], [], [], np.ones(4, np.float32))          # one hard face
+
+
+NO_BOX = [(0, 0, 0)] * 3, [(0, 0, 0)] * 3, [None] * 3
+NO_EDGE = (EDGE[0][:0], EDGE[1][:0], np.zeros(0, np.float32), np.zeros(0, np.int32))
+CLEAR = {"fdtd_sheet_set": lambda e: e.set_sheets(*NO_EDGE, np.zeros((0, 1), np.float32), np.zeros((0, 1), np.float32)),
+         "fdtd_debye_set": lambda e: e.set_debye(np.zeros((0, 1)), np.zeros((0, 1)), np.zeros((0, 1)), *NO_BOX),
+         "fdtd_lorentz_set": lambda e: e.set_lorentz(np.zeros((0, 1, 2, 2)), np.zeros((0, 1, 2)), np.zeros((0, 1, 2)), *NO_BOX),
+         "fdtd_lumped_set": lambda e: e.set_lumped(*NO_EDGE, np.zeros(0), np.zeros(0), np.zeros(0)),
+         "fdtd_magnetic_set": lambda e: e.set_magnetic([], [], *NO_BOX),
+         "fdtd_conformal_set": lambda e: e.set_conformal(EDGE[1][:0], EDGE[0][:0], np.zeros((0, 4), np.float32)),
+         "fdtd_planewave_set": lambda e: e.set_planewave(*[[]] * 10, None),
+         "fdtd_excite_set": lambda e: e.set_excite(*[[]] * 8, None)}
+
 REFUSALS = [("fdtd_sheet_set", _set_sheet, f"conducting sheets: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_debye_set", _set_debye, f"Debye media: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_lorentz_set", _set_lorentz, f"Lorentz media: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_lumped_set", _set_lumped, f"lumped elements: the two-launch schedule only ({E_PHASE})"),
             ("fdtd_magnetic_set", _set_magnetic, f"magnetic materials: the two-launch schedule only ({H_PHASE})"),
             ("fdtd_conformal_set", _set_conformal, f"conformal boundaries: the two-launch schedule only ({H_PHASE})"),
-            ("fdtd_planewave_set", _set_planewave, f"plane-wave excitation: the two-launch schedule only ({H_PHASE})")]
+            ("fdtd_planewave_set", _set_planewave, f"plane-wave excitation: the two-launch schedule only ({H_PHASE})"),
+            ("fdtd_excite_set", _set_excite, f"H-field excitations: the two-launch schedule only ({H_PHASE})")]
 
 
 @pytest.mark.gpu
@@ -169,4 +186,49 @@ def test_refusal_messages_keep_their_text(hip_lib, who, setter, two_launch):
     with pytest.raises(capi.FdtdError) as err:
         setter(e)
     assert str(err.value).endswith(f"(-2): {who}: set the operator first"), str(err.value)
+    e.close()
+
+
+_NEVER_SET = {}   # the fields of the engine that never had a set, computed by the first case that asks
+
+
+def _cavity_engine(hip_lib):
+    """The 8 x 8 x 8 cavity from seeded fields, and the three I components written once more (what the `prime` rows are asked about)."""
+    from test_lumped_model_cpu import pec_cavity
+    e = pec_cavity(n=(8, 8, 8), nr_ts=4).build(hip_lib)
+    seeded_fields(e, 8)
+    rng = np.random.default_rng(88)
+    return e, [(1e-3 * rng.standard_normal(e.local_shape)).astype(np.float32) for _ in range(3)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("who,setter", [r[:2] for r in REFUSALS], ids=[r[0] for r in REFUSALS])
+def test_a_cleared_set_leaves_the_context_what_it_was(hip_lib, who, setter):
+    """Set one element, clear it with an empty set: the schedule is the plain context's again, and four timesteps end in the bits of an
+    engine that never had the set (the row's `active` and `release`).  Magnetic and conformal faces keep i_prev: written through
+    fdtd_set_field while the set is live, the I arrays show up in the *_state() (the row's `prime`)."""
+    capi = pkg("_capi")
+    if not _NEVER_SET:
+        r, new_I = _cavity_engine(hip_lib)
+        for c in range(3):
+            r.set_field(capi.KIND_I, c, new_I[c])
+        r.run(4)
+        _NEVER_SET["fields"] = r.fields()
+        r.close()
+    e, new_I = _cavity_engine(hip_lib)
+    before = e.schedule_info()
+    setter(e)
+    assert e.schedule_info()["launches_per_timestep"] == 2
+    for c in range(3):
+        e.set_field(capi.KIND_I, c, new_I[c])
+    if who == "fdtd_magnetic_set":
+        for c in range(3):
+            assert np.array_equal(e.magnetic_state(c)[0], new_I[c][3:4, 3:4, 3:4])
+    if who == "fdtd_conformal_set":
+        assert np.array_equal(e.conformal_state(), new_I[2][3, 3, 3:4])
+    CLEAR[who](e)
+    assert e.schedule_info() == before
+    e.run(4)
+    assert np.abs(_NEVER_SET["fields"]).max() > 0
+    assert np.array_equal(e.fields(), _NEVER_SET["fields"])
     e.close()
