@@ -58,6 +58,9 @@ PLANEWAVE_SYMBOLS = ["fdtd_planewave_set"]
 EXCITE_SYMBOLS = ["fdtd_excite_set"]
 # include/fdtd_hip_fields.h: field dumps (E, H, J, rot-H on a point lattice) on the device, likewise
 FIELDS_SYMBOLS = ["fdtd_field_interp"]
+# include/fdtd_hip_farfield.h: the radiation integral over a symmetry half and its mirror images, likewise
+FARFIELD_MIRROR_SYMBOLS = ["fdtd_farfield_mirror"]
+MIRROR_PEC, MIRROR_PMC = 1, 2      # FDTD_MIRROR_PEC / FDTD_MIRROR_PMC: upstream's numbers
 # FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
 MAX_BOXES = 64
 
@@ -262,7 +265,19 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    mirror_sig = {"fdtd_farfield_mirror": (C.c_int, [C.c_int, C.c_int, p, p, p, C.c_double, C.c_int, p, p, p, C.c_int, C.c_int, p, p, p, p])}
+    assert sorted(mirror_sig) == sorted(FARFIELD_MIRROR_SYMBOLS)
+    for name, (res, args) in mirror_sig.items():     # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_farfield_mirror(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the radiation integral with mirror planes (include/fdtd_hip_farfield.h)."""
+    return all(hasattr(lib, n) for n in FARFIELD_MIRROR_SYMBOLS)
 
 
 def has_fields(lib: C.CDLL) -> bool:
@@ -927,6 +942,35 @@ def farfield(lib: C.CDLL, pos, Js, Ms, k_wave: float, theta, phi, device: int = 
     if rc != 0:
         msg = lib.fdtd_last_error(None)
         raise FdtdError(f"fdtd_farfield failed ({rc}): {msg.decode() if msg else ''}")
+    return eth[:, 0] + 1j * eth[:, 1], eph[:, 0] + 1j * eph[:, 1]
+
+
+def farfield_mirror(lib: C.CDLL, pos, Js, Ms, k_wave: float, theta, phi, mirrors=(), half_space: Optional[int] = None, device: int = 0):
+    """farfield() over the points and their images in `mirrors`: a sequence of up to three (axis, type, coordinate) with type
+    MIRROR_PEC / MIRROR_PMC (or 'PEC' / 'PMC') and the coordinate relative to the phase centre, like pos.  half_space = b names
+    plane b as an infinite ground: exact zeros behind it.  The numpy statement is nf2ff.farfield_mirror_spec."""
+    if not has_farfield_mirror(lib):
+        raise FdtdError("this library has no radiation integral with mirror planes (fdtd_farfield_mirror)")
+    pos = _arr(pos, np.float64)
+    npts = pos.shape[0]
+    Js = _arr(np.stack([np.real(Js), np.imag(Js)], -1), np.float64)
+    Ms = _arr(np.stack([np.real(Ms), np.imag(Ms)], -1), np.float64)
+    th, ph = _arr(theta, np.float64), _arr(phi, np.float64)
+    if pos.shape != (npts, 3) or Js.shape != (npts, 3, 2) or Ms.shape != (npts, 3, 2) or th.shape != ph.shape:
+        raise ValueError("farfield argument shapes")
+    mirrors = [(int(a), {"PEC": MIRROR_PEC, "PMC": MIRROR_PMC}.get(t, t), float(c)) for a, t, c in mirrors]
+    if len(mirrors) > 3:
+        raise ValueError("farfield: at most three mirror planes")
+    ax = _arr([m[0] for m in mirrors] + [0] * (3 - len(mirrors)), np.int32)
+    ty = _arr([int(m[1]) for m in mirrors] + [0] * (3 - len(mirrors)), np.int32)
+    co = _arr([m[2] for m in mirrors] + [0.0] * (3 - len(mirrors)), np.float64)
+    eth = np.zeros((th.size, 2), np.float64)
+    eph = np.zeros((th.size, 2), np.float64)
+    rc = lib.fdtd_farfield_mirror(int(device), int(npts), _ptr(pos), _ptr(Js), _ptr(Ms), float(k_wave), len(mirrors), _ptr(ax), _ptr(ty),
+                                  _ptr(co), -1 if half_space is None else int(half_space), int(th.size), _ptr(th), _ptr(ph), _ptr(eth), _ptr(eph))
+    if rc != 0:
+        msg = lib.fdtd_last_error(None)
+        raise FdtdError(f"fdtd_farfield_mirror failed ({rc}): {msg.decode() if msg else ''}")
     return eth[:, 0] + 1j * eth[:, 1], eph[:, 0] + 1j * eph[:, 1]
 
 

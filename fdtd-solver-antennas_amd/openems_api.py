@@ -750,9 +750,30 @@ class MSLPort(_ModalPort):
 
 
 class nf2ff:
-    def __init__(self, fdtd, name="nf2ff", start=None, stop=None):
+    def __init__(self, fdtd, name="nf2ff", start=None, stop=None, directions=None, mirror=None, half_space=False):
         self._fdtd, self.name = fdtd, name
         self.start, self.stop = start, stop
+        faces = ("x-", "x+", "y-", "y+", "z-", "z+")
+        self.mirror = None
+        if mirror is not None:
+            self.mirror = [int(m) for m in mirror]
+            if len(self.mirror) != 6 or any(m not in (0, 1, 2) for m in self.mirror):
+                raise ValueError(f"NF2FF box '{name}': mirror takes six entries (x-, x+, y-, y+, z-, z+) of 0 (none), 1 (PEC) or 2 (PMC)")
+            if not any(self.mirror):
+                self.mirror = None
+        self.half_space = bool(half_space)
+        if self.half_space and self.mirror is None:
+            raise ValueError(f"NF2FF box '{name}': half_space needs a PEC mirror plane, and there is no mirror")
+        self.directions = None
+        if directions is not None:
+            self.directions = [bool(d) for d in directions]
+            if len(self.directions) != 6:
+                raise ValueError(f"NF2FF box '{name}': directions takes six entries (x-, x+, y-, y+, z-, z+)")
+            # a box that is not closed by walls is not a Huygens surface: a face may be switched off only where a mirror stands
+            for f, on in enumerate(self.directions):
+                if not on and not (self.mirror is not None and self.mirror[f]):
+                    raise ValueError(f"NF2FF box '{name}': directions switches face {faces[f]} off but no mirror stands there: "
+                                     "an open box is no closed Huygens surface")
 
     def can_evaluate(self, freq) -> bool:
         """Whether CalcNF2FF can answer for `freq` after this run: any frequency inside the recorder's band when the faces
@@ -930,9 +951,13 @@ class openEMS:
         self._ports.append(port)
         return port
 
-    def CreateNF2FFBox(self, name="nf2ff", start=None, stop=None, **kw):
+    def CreateNF2FFBox(self, name="nf2ff", start=None, stop=None, directions=None, mirror=None, half_space=False, **kw):
+        """mirror: upstream's list of six (x-, x+, y-, y+, z-, z+) 0 / 1 (PEC) / 2 (PMC): that face is a symmetry wall of the run
+        (SetBoundaryCond must name the same wall there) and the box is open on it; CalcNF2FF adds the mirror images
+        (Simulation(nf2ff_mirror=)).  directions: six flags, a face may be switched off only where a mirror stands.  half_space:
+        the one PEC mirror plane is an infinite ground plane (Simulation(nf2ff_half_space=))."""
         self.calls_log.add("CreateNF2FFBox")
-        self._nf2ff = nf2ff(self, name, start, stop)
+        self._nf2ff = nf2ff(self, name, start, stop, directions=directions, mirror=mirror, half_space=half_space)
         return self._nf2ff
 
     def AddFieldDump(self, name, dump_type, start, stop, *, dump_mode=1, frequency=None, timesteps=None, sub_sampling=(1, 1, 1),
@@ -1089,7 +1114,9 @@ class openEMS:
                 fr = np.unique(np.concatenate([np.atleast_1d(np.asarray(fr, float)), dump_freqs]))
             sim = Simulation(grid, vox, f0=self._f0, fc=self._fc, boundary=bc, nr_ts=int(min(self.NrTS, 2**31 - 2)),
                              end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode,
-                             conformal=self._conformal, conformal_ratio=self._conformal_ratio)
+                             conformal=self._conformal, conformal_ratio=self._conformal_ratio,
+                             **({} if self._nf2ff is None or self._nf2ff.mirror is None
+                                else dict(nf2ff_mirror=self._nf2ff.mirror, nf2ff_half_space=self._nf2ff.half_space)))
             for p in dumps:
                 if len(p.boxes) != 1 or not isinstance(p.boxes[0], CSPrimBox) or not np.allclose(p.boxes[0].matrix, np.eye(4)):
                     raise ValueError(f"SAR dump '{p.name}': takes exactly one box, without a transform")
@@ -1161,6 +1188,7 @@ class openEMS:
                                "schedule_fallback": self.stats.schedule_fallback,
                                **({"ports": [{"number": q.port.number, **{k: v for k, v in q.info.items() if k not in ("dist_AC", "dist_loops", "meas_pos")}}
                                              for q in vox.ports if q.info is not None]} if any(q.info is not None for q in vox.ports) else {}),
+                               **({"nf2ff": self._nf2ff_report()} if self._nf2ff is not None and self._nf2ff.mirror is not None else {}),
                                **({"sar": self.stats.sar} if self.stats.sar else {}),
                                **({"fields": field_report} if field_report else {}),
                                **({"excitations": self.stats.excitations} if self.stats.excitations else {}),
@@ -1248,6 +1276,15 @@ class openEMS:
         if key in self._fields:
             return self._fields[key]
         return self.sim.field(name, freq=freq, timestep=timestep)
+
+    def _nf2ff_report(self) -> dict:
+        """The NF2FF entry of fdtd_hip_run.json for a box with mirror planes: the open box in nodes and its planes in metres."""
+        b = self.sim.nf2ff_box
+        planes, half = b.mirror_planes((0.0, 0.0, 0.0))
+        return {"name": self._nf2ff.name, "lo": list(b.lo), "hi": list(b.hi), "mirror": list(b.mirror),
+                "planes": [{"axis": "xyz"[a], "type": "PEC" if t == 1 else "PMC", "coordinate": c, "half_space": q == half}
+                           for q, (a, t, c) in enumerate(planes)],
+                "power_factor": b.power_factor}
 
     def _calc_nf2ff(self, freq, theta_deg, phi_deg, radius, center):
         if self.sim is None or self._nf2ff is None or self.sim.nf2ff_box is None:

@@ -171,7 +171,12 @@ class Simulation:
                  nf2ff_inset: Optional[int] = None, dft_oversample: float = 4.0, use_classes: bool = True,
                  device_operator: bool = True, nf2ff_mode: str = "dft", rec_budget_bytes: Optional[int] = None,
                  sheet_band: Optional[Sequence[float]] = None, sheet_K: int = _sheet.MAX_K,
-                 conformal: bool = False, conformal_ratio: float = _conformal.DEFAULT_RATIO):
+                 conformal: bool = False, conformal_ratio: float = _conformal.DEFAULT_RATIO,
+                 nf2ff_mirror: Optional[Sequence[int]] = None, nf2ff_half_space: bool = False):
+        """nf2ff_mirror: six entries per face (x-, x+, y-, y+, z-, z+), 0 none, 1 PEC, 2 PMC (upstream's numbers): that face is a
+        symmetry wall of the scene — its boundary kind must be the same wall — and the NF2FF box is open there; the far field adds
+        the mirror images (nf2ff.NF2FFBox, nf2ff.calc_nf2ff).  nf2ff_half_space: the one PEC mirror plane is an infinite ground
+        plane instead: nothing radiates behind it and Prad is the half-space's."""
         self.grid, self.vox = grid, vox
         self.f0, self.fc = float(f0), float(fc)
         self.bc = BoundarySpec.parse(boundary, cpml_cells)
@@ -192,9 +197,27 @@ class Simulation:
         self._op: Optional[ECOperator] = None
         cells = self.bc.face_cells()
         self.pmc = self.bc.pmc_faces()
+        faces = ("x-", "x+", "y-", "y+", "z-", "z+")
+        self.nf2ff_mirror = None
+        if nf2ff_mirror is not None:
+            self.nf2ff_mirror = tuple(int(v) for v in nf2ff_mirror)
+            if len(self.nf2ff_mirror) != 6 or any(m not in (0, 1, 2) for m in self.nf2ff_mirror):
+                raise ValueError("nf2ff_mirror: six entries (x-, x+, y-, y+, z-, z+) of 0 (none), 1 (PEC) or 2 (PMC)")
+            if nf2ff_freqs is None:
+                raise ValueError("nf2ff_mirror needs an NF2FF box (nf2ff_freqs=)")
+            for f, m in enumerate(self.nf2ff_mirror):
+                want = (None, "PEC", "PMC")[m]
+                if m and self.bc.kinds[f] != want:
+                    raise ValueError(f"nf2ff_mirror: face {faces[f]} carries a {want} mirror but its boundary is {self.bc.kinds[f]}: "
+                                     f"a mirror plane is a {want} wall of the run")
+        elif nf2ff_half_space:
+            raise ValueError("nf2ff_half_space needs a PEC mirror plane (nf2ff_mirror=), and there is no mirror")
         if self.pmc is not None and nf2ff_freqs is not None:
-            raise ValueError("an NF2FF box together with a PMC face is not supported: the far field of the mirror image is not added "
-                             "— run the whole structure, or leave the NF2FF box out")
+            bare = [faces[f] for f in range(6) if self.pmc[f] and (self.nf2ff_mirror is None or self.nf2ff_mirror[f] != 2)]
+            if bare:
+                raise ValueError(f"an NF2FF box together with a PMC face ({', '.join(bare)}) needs that face as a mirror plane: without "
+                                 "nf2ff_mirror= (2 on a PMC face) the far field of the mirror image is not added — or run the whole "
+                                 "structure, or leave the NF2FF box out")
         self.cpml = None
         if any(cells):
             spec = CPMLSpec(**{**self.bc.cpml.__dict__, "cells": cells})
@@ -232,13 +255,16 @@ class Simulation:
                 ih = (cells[2 * a + 1] + 2) if nf2ff_inset is None else nf2ff_inset
                 il = max(il, 3); ih = max(ih, 3)
                 lo.append(il); hi.append(n[a] - 1 - ih)
-            self.nf2ff_box = NF2FFBox(grid, lo, hi)
+            self.nf2ff_box = NF2FFBox(grid, lo, hi, mirror=self.nf2ff_mirror, half_space=bool(nf2ff_half_space))
+            lo, hi = list(self.nf2ff_box.lo), list(self.nf2ff_box.hi)     # an open box reaches its walls
             # a Huygens surface that runs ALONG metal is no closed surface around the sources: the far field computed from it is not
             # the antenna's (a ground plane on the very plane of the lower face made a 6 dBi patch read 14.6 dBi).  Metal that merely
             # CROSSES a face (an infinite ground plane, as in the legacy scene) is the caller's modelling decision and not flagged.
             self.nf2ff_warning = None
             for a in range(3):
                 for side, pos in ((0, lo[a]), (1, hi[a])):
+                    if self.nf2ff_box.mirror[2 * a + side]:      # open there: no face
+                        continue
                     sl = [slice(lo[2], hi[2] + 1), slice(lo[1], hi[1] + 1), slice(lo[0], hi[0] + 1)]
                     sl[2 - a] = pos
                     frac = max(float(vox.pec[t][tuple(sl)].mean()) for t in range(3) if t != a)
@@ -457,6 +483,8 @@ class Simulation:
         self.partition = partition
         if nk < 2:
             raise ValueError(f"slab of rank {rank} has {nk} planes; need >= 2")
+        if self.nf2ff_mirror is not None and any(self.nf2ff_mirror) and world > 1:
+            raise ValueError("nf2ff_mirror needs a single slab (world = 1): the open NF2FF box of a decomposed run is not supported")
         if self.sheets is not None and world > 1:
             raise _capi.FdtdError("conducting sheets need a single slab (world = 1): a decomposed lossy-metal run is not supported")
         if self.element_stepped.size and world > 1:
@@ -946,6 +974,8 @@ class Simulation:
         if self.nf2ff_box is None or self.engine is None:
             raise RuntimeError("rcs: needs an NF2FF box (nf2ff_freqs=) outside the plane-wave box, and a finished run")
         pw, nb = self.plane_wave, self.nf2ff_box
+        if any(nb.mirror):
+            raise ValueError("rcs: an NF2FF box with mirror planes is not supported (the incident wave has no image)")
         if not all(nb.lo[a] < pw.lo[a] and nb.hi[a] > pw.hi[a] for a in range(3)):
             raise ValueError(f"rcs: the NF2FF box (nodes {nb.lo}..{nb.hi}) does not enclose the box of plane wave '{pw.name}' (nodes {pw.lo}..{pw.hi}): "
                              f"it records the total field, not the scattered one")
