@@ -61,6 +61,8 @@ FIELDS_SYMBOLS = ["fdtd_field_interp"]
 # include/fdtd_hip_farfield.h: the radiation integral over a symmetry half and its mirror images, likewise
 FARFIELD_MIRROR_SYMBOLS = ["fdtd_farfield_mirror"]
 MIRROR_PEC, MIRROR_PMC = 1, 2      # FDTD_MIRROR_PEC / FDTD_MIRROR_PMC: upstream's numbers
+# include/fdtd_hip_aniso.h: the operator build with per-axis cell arrays (anisotropic dielectrics), likewise
+ANISO_SYMBOLS = ["fdtd_build_operator_axes"]
 # FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
 MAX_BOXES = 64
 
@@ -272,7 +274,19 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    aniso_sig = {"fdtd_build_operator_axes": (C.c_int, [p, p, p, p, C.POINTER(p), C.POINTER(p), p, C.c_double, C.c_int, p, p, p, p, p, p, C.c_int])}
+    assert sorted(aniso_sig) == sorted(ANISO_SYMBOLS)
+    for name, (res, args) in aniso_sig.items():      # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
+
+
+def has_aniso(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the operator build with per-axis cell arrays (include/fdtd_hip_aniso.h)."""
+    return all(hasattr(lib, n) for n in ANISO_SYMBOLS)
 
 
 def has_farfield_mirror(lib: C.CDLL) -> bool:
@@ -456,6 +470,34 @@ class Engine:
         eps_r, kappa = _arr(eps_r, np.float64), _arr(kappa, np.float64)
         if eps_r.shape != (nz - 1, ny - 1, nx - 1) or kappa.shape != eps_r.shape:
             raise ValueError("cell arrays must be [nz-1][ny-1][nx-1]")
+        pec, (oe, oc, ov, om), emet, hmet = self._build_operator_rest(pec, overrides, emet, hmet)
+        self._ck(self.lib.fdtd_build_operator(self._ctx, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(eps_r), _ptr(kappa), _ptr(pec),
+                                              float(eps0), int(oe.size), _ptr(oe), _ptr(oc), _ptr(ov), _ptr(om),
+                                              _ptr(emet), _ptr(hmet), 1 if prefer_classes else 0), "build_operator")
+
+    def build_operator_axes(self, d, eps_axes, kappa_axes, pec, eps0, overrides, emet, hmet, prefer_classes=True):
+        """build_operator for anisotropic dielectrics (include/fdtd_hip_aniso.h): eps_axes / kappa_axes per cell and axis
+        [3][nz-1][ny-1][nx-1] — the edges of component c read slice c; every other argument as build_operator's.  Needs a library that
+        exports fdtd_build_operator_axes (has_aniso): there is no other path to the device build."""
+        if not has_aniso(self.lib):
+            raise FdtdError("build_operator_axes: this library does not export fdtd_build_operator_axes (include/fdtd_hip_aniso.h)")
+        nx, ny, nz = self.nx, self.ny, self.nz
+        dx, dy, dz = (_arr(a, np.float64) for a in d)
+        if (dx.size, dy.size, dz.size) != (nx, ny, nz):
+            raise ValueError("cell-size tables must have nx, ny, nz entries")
+        eps_axes, kappa_axes = _arr(eps_axes, np.float64), _arr(kappa_axes, np.float64)
+        if eps_axes.shape != (3, nz - 1, ny - 1, nx - 1) or kappa_axes.shape != eps_axes.shape:
+            raise ValueError("per-axis cell arrays must be [3][nz-1][ny-1][nx-1]")
+        pec, (oe, oc, ov, om), emet, hmet = self._build_operator_rest(pec, overrides, emet, hmet)
+        e3 = (C.c_void_p * 3)(*[eps_axes[c].ctypes.data for c in range(3)])
+        k3 = (C.c_void_p * 3)(*[kappa_axes[c].ctypes.data for c in range(3)])
+        self._ck(self.lib.fdtd_build_operator_axes(self._ctx, _ptr(dx), _ptr(dy), _ptr(dz), e3, k3, _ptr(pec),
+                                                   float(eps0), int(oe.size), _ptr(oe), _ptr(oc), _ptr(ov), _ptr(om),
+                                                   _ptr(emet), _ptr(hmet), 1 if prefer_classes else 0), "build_operator_axes")
+
+    def _build_operator_rest(self, pec, overrides, emet, hmet):
+        """The checks build_operator and build_operator_axes share: pec, the override lists, the metric tables."""
+        nx, ny, nz = self.nx, self.ny, self.nz
         pec = np.ascontiguousarray(pec)
         if pec.dtype == np.bool_:
             pec = pec.view(np.uint8)
@@ -470,9 +512,7 @@ class Engine:
         tl = nx + ny + self.nk
         if emet.shape != (3, tl) or hmet.shape != (3, tl):
             raise ValueError("metric table shape mismatch")
-        self._ck(self.lib.fdtd_build_operator(self._ctx, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(eps_r), _ptr(kappa), _ptr(pec),
-                                              float(eps0), int(oe.size), _ptr(oe), _ptr(oc), _ptr(ov), _ptr(om),
-                                              _ptr(emet), _ptr(hmet), 1 if prefer_classes else 0), "build_operator")
+        return pec, (oe, oc, ov, om), emet, hmet
 
     def operator_form(self):
         """('none' | 'classes' | 'classes-packed' | 'raw', number of distinct (vv, m) pairs)."""

@@ -12,7 +12,7 @@ ContinuousStructure = _api.ContinuousStructure
 
 class CSProperties:            # names probed by probe_openems_fixed (fixed.py:104-105)
     CSProperties = _api.CSProperty
-    CSPropMaterial = _api.CSProperty
+    CSPropMaterial = _api.CSPropMaterial   # SetMaterialProperty / GetMaterialProperty / SetIsotropy / GetIsotropy
     CSPropMetal = _api.CSProperty
     CSPropProbeBox = _api.CSProbe      # what ContinuousStructure.AddProbe returns (probes.py)
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kernel_common.hpp"
+#include "../../include/fdtd_hip_aniso.h"
 
 namespace {
 
@@ -22,8 +23,8 @@ constexpr int MAXK = 256;
 struct OpGeom {
   int nx, ny, nz, k0, nk, kc_lo;
   const double* d[3];
-  const double* eps;       // cells of planes kc_lo.. : [..][ny-1][nx-1]
-  const double* kap;
+  const double* eps[3];    // cells of planes kc_lo.. : [..][ny-1][nx-1], per edge direction (isotropic: one array three times)
+  const double* kap[3];
   const uint8_t* pec[3];   // [nk][ny][nx] each, local planes
   double dt, eps0;
 };
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void k_op_vm(const OpGeom g, float2* __restric
                       pos[a2] == 0 || pos[a2] == nn[a2] - 1;
     float2 out = make_float2(0.f, 0.f);
     if (!dead) {
-      // area-weighted mean of eps_r / kappa over the four cells around the edge, summed in the host order:
+      // area-weighted mean of eps_r[c] / kappa[c] over the four cells around the edge, summed in the host order:
       // a1 offset outer (-1, 0), a2 offset inner (-1, 0); weight = d[a1] * d[a2] of the cell
       double ne = 0.0, nk_ = 0.0, den = 0.0;
       for (int o1 = -1; o1 <= 0; ++o1)
@@ -53,8 +54,8 @@ __global__ __launch_bounds__(256) void k_op_vm(const OpGeom g, float2* __restric
           ci[c] = pos[c]; ci[a1] = pos[a1] + o1; ci[a2] = pos[a2] + o2;
           const double w = g.d[a1][ci[a1]] * g.d[a2][ci[a2]];
           const size_t q = (size_t)(ci[2] - g.kc_lo) * cplane + (size_t)ci[1] * crow + ci[0];
-          ne = ne + g.eps[q] * w;
-          nk_ = nk_ + g.kap[q] * w;
+          ne = ne + g.eps[c][q] * w;
+          nk_ = nk_ + g.kap[c][q] * w;
           den = den + w;
         }
       const double eps_e = (ne / den) * g.eps0;
@@ -247,15 +248,13 @@ int collect_sorted(fdtd_ctx* c, int mode, const float2* vm, const uint8_t* cls, 
   return FDTD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fdtd_build_operator(fdtd_ctx* c, const double* dx, const double* dy, const double* dz, const double* eps_r, const double* kappa,
-                        const uint8_t* pec, double eps0, int n_over, const int64_t* over_edge, const int8_t* over_comp,
-                        const float* over_vv, const float* over_m, const float* emet, const float* hmet, int prefer_classes) {
-  if (!c || !dx || !dy || !dz || !eps_r || !kappa || !pec || !emet || !hmet || n_over < 0 ||
-      (n_over > 0 && (!over_edge || !over_comp || !over_vv || !over_m)))
+// fdtd_build_operator / fdtd_build_operator_axes: eps_r[a], kappa[a] are the cells the edges of direction a read
+int build_operator_axes(fdtd_ctx* c, const double* dx, const double* dy, const double* dz, const double* const eps_r[3],
+                        const double* const kappa[3], const uint8_t* pec, double eps0, int n_over, const int64_t* over_edge,
+                        const int8_t* over_comp, const float* over_vv, const float* over_m, const float* emet, const float* hmet,
+                        int prefer_classes) {
+  if (!c || !dx || !dy || !dz || !eps_r[0] || !eps_r[1] || !eps_r[2] || !kappa[0] || !kappa[1] || !kappa[2] || !pec || !emet || !hmet ||
+      n_over < 0 || (n_over > 0 && (!over_edge || !over_comp || !over_vv || !over_m)))
     return fdtd_fail(c, FDTD_E_ARG, "null argument");
   HIPCK(c, hipSetDevice(c->d.device));
   const int nx = c->d.nx, ny = c->d.ny, nz = c->d.nz, k0 = c->d.k0, nk = c->d.nk;
@@ -267,15 +266,22 @@ int fdtd_build_operator(fdtd_ctx* c, const double* dx, const double* dy, const d
   const int kc_lo = std::max(k0 - 1, 0), kc_hi = std::min(k0 + nk - 1, nz - 2);
   g.kc_lo = kc_lo;
   const size_t cplane = (size_t)(nx - 1) * (ny - 1), ncells_up = cplane * (size_t)(kc_hi - kc_lo + 1);
-  DevBuf<double> d_d[3], d_eps, d_kap;
+  DevBuf<double> d_d[3], d_eps[3], d_kap[3];
   DevBuf<uint8_t> d_pec;
   DevBuf<float2> vm;
   const double* hd[3] = {dx, dy, dz};
   const int nn[3] = {nx, ny, nz};
   for (int a = 0; a < 3; ++a) { HIPCK(c, d_d[a].from(hd[a], nn[a])); g.d[a] = d_d[a].p; }
-  HIPCK(c, d_eps.from(eps_r + (size_t)kc_lo * cplane, ncells_up));
-  HIPCK(c, d_kap.from(kappa + (size_t)kc_lo * cplane, ncells_up));
-  g.eps = d_eps.p; g.kap = d_kap.p;
+  // an array that serves several directions (the isotropic call: all three) is uploaded once
+  for (int a = 0; a < 3; ++a) {
+    g.eps[a] = g.kap[a] = nullptr;
+    for (int b = 0; b < a; ++b) {
+      if (eps_r[b] == eps_r[a]) g.eps[a] = g.eps[b];
+      if (kappa[b] == kappa[a]) g.kap[a] = g.kap[b];
+    }
+    if (!g.eps[a]) { HIPCK(c, d_eps[a].from(eps_r[a] + (size_t)kc_lo * cplane, ncells_up)); g.eps[a] = d_eps[a].p; }
+    if (!g.kap[a]) { HIPCK(c, d_kap[a].from(kappa[a] + (size_t)kc_lo * cplane, ncells_up)); g.kap[a] = d_kap[a].p; }
+  }
   HIPCK(c, d_pec.alloc(3 * ncell));
   const size_t gplane = (size_t)ny * nx;
   for (int comp = 0; comp < 3; ++comp) {
@@ -368,6 +374,26 @@ int fdtd_build_operator(fdtd_ctx* c, const double* dx, const double* dy, const d
   }
   HIPCK(c, hipGetLastError());
   return build_class_rows(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdtd_build_operator(fdtd_ctx* c, const double* dx, const double* dy, const double* dz, const double* eps_r, const double* kappa,
+                        const uint8_t* pec, double eps0, int n_over, const int64_t* over_edge, const int8_t* over_comp,
+                        const float* over_vv, const float* over_m, const float* emet, const float* hmet, int prefer_classes) {
+  const double* const e3[3] = {eps_r, eps_r, eps_r};
+  const double* const k3[3] = {kappa, kappa, kappa};
+  return build_operator_axes(c, dx, dy, dz, e3, k3, pec, eps0, n_over, over_edge, over_comp, over_vv, over_m, emet, hmet, prefer_classes);
+}
+
+int fdtd_build_operator_axes(fdtd_ctx* c, const double* dx, const double* dy, const double* dz, const double* const eps_r[3],
+                             const double* const kappa[3], const uint8_t* pec, double eps0, int n_over, const int64_t* over_edge,
+                             const int8_t* over_comp, const float* over_vv, const float* over_m, const float* emet, const float* hmet,
+                             int prefer_classes) {
+  if (!eps_r || !kappa) return fdtd_fail(c, FDTD_E_ARG, "null argument");
+  return build_operator_axes(c, dx, dy, dz, eps_r, kappa, pec, eps0, n_over, over_edge, over_comp, over_vv, over_m, emet, hmet, prefer_classes);
 }
 
 int fdtd_operator_form(fdtd_ctx* c, int* form, int* nclasses) {

@@ -139,20 +139,40 @@ def _edge_average(cellval: np.ndarray, grid: RectGrid, comp: int) -> np.ndarray:
     return np.pad(avg, pad, mode="edge")
 
 
+def cell_axes(cellval: np.ndarray, grid: RectGrid):
+    """The three per-cell arrays the edges of components x, y, z read: `cellval` itself three times when it is per cell
+    [nz-1][ny-1][nx-1] (an isotropic quantity), its three slices when it is per cell and axis [3][nz-1][ny-1][nx-1]."""
+    nx, ny, nz = grid.shape
+    cellval = np.asarray(cellval)
+    if cellval.shape == (nz - 1, ny - 1, nx - 1):
+        return [cellval] * 3
+    if cellval.shape == (3, nz - 1, ny - 1, nx - 1):
+        return [cellval[c] for c in range(3)]
+    raise ValueError("cell arrays must be [nz-1][ny-1][nx-1] or, per axis, [3][nz-1][ny-1][nx-1]")
+
+
 def build_operator(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np.ndarray,
                    dt: float, lumped: Sequence[LumpedEdge] = (), pmc: Optional[Sequence[bool]] = None) -> ECOperator:
-    """eps_r, kappa: per cell [nz-1][ny-1][nx-1]; pec: bool [3][nz][ny][nx] (True = PEC edge); pmc: metric_lists' argument."""
+    """eps_r, kappa: per cell [nz-1][ny-1][nx-1]; pec: bool [3][nz][ny][nx] (True = PEC edge); pmc: metric_lists' argument.
+
+    Anisotropic dielectrics (diagonal tensors).  eps_r and kappa may each be per cell and axis, [3][nz-1][ny-1][nx-1].  The operator
+    holds one (vv, m) pair per EDGE, and an edge has a direction: for a live edge of component c, eps_e and kap_e are the same
+    area-weighted four-cell means, taken over eps_r[c] and kappa[c] of the cells — an x-edge averages eps_x of its four cells, a
+    y-edge eps_y, a z-edge eps_z — in the same summation order and with the same float64 expressions for x, vv and m.  Hence the
+    composition identity every parity test rests on: component c of the anisotropic operator is, bit for bit, component c of the
+    isotropic operator built from (eps_r[c], kappa[c]) — the lumped overrides included — and three equal slices give the bits of the
+    per-cell call.  emet / hmet (ii, iv and the metric of vi) do not depend on materials.  fdtd_build_operator_axes
+    (include/fdtd_hip_aniso.h) must reproduce these arrays bit for bit."""
     nx, ny, nz = grid.shape
-    if eps_r.shape != (nz - 1, ny - 1, nx - 1) or kappa.shape != eps_r.shape:
-        raise ValueError("cell arrays must be [nz-1][ny-1][nx-1]")
+    eps_c, kap_c = cell_axes(eps_r, grid), cell_axes(kappa, grid)
     if pec.shape != (3, nz, ny, nx):
         raise ValueError("pec must be [3][nz][ny][nx]")
     n_axis = (nx, ny, nz)
     vv = np.empty((3, nz, ny, nx), np.float32)
     m = np.empty((3, nz, ny, nx), np.float32)
     for c in range(3):
-        eps_e = _edge_average(eps_r, grid, c) * EPS0
-        kap_e = _edge_average(kappa, grid, c)
+        eps_e = _edge_average(eps_c[c], grid, c) * EPS0
+        kap_e = _edge_average(kap_c[c], grid, c)
         x = 0.5 * dt * kap_e / eps_e
         vv_c = (1.0 - x) / (1.0 + x)
         m_c = dt / (eps_e * (1.0 + x))
@@ -228,8 +248,10 @@ def pack_metric_tables(emet, hmet, grid: RectGrid, k0: int = 0, nk: Optional[int
 def lumped_overrides(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np.ndarray, dt: float,
                      lumped: Sequence[LumpedEdge], dtype=np.float32):
     """(global edge index int64, comp int8, vv float32, m float32) of the edges that carry a lumped conductance (and,
-    for a lumped element's capacitor, a capacitance: eps_e gains C l / A~) — the few coefficients the host fixes itself when the operator is built on the device (fdtd_build_operator)."""
+    for a lumped element's capacitor, a capacitance: eps_e gains C l / A~) — the few coefficients the host fixes itself when the operator is built on the device (fdtd_build_operator).
+    eps_r / kappa per cell or per cell and axis, as build_operator takes them: an edge of component c reads slice c."""
     nx, ny, nz = grid.shape
+    eps_c, kap_c = cell_axes(eps_r, grid), cell_axes(kappa, grid)
     edge, comp, o_vv, o_m = [], [], [], []
     for le in lumped:
         c, i, j, k = le.comp, le.i, le.j, le.k
@@ -239,10 +261,10 @@ def lumped_overrides(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: 
         a1, a2 = (c + 1) % 3, (c + 2) % 3
         l = grid.d[c][pos[c]]
         A = grid.dd[a1][pos[a1]] * grid.dd[a2][pos[a2]]
-        eps_e = _edge_scalar(eps_r, grid, c, pos) * EPS0
+        eps_e = _edge_scalar(eps_c[c], grid, c, pos) * EPS0
         if le.C:
             eps_e = eps_e + le.C * l / A
-        kap_e = _edge_scalar(kappa, grid, c, pos)
+        kap_e = _edge_scalar(kap_c[c], grid, c, pos)
         C = eps_e * A / l
         G = kap_e * A / l + le.G
         x = 0.5 * dt * G / C

@@ -315,6 +315,60 @@ class CSProperty:
         self._out_of_scope("AddMultiBox")
 
 
+class CSPropMaterial(CSProperty):
+    """What ContinuousStructure.AddMaterial returns, with CSXCAD's CSPropMaterial calls: SetMaterialProperty / GetMaterialProperty,
+    SetIsotropy / GetIsotropy.  ``epsilon`` and ``kappa`` take one value or three, (x, y, z): an anisotropic dielectric with a diagonal
+    tensor along the grid axes (scene.Scene.add_material); three values imply anisotropy, as upstream.  ``mue`` and ``sigma`` stay
+    isotropic (a sequence is refused when the scene is drawn, as before)."""
+    _AXES_OK = ("epsilon", "kappa")
+
+    def __init__(self, log: _CallLog, name: str, **kw):
+        kw = {k: self._value(name, k, v) for k, v in kw.items()}
+        super().__init__(log, "Material", name, **kw)
+        self._isotropic = not any(isinstance(kw.get(k), list) for k in self._AXES_OK)
+
+    @classmethod
+    def _value(cls, name, key, v):
+        """One value as it was given; three values of epsilon / kappa as a list of floats, anything else refused by name."""
+        if key not in cls._AXES_OK or np.ndim(v) == 0:
+            return v
+        try:
+            out = [float(x) for x in np.asarray(v, float).reshape(-1)] if np.ndim(v) == 1 else []
+        except (TypeError, ValueError):
+            out = []
+        if len(out) != 3 or not all(np.isfinite(x) for x in out):
+            raise ValueError(f"material '{name}': {key} = {v!r} must be one value or three finite values (x, y, z)")
+        return out
+
+    def SetMaterialProperty(self, **kw):
+        kw = {k: self._value(self.name, k, v) for k, v in kw.items()}
+        self._log.add("SetMaterialProperty", prop=self.name, **kw)
+        self.params.update(kw)
+        if any(isinstance(kw.get(k), list) for k in self._AXES_OK):
+            self._isotropic = False
+
+    def GetMaterialProperty(self, prop_name):
+        """The value as set: one number, or a (3,) array for an anisotropic epsilon / kappa; CSXCAD's defaults where nothing was set."""
+        if prop_name not in ("epsilon", "mue", "kappa", "sigma", "density"):
+            raise ValueError(f"material '{self.name}': unknown material property {prop_name!r}")
+        v = self.params.get(prop_name, 1.0 if prop_name in ("epsilon", "mue") else 0.0)
+        return np.array(v, float) if isinstance(v, list) else v
+
+    def SetIsotropy(self, val):
+        val = bool(val)
+        if val:
+            for k in self._AXES_OK:
+                v = self.params.get(k)
+                if isinstance(v, list) and not (v[0] == v[1] == v[2]):
+                    raise ValueError(f"material '{self.name}': SetIsotropy(True) with {k} = {v}: the three values differ — set one value "
+                                     f"first (SetMaterialProperty({k}=...))")
+        self._log.add("SetIsotropy", prop=self.name, val=val)
+        self._isotropic = val
+
+    def GetIsotropy(self):
+        return self._isotropic
+
+
 class CSPropDiscMaterial(CSProperty):
     """What ContinuousStructure.AddDiscMaterial returns: a voxel body model (discmaterial.py); AddBox (with or without AddTransform)
     and the analytic solids delimit it, a polyhedron does not."""
@@ -395,6 +449,14 @@ def _take(kw, names, numbered):
     return out
 
 
+def _one(call, name, key, v):
+    """`v` of a dispersive medium, which is isotropic by construction: three values are refused by name."""
+    if np.ndim(v) != 0:
+        raise ValueError(f"{call} '{name}': {key} = {v!r} must be one value: anisotropic dispersive media are not supported "
+                         f"(AddMaterial takes three values)")
+    return v
+
+
 class ContinuousStructure:
     def __init__(self, log: Optional[_CallLog] = None):
         self._log = log or _CallLog()
@@ -405,7 +467,8 @@ class ContinuousStructure:
         return self._grid
 
     def AddMaterial(self, name, **kw):
-        p = CSProperty(self._log, "Material", name, **kw)
+        """``epsilon``, ``kappa``: one value or three (x, y, z) — an anisotropic dielectric (CSPropMaterial)."""
+        p = CSPropMaterial(self._log, name, **kw)
         self.properties.append(p)
         return p
 
@@ -444,8 +507,8 @@ class ContinuousStructure:
         deps = take(("eps_delta", "delta_eps", "epsDelta"), ("eps_delta", "delta_eps", "epsDelta"))
         tau = take(("eps_relax_time", "eps_relaxtime", "tau", "epsRelaxTime"), ("eps_relaxtime", "eps_relax_time", "tau", "epsRelaxTime"))
         order = int(kw.pop("order", len(deps)))
-        eps_inf = float(kw.pop("epsilon", kw.pop("eps_inf", 1.0)))
-        kappa = float(kw.pop("kappa", 0.0))
+        eps_inf = float(_one("AddDebyeMaterial", name, "epsilon", kw.pop("epsilon", kw.pop("eps_inf", 1.0))))
+        kappa = float(_one("AddDebyeMaterial", name, "kappa", kw.pop("kappa", 0.0)))
         density = kw.pop("density", None)
         if kw:
             raise TypeError(f"AddDebyeMaterial: unknown keyword(s) {sorted(kw)}")
@@ -472,8 +535,8 @@ class ContinuousStructure:
         per_pole = lambda n: _take(kw, (n,), ()) + _take(kw, (), (n,))
         fp, f0, relax = per_pole("eps_plasma"), per_pole("eps_pole_freq"), per_pole("eps_relax")
         order = int(kw.pop("order", len(fp)))
-        eps_inf = float(kw.pop("epsilon", 1.0))
-        kappa = float(kw.pop("kappa", 0.0))
+        eps_inf = float(_one("AddLorentzMaterial", name, "epsilon", kw.pop("epsilon", 1.0)))
+        kappa = float(_one("AddLorentzMaterial", name, "kappa", kw.pop("kappa", 0.0)))
         density = kw.pop("density", None)
         if kw:
             raise TypeError(f"AddLorentzMaterial: unknown keyword(s) {sorted(kw)}")

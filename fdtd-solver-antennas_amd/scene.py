@@ -88,10 +88,49 @@ class Material(_Drawable):
     mu_r: float = 1.0        # relative permeability (>= 1) and magnetic loss sigma* [ohm/m]: magnetic.py
     sigma_m: float = 0.0
     density: float = 0.0     # [kg/m^3], 0: no tissue — what SAR divides by (sar.py)
+    # anisotropic dielectric (a diagonal tensor): the (x, y, z) values, None for an isotropic quantity.  eps_r / kappa above then hold
+    # the mean of the three — a scalar view for reports, which the operator never reads (ecoperator.build_operator reads the triple)
+    eps_axes: Optional[Tuple[float, float, float]] = None
+    kappa_axes: Optional[Tuple[float, float, float]] = None
 
     def add_box(self, start, stop, priority=0):
         self.boxes.append(Box(tuple(map(float, start)), tuple(map(float, stop)), int(priority)))
         return self
+
+    @property
+    def anisotropic(self) -> bool:
+        return self.eps_axes is not None or self.kappa_axes is not None
+
+    def axes(self):
+        """((eps_x, eps_y, eps_z), (kappa_x, kappa_y, kappa_z)), whether the material is anisotropic or not."""
+        return (self.eps_axes or (self.eps_r,) * 3, self.kappa_axes or (self.kappa,) * 3)
+
+
+def _scalar_or_axes(name, what, value, positive):
+    """(scalar view, triple or None) of a material value given as one number or as three (x, y, z).  One number is taken as it
+    always was, float(value).  Three are checked: finite, and > 0 (`positive`) or >= 0; three equal values are the isotropic
+    material.  Anything else is a ValueError naming the material."""
+    if np.ndim(value) == 0:
+        return float(value), None
+    try:
+        v = tuple(float(x) for x in np.asarray(value, float).reshape(-1)) if np.ndim(value) == 1 else ()
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 3:
+        raise ValueError(f"material '{name}': {what} = {value!r} must be one value or three (x, y, z)")
+    if not all(np.isfinite(x) and (x > 0 if positive else x >= 0) for x in v):
+        raise ValueError(f"material '{name}': {what} = {value!r} must be finite and {'> 0' if positive else '>= 0'} on every axis")
+    if v[0] == v[1] == v[2]:
+        return v[0], None
+    return (v[0] + v[1] + v[2]) / 3.0, v
+
+
+def _one_value(name, kind, what, value):
+    """`value` of a medium that is isotropic by construction; three values are refused by name."""
+    if np.ndim(value) != 0:
+        raise ValueError(f"{kind} material '{name}': {what} = {value!r} must be one value: anisotropic dispersive media are not supported "
+                         f"(add_material takes three values)")
+    return value
 
 
 @dataclass
@@ -206,16 +245,21 @@ class Scene:
 
     def add_material(self, name, eps_r=1.0, kappa=0.0, mu_r=1.0, sigma_m=0.0, density=0.0) -> Material:
         """mu_r >= 1 and sigma_m >= 0 (magnetic loss sigma* [ohm/m]) make the material magnetic (magnetic.py); anisotropic
-        (sequence), negative or non-finite values and mu_r < 1 are refused.  density [kg/m^3] > 0 makes it tissue for SAR (sar.py)."""
+        (sequence), negative or non-finite values and mu_r < 1 are refused.  density [kg/m^3] > 0 makes it tissue for SAR (sar.py).
+        eps_r and kappa take one value or three, (x, y, z): an anisotropic dielectric with a diagonal tensor along the grid axes
+        (ecoperator.build_operator: an edge of direction c sees eps_r[c] and kappa[c]).  Three values are finite, eps_r > 0, kappa >= 0."""
         _magnetic.check_material(name, mu_r, sigma_m)
-        m = Material(name, float(eps_r), float(kappa), mu_r=float(mu_r), sigma_m=float(sigma_m), density=_density(name, density))
+        eps, eps_axes = _scalar_or_axes(name, "eps_r", eps_r, True)
+        kap, kappa_axes = _scalar_or_axes(name, "kappa", kappa, False)
+        m = Material(name, eps, kap, mu_r=float(mu_r), sigma_m=float(sigma_m), density=_density(name, density),
+                     eps_axes=eps_axes, kappa_axes=kappa_axes)
         self.materials.append(m)
         return m
 
     def add_debye_material(self, name, eps_inf, kappa=0.0, delta_eps=(), tau=(), density=0.0) -> DebyeMaterial:
         """A dispersive dielectric eps(w) = eps_inf + sum_k delta_eps[k] / (1 + j w tau[k]) - j kappa / (w eps0), 1..8 poles.
         Boxes, rotations and priorities work as for add_material; the highest priority owns a cell."""
-        med = _disp.DebyeMedium(eps_inf, kappa, delta_eps, tau)
+        med = _disp.DebyeMedium(_one_value(name, "Debye", "eps_inf", eps_inf), _one_value(name, "Debye", "kappa", kappa), delta_eps, tau)
         m = DebyeMaterial(name, med.eps_inf, med.kappa, medium=med, density=_density(name, density))
         self.materials.append(m)
         return m
@@ -224,7 +268,7 @@ class Scene:
         """A resonant dielectric eps(w) = eps_inf (1 + sum_k wp[k]^2 / (w0[k]^2 - w^2 + j w gamma[k])) - j kappa / (w eps0), 1..4
         poles, all in rad/s; w0[k] = 0 (or w0 left out) is a Drude pole, gamma left out a loss-free one.  Boxes, rotations and
         priorities work as for add_material; the highest priority owns a cell."""
-        med = _lorentz.LorentzMedium(eps_inf, kappa, wp, w0, gamma)
+        med = _lorentz.LorentzMedium(_one_value(name, "Lorentz", "eps_inf", eps_inf), _one_value(name, "Lorentz", "kappa", kappa), wp, w0, gamma)
         m = LorentzMaterial(name, med.eps_inf, med.kappa, medium=med, density=_density(name, density))
         self.materials.append(m)
         return m
@@ -387,6 +431,21 @@ class VoxelScene:
     # turns them into lists
     field_excitations: Optional[list] = None
     unit: float = 1e-3
+    # anisotropic dielectrics (None unless some material of the scene is anisotropic): eps_r / kappa per cell and axis,
+    # [3][nz-1][ny-1][nx-1], filled by the ownership rule of eps_r — slice c is what the edges of direction c read
+    # (ecoperator.build_operator).  eps_r / kappa above then hold, in the cells of an anisotropic material, the MEAN of its three values
+    # (Material.eps_r / .kappa): a scalar view for reports and for the checks that only ask "is this vacuum"; the operator, the
+    # lumped overrides and the edge conductivities of the J dumps read the per-axis arrays and never this view.
+    eps_axes: Optional[np.ndarray] = None
+    kappa_axes: Optional[np.ndarray] = None
+    anisotropic_names: Optional[List[str]] = None   # the anisotropic materials that own at least one cell
+
+    def cell_eps(self) -> np.ndarray:
+        """What the operator reads: eps_axes when the scene is anisotropic, eps_r otherwise."""
+        return self.eps_r if self.eps_axes is None else self.eps_axes
+
+    def cell_kappa(self) -> np.ndarray:
+        return self.kappa if self.kappa_axes is None else self.kappa_axes
 
     @property
     def lumped(self) -> List[LumpedEdge]:
@@ -481,9 +540,34 @@ def _from_voxels(scene: Scene, cell_material, cell_voxel, what: str, out: np.nda
             out[sel] = getattr(m.vmap, what)[m.vmap.data.reshape(-1)[cell_voxel[sel]]]
 
 
+def _fill_axes(scene: Scene, vs: VoxelScene) -> VoxelScene:
+    """eps_axes / kappa_axes of a scene with an anisotropic material, from the cells' owners (cell_material: highest priority wins,
+    later wins ties — the rule that filled eps_r): the owner's three values per axis, eps_r / kappa of the cell (background, disc
+    voxels and folds included) three times where the owner is isotropic.  Both voxelisers end here."""
+    if not any(m.anisotropic for m in scene.materials):
+        return vs
+    vs.eps_axes = np.stack([vs.eps_r] * 3)
+    vs.kappa_axes = np.stack([vs.kappa] * 3)
+    vs.anisotropic_names = []
+    for qi, m in enumerate(scene.materials):
+        if not m.anisotropic:
+            continue
+        sel = vs.cell_material == qi
+        if sel.any():
+            vs.anisotropic_names.append(m.name)
+        for c, (e, k) in enumerate(zip(*m.axes())):
+            vs.eps_axes[c][sel] = e
+            vs.kappa_axes[c][sel] = k
+    return vs
+
+
 def _voxelize(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
     if _prims.has_new(scene):
         return voxelize_owners(scene, grid, rasteriser)
+    return _fill_axes(scene, _voxelize_boxes(scene, grid))
+
+
+def _voxelize_boxes(scene: Scene, grid: RectGrid) -> VoxelScene:
     nx, ny, nz = grid.shape
     u = scene.unit
     tol = _tol(grid)
@@ -800,6 +884,10 @@ def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene
     """voxelize() through the owner arrays (primitives.pack_table -> rasteriser(grid, table) -> (cell_owner, edge_owner)): every
     VoxelScene field is filled from the owners, by the ownership rules of the box path (highest priority, later wins ties; an edge
     is metal when one primitive holds both its end nodes).  Curves and wire centre lines are snapped to grid edges on the host."""
+    return _fill_axes(scene, _voxelize_owners(scene, grid, rasteriser))
+
+
+def _voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene:
     import warnings
     nx, ny, nz = grid.shape
     u = scene.unit
@@ -849,7 +937,7 @@ def voxelize_owners(scene: Scene, grid: RectGrid, rasteriser=None) -> VoxelScene
     for mi, met in enumerate(scene.metals):
         if met.boxes and mi not in owned and not any(_prims.marks_any_edge(grid, table, q) for q in metal_recs if rec["prop"][q] == mi):
             warnings.warn(f"metal '{met.name}' marks no edge of this mesh: it is thinner than a cell and misses every node "
-                          f"(add mesh lines through it)", RuntimeWarning, stacklevel=3)
+                          f"(add mesh lines through it)", RuntimeWarning, stacklevel=4)
     names = [m.name for m in mats]
     if any(isinstance(m, ConductingSheet) for m in scene.metals):
         node_masks = {}

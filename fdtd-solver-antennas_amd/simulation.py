@@ -161,6 +161,7 @@ class RunStats:
     fields: Optional[dict] = None             # field boxes (fields.py): per name the kind, mode, box and points and, once Simulation.field has run, the interpolation time and device yes/no
     excitations: Optional[list] = None        # field excitations (field_excitation.py): per excitation its type, edges / faces, metal edges dropped, delay
     probes: Optional[list] = None             # stand-alone probes (openems_api: CSX.AddProbe): per probe its type, entries and file
+    anisotropic: Optional[dict] = None        # anisotropic dielectrics (scene.py): the materials' names, the cells they own, how the operator was built
     sar: Optional[dict] = None                # SAR boxes (sar.py): per name the voxels, tissue voxels, mass, method and, once Simulation.sar has run, status counts and averaging time
 
 
@@ -306,24 +307,30 @@ class Simulation:
         # Debye media: discretised with the run's dt; the part of the branch currents proportional to the mean edge voltage folded
         # into the cells' kappa (exact: linear in per-cell values), the rest stepped by the engine (fdtd_debye_set)
         self.debye = vox.debye if getattr(vox, "debye", None) is not None and len(vox.debye) else None
-        self.kappa_cells = vox.kappa
+        # anisotropic dielectrics (scene.VoxelScene.eps_axes): the cells' eps_r / kappa per axis, [3][nz-1][ny-1][nx-1] — what the operator,
+        # the lumped overrides and the edge conductivities read in place of the per-cell arrays; the folds below add their term to all
+        # three axes of their own cells (dispersive media are isotropic)
+        self.anisotropic = getattr(vox, "eps_axes", None) is not None
+        self.eps_cells = vox.eps_axes if self.anisotropic else vox.eps_r
+        kappa0 = vox.kappa_axes if self.anisotropic else vox.kappa
+        self.kappa_cells = kappa0
         if self.debye is not None:
             _disp.check_placement(grid, self.debye.cell_medium, cells, [" / ".join(n) for n in self.debye.names])
-            self.kappa_cells = vox.kappa.copy()
+            self.kappa_cells = kappa0.copy()
             for q, m in enumerate(self.debye.media):
                 on = self.debye.cell_medium == q
-                assert np.all(vox.eps_r[on] == m.eps_inf)
-                self.kappa_cells[on] = m.folded(self.dt)[1]
+                assert np.all(self.eps_cells[..., on] == m.eps_inf)
+                self.kappa_cells[..., on] = m.folded(self.dt)[1]
         # Lorentz / Drude media: the same fold with the branches' g0 (lorentz.py), the rest stepped by the engine (fdtd_lorentz_set)
         self.lorentz = vox.lorentz if getattr(vox, "lorentz", None) is not None and len(vox.lorentz) else None
         if self.lorentz is not None:
             _lorentz.check_placement(grid, self.lorentz.cell_medium, cells, [" / ".join(n) for n in self.lorentz.names])
-            if self.kappa_cells is vox.kappa:
-                self.kappa_cells = vox.kappa.copy()
+            if self.kappa_cells is kappa0:
+                self.kappa_cells = kappa0.copy()
             for q, m in enumerate(self.lorentz.media):
                 on = self.lorentz.cell_medium == q
-                assert np.all(vox.eps_r[on] == m.eps_inf)
-                self.kappa_cells[on] = m.folded(self.dt)[1]
+                assert np.all(self.eps_cells[..., on] == m.eps_inf)
+                self.kappa_cells[..., on] = m.folded(self.dt)[1]
         # magnetic materials: per-cell mu_r / sigma_m -> face coefficients at this dt -> classes and boxes; the operator stays the
         # base one (ii = 1, iv0), the faces are corrected by the engine after every H update (fdtd_magnetic_set)
         self.magnetic = None
@@ -393,7 +400,12 @@ class Simulation:
         """planewave.check_placement against the scene as this simulation holds it (again when a SAR box is added)."""
         v = self.vox
         reqs = [] if self.nf2ff_box is None else [(r.kind, r.comp, r.lo, r.hi) for r in self.nf2ff_box.requests]
-        _planewave.check_placement(self.grid, self.plane_wave, cpml_cells=self.bc.face_cells(), kinds=self.bc.kinds, eps_r=v.eps_r, kappa=v.kappa,
+        eps_r, kappa = v.eps_r, v.kappa
+        if self.anisotropic:      # vacuum means vacuum on all three axes: per cell the first axis value that is not the vacuum's
+            ea, ka = v.eps_axes, v.kappa_axes
+            eps_r = np.where(ea[0] != 1.0, ea[0], np.where(ea[1] != 1.0, ea[1], ea[2]))
+            kappa = np.where(ka[0] != 0.0, ka[0], np.where(ka[1] != 0.0, ka[1], ka[2]))
+        _planewave.check_placement(self.grid, self.plane_wave, cpml_cells=self.bc.face_cells(), kinds=self.bc.kinds, eps_r=eps_r, kappa=kappa,
                                    mu_r=getattr(v, "mu_r", None), sigma_m=getattr(v, "sigma_m", None), pec=v.pec, sheets=self.sheets,
                                    elements=self.elements, debye=self.debye, lorentz=self.lorentz, conformal=self.conformal, ports=v.ports,
                                    dft_boxes=reqs, sar_boxes=self.sar_boxes, field_boxes=self.field_boxes)
@@ -443,7 +455,7 @@ class Simulation:
         """(edge, comp, vv, m) of the edges whose operator entries the host fixes: the lumped conductances and capacitances, and the
         hard E edges of the field excitations with vv = m = 0 (their voltage is the source's alone)."""
         v = self.vox
-        edge, comp, vv, m = lumped_overrides(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, dtype=dtype)
+        edge, comp, vv, m = lumped_overrides(self.grid, self.eps_cells, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, dtype=dtype)
         if self.excite_lists is not None and self.excite_lists.hard_e[0].size:
             h = self.excite_lists.hard_e
             key, first = np.unique(h[0] * 3 + h[1], return_index=True)
@@ -457,7 +469,7 @@ class Simulation:
         if self._op is None:
             v = self.vox
             walls = {} if self.pmc is None else {"pmc": self.pmc}
-            self._op = build_operator(self.grid, v.eps_r, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, **walls)
+            self._op = build_operator(self.grid, self.eps_cells, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, **walls)
             if self.excite_lists is not None and self.excite_lists.hard_e[0].size:      # hard E edges: vv = m = 0 (as _overrides)
                 h = self.excite_lists.hard_e
                 self._op.vv.reshape(3, -1)[h[1].astype(np.int64), h[0]] = 0.0
@@ -507,14 +519,21 @@ class Simulation:
             self._check_field_excitations(world)      # (an H-type excitation on a decomposed run: ValueError naming it)
         e = Engine(lib, nx, ny, nz, self.dt, k0=k0, nk=nk, rank=rank, world=world, device=device,
                    max_steps=self.nr_ts, flags=flags)
-        if self.device_operator:
+        # an anisotropic scene on a library without fdtd_build_operator_axes (the oracle): the host arrays
+        if self.device_operator and not (self.anisotropic and not _capi.has_aniso(lib)):
             v = self.vox
             emet, hmet = pack_metric_tables(*metric_lists(g, self.dt, pmc=self.pmc), g, k0, nk)
-            e.build_operator(g.d, v.eps_r, self.kappa_cells, v.pec, EPS0,
-                             self._overrides(), emet, hmet,
-                             prefer_classes=self.use_classes)
+            if self.anisotropic:
+                e.build_operator_axes(g.d, self.eps_cells, self.kappa_cells, v.pec, EPS0, self._overrides(), emet, hmet,
+                                      prefer_classes=self.use_classes)
+            else:
+                e.build_operator(g.d, v.eps_r, self.kappa_cells, v.pec, EPS0,
+                                 self._overrides(), emet, hmet,
+                                 prefer_classes=self.use_classes)
             self.operator_form = "raw" if e.operator_form()[0] == "raw" else "classes"
+            self.operator_build = "device"
         else:
+            self.operator_build = "host"
             cls = self.op.classes(k0, nk) if self.use_classes else None
             if cls is not None:
                 emet, hmet = self.op.metric_tables(k0, nk)
@@ -622,6 +641,15 @@ class Simulation:
                 m = int(edges.cell_medium[sl][edges.cell_medium[sl] >= 0][0])
                 raise ValueError(f"SAR box '{name}' holds cells of the {kind} medium '{' / '.join(edges.names[m])}': the loss of a dispersive "
                                  f"medium depends on frequency, its SAR is not supported — use a material with kappa")
+        if self.anisotropic:
+            ka = self.vox.kappa_axes
+            odd = (ka[0][sl] != ka[1][sl]) | (ka[0][sl] != ka[2][sl])
+            if odd.any():
+                cm, names = getattr(self.vox, "cell_material", None), getattr(self.vox, "material_names", None)
+                q = -1 if cm is None else int(cm[sl][odd][0])
+                mat = names[q] if names is not None and q >= 0 else "?"
+                raise ValueError(f"SAR box '{name}' holds cells of the material '{mat}', whose kappa is anisotropic: SAR takes one "
+                                 f"conductivity per cell (anisotropic eps_r alone is fine) — SAR with anisotropic kappa is not supported")
         rho = getattr(self.vox, "density", None)
         if rho is None or not np.any(rho[sl] > 0):
             raise ValueError(f"SAR box '{name}' holds no cell of a material with density > 0: there is no tissue to average over "
@@ -808,10 +836,11 @@ class Simulation:
                                     "points": list(_fields.out_counts(mode, lo, hi, sub)), "seconds": None, "device": None}
 
     def edge_conductivity(self):
-        """The three kap_e arrays [nz][ny][nx] of the operator (ecoperator._edge_average of the cells' kappa as this run folds it)."""
+        """The three kap_e arrays [nz][ny][nx] of the operator (ecoperator._edge_average of the cells' kappa as this run folds it; component
+        c averages kappa[c] of an anisotropic scene)."""
         if self._kap_e is None:
-            from .ecoperator import _edge_average
-            self._kap_e = [_edge_average(np.asarray(self.kappa_cells, np.float64), self.grid, c) for c in range(3)]
+            from .ecoperator import _edge_average, cell_axes
+            self._kap_e = [_edge_average(k, self.grid, c) for c, k in enumerate(cell_axes(np.asarray(self.kappa_cells, np.float64), self.grid))]
         return self._kap_e
 
     def field(self, name, freq=None, timestep=None) -> "_fields.FieldDump":
@@ -876,7 +905,7 @@ class Simulation:
 
     def _override_vi(self, lumped, idx, comp) -> np.ndarray:
         g, v = self.grid, self.vox
-        m = lumped_overrides(g, v.eps_r, self.kappa_cells, v.pec, self.dt, lumped)[3]
+        m = lumped_overrides(g, self.eps_cells, self.kappa_cells, v.pec, self.dt, lumped)[3]
         nx, ny, _ = g.shape
         k, r = np.divmod(idx, nx * ny)
         j, i = np.divmod(r, nx)
@@ -949,6 +978,16 @@ class Simulation:
             return None
         c = self.conformal
         return {"faces": c.faces(), "cut_edges": int(c.frac.idx.size), "ratio": c.ratio, "dt_factor": c.dt_factor, "clamped": c.clamped}
+
+    def anisotropic_info(self) -> Optional[dict]:
+        """What RunStats.anisotropic reports: the anisotropic materials that own cells, those cells' number, and whether the operator
+        came from fdtd_build_operator_axes ("device") or from the host arrays ("host")."""
+        if not self.anisotropic:
+            return None
+        v = self.vox
+        odd = np.any(v.eps_axes != v.eps_axes[0], axis=0) | np.any(v.kappa_axes != v.kappa_axes[0], axis=0)
+        return {"materials": list(getattr(v, "anisotropic_names", None) or []), "cells": int(np.count_nonzero(odd)),
+                "operator_build": getattr(self, "operator_build", None)}
 
     def planewave_info(self) -> Optional[dict]:
         """What RunStats.planewave reports: direction, e0, the box in nodes and the entries of the two lists."""
@@ -1111,6 +1150,7 @@ class Simulation:
         stats.magnetic = self.magnetic_info()
         stats.conformal = self.conformal_info()
         stats.planewave = self.planewave_info()
+        stats.anisotropic = self.anisotropic_info()
         stats.excitations = None if self.excite_lists is None else self.excite_lists.info
         stats.probes = [pl.info for pl in self.probes.values()] or None
         stats.fields = self._field_report if self.field_boxes else None  # Simulation.field fills in the seconds and device yes/no

@@ -754,6 +754,8 @@ def run_prepared_hip(prepared: FDTDPrepared, *, frequency_hz: float, verbose: in
             out.stats["magnetic"] = st.magnetic
         if getattr(st, "conformal", None) is not None:      # conformal PEC boundaries (openEMS(conformal=True))
             out.stats["conformal"] = st.conformal
+        if getattr(st, "anisotropic", None) is not None:    # anisotropic dielectrics (AddMaterial(epsilon=[ex, ey, ez], kappa=[...]))
+            out.stats["anisotropic"] = st.anisotropic
         if getattr(st, "sar", None) is not None:            # SAR dumps (AddDump(dump_type=20 / 21 / 22))
             out.stats["sar"] = st.sar
         if verbose:
