@@ -63,6 +63,8 @@ FARFIELD_MIRROR_SYMBOLS = ["fdtd_farfield_mirror"]
 MIRROR_PEC, MIRROR_PMC = 1, 2      # FDTD_MIRROR_PEC / FDTD_MIRROR_PMC: upstream's numbers
 # include/fdtd_hip_aniso.h: the operator build with per-axis cell arrays (anisotropic dielectrics), likewise
 ANISO_SYMBOLS = ["fdtd_build_operator_axes"]
+# include/fdtd_hip_subcell.h: sub-cell averaged dielectric surfaces sampled on the device, likewise
+SUBCELL_SYMBOLS = ["fdtd_voxel_subcell"]
 # FDTD_MAX_BOXES (csrc/fdtd_ctx.h; MAX_BOXES of the oracle): the DFT / recorder boxes one context takes
 MAX_BOXES = 64
 
@@ -236,6 +238,14 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if fn is not None:
             fn.restype = res
             fn.argtypes = args
+    subcell_sig = {"fdtd_voxel_subcell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p, C.c_int, p, C.c_int, p, C.c_double, p, C.c_int, C.c_int,
+                                                   p, p, p, p, C.c_int64, p, p, p, p, p, p])}
+    assert sorted(subcell_sig) == sorted(SUBCELL_SYMBOLS)
+    for name, (res, args) in subcell_sig.items():    # optional, likewise
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     planewave_sig = {"fdtd_planewave_set": (C.c_int, [p, C.c_int, p, p, p, p, p, C.c_int, p, p, p, p, p, p, C.c_int])}
     assert sorted(planewave_sig) == sorted(PLANEWAVE_SYMBOLS)
     for name, (res, args) in planewave_sig.items():  # optional, likewise
@@ -317,6 +327,11 @@ def has_planewave(lib: C.CDLL) -> bool:
 def has_conformal(lib: C.CDLL) -> bool:
     """Whether `lib` exports the conformal-boundary entry points (include/fdtd_hip_conformal.h)."""
     return all(hasattr(lib, n) for n in CONFORMAL_SYMBOLS)
+
+
+def has_subcell(lib: C.CDLL) -> bool:
+    """Whether `lib` exports the sub-cell sampling entry point (include/fdtd_hip_subcell.h)."""
+    return all(hasattr(lib, n) for n in SUBCELL_SYMBOLS)
 
 
 def has_voxelize(lib: C.CDLL) -> bool:
@@ -1232,3 +1247,49 @@ def default_fractions(lib: C.CDLL, device: int = 0):
     if os.environ.get("FDTD_VOXELIZE", "").lower() == "host" or not has_conformal(lib):
         return None
     return lambda grid, table: fractions_raw(lib, grid, table, device)
+
+
+def subcell_raw(lib: C.CDLL, grid, table, nsub, prop_eps, prop_kap, prop_plain, skip, device: int = 0):
+    """fdtd_voxel_subcell on a primitives.Table: subcell.edges_spec's result (a subcell.Listed), bit for bit."""
+    from . import subcell as _subcell
+    if not has_subcell(lib):
+        raise FdtdError("this library has no device sub-cell sampling (fdtd_voxel_subcell)")
+    nsub = _subcell.check_nsub(nsub)
+    nx, ny, nz = grid.shape
+    lines = _arr(np.concatenate(grid.lines), np.float64)
+    rec = np.ascontiguousarray(table.rec)
+    verts = _arr(table.verts, np.float64)
+    if rec.dtype.itemsize != 248:
+        raise ValueError("the table's records must be primitives.RECORD")
+    peps, pkap, plain = _arr(prop_eps, np.float64).reshape(-1, 3), _arr(prop_kap, np.float64).reshape(-1, 3), _arr(prop_plain, np.uint8).reshape(-1)
+    if peps.shape != pkap.shape or peps.shape[0] != plain.size or plain.size < 1:
+        raise ValueError("subcell: the property tables need one row per material and the background's")
+    skip = _arr(skip, np.uint8)
+    if skip.shape != (3, nz, ny, nx):
+        raise ValueError("subcell: skip must be [3][nz][ny][nx]")
+    rec_map = None if getattr(table, "rec_map", None) is None else _arr(table.rec_map, np.int32)
+    cap = max(1 << 16, (3 * nx * ny * nz) // 16)
+    while True:
+        comp, idx = np.empty(cap, np.int8), np.empty(cap, np.int64)
+        eps, kap = np.empty(cap, np.float64), np.empty(cap, np.float64)
+        n, dropped = C.c_int64(0), np.zeros(2, np.int64)
+        rc = lib.fdtd_voxel_subcell(int(device), nx, ny, nz, _ptr(lines), int(rec.size), _ptr(rec) if rec.size else None, int(verts.size),
+                                    _ptr(verts) if verts.size else None, float(table.tol), _ptr(rec_map), nsub, int(plain.size - 1), _ptr(peps),
+                                    _ptr(pkap), _ptr(plain), _ptr(skip), int(cap), _ptr(comp), _ptr(idx), _ptr(eps), _ptr(kap),
+                                    C.byref(n), _ptr(dropped))
+        if rc != 0:
+            msg = lib.fdtd_last_error(None)
+            raise FdtdError(f"fdtd_voxel_subcell failed ({rc}): {msg.decode() if msg else ''}")
+        if n.value <= cap:
+            break
+        cap = int(n.value)           # the list did not fit: once more with room for it
+    k = int(n.value)
+    return _subcell.Listed(comp[:k].copy(), idx[:k].copy(), eps[:k].copy(), kap[:k].copy(), nsub, int(dropped[0]), int(dropped[1]))
+
+
+def default_subcell(lib: C.CDLL, device: int = 0):
+    """What openEMS.Run hands to scene.voxelize(subcell=..., device_subcell=): the device call when `lib` exports fdtd_voxel_subcell
+    and FDTD_SUBCELL is not "host", else None (the numpy specification, subcell.edges_spec)."""
+    if os.environ.get("FDTD_SUBCELL", "").lower() == "host" or not has_subcell(lib):
+        return None
+    return lambda grid, table, nsub, peps, pkap, plain, skip: subcell_raw(lib, grid, table, nsub, peps, pkap, plain, skip, device)

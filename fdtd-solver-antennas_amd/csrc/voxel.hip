@@ -984,3 +984,352 @@ extern "C" int fdtd_voxel_fractions(int device, int nx, int ny, int nz, const do
   hipFree(d_lines); hipFree(d_verts); hipFree(d_tab); hipFree(d_node); hipFree(d_code); hipFree(d_idx); hipFree(d_f);
   return rc;
 }
+
+// ---- sub-cell averaged dielectric surfaces (include/fdtd_hip_subcell.h, subcell.edges_spec) -------------------------------------------
+// Pass A (k_sub_cells) owns the sub-voxel lattice: the lanes of a wave are the sub-voxels of one cell (nsub = 4: 64 lanes, one point
+// each; nsub = 8: eight points a lane; nsub = 2: eight cells a wave), the record loop is wave-uniform (the records are read through a
+// uniform pointer, a record whose grown cell box misses every cell of the wave is skipped by a ballot), and the predicate is vx_test,
+// the rasteriser's own text.  Its first launch stores one uint16 per cell: the material of a cell whose sub-voxels all have one owner's,
+// SUB_MIXED otherwise (a ballot).  The host numbers the mixed cells and lists the candidate edges (an edge with a mixed cell among its
+// four, found from the mixed cells); the second launch stores the lattices of the mixed cells alone, compacted — the lattice of the whole grid is never held.
+// Pass B (k_sub_edges), one thread per candidate edge, reads them and does the header's sums in the header's order.  Every output
+// word has one writer; plain vector stores, no atomics.
+#include <algorithm>
+
+#include "../../include/fdtd_hip_subcell.h"
+
+namespace {
+constexpr uint16_t SUB_MIXED = 0xFFFF;
+
+struct SubArgs {
+  int nx, ny, nz;
+  const double* lines;
+  int nprim;
+  const fdtd_voxel_prim* table;      // index boxes clipped to the grid (vx_check_table)
+  const double* verts;
+  double tol;
+  int nsub, nprop;
+  long long ncells;                  // the cells of this launch, >= 1
+  const int32_t* cells;              // FILL: their flat cell indices; otherwise the launch covers cells 0 .. ncells - 1
+  uint16_t* out;                     // per cell one code, or FILL: per cell nsub^3 materials, sub-voxel x fastest
+};
+
+template <int N, bool FILL>
+__global__ __launch_bounds__(VX_BLOCK) void k_sub_cells(const SubArgs a) {
+  const int nsub = a.nsub, pts = nsub * nsub * nsub;
+  const int per_cell = pts / N;                                   // lanes of one cell: 8, 64, 64
+  const int cpw = 64 / per_cell;                                  // cells of one wave: 8, 1, 1
+  const int lane = threadIdx.x & 63;
+  const long long wave = (long long)blockIdx.x * (VX_BLOCK / 64) + (threadIdx.x >> 6);
+  const int g = lane / per_cell, sv0 = lane % per_cell;           // point q of this lane is sub-voxel sv0 + q * per_cell
+  const long long w = wave * cpw + g;
+  const bool valid = w < a.ncells;
+  const long long wc = valid ? w : a.ncells - 1;                  // a lane beyond the end repeats the last cell and stores nothing
+  const long long cell = FILL ? (long long)a.cells[wc] : wc;
+  const int cx = a.nx - 1, cy = a.ny - 1, cz = a.nz - 1;
+  const int i = (int)(cell % cx), j = (int)((cell / cx) % cy), k = (int)(cell / ((long long)cx * cy));   // 0 <= i, j, k <= n - 2
+  const double* lx = a.lines;
+  const double* ly = a.lines + a.nx;
+  const double* lz = a.lines + a.nx + a.ny;
+  const double inv = 1.0 / nsub;
+  const double x0 = lx[i], dx = lx[i + 1] - lx[i], y0 = ly[j], dy = ly[j + 1] - ly[j], z0 = lz[k], dz = lz[k + 1] - lz[k];
+  double wx[N], wy[N], wz[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const int sv = sv0 + q * per_cell;
+    const int sx = sv % nsub, sy = (sv / nsub) % nsub, sz = sv / (nsub * nsub);
+    wx[q] = x0 + ((sx + 0.5) * inv) * dx;
+    wy[q] = y0 + ((sy + 0.5) * inv) * dy;
+    wz[q] = z0 + ((sz + 0.5) * inv) * dz;
+  }
+  int best[N], own[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) { best[q] = INT32_MIN; own[q] = -1; }
+  for (int p = 0; p < a.nprim; ++p) {
+    const fdtd_voxel_prim* r = a.table + p;                       // wave-uniform
+    if (r->role != FDTD_VOXEL_MATERIAL) continue;
+    const int b0 = r->cbox[0], b1 = r->cbox[1], b2 = r->cbox[2], b3 = r->cbox[3], b4 = r->cbox[4], b5 = r->cbox[5];
+    if (b3 < b0 || b4 < b1 || b5 < b2) continue;                  // holds no cell centre: invisible, as to the staircase
+    const int l0 = max(b0 - 1, 0), l1 = max(b1 - 1, 0), l2 = max(b2 - 1, 0);
+    const int h0 = min(b3 + 1, cx - 1), h1 = min(b4 + 1, cy - 1), h2 = min(b5 + 1, cz - 1);
+    const bool gc = i >= l0 && i <= h0 && j >= l1 && j <= h1 && k >= l2 && k <= h2;
+    if (__ballot(gc) == 0ull) continue;
+    const unsigned gate = gc ? ((1u << N) - 1u) : 0u;
+    const unsigned in = vx_test<N, true>(r, r->type, false, r->norm_dir, r->vert0, r->nvert, r->has_matrix != 0, a.verts, a.tol, wx, wy, wz, gate);
+    const int prio = r->priority;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      const bool win = ((in >> q) & 1u) && prio >= best[q];        // records in order: >= lets the later one win a tie
+      best[q] = win ? prio : best[q];
+      own[q] = win ? p : own[q];
+    }
+  }
+  int pid[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) pid[q] = own[q] >= 0 ? a.table[own[q]].prop : a.nprop;
+  if constexpr (FILL) {
+    if (valid) {
+#pragma unroll
+      for (int q = 0; q < N; ++q) a.out[(size_t)w * (size_t)pts + (size_t)(sv0 + q * per_cell)] = (uint16_t)pid[q];
+    }
+  } else {
+    bool same = true;
+#pragma unroll
+    for (int q = 1; q < N; ++q) same = same && pid[q] == pid[0];
+    const int first = __shfl(pid[0], g * per_cell);
+    const unsigned long long m = __ballot(!same || pid[0] != first);
+    const unsigned long long gm = per_cell == 64 ? ~0ull : (((1ull << per_cell) - 1ull) << (g * per_cell));
+    if (valid && sv0 == 0) a.out[cell] = (m & gm) ? SUB_MIXED : (uint16_t)first;
+  }
+}
+
+struct SubEdgeArgs {
+  int nx, ny, nz;
+  const double* lines;
+  int nsub;
+  const double* prop_eps;            // [nprop + 1][3]
+  const double* prop_kap;
+  const uint8_t* prop_plain;
+  long long ncand;
+  const uint8_t* comp;               // per candidate edge: its component,
+  const long long* idx;              // the flat index of its node (interior along a1 and a2, below the last along c: host),
+  const int32_t* quarter;            // [ncand][4], (h1, h2) = (0,0) (0,1) (1,0) (1,1): the lattice slot of that cell, or -(material + 1)
+  const uint16_t* lat;
+  uint8_t* status;                   // bit 0: one of the four cells is mixed for the component; bit 1: some sample's material is not plain
+  double* eps;
+  double* kap;
+};
+
+__global__ __launch_bounds__(VX_BLOCK) void k_sub_edges(const SubEdgeArgs a) {
+  const long long e = (long long)blockIdx.x * VX_BLOCK + threadIdx.x;
+  if (e >= a.ncand) return;
+  const int c = a.comp[e], a1 = (c + 1) % 3, a2 = (c + 2) % 3;
+  const long long g = a.idx[e];
+  const int n[3] = {(int)(g % a.nx), (int)((g / a.nx) % a.ny), (int)(g / ((long long)a.nx * a.ny))};
+  const int off[3] = {0, a.nx, a.nx + a.ny};
+  const int nsub = a.nsub, h = nsub / 2, pts = nsub * nsub * nsub;
+  const int st[3] = {1, nsub, nsub * nsub};
+  const double* L1 = a.lines + off[a1];
+  const double* L2 = a.lines + off[a2];
+  const double dn = (double)nsub;
+  double ne = 0.0, nk = 0.0, den = 0.0;
+  bool mixed = false, bad = false;
+  for (int h1 = 0; h1 < 2; ++h1) {
+    for (int h2 = 0; h2 < 2; ++h2) {
+      const int q1 = n[a1] - 1 + h1, q2 = n[a2] - 1 + h2;            // 0 <= q <= n - 2: the node is interior along a1 and a2
+      const double w = (L1[q1 + 1] - L1[q1]) * (L2[q2 + 1] - L2[q2]);
+      const int code = a.quarter[4 * e + 2 * h1 + h2];
+      const uint16_t* lat = code >= 0 ? a.lat + (size_t)code * (size_t)pts : nullptr;
+      if (lat) {                                                     // the whole cell, not only the quarter: mixed for component c?
+        const int p0 = (int)lat[0];
+        const double e0 = a.prop_eps[3 * p0 + c], k0 = a.prop_kap[3 * p0 + c];
+        for (int s = 1; s < pts; ++s) {
+          const int pid = (int)lat[s];
+          mixed = mixed || a.prop_eps[3 * pid + c] != e0 || a.prop_kap[3 * pid + c] != k0;
+        }
+      }
+      for (int u1 = 0; u1 < h; ++u1) {
+        for (int u2 = 0; u2 < h; ++u2) {
+          const int s1 = h1 ? u1 : h + u1, s2 = h2 ? u2 : h + u2;
+          const int base = s1 * st[a1] + s2 * st[a2];
+          double R = 0.0, K = 0.0;
+          for (int sc = 0; sc < nsub; ++sc) {
+            const int pid = lat ? (int)lat[base + sc * st[c]] : -code - 1;
+            const double ev = a.prop_eps[3 * pid + c], kv = a.prop_kap[3 * pid + c];
+            bad = bad || a.prop_plain[pid] == 0;
+            R = R + 1.0 / ev;
+            K = K + kv;
+          }
+          ne = ne + (dn / R) * w;
+          nk = nk + (K / dn) * w;
+          den = den + w;
+        }
+      }
+    }
+  }
+  a.status[e] = (uint8_t)((mixed ? 1 : 0) | (bad ? 2 : 0));
+  a.eps[e] = ne / den;
+  a.kap[e] = nk / den;
+}
+
+template <bool FILL>
+void sub_launch_cells(const SubArgs& a) {
+  const int nsub = a.nsub;
+  const long long cpw = nsub == 2 ? 8 : 1;
+  const long long waves = (a.ncells + cpw - 1) / cpw;
+  const dim3 grid((unsigned)((waves + VX_BLOCK / 64 - 1) / (VX_BLOCK / 64))), block(VX_BLOCK);
+  if (nsub == 8) hipLaunchKernelGGL((k_sub_cells<8, FILL>), grid, block, 0, 0, a);
+  else hipLaunchKernelGGL((k_sub_cells<1, FILL>), grid, block, 0, 0, a);
+}
+}  // namespace
+
+extern "C" int fdtd_voxel_subcell(int device, int nx, int ny, int nz, const double* lines, int nprim, const void* table, int nvert,
+                                  const double* verts, double tol, const int32_t* rec_map, int nsub, int nprop, const double* prop_eps,
+                                  const double* prop_kap, const uint8_t* prop_plain, const uint8_t* skip, int64_t cap, int8_t* comp,
+                                  int64_t* idx, double* eps_rel, double* kap_e, int64_t* nlisted, int64_t* dropped) {
+  if (!lines || (nvert > 0 && !verts) || !(tol >= 0.0) || (nsub != 2 && nsub != 4 && nsub != 8) || nprop < 0 || nprop >= (int)SUB_MIXED ||
+      !prop_eps || !prop_kap || !prop_plain || !skip || cap < 0 || (cap > 0 && (!comp || !idx || !eps_rel || !kap_e)) || !nlisted)
+    return fdtd_fail(nullptr, FDTD_E_ARG, "bad subcell argument");
+  for (int p = 0; p <= nprop; ++p)
+    for (int c = 0; c < 3; ++c)
+      if (!(prop_eps[3 * p + c] > 0.0) || !(prop_kap[3 * p + c] >= 0.0) || !(prop_eps[3 * p + c] <= 1.7e308) || !(prop_kap[3 * p + c] <= 1.7e308))
+        return fdtd_fail(nullptr, FDTD_E_ARG, "subcell: material %d needs finite eps > 0 and kappa >= 0 on every axis", p);
+  int rc = FDTD_OK;
+  *nlisted = 0;
+  if (dropped) dropped[0] = dropped[1] = 0;
+  try {
+    std::vector<fdtd_voxel_prim> tab((size_t)(nprim > 0 ? nprim : 0));
+    rc = vx_check_table(nx, ny, nz, nprim, table, nvert, tab.data());
+    if (rc != FDTD_OK) return rc;
+    if (nx < 3 || ny < 3 || nz < 3) return FDTD_OK;               // no interior node: every edge is dead
+    bool any = false;
+    for (int p = 0; p < nprim; ++p) {
+      if (rec_map && rec_map[p] != 0) return fdtd_fail(nullptr, FDTD_E_ARG, "subcell: record %d delimits a voxel map: not supported", p);
+      if (tab[p].role != FDTD_VOXEL_MATERIAL) continue;
+      if (tab[p].prop < 0 || tab[p].prop >= nprop) return fdtd_fail(nullptr, FDTD_E_ARG, "subcell: record %d has material %d of %d", p, tab[p].prop, nprop);
+      any = any || (tab[p].cbox[3] >= tab[p].cbox[0] && tab[p].cbox[4] >= tab[p].cbox[1] && tab[p].cbox[5] >= tab[p].cbox[2]);
+    }
+    if (!any) return FDTD_OK;                                     // no material holds a cell centre: no device work
+    const long long cx = nx - 1, cy = ny - 1, cz = nz - 1, ncell = cx * cy * cz, nn = (long long)nx * ny * nz;
+    if (ncell > (long long)INT32_MAX) return fdtd_fail(nullptr, FDTD_E_ARG, "subcell: more than 2^31 - 1 cells");
+    const int pts = nsub * nsub * nsub;
+    HIPCK(nullptr, hipSetDevice(device));
+    double *d_lines = nullptr, *d_verts = nullptr, *d_peps = nullptr, *d_pkap = nullptr, *d_eps = nullptr, *d_kap = nullptr;
+    fdtd_voxel_prim* d_tab = nullptr;
+    uint16_t *d_code = nullptr, *d_lat = nullptr;
+    int32_t *d_cells = nullptr, *d_quarter = nullptr;
+    uint8_t *d_plain = nullptr, *d_comp = nullptr, *d_status = nullptr;
+    long long* d_idx = nullptr;
+    const size_t nl = (size_t)nx + (size_t)ny + (size_t)nz;
+    std::vector<uint16_t> code((size_t)ncell);
+    std::vector<int32_t> mixed_cells, quarter;
+    std::vector<uint8_t> ccomp, status;
+    std::vector<long long> cidx;
+    std::vector<double> ceps, ckap;
+#define VX(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess && rc == FDTD_OK) rc = fdtd_fail(nullptr, e_ == hipErrorOutOfMemory ? FDTD_E_NOMEM : FDTD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+    VX(hipMalloc(&d_lines, nl * sizeof(double)));
+    VX(hipMalloc(&d_verts, (size_t)(nvert > 0 ? nvert : 1) * sizeof(double)));
+    VX(hipMalloc(&d_tab, (size_t)nprim * sizeof(fdtd_voxel_prim)));
+    VX(hipMalloc(&d_code, (size_t)ncell * sizeof(uint16_t)));
+    if (rc == FDTD_OK) {
+      VX(hipMemcpy(d_lines, lines, nl * sizeof(double), hipMemcpyHostToDevice));
+      if (nvert > 0) VX(hipMemcpy(d_verts, verts, (size_t)nvert * sizeof(double), hipMemcpyHostToDevice));
+      VX(hipMemcpy(d_tab, tab.data(), (size_t)nprim * sizeof(fdtd_voxel_prim), hipMemcpyHostToDevice));
+    }
+    SubArgs a{nx, ny, nz, d_lines, nprim, d_tab, d_verts, tol, nsub, nprop, ncell, nullptr, d_code};
+    if (rc == FDTD_OK) {
+      sub_launch_cells<false>(a);
+      VX(hipGetLastError());
+      VX(hipDeviceSynchronize());
+      if (rc == FDTD_OK) VX(hipMemcpy(code.data(), d_code, (size_t)ncell * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    if (rc == FDTD_OK) {
+      // the mixed cells, numbered in cell order (a cell's lattice slot is its position in that list)
+      for (long long q = 0; q < ncell; ++q)
+        if (code[(size_t)q] == SUB_MIXED) mixed_cells.push_back((int32_t)q);
+        else if ((int)code[(size_t)q] > nprop) rc = fdtd_fail(nullptr, FDTD_E_DEVICE, "subcell: cell %lld came back with material %d", q, (int)code[(size_t)q]);
+      // The candidate edges: the four edges per component around every mixed cell that have their four cells (interior along a1 and
+      // a2), as keys component * nn + flat node index; sorted and made unique, they stand in list order.  The walk is over the mixed
+      // cells, a surface, not over the grid's edges.
+      const int lim[3] = {nx, ny, nz};
+      std::vector<long long> keys;
+      keys.reserve(rc == FDTD_OK ? mixed_cells.size() * 12 : 0);
+      for (size_t m = 0; m < mixed_cells.size() && rc == FDTD_OK; ++m) {
+        const long long cell = mixed_cells[m];
+        const int q[3] = {(int)(cell % cx), (int)((cell / cx) % cy), (int)(cell / (cx * cy))};
+        for (int c = 0; c < 3; ++c) {
+          const int a1 = (c + 1) % 3, a2 = (c + 2) % 3;
+          for (int o1 = 0; o1 < 2; ++o1)
+            for (int o2 = 0; o2 < 2; ++o2) {
+              int n[3];
+              n[c] = q[c]; n[a1] = q[a1] + o1; n[a2] = q[a2] + o2;           // n[c] <= lim[c] - 2: a cell index
+              if (n[a1] < 1 || n[a1] > lim[a1] - 2 || n[a2] < 1 || n[a2] > lim[a2] - 2) continue;   // an outer plane: no four cells
+              keys.push_back((long long)c * nn + ((long long)n[2] * ny + n[1]) * nx + n[0]);
+            }
+        }
+      }
+      std::sort(keys.begin(), keys.end());
+      keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+      for (size_t e = 0; e < keys.size() && rc == FDTD_OK; ++e) {
+        const int c = (int)(keys[e] / nn), a1 = (c + 1) % 3, a2 = (c + 2) % 3;
+        const long long g = keys[e] % nn;
+        if (skip[(size_t)keys[e]] == 1) continue;
+        const int n[3] = {(int)(g % nx), (int)((g / nx) % ny), (int)(g / ((long long)nx * ny))};
+        int32_t q4[4];
+        for (int h1 = 0; h1 < 2; ++h1)
+          for (int h2 = 0; h2 < 2; ++h2) {
+            int q[3];
+            q[c] = n[c]; q[a1] = n[a1] - 1 + h1; q[a2] = n[a2] - 1 + h2;     // 0 <= q <= lim - 2 on every axis
+            const long long cell = ((long long)q[2] * cy + q[1]) * cx + q[0];
+            if (code[(size_t)cell] == SUB_MIXED)
+              q4[2 * h1 + h2] = (int32_t)(std::lower_bound(mixed_cells.begin(), mixed_cells.end(), (int32_t)cell) - mixed_cells.begin());
+            else
+              q4[2 * h1 + h2] = -(int32_t)code[(size_t)cell] - 1;
+          }
+        ccomp.push_back((uint8_t)c); cidx.push_back(g);
+        quarter.insert(quarter.end(), q4, q4 + 4);
+      }
+    }
+    const size_t nmixed = mixed_cells.size(), ncand = cidx.size();
+    if (rc == FDTD_OK && ncand > 0) {
+      status.resize(ncand); ceps.resize(ncand); ckap.resize(ncand);
+      VX(hipMalloc(&d_cells, nmixed * sizeof(int32_t)));
+      VX(hipMalloc(&d_lat, nmixed * (size_t)pts * sizeof(uint16_t)));
+      VX(hipMalloc(&d_peps, (size_t)(nprop + 1) * 3 * sizeof(double)));
+      VX(hipMalloc(&d_pkap, (size_t)(nprop + 1) * 3 * sizeof(double)));
+      VX(hipMalloc(&d_plain, (size_t)(nprop + 1)));
+      VX(hipMalloc(&d_comp, ncand));
+      VX(hipMalloc(&d_idx, ncand * sizeof(long long)));
+      VX(hipMalloc(&d_quarter, ncand * 4 * sizeof(int32_t)));
+      VX(hipMalloc(&d_status, ncand));
+      VX(hipMalloc(&d_eps, ncand * sizeof(double)));
+      VX(hipMalloc(&d_kap, ncand * sizeof(double)));
+      if (rc == FDTD_OK) {
+        VX(hipMemcpy(d_cells, mixed_cells.data(), nmixed * sizeof(int32_t), hipMemcpyHostToDevice));
+        VX(hipMemcpy(d_peps, prop_eps, (size_t)(nprop + 1) * 3 * sizeof(double), hipMemcpyHostToDevice));
+        VX(hipMemcpy(d_pkap, prop_kap, (size_t)(nprop + 1) * 3 * sizeof(double), hipMemcpyHostToDevice));
+        VX(hipMemcpy(d_plain, prop_plain, (size_t)(nprop + 1), hipMemcpyHostToDevice));
+        VX(hipMemcpy(d_comp, ccomp.data(), ncand, hipMemcpyHostToDevice));
+        VX(hipMemcpy(d_idx, cidx.data(), ncand * sizeof(long long), hipMemcpyHostToDevice));
+        VX(hipMemcpy(d_quarter, quarter.data(), ncand * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
+      }
+      if (rc == FDTD_OK) {
+        SubArgs f = a;
+        f.ncells = (long long)nmixed; f.cells = d_cells; f.out = d_lat;
+        sub_launch_cells<true>(f);
+        VX(hipGetLastError());
+        SubEdgeArgs b{nx, ny, nz, d_lines, nsub, d_peps, d_pkap, d_plain, (long long)ncand, d_comp, d_idx, d_quarter, d_lat, d_status, d_eps, d_kap};
+        hipLaunchKernelGGL(k_sub_edges, dim3((unsigned)((ncand + VX_BLOCK - 1) / VX_BLOCK)), dim3(VX_BLOCK), 0, 0, b);
+        VX(hipGetLastError());
+        VX(hipDeviceSynchronize());
+        if (rc == FDTD_OK) VX(hipMemcpy(status.data(), d_status, ncand, hipMemcpyDeviceToHost));
+        if (rc == FDTD_OK) VX(hipMemcpy(ceps.data(), d_eps, ncand * sizeof(double), hipMemcpyDeviceToHost));
+        if (rc == FDTD_OK) VX(hipMemcpy(ckap.data(), d_kap, ncand * sizeof(double), hipMemcpyDeviceToHost));
+      }
+    }
+#undef VX
+    hipFree(d_lines); hipFree(d_verts); hipFree(d_tab); hipFree(d_code); hipFree(d_lat); hipFree(d_cells); hipFree(d_quarter);
+    hipFree(d_peps); hipFree(d_pkap); hipFree(d_plain); hipFree(d_comp); hipFree(d_idx); hipFree(d_status); hipFree(d_eps); hipFree(d_kap);
+    if (rc != FDTD_OK) return rc;
+    int64_t n = 0, drop[2] = {0, 0};
+    for (int pass = 0; pass < 2; ++pass) {                         // count, then store if the list fits
+      if (pass == 1 && n > cap) break;
+      int64_t at = 0;
+      for (size_t e = 0; e < ncand; ++e) {
+        if (!(status[e] & 1)) continue;
+        const uint8_t sk = skip[(size_t)ccomp[e] * (size_t)nn + (size_t)cidx[e]];
+        if (sk == 2) { if (pass == 0) ++drop[0]; continue; }
+        if (sk != 0) continue;
+        if (status[e] & 2) { if (pass == 0) ++drop[1]; continue; }
+        if (pass == 0) { ++n; continue; }
+        comp[at] = (int8_t)ccomp[e]; idx[at] = (int64_t)cidx[e]; eps_rel[at] = ceps[e]; kap_e[at] = ckap[e];
+        ++at;
+      }
+    }
+    *nlisted = n;
+    if (dropped) { dropped[0] = drop[0]; dropped[1] = drop[1]; }
+    return FDTD_OK;
+  } catch (...) {
+    return fdtd_fail(nullptr, FDTD_E_NOMEM, "subcell: no host memory");
+  }
+}

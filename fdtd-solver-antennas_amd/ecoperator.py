@@ -152,8 +152,11 @@ def cell_axes(cellval: np.ndarray, grid: RectGrid):
 
 
 def build_operator(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np.ndarray,
-                   dt: float, lumped: Sequence[LumpedEdge] = (), pmc: Optional[Sequence[bool]] = None) -> ECOperator:
+                   dt: float, lumped: Sequence[LumpedEdge] = (), pmc: Optional[Sequence[bool]] = None,
+                   edge_overrides=None) -> ECOperator:
     """eps_r, kappa: per cell [nz-1][ny-1][nx-1]; pec: bool [3][nz][ny][nx] (True = PEC edge); pmc: metric_lists' argument.
+    edge_overrides: (edge int64, comp int8, vv float32, m float32) of further host-fixed edges (subcell.overrides), applied after
+    the lumped ones exactly as they are — what fdtd_build_operator does with its override list; None: nothing moves.
 
     Anisotropic dielectrics (diagonal tensors).  eps_r and kappa may each be per cell and axis, [3][nz-1][ny-1][nx-1].  The operator
     holds one (vv, m) pair per EDGE, and an edge has a direction: for a live edge of component c, eps_e and kap_e are the same
@@ -200,6 +203,11 @@ def build_operator(grid: RectGrid, eps_r: np.ndarray, kappa: np.ndarray, pec: np
     edge, comp, o_vv, o_m = lumped_overrides(grid, eps_r, kappa, pec, dt, lumped)
     op.vv.reshape(3, -1)[comp, edge] = o_vv
     op.m.reshape(3, -1)[comp, edge] = o_m
+    if edge_overrides is not None:
+        edge, comp, o_vv, o_m = edge_overrides
+        comp, edge = np.asarray(comp, np.int64), np.asarray(edge, np.int64)
+        op.vv.reshape(3, -1)[comp, edge] = np.asarray(o_vv, np.float32)
+        op.m.reshape(3, -1)[comp, edge] = np.asarray(o_m, np.float32)
     return op
 
 

@@ -882,10 +882,15 @@ class openEMS:
     nf2ff_freqs (default then: a 21-point comb over the reference's S11 band, CalcNF2FF snaps to the nearest).
     conformal=True: conformal (Dey-Mittra) PEC boundaries on the surfaces of curved and slanted metals (conformal.py) instead of the
     bare staircase, every g_e = f_e / a_f bounded by conformal_ratio (R, default 2); a scene with cut faces then runs at
-    courant_dt / sqrt(R).  The default False changes nothing."""
+    courant_dt / sqrt(R).  The default False changes nothing.
+    subcell=True: sub-cell averaged dielectric surfaces (subcell.py) — an edge that the surface of a curved or slanted dielectric
+    crosses takes its permittivity and conductivity from subcell_samples (2, 4 or 8, default 4) sub-voxels per cell and axis instead of
+    the staircase's four-cell mean; a scene whose dielectrics are boxes on mesh lines lists no edge and builds today's operator.  A
+    scene with AddDiscMaterial is refused.  The default False changes nothing."""
 
     def __init__(self, NrTS=1e9, EndCriteria=1e-5, *, lib=None, device=0, rank=0, world=1, cpml_cells=None,
-                 nf2ff_freqs=None, nf2ff_mode="auto", comm=None, conformal=False, conformal_ratio=2.0, **kw):
+                 nf2ff_freqs=None, nf2ff_mode="auto", comm=None, conformal=False, conformal_ratio=2.0,
+                 subcell=False, subcell_samples=4, **kw):
         self.calls_log = _CallLog()
         self.NrTS, self.EndCriteria = NrTS, EndCriteria
         self.calls_log.add("openEMS", NrTS=NrTS, EndCriteria=EndCriteria)
@@ -893,6 +898,10 @@ class openEMS:
         self._cpml_cells, self._nf2ff_freqs, self._comm = cpml_cells, nf2ff_freqs, comm
         self._nf2ff_mode, self._nf2ff_snap, self._box_cache = nf2ff_mode, False, {}
         self._conformal, self._conformal_ratio = bool(conformal), float(conformal_ratio)
+        self._subcell, self._subcell_samples = bool(subcell), subcell_samples
+        if self._subcell:
+            from .subcell import check_nsub
+            check_nsub(subcell_samples)
         self._csx: Optional[ContinuousStructure] = None
         self._bc = ["PEC"] * 6
         self._f0 = self._fc = None
@@ -1154,7 +1163,7 @@ class openEMS:
     def Run(self, sim_path, cleanup=False, setup_only=False, verbose=None, **kw):
         """Time-step on the GPU.  Blocks; ctypes releases the GIL so a GUI thread stays live
         (the reference calls this from one background thread, gui_app.py:2688-2690)."""
-        from ._capi import load_hip_library, default_rasteriser, default_fractions
+        from ._capi import load_hip_library, default_rasteriser, default_fractions, default_subcell
         self.calls_log.add("Run", verbose=verbose, cleanup=cleanup)
         if self._csx is None or self._f0 is None:
             raise RuntimeError("SetCSX and SetGaussExcite must be called before Run")
@@ -1163,6 +1172,8 @@ class openEMS:
         lib = self._lib or load_hip_library()
         grid, sc = self._build_scene()
         fractions = dict(conformal=True, device_fractions=default_fractions(lib, self._device)) if self._conformal else {}
+        if self._subcell:
+            fractions.update(subcell=int(self._subcell_samples), device_subcell=default_subcell(lib, self._device))
         vox = voxelize(sc, grid, rasteriser=default_rasteriser(lib, self._device), **fractions)
         bc = BoundarySpec.parse(self._bc, self._cpml_cells)
         freqs = None
@@ -1178,6 +1189,7 @@ class openEMS:
             sim = Simulation(grid, vox, f0=self._f0, fc=self._fc, boundary=bc, nr_ts=int(min(self.NrTS, 2**31 - 2)),
                              end_criteria=float(self.EndCriteria), nf2ff_freqs=fr, nf2ff_mode=self._nf2ff_mode,
                              conformal=self._conformal, conformal_ratio=self._conformal_ratio,
+                             subcell=self._subcell, subcell_samples=self._subcell_samples,
                              **({} if self._nf2ff is None or self._nf2ff.mirror is None
                                 else dict(nf2ff_mirror=self._nf2ff.mirror, nf2ff_half_space=self._nf2ff.half_space)))
             for p in dumps:

@@ -30,6 +30,7 @@ from . import lorentz as _lorentz
 from . import lumped as _lumped
 from . import magnetic as _magnetic
 from . import conformal as _conformal
+from . import subcell as _subcell
 from . import primitives as _prims
 from . import planewave as _planewave
 from . import discmaterial as _discmaterial
@@ -439,6 +440,9 @@ class VoxelScene:
     eps_axes: Optional[np.ndarray] = None
     kappa_axes: Optional[np.ndarray] = None
     anisotropic_names: Optional[List[str]] = None   # the anisotropic materials that own at least one cell
+    # sub-cell averaged dielectric surfaces (None: not asked for): the listed edges with their eps_rel / kap_e (subcell.Listed);
+    # Simulation(subcell=True) turns them into per-edge operator overrides
+    subcell: Optional["_subcell.Listed"] = None
 
     def cell_eps(self) -> np.ndarray:
         """What the operator reads: eps_axes when the scene is anisotropic, eps_r otherwise."""
@@ -507,12 +511,27 @@ def _merged_media(materials, kind):
     return media, names, medium_of
 
 
-def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = False, device_fractions=None) -> VoxelScene:
+def voxelize(scene: Scene, grid: RectGrid, rasteriser=None, conformal: bool = False, device_fractions=None, subcell: int = 0,
+             device_subcell=None) -> VoxelScene:
     """A scene drawn with boxes only takes the box path; any other primitive sends every primitive, boxes included, through the
     owner arrays of `rasteriser` (default: primitives.rasterise_spec; _capi.voxelize_device gives the device one).  `conformal`:
     also the fractions of the edges the plain metals cut (conformal.fractions; `device_fractions`: _capi.default_fractions' callable,
-    None: numpy) — the staircase itself, every other field of the result, stays what it is."""
+    None: numpy) — the staircase itself, every other field of the result, stays what it is.  `subcell` (0: off; 2, 4 or 8 sub-voxels
+    per cell and axis): also the edges that dielectric surfaces cross, with their sub-cell averaged eps_rel / kap_e (subcell.listed;
+    `device_subcell`: _capi.default_subcell's callable, None: numpy); nothing else of the result changes."""
+    if subcell:
+        _subcell.check_nsub(subcell)
+        _subcell.prop_tables(scene)             # refuses a disc material by name before anything is rasterised
     vs = _voxelize(scene, grid, rasteriser)
+    if subcell:
+        # the edges whose operator entries the host fixes anyway: the ports' resistors, the sheet edges, the lumped elements' edges
+        le = vs.lumped
+        edge = [grid.flat(np.array([e.i for e in le], np.int64), np.array([e.j for e in le], np.int64), np.array([e.k for e in le], np.int64))]
+        comp = [np.array([e.comp for e in le], np.int64)]
+        for lst in (vs.sheets, vs.elements):
+            if lst is not None and len(lst):
+                edge.append(np.asarray(lst.idx, np.int64)); comp.append(np.asarray(lst.comp, np.int64))
+        vs.subcell = _subcell.listed(scene, grid, int(subcell), vs.pec, np.concatenate(edge), np.concatenate(comp), device_subcell)
     if any(m.density > 0 or (isinstance(m, DiscMaterial) and np.any(m.vmap.density > 0)) for m in scene.materials):
         vs.density = np.array([m.density for m in scene.materials] + [0.0])[vs.cell_material]
         _from_voxels(scene, vs.cell_material, vs.cell_voxel, "density", vs.density)

@@ -22,6 +22,7 @@ from . import dispersion as _disp
 from . import lorentz as _lorentz
 from . import magnetic as _magnetic
 from . import conformal as _conformal
+from . import subcell as _subcell
 from . import sar as _sar
 from . import planewave as _planewave
 from . import fields as _fields
@@ -157,6 +158,7 @@ class RunStats:
     lumped: Optional[list] = None             # lumped elements (lumped.py): per element name, kind, R/L/C, edges, split, resonances
     magnetic: Optional[dict] = None           # magnetic materials (magnetic.py): media, classes, faces per component, box extents
     conformal: Optional[dict] = None          # conformal PEC boundaries (conformal.py): faces per component, R, dt factor, faces clamped
+    subcell: Optional[dict] = None            # sub-cell averaged dielectric surfaces (subcell.py): listed edges per component, nsub, edges dropped for lumped overrides / dispersive owners, the operator form
     planewave: Optional[dict] = None          # plane-wave excitation (planewave.py): direction, e0, the box in nodes, entries per list
     fields: Optional[dict] = None             # field boxes (fields.py): per name the kind, mode, box and points and, once Simulation.field has run, the interpolation time and device yes/no
     excitations: Optional[list] = None        # field excitations (field_excitation.py): per excitation its type, edges / faces, metal edges dropped, delay
@@ -173,7 +175,8 @@ class Simulation:
                  device_operator: bool = True, nf2ff_mode: str = "dft", rec_budget_bytes: Optional[int] = None,
                  sheet_band: Optional[Sequence[float]] = None, sheet_K: int = _sheet.MAX_K,
                  conformal: bool = False, conformal_ratio: float = _conformal.DEFAULT_RATIO,
-                 nf2ff_mirror: Optional[Sequence[int]] = None, nf2ff_half_space: bool = False):
+                 nf2ff_mirror: Optional[Sequence[int]] = None, nf2ff_half_space: bool = False,
+                 subcell: bool = False, subcell_samples: int = 4):
         """nf2ff_mirror: six entries per face (x-, x+, y-, y+, z-, z+), 0 none, 1 PEC, 2 PMC (upstream's numbers): that face is a
         symmetry wall of the scene — its boundary kind must be the same wall — and the NF2FF box is open there; the far field adds
         the mirror images (nf2ff.NF2FFBox, nf2ff.calc_nf2ff).  nf2ff_half_space: the one PEC mirror plane is an infinite ground
@@ -190,6 +193,19 @@ class Simulation:
             if getattr(vox, "fractions", None) is None:
                 raise ValueError("conformal=True needs the fractions of the cut edges: scene.voxelize(scene, grid, conformal=True)")
             self.conformal = _conformal.make_faces(grid, vox.fractions, vox.pec, conformal_ratio)
+        # sub-cell averaged dielectric surfaces: the listed edges of scene.voxelize(subcell=) become per-edge (vv, m) overrides next to
+        # the lumped ones (_overrides); the Courant limit stays, a mean of eps >= 1 is >= 1
+        self.subcell = None
+        if subcell:
+            nsub = _subcell.check_nsub(subcell_samples)
+            if getattr(vox, "cell_voxel", None) is not None:
+                raise ValueError("subcell=True on a scene with a disc material (AddDiscMaterial): sub-cell averaging of voxel body models is not supported")
+            if getattr(vox, "subcell", None) is None:
+                raise ValueError(f"subcell=True needs the listed edges: scene.voxelize(scene, grid, subcell={nsub})")
+            if vox.subcell.nsub != nsub:
+                raise ValueError(f"subcell_samples = {nsub}, but the scene was voxelised with subcell={vox.subcell.nsub}")
+            self.subcell = vox.subcell
+        self._subcell_clash = 0
         self.dt = (grid.courant_dt() if self.conformal is None else float(grid.courant_dt() / np.sqrt(self.conformal.ratio))) if dt is None else float(dt)
         self.use_classes = use_classes
         # True: the engine builds the operator itself from materials + mesh (fdtd_build_operator: on the GPU for
@@ -451,9 +467,10 @@ class Simulation:
                               conformal=self.conformal, plane_wave_elems=pw_elems, ports=self.vox.ports, elements=self.elements, sheets=self.sheets,
                               debye=self.debye, lorentz=self.lorentz, world=world)
 
-    def _overrides(self, dtype=np.float32):
-        """(edge, comp, vv, m) of the edges whose operator entries the host fixes: the lumped conductances and capacitances, and the
-        hard E edges of the field excitations with vv = m = 0 (their voltage is the source's alone)."""
+    def _overrides(self, dtype=np.float32, subcell: bool = True):
+        """(edge, comp, vv, m) of the edges whose operator entries the host fixes: the lumped conductances and capacitances, the
+        hard E edges of the field excitations with vv = m = 0 (their voltage is the source's alone), and last (`subcell`) the listed
+        edges of the sub-cell averaged dielectric surfaces that are none of the former."""
         v = self.vox
         edge, comp, vv, m = lumped_overrides(self.grid, self.eps_cells, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, dtype=dtype)
         if self.excite_lists is not None and self.excite_lists.hard_e[0].size:
@@ -461,7 +478,17 @@ class Simulation:
             key, first = np.unique(h[0] * 3 + h[1], return_index=True)
             z = np.zeros(first.size, dtype)
             edge, comp, vv, m = np.concatenate([edge, h[0][first]]), np.concatenate([comp, h[1][first]]), np.concatenate([vv, z]), np.concatenate([m, z])
+        if subcell and self.subcell is not None:
+            s_edge, s_comp, s_vv, s_m = self._subcell_overrides(edge, comp, dtype)
+            edge, comp, vv, m = np.concatenate([edge, s_edge]), np.concatenate([comp, s_comp]), np.concatenate([vv, s_vv]), np.concatenate([m, s_m])
         return edge, comp, vv, m
+
+    def _subcell_overrides(self, edge, comp, dtype=np.float32):
+        """subcell.overrides of the listed edges that carry no other host-fixed override (edge, comp): the lists stay disjoint."""
+        s_edge, s_comp, s_vv, s_m = _subcell.overrides(self.subcell, self.dt, dtype)
+        keep = ~np.isin(s_edge * 3 + s_comp, np.asarray(edge, np.int64) * 3 + np.asarray(comp, np.int64))
+        self._subcell_clash = int(np.count_nonzero(~keep))
+        return s_edge[keep], s_comp[keep], s_vv[keep], s_m[keep]
 
     @property
     def op(self) -> ECOperator:
@@ -469,6 +496,8 @@ class Simulation:
         if self._op is None:
             v = self.vox
             walls = {} if self.pmc is None else {"pmc": self.pmc}
+            if self.subcell is not None:      # the listed edges, never one the host fixes otherwise (as _overrides)
+                walls["edge_overrides"] = self._subcell_overrides(*self._overrides(subcell=False)[:2])
             self._op = build_operator(self.grid, self.eps_cells, self.kappa_cells, v.pec, self.dt, v.lumped + self.sheet_lumped + self.element_lumped, **walls)
             if self.excite_lists is not None and self.excite_lists.hard_e[0].size:      # hard E edges: vv = m = 0 (as _overrides)
                 h = self.excite_lists.hard_e
@@ -979,6 +1008,16 @@ class Simulation:
         c = self.conformal
         return {"faces": c.faces(), "cut_edges": int(c.frac.idx.size), "ratio": c.ratio, "dt_factor": c.dt_factor, "clamped": c.clamped}
 
+    def subcell_info(self) -> Optional[dict]:
+        """What RunStats.subcell reports: the listed edges per component, nsub, the edges dropped because they carry a lumped override
+        (those the set-up knew of and those that met a host-fixed edge of this run) or have a sample owned by a dispersive material, and
+        the operator form the build ended in ("classes" or "raw"; None before build)."""
+        if self.subcell is None:
+            return None
+        s = self.subcell
+        return {"edges": s.edges(), "nsub": s.nsub, "dropped_lumped": s.dropped_lumped + self._subcell_clash,
+                "dropped_nonplain": s.dropped_nonplain, "operator_form": getattr(self, "operator_form", None)}
+
     def anisotropic_info(self) -> Optional[dict]:
         """What RunStats.anisotropic reports: the anisotropic materials that own cells, those cells' number, and whether the operator
         came from fdtd_build_operator_axes ("device") or from the host arrays ("host")."""
@@ -1149,6 +1188,7 @@ class Simulation:
         stats.lumped = self.lumped_info()
         stats.magnetic = self.magnetic_info()
         stats.conformal = self.conformal_info()
+        stats.subcell = self.subcell_info()
         stats.planewave = self.planewave_info()
         stats.anisotropic = self.anisotropic_info()
         stats.excitations = None if self.excite_lists is None else self.excite_lists.info
